@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the path_tracer_stage hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload sponza_teapots|sponza_class|test_glb]
+    python bench.py --gpus N --steps K --warmup W [--workload sponza_teapots|sponza_class|test_glb] [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher in the environment (no RANK) the script starts its own ranks: it re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one process per GPU.
@@ -15,11 +15,19 @@ save are outside the timed region (reference README "Benchmarking", docs/MANUAL.
 
 Prints ONE JSON line (rank 0).
 
+A plain run does what its headline figure needs: it sets up, renders the untimed frames (clocks, page faults and, N > 1, the
+load balancer's shares), times W warm-up and K timed frames, writes the arrays of the last timed frame if --dump-outputs DIR is
+given, and prints the line.  Everything else below (value_pipelined, value_two_in_flight, sustained, rank_phases, roofline,
+cpu_baseline, parity, display_frame) is measured only with --full (display_frame also with --save-display).
+
 `value` follows SURVEY.md section 8(d) to the letter: Mray/s = rays actually traced (closest-hit + shadow, device counters) over
 all GPUs / host wall time, where every frame is timed from before render() to after the stream sync - ONE FRAME AT A TIME, no
-frames in flight, one frame per launch.  The timed region holds max(K, 50) such frames (`steps_effective`: K = 20 frames would
-be 0.1 s) between barriers; `ms_per_step` = elapsed / steps_effective, `frame_ms` holds mean and p50 of the per-frame times.
-`value_pipelined` is the same workload the way a renderer that does not wait runs it: four frames in flight on their own
+frames in flight, one frame per launch.  The timed region holds K such frames (`steps_effective` = K; SURVEY.md asks for at
+least 50, the default) between barriers; `ms_per_step` = elapsed / K, `frame_ms` holds mean and p50 of the per-frame times.
+--dump-outputs DIR: the last timed frame as its caller receives it, DIR/color.npy (radiance) and DIR/display.npy (tonemapped),
+float32 of shape (views, H, W, 4) - or, where the two would exceed DUMP_BUDGET_BYTES, the same fixed seeded sample of pixels of
+each, shape (pixels, 4).  The same arguments give the same inputs and frame indices in every run.
+With --full, `value_pipelined` is the same workload the way a renderer that does not wait runs it: four frames in flight on their own
 streams like the reference's frame slots (src/context.hh:26), two frames per launch on one GPU (`pipelined` holds the details).
 With N > 1 the pixels of the frame are sharded - shuffled strips (DISTRIBUTION_SHUFFLED_STRIPS, the reference's command-line
 default) whose shares its load balancer settles during the untimed frames, or interleaved scanlines with --strategy scanline -
@@ -51,7 +59,8 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md); 6.3-6.9 TB/s measured with a float4 stream
 L2_PEAK_GBS = 34500.0   # aggregate L2 bandwidth (MI355X_MICROARCH.md section L2)
-MIN_TIMED_FRAMES = 50   # mean and p50 over >= 50 frames with distinct frame indices
+MIN_TIMED_FRAMES = 50   # mean and p50 over >= 50 frames with distinct frame indices (the --full regions time at least this many)
+DUMP_BUDGET_BYTES = 60_000_000      # --dump-outputs: data bytes of all arrays together (two full 1080p RGBA float32 frames are 66 MB)
 
 # rocprofv3 counter passes of the roofline (each its own run; SQ has 8 slots, TCC 4 - MI355X_MICROARCH.md section PMC slots)
 PMC_PASSES = {
@@ -111,7 +120,15 @@ def parse():
                     help="start the ranks, meet in one all-reduce, print the world size and stop (checks the launcher path without a GPU)")
     ap.add_argument("--sustained-frames", type=int, default=400,
                     help="N = 1: a longer pipelined region of this many frames reported as `sustained` (0 switches it off)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed frame's radiance and tonemapped image as DIR/color.npy and DIR/display.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: pipelined, two-in-flight and sustained regions, rank "
+                         "phases, roofline with its counter passes, CPU baseline, parity against the oracle, display frame hash")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def self_launch(args):
@@ -337,6 +354,23 @@ def expected_scaling(workload, world):
     return None, rel
 
 
+def dump_outputs(out_dir, arrays):
+    """Writes every array as out_dir/<name>.npy in float32.  If together they exceed DUMP_BUDGET_BYTES, each keeps the same fixed,
+    seeded sample of its pixels (rows over the last axis, in raster order), as many as the budget allows.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    shapes = {}
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            px = a.reshape(-1, a.shape[-1])
+            keep = int(px.shape[0] * DUMP_BUDGET_BYTES // total)
+            a = px[np.sort(np.random.default_rng(0).permutation(px.shape[0])[:keep])]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def frame_hash(img):
     """64 bits of SHA-256 over the bytes of a frame: frames are a pure function of (scene, options, frame index) whatever N is, so the
     hash of the N-rank job's display frame must equal the N = 1 line's."""
@@ -428,7 +462,8 @@ def main():
     opt = stage_options(args, scene, R)
     strips = world > 1 and args.shard == "pixels" and args.strategy != "scanline"
     strategy = DISTRIBUTION_SHUFFLED_STRIPS if strips else DISTRIBUTION_SCANLINE
-    steps = max(args.steps, MIN_TIMED_FRAMES)           # frames of every timed region
+    steps = args.steps                                  # frames of the timed region of `value`
+    steps_full = max(args.steps, MIN_TIMED_FRAMES)      # frames of every other timed region (--full)
     # Pipelined region.  A rank of a pixel-sharded job traces 1 / N of a frame per launch: at N = 8 a launch no longer fills the GPU,
     # and several frames per launch cost 12 % less per frame (tools/shard_share_probe.py).  The frames are the
     # same frames (tests/test_gpu_parity.py::test_frame_batches_render_the_frames_of_separate_calls).
@@ -438,7 +473,7 @@ def main():
             B = 5
         else:       # whole frames: two per launch are worth 2 % on sponza_teapots and 5 % on test.glb, more are not
             B = 2 if (world == 1 and args.views == 1 and args.spp == 1) else 1
-    steps_pipelined = ((steps + B - 1) // B) * B
+    steps_pipelined = ((steps_full + B - 1) // B) * B
     if world > 1 and args.shard == "pixels" and args.exchange == "ipc":
         # The copy-engine exchange (include/trhip_comm.h trhip_ipc_*): partial frames are written into the display rank's IPC-mapped
         # arena by hipMemcpyAsync - no RCCL kernel on either device - and ordered by tags.  A/B against the RCCL exchange: the display
@@ -460,7 +495,7 @@ def main():
 
     # which kernels shade the frames: asked of the stage (trhip_pt_get_program), and - N > 1 - the same on every rank or nobody renders
     program = lone.check_same_program() if dist is not None else lone.program()
-    if rr.program()["identity"] != program["identity"]:
+    if args.full and rr.program()["identity"] != program["identity"]:
         raise RuntimeError("the two renderers of this process resolved different shading programs")
 
     def sync_all(r):
@@ -534,7 +569,7 @@ def main():
         run_frames(rr, args.prewarm)
     sync_all(rr)
 
-    # ---- timed region (`value`): W warm-up frames, then max(K, 50) frames, one at a time, host sync after each, between barriers
+    # ---- timed region (`value`): W warm-up frames, then K frames, one at a time, host sync after each, between barriers
     lone.reset_accumulation(reset_sample_counter=True)
     run_frames(lone, args.warmup, True)
     sync_all(lone)
@@ -548,35 +583,40 @@ def main():
     lone_lanes, lone_pipes = lone.slots[0].pt.lane_pipes()      # the schedule the timed frames ran with (trhip_pt_get_lane_pipes)
     ms_per_step = elapsed / steps * 1e3
     frame_times.sort()
+    dumped = None
+    if args.dump_outputs and rank == 0:       # the last timed frame, as the caller of render() receives it
+        dumped = {"dir": args.dump_outputs, "frame_index": lone.frame_index - 1,
+                  "arrays": dump_outputs(args.dump_outputs, {"color": lone.download("color"), "display": lone.download("display")})}
 
-    # ---- the same frames pipelined (`value_pipelined`): frame slots, B frames per launch, one synchronisation at the end
-    rr.reset_accumulation(reset_sample_counter=True)
-    run_frames(rr, max(args.warmup, B))
-    sync_all(rr)
-    rr.reset_counters()
-    t0 = time.perf_counter()
-    run_frames(rr, steps_pipelined)
-    sync_all(rr)
-    elapsed_p = time.perf_counter() - t0
-    rays_p, elapsed_p, _ = total_rays(rr, elapsed_p)
+    if args.full:
+        # ---- the same frames pipelined (`value_pipelined`): frame slots, B frames per launch, one synchronisation at the end
+        rr.reset_accumulation(reset_sample_counter=True)
+        run_frames(rr, max(args.warmup, B))
+        sync_all(rr)
+        rr.reset_counters()
+        t0 = time.perf_counter()
+        run_frames(rr, steps_pipelined)
+        sync_all(rr)
+        elapsed_p = time.perf_counter() - t0
+        rays_p, elapsed_p, _ = total_rays(rr, elapsed_p)
 
-    # ---- ... and as the reference itself would run them (`value_two_in_flight`): MAX_FRAMES_IN_FLIGHT = 2 (src/context.hh:26), one frame per
-    # launch - what a Tauray user gets from the render loop of src/tauray.cc without asking for anything
-    two = R.RtRenderer(ctx, scene, opt, (W, H), strategy=strategy, rank=rank, world_size=world, viewports=args.views, shard=args.shard,
-                       frames_in_flight=2, frames_per_launch=1, exchange=exchange)
-    two.set_profiling(False, False)
-    if balance is not None:
-        two.set_device_workloads(list(balance["workloads_exact"]))
-    two.reset_accumulation(reset_sample_counter=True)
-    run_frames(two, max(args.warmup, 4))
-    sync_all(two)
-    two.reset_counters()
-    t0 = time.perf_counter()
-    run_frames(two, steps)
-    sync_all(two)
-    elapsed_2 = time.perf_counter() - t0
-    rays_2, elapsed_2, _ = total_rays(two, elapsed_2)
-    two.close()
+        # ---- ... and as the reference itself would run them (`value_two_in_flight`): MAX_FRAMES_IN_FLIGHT = 2 (src/context.hh:26), one frame per
+        # launch - what a Tauray user gets from the render loop of src/tauray.cc without asking for anything
+        two = R.RtRenderer(ctx, scene, opt, (W, H), strategy=strategy, rank=rank, world_size=world, viewports=args.views, shard=args.shard,
+                           frames_in_flight=2, frames_per_launch=1, exchange=exchange)
+        two.set_profiling(False, False)
+        if balance is not None:
+            two.set_device_workloads(list(balance["workloads_exact"]))
+        two.reset_accumulation(reset_sample_counter=True)
+        run_frames(two, max(args.warmup, 4))
+        sync_all(two)
+        two.reset_counters()
+        t0 = time.perf_counter()
+        run_frames(two, steps_full)
+        sync_all(two)
+        elapsed_2 = time.perf_counter() - t0
+        rays_2, elapsed_2, _ = total_rays(two, elapsed_2)
+        two.close()
 
     # ---- N > 1, pixel shards: where a rank's frame goes (one frame at a time, after the timed regions).  Three loops of the same frames:
     # the whole frame; the frame with nothing travelling (transfer.StandaloneExchange: the display rank stitches standing buffers);
@@ -584,9 +624,9 @@ def main():
     # rank waits for the transport (on the display rank: for the last partial frame to arrive - behind RCCL's kernels or the copy
     # engines, --exchange ipc - on the others: for their send to drain).  Every rank reports; expectations from DESIGN.md section 6.
     phases = None
-    if world > 1 and args.shard == "pixels":
+    if args.full and world > 1 and args.shard == "pixels":
         from tauray_amd.transfer import StandaloneExchange
-        n_ph = max(min(steps, 50), 20)
+        n_ph = max(min(steps_full, 50), 20)
 
         def loop_ms(body):
             sync_all(lone)
@@ -637,15 +677,15 @@ def main():
         "dtype": "f32", "data": "synthetic" if args.workload != "test_glb" else "reference fixture test/test.glb (81 364 triangles)",
         "steps_effective": steps,
         "value_definition": "SURVEY.md 8(d): one frame at a time, host wall time from before render() to after the stream sync, "
-                            f"{steps} frames between barriers (--steps {args.steps}, at least {MIN_TIMED_FRAMES}); frames in flight: see value_pipelined",
+                            f"{steps} frames between barriers (--steps {args.steps}); frames in flight: see value_pipelined (--full)",
         "frame_ms": {"mean": round(sum(frame_times) / len(frame_times), 4), "p50": round(frame_times[len(frame_times) // 2], 4),
                      "min": round(frame_times[0], 4), "max": round(frame_times[-1], 4), "frames": len(frame_times)},
-        "value_two_in_flight": round(rays_2 / elapsed_2 / 1e6, 2),
-        "two_in_flight": {"ms_per_frame": round(elapsed_2 / steps * 1e3, 4), "frames": steps, "frames_in_flight": 2, "frames_per_launch": 1, "unit": "Mray/s",
-                          "definition": "the reference's own MAX_FRAMES_IN_FLIGHT = 2 (src/context.hh:26), one frame per launch, one synchronisation at the end"},
-        "value_pipelined": round(rays_p / elapsed_p / 1e6, 2),
-        "pipelined": {"ms_per_frame": round(elapsed_p / steps_pipelined * 1e3, 4), "frames": steps_pipelined, "frames_in_flight": args.frames_in_flight,
-                      "frames_per_launch": B, "unit": "Mray/s"},
+        **({"value_two_in_flight": round(rays_2 / elapsed_2 / 1e6, 2),
+            "two_in_flight": {"ms_per_frame": round(elapsed_2 / steps_full * 1e3, 4), "frames": steps_full, "frames_in_flight": 2, "frames_per_launch": 1, "unit": "Mray/s",
+                              "definition": "the reference's own MAX_FRAMES_IN_FLIGHT = 2 (src/context.hh:26), one frame per launch, one synchronisation at the end"},
+            "value_pipelined": round(rays_p / elapsed_p / 1e6, 2),
+            "pipelined": {"ms_per_frame": round(elapsed_p / steps_pipelined * 1e3, 4), "frames": steps_pipelined, "frames_in_flight": args.frames_in_flight,
+                          "frames_per_launch": B, "unit": "Mray/s"}} if args.full else {}),
         "config": {"workload": args.workload, "triangles": scene.triangle_count, "width": W, "height": H, "bounces": args.bounces,
                    "spp": args.spp, "sampler": ["uniform-random", "sobol-owen", "sobol-z2", "sobol-z3"][opt.sampler],
                    "preset": args.preset, "film": ["point", "box", "blackman-harris"][opt.film], "regularization": round(opt.regularization_gamma, 3),
@@ -673,9 +713,10 @@ def main():
         **({"load_balance": {k: v for k, v in balance.items() if k != "workloads_exact"}} if balance else {}),
         "rays_per_frame": rays_total // steps,
         "msample_per_s": round(W * H * args.views * args.spp * steps / elapsed / 1e6, 2),
+        **({"dumped_outputs": dumped} if dumped else {}),
     }
 
-    if world == 1 and args.sustained_frames > 0:      # a timed region long enough for a 1 Hz utilisation sampler to see
+    if args.full and world == 1 and args.sustained_frames > 0:      # a timed region long enough for a 1 Hz utilisation sampler to see
         sync_all(rr)
         t1 = time.perf_counter()
         run_frames(rr, args.sustained_frames)
@@ -686,11 +727,11 @@ def main():
                                "unit": "Mray/s", "mode": "pipelined"}
 
     # ---- roofline of the dominant kernel (k_trace_closest), rank 0
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # every rank takes part (a frame of a multi-GPU job ends in an exchange between the ranks); rank 0's kernels are reported.
         # re-run of the identical frames (same frame indices) with per-kernel HIP events; detailed timing serialises the
         # frame (one lane, no shadow/closest overlap), so every kernel is measured owning the chip (instance k_trace_closest<false, true>)
-        n_r = ((min(steps, 20) + B - 1) // B) * B
+        n_r = ((min(steps_full, 20) + B - 1) // B) * B
         rr.set_profiling(False, True)
         rr.reset_accumulation(reset_sample_counter=True)
         run_frames(rr, max(args.warmup, B), True)
@@ -792,7 +833,7 @@ def main():
         result["roofline"] = roof
 
     # ---- CPU baseline: the oracle (a port; the reference has no CPU path) on the host cores, rank 0, N = 1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import binding as OB
         osc = OB.OracleScene(scene)
         oopt = OB.options_for_scene(scene, **args.option_kw)
@@ -903,18 +944,19 @@ def main():
         if not result["parity"]["pass"]:
             print("bench.py: the HIP frame deviates from the oracle's: %s" % json.dumps(result["parity"]), file=sys.stderr)
 
-    # frame 0 again on every rank, outside all timing: the display frame's hash is part of every line.  Frames do not depend on N (RNG keyed by
-    # absolute pixel, shards stitched bit for bit), so the N-rank line's hash equals the N = 1 line's of the same workload and options.
-    lone.set_profiling(False, False)
-    lone.reset_accumulation(reset_sample_counter=True)
-    lone.render()
-    sync_all(lone)
-    if rank == 0:
-        disp = lone.download("display")[:args.views]
-        result["display_frame"] = {"frame_index": 0, "sha256_64": frame_hash(disp), "shape": list(disp.shape),
-                                   "note": "tonemapped frame 0 on the display rank; identical for every N by construction (tests/test_multi_rank_gloo.py, test_multi_device.py)"}
-        if args.save_display:
-            np.save(args.save_display, disp)
+    # frame 0 again on every rank, outside all timing: the display frame's hash is part of every --full line.  Frames do not depend on N (RNG keyed
+    # by absolute pixel, shards stitched bit for bit), so the N-rank line's hash equals the N = 1 line's of the same workload and options.
+    if args.full or args.save_display:
+        lone.set_profiling(False, False)
+        lone.reset_accumulation(reset_sample_counter=True)
+        lone.render()
+        sync_all(lone)
+        if rank == 0:
+            disp = lone.download("display")[:args.views]
+            result["display_frame"] = {"frame_index": 0, "sha256_64": frame_hash(disp), "shape": list(disp.shape),
+                                       "note": "tonemapped frame 0 on the display rank; identical for every N by construction (tests/test_multi_rank_gloo.py, test_multi_device.py)"}
+            if args.save_display:
+                np.save(args.save_display, disp)
     if rank == 0:
         print(json.dumps(result))
     if dist is not None:

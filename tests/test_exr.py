@@ -7,18 +7,14 @@ Pins:
   images - 512 x 512 half files Tauray wrote through tinyexr (tests/golden/ref_piz_*.exr = test/references/validate_*.exr; their
   pixels as tinyexr decodes them are tests/golden/validate_*.npz, tools/make_golden.py);
 * every codec by round trips over sizes that exercise ragged last blocks, odd widths and both wavelet arithmetic modes;
-* the encoders against the reference's tinyexr where the reference checkout is present (the build container)."""
+* the encoders against the reference's tinyexr, through digests of files it decoded (tests/golden/exr_tinyexr_verified.json)."""
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
-
-REF = "/root/reference"
-
 
 def _picture(w, h, kind, seed):
     rng = np.random.default_rng(seed)
@@ -193,28 +189,64 @@ def test_damaged_files_fail_loudly():
         assert hits > 0, comp
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "external", "tinyexr.h")), reason="needs the reference checkout (build container only)")
-def test_written_files_are_read_by_the_references_tinyexr(tmp_path):
-    """The other direction of the pin: files from this encoder - all five codecs, half and float - decoded by the tinyexr the
-    reference vendors (tools/exr_to_raw.cc, compiled here against /root/reference/external) give the source pixels."""
+# Files of this encoder that the reference's tinyexr decoded to their source pixels (tools/make_golden.py --exr-writer): per case, the
+# digest of the file with every ZIP / ZIPS block inflated, so that the pin holds whatever deflate stream zlib picks for the same bytes
+TINYEXR_SIZES = [(64, 48), (33, 70), (517, 33)]
+TINYEXR_KINDS = ("smooth", "noise", "levels")
+LINES_PER_BLOCK = {0: 1, 1: 1, 2: 1, 3: 16, 4: 32}
+
+
+def tinyexr_cases():
+    """(key, image, alpha, half, compression) of every file the pin covers."""
     from tauray_amd import exr
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "exr_to_raw")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-I", os.path.join(REF, "external"), os.path.join(root, "tools", "exr_to_raw.cc"), "-o", exe, "-lpthread"])
-    rng = np.random.default_rng(int(os.environ.get("TRHIP_FUZZ_SEED", "0")))      # TRHIP_FUZZ_DRAWS_SMALL further random sizes (a campaign by hand)
-    sizes = [(64, 48), (33, 70), (517, 33)] + [(int(rng.integers(1, 700)), int(rng.integers(1, 140))) for _ in range(int(os.environ.get("TRHIP_FUZZ_DRAWS_SMALL", "0")))]
-    for (w, h) in sizes:
-        for k, kind in enumerate(("smooth", "noise", "levels")):
+    for (w, h) in TINYEXR_SIZES:
+        for k, kind in enumerate(TINYEXR_KINDS):
             img = _picture(w, h, kind, seed=k + w)
             for comp in (exr.NONE, exr.RLE, exr.ZIPS, exr.ZIP, exr.PIZ):
                 for half in (False, True):
-                    f, raw = str(tmp_path / "a.exr"), str(tmp_path / "a.raw")
-                    open(f, "wb").write(exr.encode_exr(img, alpha=(comp == exr.PIZ and kind == "smooth"), half=half, compression=comp))
-                    subprocess.check_call([exe, f, raw], stdout=subprocess.DEVNULL)
-                    d = open(raw, "rb").read()
-                    assert struct.unpack("<ii", d[:8]) == (w, h)
-                    got = np.frombuffer(d[8:], dtype=np.float32).reshape(h, w, 3)
-                    assert np.array_equal(got.view(np.uint32), _expected(img, False, half).view(np.uint32)), (w, h, kind, comp, half)
+                    alpha = comp == exr.PIZ and kind == "smooth"
+                    yield f"{w}x{h}/{kind}/{comp}/{'half' if half else 'float'}", img, alpha, half, comp
+
+
+def normalised_digest(data, w, h, channels, half, comp):
+    """SHA-256 (64 bits) of a scanline EXR file with the offset table left out and the zlib blocks of ZIP / ZIPS inflated."""
+    import hashlib
+    import zlib
+    p = 8
+    while data[p] != 0:                                   # attributes: name \0 type \0 size value, up to an empty name
+        p = data.index(b"\0", data.index(b"\0", p) + 1) + 1
+        p += 4 + struct.unpack_from("<i", data, p)[0]
+    p += 1
+    out = [data[:p]]
+    lpb = LINES_PER_BLOCK[comp]
+    nblocks = (h + lpb - 1) // lpb
+    p += 8 * nblocks
+    for b in range(nblocks):
+        y, size = struct.unpack_from("<ii", data, p)
+        block = data[p + 8:p + 8 + size]
+        raw = min(lpb, h - y) * w * channels * (2 if half else 4)
+        if comp in (2, 3) and size < raw:
+            block = zlib.decompress(block)
+        out += [struct.pack("<i", y), block]
+        p += 8 + size
+    assert p == len(data)
+    return hashlib.sha256(b"".join(out)).hexdigest()[:16]
+
+
+def test_written_files_are_read_by_the_references_tinyexr():
+    """The other direction of the pin: files from this encoder - all five codecs, half and float - are the files the tinyexr the
+    reference vendors decoded to their source pixels (tools/exr_to_raw.cc through tools/make_golden.py --exr-writer, which records
+    tests/golden/exr_tinyexr_verified.json only for files it checked so)."""
+    import json
+    from tauray_amd import exr
+    verified = json.load(open(os.path.join(GOLDEN, "exr_tinyexr_verified.json")))
+    seen = 0
+    for key, img, alpha, half, comp in tinyexr_cases():
+        data = exr.encode_exr(img, alpha=alpha, half=half, compression=comp)
+        h, w = img.shape[:2]
+        assert normalised_digest(data, w, h, 4 if alpha else 3, half, comp) == verified[key], key
+        seen += 1
+    assert seen == len(verified) == 90
 
 
 def test_hdr_texels_are_half_precision_like_the_references_texture(tmp_path):

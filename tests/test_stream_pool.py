@@ -30,10 +30,10 @@ def test_pool_streams_are_spread_over_the_pipes(R, ctx):
         assert null_class >= 0 and all(c >= 0 for c in classes)
         known = len(set(classes + [null_class]))
         assert known >= 2, "the pipe experiment found one pipe only"      # gfx950 under ROCm 7.2: four
-        # four slots of a renderer: on as many pipes as there are (no two on one pipe while another pipe has none); with the runtime's
-        # default of four hardware queues the null stream holds one of them and the fourth stream has to share
-        queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
-        assert len(set(classes)) == min(4 if queues >= 8 else 3, known), (null_class, classes)
+        # four slots of a renderer: on as many pipes as there are (no two on one pipe while another pipe has none).  This holds with the
+        # runtime's default of four hardware queues too: a pool stream may share the null stream's queue, and that queue has a pipe of
+        # its own among the four (gfx950 under ROCm 7.2 with GPU_MAX_HW_QUEUES=4: null stream on class 3, the four streams on 0, 1, 2, 3)
+        assert len(set(classes)) == min(4, known), (null_class, classes)
         assert ctx.stream_pipe_class(ss[0]) == classes[0]                 # a stream keeps its class
     finally:
         for s in ss:

@@ -7,7 +7,7 @@ for w in $WL; do
   for e in $SETS; do
     envs=""; [ "$e" != "-" ] && envs=$(echo $e | tr ',' ' ')
     tag=$(echo $e | tr -c 'A-Za-z0-9=\n' '_')
-    env $envs python $R/bench.py --workload $w --no-pmc --no-cpu-baseline --sustained-frames 0 "$@" > $OUT/${w}_$tag.json 2> $OUT/${w}_$tag.err
+    env $envs python $R/bench.py --full --workload $w --no-pmc --no-cpu-baseline --sustained-frames 0 "$@" > $OUT/${w}_$tag.json 2> $OUT/${w}_$tag.err
     python - $OUT/${w}_$tag.json $w "$e" <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

@@ -21,4 +21,4 @@ for F in "2" "4" "4 --frames-per-launch=2" "6 --frames-per-launch=2" "4 --frames
   $C -t --frames-in-flight=$F 2>&1 | grep "^FRAMES" | sed "s/^/C++ host, slots: /"
 done
 rm -f $OUT/sponza_teapots.trsc
-(timeout 300 python bench.py --no-pmc --no-cpu-baseline --sustained-frames 0 | python -c "import json,sys; r=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('bench.py: sync ms', r['ms_per_step'], 'pipelined ms', r['pipelined']['ms_per_frame'])")
+(timeout 300 python bench.py --full --no-pmc --no-cpu-baseline --sustained-frames 0 | python -c "import json,sys; r=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('bench.py: sync ms', r['ms_per_step'], 'pipelined ms', r['pipelined']['ms_per_frame'])")

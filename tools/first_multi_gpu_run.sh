@@ -27,7 +27,7 @@ python -m pytest tests/test_multi_device.py -m gpu -q -x -rs 2>&1 | tee "$OUT/te
 grep -q " failed\|error" "$OUT/test_multi_device.txt" && echo "!! the transports are not correct on this node: the rates below are not to be quoted"
 
 echo "== 2. N = 1 (the reference frame and rate)"
-python bench.py --steps "$STEPS" --no-cpu-baseline --no-pmc --save-display "$OUT/display_n1.npy" > "$OUT/n1.json" 2> "$OUT/n1.err" || tail -5 "$OUT/n1.err"
+python bench.py --full --steps "$STEPS" --no-cpu-baseline --no-pmc --save-display "$OUT/display_n1.npy" > "$OUT/n1.json" 2> "$OUT/n1.err" || tail -5 "$OUT/n1.err"
 
 echo "== 3. N x exchange x distribution"
 PORT=29611
@@ -36,7 +36,7 @@ for n in 2 4 8; do
   for ex in native ipc; do
     for st in auto scanline; do
       tag="n${n}_${ex}_${st}"; PORT=$((PORT + 1))
-      timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port "$PORT" bench.py --gpus "$n" --steps "$STEPS" --warmup 5 \
+      timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port "$PORT" bench.py --full --gpus "$n" --steps "$STEPS" --warmup 5 \
         --exchange "$ex" --strategy "$st" --save-display "$OUT/display_$tag.npy" > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { echo "$tag FAILED"; tail -5 "$OUT/$tag.err"; }
     done
   done

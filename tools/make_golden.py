@@ -39,5 +39,36 @@ def main():
         print(n, img.shape, "mean", img.reshape(-1, 3).mean(0), "min", img.min(), "max", img.max())
 
 
+def exr_writer():
+    """tests/golden/exr_tinyexr_verified.json: every file of tests/test_exr.py's tinyexr cases, written by this project's encoder and
+    decoded by the reference's tinyexr; a digest is recorded only if tinyexr gave back the source pixels bit for bit."""
+    import json
+    import struct
+    import tempfile
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_exr as T
+    from tauray_amd import exr
+    tmp = tempfile.mkdtemp()
+    exe = os.path.join(tmp, "exr_to_raw")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-I", os.path.join(REF, "external"),
+                           os.path.join(ROOT, "tools/exr_to_raw.cc"), "-o", exe, "-lpthread"])
+    f, raw = os.path.join(tmp, "a.exr"), os.path.join(tmp, "a.raw")
+    verified = {}
+    for key, img, alpha, half, comp in T.tinyexr_cases():
+        data = exr.encode_exr(img, alpha=alpha, half=half, compression=comp)
+        open(f, "wb").write(data)
+        subprocess.check_call([exe, f, raw], stdout=subprocess.DEVNULL)
+        d = open(raw, "rb").read()
+        h, w = img.shape[:2]
+        assert struct.unpack("<ii", d[:8]) == (w, h), key
+        got = np.frombuffer(d[8:], dtype=np.float32).reshape(h, w, 3)
+        assert np.array_equal(got.view(np.uint32), T._expected(img, False, half).view(np.uint32)), key
+        verified[key] = T.normalised_digest(data, w, h, 4 if alpha else 3, half, comp)
+    shutil.rmtree(tmp)
+    json.dump(verified, open(os.path.join(ROOT, "tests/golden/exr_tinyexr_verified.json"), "w"), indent=0, sort_keys=True)
+    print(len(verified), "files decoded by tinyexr to their source pixels")
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(exr_writer() if sys.argv[1:] == ["--exr-writer"] else main())

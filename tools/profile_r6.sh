@@ -12,18 +12,18 @@ cd /tmp && export TMPDIR=/tmp
 for W in ${@:-sponza_teapots test_glb sponza_class}; do
   D=/tmp/prof_$W; rm -rf $D
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o t -- \
-      python $R/bench.py --steps 20 --warmup 5 --workload $W --no-pmc --no-cpu-baseline > $OUT/${W}_bench_under_rocprof.json 2> $OUT/${W}_stats.log || echo "stats pass failed ($W)"
+      python $R/bench.py --full --steps 20 --warmup 5 --workload $W --no-pmc --no-cpu-baseline > $OUT/${W}_bench_under_rocprof.json 2> $OUT/${W}_stats.log || echo "stats pass failed ($W)"
   S=$(find $D -name "*kernel_stats.csv" | head -1); [ -n "$S" ] && cp $S $OUT/${W}_kernel_stats.csv
   if [ "$W" = sponza_teapots ]; then
     T=$(find $D -name "*kernel_trace.csv" | head -1); [ -n "$T" ] && python $R/tools/sync_frame_timeline.py $T > $OUT/sync_frame_timeline.txt 2>&1
   fi
   rm -rf $D
-  (cd $R && timeout 600 python bench.py --steps 20 --warmup 5 --workload $W --pmc-dump $OUT > $OUT/${W}_bench.json 2> $OUT/${W}_bench.err) || echo "bench failed ($W)"
+  (cd $R && timeout 600 python bench.py --full --steps 20 --warmup 5 --workload $W --pmc-dump $OUT > $OUT/${W}_bench.json 2> $OUT/${W}_bench.err) || echo "bench failed ($W)"
 done
 cd $R
 for a in "--sampler 1" "--preset quality"; do
   n=$(echo $a | sed 's/--//g; s/ /_/g')
-  timeout 300 python bench.py $a --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --sustained-frames 0 > $OUT/option_set_$n.json 2> $OUT/option_set_$n.err || echo "failed: $a"
+  timeout 300 python bench.py --full $a --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --sustained-frames 0 > $OUT/option_set_$n.json 2> $OUT/option_set_$n.err || echo "failed: $a"
 done
 [ -f $R/tauray_amd/libtrhip_timeline.so ] && TRHIP_LIB=$R/tauray_amd/libtrhip_timeline.so timeout 300 python tools/trace_timeline.py sponza_teapots 8 > $OUT/trace_phase_timeline_final_kernels.txt 2> $OUT/timeline.err
 if [ -f $R/tauray_amd/libtrhip_shadetl.so ]; then

@@ -5,8 +5,8 @@
 # single-rank frame bit for bit.
 R=$GRAFT_REPO_ROOT; N=${1:-8}; EX=${2:-auto}; OUT=$R/gpurun_out/rehearse_$EX; mkdir -p $OUT
 cd $R
-timeout 300 python bench.py --steps 20 --no-cpu-baseline --no-roofline --sustained-frames 0 --save-display $OUT/disp1.npy > $OUT/n1.json 2> $OUT/n1.err || echo "single-rank run failed"
-timeout 900 python bench.py --gpus $N --dist-backend gloo --one-device --exchange $EX --steps 20 --no-roofline --save-display $OUT/disp$N.npy > $OUT/n$N.json 2> $OUT/n$N.err || { echo "$N-rank run failed"; tail -30 $OUT/n$N.err; }
+timeout 300 python bench.py --full --steps 20 --no-cpu-baseline --no-roofline --sustained-frames 0 --save-display $OUT/disp1.npy > $OUT/n1.json 2> $OUT/n1.err || echo "single-rank run failed"
+timeout 900 python bench.py --full --gpus $N --dist-backend gloo --one-device --exchange $EX --steps 20 --no-roofline --save-display $OUT/disp$N.npy > $OUT/n$N.json 2> $OUT/n$N.err || { echo "$N-rank run failed"; tail -30 $OUT/n$N.err; }
 python - $OUT $N <<'PY'
 import json, sys, numpy as np
 out, n = sys.argv[1], sys.argv[2]

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/s6; mkdir -p $OUT; cd $R
 export GPU_MAX_HW_QUEUES=8
 one() {  # env-set workload -> "sync ms, two-in-flight ms, pipelined ms"
-  env $1 python bench.py --workload $2 --steps 100 --warmup 5 --no-cpu-baseline --no-pmc --no-roofline --sustained-frames 0 2>/dev/null | python -c "
+  env $1 python bench.py --full --workload $2 --steps 100 --warmup 5 --no-cpu-baseline --no-pmc --no-roofline --sustained-frames 0 2>/dev/null | python -c "
 import json,sys
 l=[x for x in sys.stdin if x.startswith(chr(123))]
 if not l: print('%-70s FAILED' % sys.argv[1]); sys.exit(0)
