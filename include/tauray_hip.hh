@@ -239,7 +239,16 @@ inline scene_data load_scene_dump(const std::string& path)
 class scene_stage
 {
 public:
+    // scene_stage::options::group_strategy (src/scene_stage.hh): how the acceleration structure is laid out (trhip_scene_set_accel_strategy;
+    // TRHIP_AS_ALL_MERGED by default, the reference's `all-merged`) and which instances are dynamic (the reference's
+    // !static_mesh || !static_transformable; one mark per instance, empty = all static).
+    struct options
+    {
+        int as_strategy = TRHIP_AS_ALL_MERGED;
+        std::vector<uint8_t> dynamic;
+    };
     explicit scene_stage(device& dev): dev(&dev) {}
+    scene_stage(device& dev, const options& opt): dev(&dev), opt(opt) {}
 
     void set_scene(const scene_data& s)
     {
@@ -269,9 +278,16 @@ public:
             set_skin(sk.instance, sk.skins.data(), (uint32_t)sk.skins.size());
             skin(sk.instance, sk.joint_transforms.data(), (uint32_t)(sk.joint_transforms.size() / 16));
         }
+        check(trhip_scene_set_accel_strategy(dev->h, opt.as_strategy));
+        if(!opt.dynamic.empty())
+        {
+            if(opt.dynamic.size() != s.instance_count()) throw std::runtime_error("scene_stage: one dynamic mark per instance");
+            check(trhip_scene_set_dynamic_instances(dev->h, opt.dynamic.data(), (uint32_t)opt.dynamic.size()));
+        }
         check(trhip_scene_set_build_mode(dev->h, 0));     // first build of a scene: ePreferFastTrace
         check(trhip_scene_build_accel(dev->h, &accel));
     }
+    trhip_accel_layout layout() const { trhip_accel_layout l; check(trhip_scene_get_accel_layout(dev->h, &l)); return l; }
 
     // Per-frame scene changes of scene_stage::update (src/scene_stage.cc:1066-1116, 1543-1612).  `update_acceleration`
     // keeps the tree and recomputes its boxes (a BLAS/TLAS update) or, with `rebuild`, builds it again on the device.
@@ -306,6 +322,7 @@ public:
     }
 
     device* dev;
+    options opt;
     trhip_accel_info accel = {};
 };
 
@@ -506,6 +523,7 @@ public:
     struct options: path_tracer_stage::options
     {
         tonemap_stage::options tonemap;
+        scene_stage::options scene;         // acceleration-structure strategy and dynamic instances of every device's scene stage
         bool accumulate = false;
         // Frame slots: frame i renders, is gathered and tonemapped on the streams of slot i % N while its predecessors are
         // still running; `display` and finish_frame() refer to the frame render() was last called for, frame_slots[k] to
@@ -538,7 +556,7 @@ public:
         {
             per_device_data& d = per_device[i];
             d.dev = std::make_unique<device>(devices[i]);
-            d.scene_update = std::make_unique<scene_stage>(*d.dev);
+            d.scene_update = std::make_unique<scene_stage>(*d.dev, this->opt.scene);
             d.scene_update->set_scene(scene);               // scene replicated on every device (src/gpu_buffer.hh:63-116)
             d.dist = get_device_distribution_params(size, this->opt.distribution.strategy, cumulative, ratios[i], (unsigned)i,
                                                     (unsigned)devices.size(), i == 0);

@@ -140,7 +140,8 @@ typedef struct trhip_accel_info {
     uint32_t node_count;
     uint32_t tri_light_count;
     float build_ms;                   /* device time of the whole build */
-    float bounds_min[3], bounds_max[3];
+    float bounds_min[3], bounds_max[3];   /* all-merged: bounds of the triangle centroids (what the Morton codes quantise); two-level
+                                            * strategies: the union of the instances' (conservative) world boxes, after a refit too */
     uint32_t node_bytes;              /* bytes one node visit reads (112: six box planes + child refs of a 4-wide node) */
     uint32_t leaf_count;              /* leaves of the tree (= triangle_count: one triangle per leaf); node_count = leaf_count - 1 */
 } trhip_accel_info;
@@ -192,6 +193,38 @@ int trhip_scene_build_accel(trhip_device* dev, trhip_accel_info* out);
  * nodes by cost (csrc/bvh_optimize.h): 12 % fewer node visits per ray, 16 instead of 9 ms for a million triangles; != 0: it does
  * neither - for callers that rebuild every frame.  Hits, and therefore frames, do not depend on the choice. */
 int trhip_scene_set_build_mode(trhip_device* dev, int prefer_fast_build);
+/* How the acceleration structure is laid out (the reference's --as-strategy, scene_stage::options::group_strategy); takes effect at
+ * the next trhip_scene_build_accel and is kept over uploads.
+ *   TRHIP_AS_ALL_MERGED (the default): every instance's triangles pre-transformed into one tree - the structure and kernels of before.
+ *   TRHIP_AS_PER_MESH: one BLAS per distinct mesh span (equal vertex_offset, vertex_count, index_offset and triangle_count), built in
+ *     object space and shared by every instance of that span, under a TLAS over the instances.
+ *   TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH: the static instances world-space in one merged BLAS under an identity TLAS leaf, the dynamic
+ *     ones (trhip_scene_set_dynamic_instances, and every skinned instance) in per-mesh BLASes.
+ * An instance here is one glTF primitive with one material, so the reference's `per-material` is TRHIP_AS_PER_MESH exactly, and its
+ * `per-model` is TRHIP_AS_PER_MESH wherever a model has one primitive; its default `static-merged-dynamic-per-model` is
+ * TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH.  Deviation: the default here stays `all-merged`, so that nothing existing changes.
+ * Hits do not depend on the strategy beyond the rounding of the object-space ray (exact for identity transforms).  Under a two-level
+ * strategy trhip_scene_refit_accel rebuilds the TLAS from the current transforms, refits the BLASes whose vertices were skinned and the
+ * merged static BLAS only if a static instance's record changed: trhip_scene_update_instances + trhip_scene_refit_accel is the
+ * reference's rigid-body update. */
+#define TRHIP_AS_ALL_MERGED 0
+#define TRHIP_AS_PER_MESH 1
+#define TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH 2
+int trhip_scene_set_accel_strategy(trhip_device* dev, int strategy);
+/* Marks instances dynamic (1) or static (0): the reference's !static_mesh || !static_transformable.  `count` = the uploaded instance
+ * count; an upload clears the marks.  Skinned instances are dynamic without a mark.  Takes effect at the next build. */
+int trhip_scene_set_dynamic_instances(trhip_device* dev, const uint8_t* dynamic, uint32_t count);
+typedef struct trhip_accel_layout {
+    int32_t strategy;                 /* of the last build */
+    uint32_t blas_count;              /* 1 for all-merged */
+    uint32_t tlas_leaf_count;         /* 0 for all-merged */
+    uint32_t blas_updated;            /* BLASes built or refit by the last build / refit call */
+    uint64_t node_bytes;              /* 128-byte node slots of both levels */
+    uint64_t record_bytes;            /* triangle records of every BLAS + the 64-byte instance records of the TLAS leaves */
+    float blas_ms;                    /* device time of the last call's BLAS work (build or refit) */
+    float tlas_ms;                    /* device time of the last TLAS build (0 for all-merged) */
+} trhip_accel_layout;
+int trhip_scene_get_accel_layout(trhip_device* dev, trhip_accel_layout* out);
 /* copies the 64-byte tri_light records back to the host (test hook) */
 int trhip_scene_get_tri_lights(trhip_device* dev, void* out_host, uint32_t max_count);
 

@@ -39,6 +39,16 @@ class AccelInfoC(C.Structure):
                 ("node_bytes", C.c_uint32), ("leaf_count", C.c_uint32)]
 
 
+class AccelLayoutC(C.Structure):
+    """trhip_accel_layout: how the last build laid the acceleration structure out (include/trhip.h)."""
+    _fields_ = [("strategy", C.c_int32), ("blas_count", C.c_uint32), ("tlas_leaf_count", C.c_uint32), ("blas_updated", C.c_uint32),
+                ("node_bytes", C.c_uint64), ("record_bytes", C.c_uint64), ("blas_ms", C.c_float), ("tlas_ms", C.c_float)]
+
+
+# trhip_scene_set_accel_strategy
+AS_ALL_MERGED, AS_PER_MESH, AS_STATIC_MERGED_DYNAMIC_PER_MESH = 0, 1, 2
+
+
 class PtOptionsC(C.Structure):
     """== path_tracer_stage::options (reference src/path_tracer_stage.hh:13-30), flattened."""
     _fields_ = [
@@ -115,6 +125,9 @@ SYMBOLS = {
     "trhip_pt_set_frame_batch": (_i, [_vp, C.c_uint32]),
     "trhip_scene_update_lights": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32]),
     "trhip_scene_set_build_mode": (_i, [_vp, _i]),
+    "trhip_scene_set_accel_strategy": (_i, [_vp, _i]),
+    "trhip_scene_set_dynamic_instances": (_i, [_vp, _vp, _u32]),
+    "trhip_scene_get_accel_layout": (_i, [_vp, C.POINTER(AccelLayoutC)]),
     "trhip_stitch_batch": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, C.c_float, _vp]),
     "trhip_stream_create": (_i, [_vp, C.POINTER(C.c_void_p)]),
     "trhip_stream_destroy": (_i, [_vp, _vp]),

@@ -27,6 +27,7 @@ constexpr int KB = TR_BLOCK;
 
 // ---------------------------------------------------------------------------------------------------
 // feature_stage: shader/rt_feature.rgen:21-45 + rt_feature.rchit:16-27 with FEATURE of src/feature_stage.cc:33-65
+template <bool TWO_LEVEL>
 __global__ __launch_bounds__(KB) void k_feature(SceneView sv, LaunchCtx L, int feature, int projection, uint viewport, float min_ray_dist,
                                                 f4 default_value, f4* target, uint target_w, uint target_h, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(KB) void k_feature(SceneView sv, LaunchCtx L, int f
     HitRecord hit;
     TraceStats st = {};
     int overflow = 0;
-    trace_closest4<1, false>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), false, 0u, s_stack + threadIdx.x, hit, st, overflow);
+    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), false, 0u, s_stack + threadIdx.x, hit, st, overflow);
     if (overflow) *overflow_flag = 1;
     f4 data = default_value;
     if (hit.instance_id >= 0) {
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(KB) void k_calibrate_l1(const char* base, int iters
 // ray-level hooks
 // Whole waves walk the ray list together and use the wave-level traversal with its quad-cooperative tail (trace_quad.h),
 // which is what the frame's closest-hit kernels run.
+template <bool TWO_LEVEL>
 __global__ __launch_bounds__(KB) void k_query_closest(SceneView sv, uint n, const float* rays, const uint* seeds, int include_lights,
                                                       HitRecord* out, uint* overflow_flag, int* qspill) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
@@ -133,18 +135,19 @@ __global__ __launch_bounds__(KB) void k_query_closest(SceneView sv, uint n, cons
         const uint seed = (valid && seeds) ? seeds[i] : 0u;
         HitRecord hit;
 #if TR_QUAD_SWITCH > 0
-        if (seeds) trace_closest_wave4<0, false>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, seed, my_stack, qc, hit, st, overflow);
-        else trace_closest_wave4<1, false>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, 0u, my_stack, qc, hit, st, overflow);
+        if (seeds) trace_closest_wave4<0, false, TWO_LEVEL>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, seed, my_stack, qc, hit, st, overflow);
+        else trace_closest_wave4<1, false, TWO_LEVEL>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, 0u, my_stack, qc, hit, st, overflow);
 #else
         if (valid) {
-            if (seeds) trace_closest4<0, false>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, seed, my_stack, hit, st, overflow);
-            else trace_closest4<1, false>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, 0u, my_stack, hit, st, overflow);
+            if (seeds) trace_closest4<0, false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, seed, my_stack, hit, st, overflow);
+            else trace_closest4<1, false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, 0u, my_stack, hit, st, overflow);
         }
 #endif
         if (valid) out[i] = hit;
     }
     if (overflow) *overflow_flag = 1;
 }
+template <bool TWO_LEVEL>
 __global__ __launch_bounds__(KB) void k_query_shadow(SceneView sv, uint n, const float* rays, float* out, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
     int* const s_stack = s_stack_rows + TR_STACK_ROW0;     // row -1 exists (LaneStack, trace.h)
@@ -152,7 +155,7 @@ __global__ __launch_bounds__(KB) void k_query_shadow(SceneView sv, uint n, const
     TraceStats st = {};
     for (uint i = blockIdx.x * KB + threadIdx.x; i < n; i += gridDim.x * KB) {
         const float* r = rays + (size_t)i * 8;
-        out[i] = trace_shadow4<false>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], s_stack + threadIdx.x, st, overflow);
+        out[i] = trace_shadow4<false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], s_stack + threadIdx.x, st, overflow);
     }
     if (overflow) *overflow_flag = 1;
 }
@@ -450,6 +453,7 @@ int trhip_scene_upload(trhip_device* dev, const trhip_scene_desc* d) {
                 return set_error("trhip_scene_upload: non-finite vertex position");
     }
     if (upload_array(s.instances, d->instances, d->instance_count)) return 1;
+    s.host_instances.assign(insts, insts + d->instance_count);
     if (upload_array(s.spans, d->spans, d->instance_count)) return 1;
     {   // spans of the pre-transformed copy: every instance gets its own vertex range (instances may share a mesh)
         s.host_spans.assign(spans, spans + d->instance_count);
@@ -482,6 +486,8 @@ int trhip_scene_upload(trhip_device* dev, const trhip_scene_desc* d) {
         for (uint i = 0; i < d->instance_count; ++i) if (d->non_opaque[i]) { alpha_base[i] = (uint)n_alpha; n_alpha += spans[i].triangle_count; }
         if (n_alpha > 0x7FFFFFFFull) return set_error("trhip_scene_upload: more than 2^31 non-opaque triangles");
         if (upload_array(s.alpha_base, alpha_base.data(), alpha_base.size())) return 1;
+        s.host_alpha_base = alpha_base;
+        s.host_non_opaque.assign(d->non_opaque, d->non_opaque + d->instance_count);
         s.alpha_count = (uint)n_alpha;
         if (n_alpha) HIPCHK(hipMalloc(&s.alpha_tris, (size_t)n_alpha * sizeof(AlphaTri)));
     }
@@ -553,6 +559,15 @@ int trhip_scene_update_instances(trhip_device* dev, const void* instances, uint3
     }
     HIPCHK(hipDeviceSynchronize());
     if (count) HIPCHK(hipMemcpy(s.instances, instances, (size_t)count * sizeof(Instance), hipMemcpyHostToDevice));
+    {   // two-level structure: the merged static BLAS is refit only when one of its instances changed, any-hit records only where a
+        // non-opaque instance's material did
+        const Instance* in = (const Instance*)instances;
+        for (uint32_t i = 0; s.two_level && i < count && i < s.inst_blas.size(); ++i) {
+            if (s.inst_blas[i] >= 0 && s.blases[s.inst_blas[i]].world && memcmp(&in[i], &s.host_instances[i], sizeof(Instance)) != 0) s.static_dirty = true;
+            if (s.host_non_opaque[i] && memcmp(&in[i].mat, &s.host_instances[i].mat, sizeof(Material)) != 0) s.alpha_dirty[i] = 1;
+        }
+        if (count) s.host_instances.assign(in, in + count);
+    }
     // transforms changed: the acceleration structure, the tri lights and the pre-transformed vertex copy are stale
     // (their buffers stay: trhip_scene_build_accel refills them without allocating)
     s.accel_built = false;
@@ -588,6 +603,8 @@ int trhip_scene_skin(trhip_device* dev, uint32_t instance, const float* joint_tr
         if (!std::isfinite(joint_transforms[k])) return set_error("trhip_scene_skin: non-finite joint transform");
     HIPCHK(hipDeviceSynchronize());   // frames in flight read the vertices
     if (int rc = skin_instance(s, instance, joint_transforms, joint_count, nullptr)) return rc;
+    for (uint32_t i = 0; i < s.instance_count; ++i)      // every instance of the span moved: their BLAS (two-level structure)
+        if (memcmp(&s.host_spans[i], &s.host_spans[instance], sizeof(MeshSpan)) == 0) mark_skinned(s, i);
     s.accel_built = false;
     if (s.world_vertices) { (void)hipFree(s.world_vertices); s.world_vertices = nullptr; }
     return 0;
@@ -616,6 +633,27 @@ int trhip_scene_build_accel(trhip_device* dev, trhip_accel_info* out) {
 int trhip_scene_set_build_mode(trhip_device* dev, int prefer_fast_build) {
     DEVCHK(dev);
     dev->scene.fast_build = prefer_fast_build != 0;
+    return 0;
+}
+int trhip_scene_set_accel_strategy(trhip_device* dev, int strategy) {
+    DEVCHK(dev);
+    if (strategy < TRHIP_AS_ALL_MERGED || strategy > TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH)
+        return set_error("trhip_scene_set_accel_strategy: unknown strategy " + std::to_string(strategy) + " (0 all-merged, 1 per-mesh, 2 static-merged-dynamic-per-mesh)");
+    dev->scene.accel_strategy = strategy;
+    return 0;
+}
+int trhip_scene_set_dynamic_instances(trhip_device* dev, const uint8_t* dynamic, uint32_t count) {
+    DEVCHK(dev);
+    DeviceScene& s = dev->scene;
+    if (count != s.instance_count) return set_error("trhip_scene_set_dynamic_instances: count differs from the uploaded instances");
+    if (count && !dynamic) return set_error("trhip_scene_set_dynamic_instances: null marks");
+    s.dynamic_marks.assign(dynamic, dynamic + count);
+    return 0;
+}
+int trhip_scene_get_accel_layout(trhip_device* dev, trhip_accel_layout* out) {
+    DEVCHK(dev);
+    if (!out) return set_error("trhip_scene_get_accel_layout: null output");
+    *out = dev->scene.layout;
     return 0;
 }
 int trhip_scene_refit_accel(trhip_device* dev, trhip_accel_info* out) {
@@ -834,7 +872,7 @@ int trhip_feature_render(trhip_device* dev, int feature, const trhip_distributio
     size_t n = (size_t)L.launch_w * L.launch_h;
     if (n == 0) return 0;
     f4 dv = F4(default_value[0], default_value[1], default_value[2], default_value[3]);
-    hipLaunchKernelGGL(k_feature, dim3((uint)((n + KB - 1) / KB)), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), L, feature, projection,
+    hipLaunchKernelGGL(dev->scene.two_level ? k_feature<true> : k_feature<false>, dim3((uint)((n + KB - 1) / KB)), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), L, feature, projection,
                        viewport, min_ray_dist, dv, (f4*)color_dev, target_w, target_h, dev->overflow_flag);
     HIPCHK(hipGetLastError());
     return 0;
@@ -846,7 +884,7 @@ int trhip_trace_closest(trhip_device* dev, uint32_t n, const void* rays_dev, con
     if (n == 0) return 0;
     uint blocks = std::min((n + KB - 1) / KB, QUERY_BLOCKS);
     if (!dev->qspill) HIPCHK(hipMalloc(&dev->qspill, (size_t)QUERY_BLOCKS * (KB / 64) * 16u * TR_QSPILL * sizeof(int)));
-    hipLaunchKernelGGL(k_query_closest, dim3(blocks), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), n, (const float*)rays_dev,
+    hipLaunchKernelGGL(dev->scene.two_level ? k_query_closest<true> : k_query_closest<false>, dim3(blocks), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), n, (const float*)rays_dev,
                        (const uint*)seeds_dev, include_lights, (HitRecord*)hits_dev, dev->overflow_flag, dev->qspill);
     HIPCHK(hipGetLastError());
     return 0;
@@ -856,7 +894,7 @@ int trhip_trace_shadow(trhip_device* dev, uint32_t n, const void* rays_dev, void
     if (!dev->scene.accel_built) return set_error("trhip_trace_shadow: call trhip_scene_build_accel first");
     if (n == 0) return 0;
     uint blocks = std::min((n + KB - 1) / KB, 2048u);
-    hipLaunchKernelGGL(k_query_shadow, dim3(blocks), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), n, (const float*)rays_dev,
+    hipLaunchKernelGGL(dev->scene.two_level ? k_query_shadow<true> : k_query_shadow<false>, dim3(blocks), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), n, (const float*)rays_dev,
                        (float*)visibility_dev, dev->overflow_flag);
     HIPCHK(hipGetLastError());
     return 0;

@@ -68,6 +68,34 @@ struct DeviceScene {
     std::vector<uint> level_offsets;     // level l = level_nodes[level_offsets[l] .. level_offsets[l + 1])
     bool levels_valid = false;
     size_t scratch_bytes = 0;
+    // ---- two-level structure (trhip_scene_set_accel_strategy)
+    int accel_strategy = TRHIP_AS_ALL_MERGED;   // kept over uploads; takes effect at the next build
+    std::vector<uint8_t> dynamic_marks;         // trhip_scene_set_dynamic_instances (cleared by an upload)
+    std::vector<Instance> host_instances;       // what the device holds: the TLAS transforms, and which static record changed
+    struct Blas {
+        int root;                  // >= 0 node, < 0 ~record, in the shared arrays
+        uint node_off, node_slots, tri_off, tri_count;
+        uint rep;                  // an instance of the BLAS's span (object-space BLAS), whose records it rebuilds from
+        bool world;                // the merged BLAS of the static instances: world-space records with their own words
+    };
+    std::vector<Blas> blases;
+    std::vector<int> inst_blas;     // per instance: its BLAS, or -1 (no triangles)
+    std::vector<uint> tlas_src;     // instance of each TLAS leaf before the TLAS sort; 0xFFFFFFFF = the merged static BLAS
+    std::vector<uint8_t> blas_dirty;   // vertices changed since the BLAS was built (trhip_scene_skin)
+    bool static_dirty = false;      // a static instance's record changed (trhip_scene_update_instances)
+    std::vector<uint8_t> alpha_dirty;   // per instance: its AlphaTri records are stale (material changed, mesh skinned)
+    uint* alpha_list = nullptr;     // device copy of the refit's list of such instances (+ prefix sums of their triangle counts)
+    size_t alpha_list_words = 0;
+    bool two_level = false;         // the last build was two-level
+    TlasLeaf* tlas = nullptr;       // instance records in TLAS leaf order: inside the nodes4 allocation, behind the node slots
+    TlasLeaf* tlas_src_leaves = nullptr;   // ... in tlas_src order (build input)
+    uint tlas_leaf_count = 0, tlas_node_slots = 0, tlas_capacity = 0;
+    size_t node_capacity = 0, tri_capacity = 0;   // node slots / records the two-level outputs hold
+    trhip_accel_layout layout = {};
+    std::vector<uint> host_alpha_base;
+    std::vector<uint8_t> host_non_opaque;
+    void* tl_aux = nullptr;         // TLAS build: BLAS root references and boxes, sorted instance boxes
+    size_t tl_aux_bytes = 0;
 
     SceneView view() const {
         SceneView v;
@@ -86,6 +114,13 @@ struct DeviceScene {
         if (nodes4) (void)hipFree(nodes4);
         if (tris) (void)hipFree(tris);
         if (tri_lights) (void)hipFree(tri_lights);
+        if (tlas_src_leaves) (void)hipFree(tlas_src_leaves);
+        if (tl_aux) (void)hipFree(tl_aux);
+        tl_aux = nullptr; tl_aux_bytes = 0;
+        if (alpha_list) (void)hipFree(alpha_list);
+        alpha_list = nullptr; alpha_list_words = 0; alpha_dirty.clear();
+        tlas = nullptr; tlas_src_leaves = nullptr; tlas_capacity = 0; node_capacity = 0; tri_capacity = 0; two_level = false;
+        blases.clear(); inst_blas.clear(); tlas_src.clear(); blas_dirty.clear(); static_dirty = false;
         nodes = nullptr; nodes4 = nullptr; tris = nullptr; tri_lights = nullptr; node_count = 0; tri_light_count = 0; accel_built = false;
         accel_capacity = 0xFFFFFFFFu;
         if (level_nodes) (void)hipFree(level_nodes);
@@ -105,7 +140,9 @@ struct DeviceScene {
         void* ptrs[] = {instances, spans, vertices, indices, point_lights, directional_lights, tex_infos, texels, envmap,
                         alias_table, cameras, prev_cameras, non_opaque, tri_prefix, world_spans, world_vertices, scratch, shade_tris, alpha_base, alpha_tris};
         for (void* p : ptrs) if (p) (void)hipFree(p);
+        const int strategy = accel_strategy;
         *this = DeviceScene();
+        accel_strategy = strategy;
     }
 };
 
@@ -114,5 +151,6 @@ int ensure_world_vertices(DeviceScene& ds, hipStream_t stream);
 int build_shade_tris(DeviceScene& ds, int instance, hipStream_t stream);   // instance < 0: every mesh (after an upload); else the mesh of that instance (after skinning)
 int skin_instance(DeviceScene& ds, uint instance, const float* joint_transforms, uint joint_count, hipStream_t stream);   // skinning.comp
 int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);   // same tree, new boxes (after trhip_scene_update_instances)   // pre_transform.comp per instance
+void mark_skinned(DeviceScene& ds, uint instance);   // the BLAS of the instance's span needs a refit (two-level structure)
 
 }  // namespace tr

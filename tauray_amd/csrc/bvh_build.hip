@@ -6,6 +6,9 @@
 // trhip_scene_refit_accel keeps the tree and recomputes its boxes level by level.  Also here: extract_tri_lights
 // (shader/extract_tri_lights.comp:17-54) and the pre-transformed vertex copy (shader/pre_transform.comp:26-42).
 #include <algorithm>
+#include <cmath>
+#include <map>
+#include <tuple>
 #include <vector>
 #include "build.h"
 
@@ -728,7 +731,13 @@ __global__ __launch_bounds__(BT) void k_refit_level(uint count, const uint* leve
     for (int k = 0; k < 3; ++k) { node_bounds[6 * (size_t)id + k] = lo[k]; node_bounds[6 * (size_t)id + 3 + k] = hi[k]; }
 }
 
+static int refit_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);
 int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
+    if (ds.two_level) {
+        if (ds.accel_tri_count != ds.tri_count || ds.tlas_capacity != ds.tlas_leaf_count)
+            return set_error("trhip_scene_refit_accel: no acceleration structure to refit; call trhip_scene_build_accel first");
+        return refit_two_level(ds, stream, info);
+    }
     const uint n = ds.leaf_count;      // records in ds.tris: triangles, or the references of a pre-split build (their leaf boxes grow to the whole triangle here)
     if (ds.accel_tri_count != ds.tri_count || ds.accel_capacity == 0xFFFFFFFFu || (n > 0 && !ds.tris) || (n > 1 && !ds.nodes4))
         return set_error("trhip_scene_refit_accel: no acceleration structure to refit; call trhip_scene_build_accel first");
@@ -781,6 +790,7 @@ int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    ds.layout.blas_updated = 1; ds.layout.blas_ms = ms;
     if (info) {
         memset(info, 0, sizeof(*info));
         info->triangle_count = ds.tri_count; info->leaf_count = n; info->node_count = ds.node_count; info->node_bytes = 112u; info->tri_light_count = ds.tri_light_count;
@@ -965,63 +975,69 @@ static int pair_leaves_postpass(DeviceScene& ds, hipStream_t stream, uint n_node
     return 0;
 }
 
-int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
-    const uint n_scene = ds.tri_count;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, stream));
-    ds.accel_built = false;
-    ds.levels_valid = false;   // a new tree: the refit level lists are rebuilt on demand
-    SceneView sv = ds.view();
-    sv.tri_count = n_scene;
-    // Temporaries come out of one scratch arena that survives the call, and the outputs keep their allocation while the
-    // triangle count does not change: a rebuild (dynamic scenes) performs no allocation at all.
+// ---------------------------------------------------------------------------------------------------------------
+// One tree over n records: the scratch plan (sized for up to n_cap leaves; the arena survives the call) and the pipeline from the
+// unsorted records + their centroid bounds to sorted records and 4-wide nodes.  trhip_scene_build_accel runs it once over every world
+// triangle (all-merged); the two-level build once per BLAS and once over the instance boxes of the TLAS.
+struct TreePlan {
+    size_t sort_bytes = 0, scan_bytes = 0;
+    size_t o_cbounds, o_unsorted, o_keys, o_keys_sorted, o_vals, o_vals_sorted, o_leaf_box, o_sort, o_children, o_sizes, o_parent, o_parent_leaf,
+           o_node_box, o_arrive, o_cref0, o_cref1, o_cbox0, o_cbox1, o_nn, o_valid, o_pos, o_scan, o_new_id, o_nodes2;
+    size_t o_uparent, o_moves, o_lock, o_optstat, o_ccost, o_cdec;
+    char* base = nullptr;
+    uint* cbounds() const { return reinterpret_cast<uint*>(base + o_cbounds); }   // 6 flipped centroid bounds, [6] PLOC node allocator, [8..9] cluster counts
+    TriRecord* unsorted() const { return reinterpret_cast<TriRecord*>(base + o_unsorted); }
+};
+
+static int plan_tree(DeviceScene& ds, hipStream_t stream, uint n_cap, TreePlan& P) {
+    size_t& sort_bytes = P.sort_bytes;
+    size_t& scan_bytes = P.scan_bytes;
+    const uint n_tri = n_cap;
     size_t plan_bytes = 0;
     auto plan = [&](size_t bytes) { size_t o = plan_bytes; plan_bytes += (bytes + 255) & ~(size_t)255; return o; };
-    // n_tri = triangles = leaves; n_cap = what everything is sized for
-    const uint n_tri = n_scene;
-    const uint n_cap = n_tri;
-    uint n = n_tri;
     const size_t n1 = n_cap > 1 ? n_cap - 1 : 0;     // inner nodes the buffers hold
-    size_t sort_bytes = 0, scan_bytes = 0;
     if (n_cap > 0) {
         HIPCHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint*)nullptr, (uint*)nullptr, n_cap, 0, 64, stream));
         HIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, (uint*)nullptr, (uint*)nullptr, 0u, n_cap + BT, rocprim::plus<uint>(), stream));
     }
-    const size_t o_cbounds = plan(32 * sizeof(uint)), o_unsorted = plan((size_t)n_cap * sizeof(TriRecord)), o_keys = plan((size_t)n_cap * 8),
-                 o_keys_sorted = plan((size_t)n_cap * 8), o_vals = plan((size_t)n_cap * 4), o_vals_sorted = plan((size_t)n_cap * 4),
-                 o_leaf_box = plan((size_t)n_cap * 24), o_sort = plan(sort_bytes + 16), o_children = plan(n1 * sizeof(int2)),
-                 o_sizes = plan(n1 * 4), o_parent = plan(n1 * 4), o_parent_leaf = plan((size_t)n_cap * 4), o_node_box = plan(n1 * 24),
-                 o_arrive = plan(n1 * 4), o_cref0 = plan((size_t)n_cap * 4), o_cref1 = plan((size_t)n_cap * 4), o_cbox0 = plan((size_t)n_cap * 24),
-                 o_cbox1 = plan((size_t)n_cap * 24), o_nn = plan((size_t)n_cap * 4), o_valid = plan(((size_t)n_cap + BT) * 4), o_pos = plan(((size_t)n_cap + BT) * 4),
-                 o_scan = plan(scan_bytes + 16), o_new_id = plan(n1 * 4), o_nodes2 = plan(n1 * sizeof(BvhNode));
+    P.o_cbounds = plan(32 * sizeof(uint)); P.o_unsorted = plan((size_t)n_cap * sizeof(TriRecord)); P.o_keys = plan((size_t)n_cap * 8);
+    P.o_keys_sorted = plan((size_t)n_cap * 8); P.o_vals = plan((size_t)n_cap * 4); P.o_vals_sorted = plan((size_t)n_cap * 4);
+    P.o_leaf_box = plan((size_t)n_cap * 24); P.o_sort = plan(sort_bytes + 16); P.o_children = plan(n1 * sizeof(int2));
+    P.o_sizes = plan(n1 * 4); P.o_parent = plan(n1 * 4); P.o_parent_leaf = plan((size_t)n_cap * 4); P.o_node_box = plan(n1 * 24);
+    P.o_arrive = plan(n1 * 4); P.o_cref0 = plan((size_t)n_cap * 4); P.o_cref1 = plan((size_t)n_cap * 4);
+    P.o_cbox0 = plan((size_t)n_cap * 24); P.o_cbox1 = plan((size_t)n_cap * 24); P.o_nn = plan((size_t)n_cap * 4);
+    P.o_valid = plan(((size_t)n_cap + BT) * 4); P.o_pos = plan(((size_t)n_cap + BT) * 4); P.o_scan = plan(scan_bytes + 16);
+    P.o_new_id = plan(n1 * 4); P.o_nodes2 = plan(n1 * sizeof(BvhNode));
     const bool optimise = ds.optimise_rounds > 0 && !ds.fast_build && n_tri > 2;
     const size_t n_all_cap = (size_t)n_cap + n1;
     const bool dp_collapse = ds.collapse_by_cost && !ds.fast_build && n_tri > 2;   // a fast build keeps the greedy choice (the cost pass would double its time)
-    const size_t o_uparent = plan(optimise || dp_collapse ? n_all_cap * 4 : 0), o_moves = plan(optimise ? n_all_cap * sizeof(OptMove) : 0), o_lock = plan(optimise ? n_all_cap * 8 : 0),
-                 o_optstat = plan(64), o_ccost = plan(dp_collapse ? n1 * 12 : 0), o_cdec = plan(dp_collapse ? n1 : 0);
+    P.o_uparent = plan(optimise || dp_collapse ? n_all_cap * 4 : 0); P.o_moves = plan(optimise ? n_all_cap * sizeof(OptMove) : 0);
+    P.o_lock = plan(optimise ? n_all_cap * 8 : 0); P.o_optstat = plan(64); P.o_ccost = plan(dp_collapse ? n1 * 12 : 0);
+    P.o_cdec = plan(dp_collapse ? n1 : 0);
     if (plan_bytes > ds.scratch_bytes) {
         if (ds.scratch) (void)hipFree(ds.scratch);
         ds.scratch = nullptr; ds.scratch_bytes = 0;
         HIPCHK(hipMalloc(&ds.scratch, plan_bytes));
         ds.scratch_bytes = plan_bytes;
     }
-    char* base = static_cast<char*>(ds.scratch);
-    uint* cbounds = reinterpret_cast<uint*>(base + o_cbounds);   // 6 flipped centroid bounds, [6] PLOC node allocator, [8..9] cluster counts
-    {
-        const uint init[32] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        HIPCHK(hipMemcpyAsync(cbounds, init, sizeof(init), hipMemcpyHostToDevice, stream));
-    }
-    if (ds.accel_capacity != n_cap) {   // outputs
-        ds.free_accel();
-        if (n_cap > 0) HIPCHK(hipMalloc(&ds.tris, (size_t)n_cap * sizeof(TriRecord)));
-        if (n1 > 0) {
-            // traversal addresses a node's planes with 32-bit byte offsets (node << 7 | plane)
-            if ((uint64_t)n1 * sizeof(Bvh4Node) > 0xFFFFFFFFull) return set_error("trhip_scene_build_accel: more than 2^25 nodes");
-            HIPCHK(hipMalloc(&ds.nodes4, n1 * sizeof(Bvh4Node)));
-        }
-        ds.accel_capacity = n_cap;
-    }
+    P.base = static_cast<char*>(ds.scratch);
+    return 0;
+}
+
+static int build_tree(DeviceScene& ds, hipStream_t stream, const TreePlan& P, uint n, TriRecord* out_tris, Bvh4Node* out_nodes, bool experiments) {
+    char* base = P.base;
+    size_t sort_bytes = P.sort_bytes, scan_bytes = P.scan_bytes;
+    const size_t o_cbounds = P.o_cbounds, o_unsorted = P.o_unsorted, o_keys = P.o_keys, o_keys_sorted = P.o_keys_sorted, o_vals = P.o_vals,
+                 o_vals_sorted = P.o_vals_sorted, o_leaf_box = P.o_leaf_box, o_sort = P.o_sort, o_children = P.o_children, o_sizes = P.o_sizes,
+                 o_parent = P.o_parent, o_parent_leaf = P.o_parent_leaf, o_node_box = P.o_node_box, o_arrive = P.o_arrive, o_cref0 = P.o_cref0,
+                 o_cref1 = P.o_cref1, o_cbox0 = P.o_cbox0, o_cbox1 = P.o_cbox1, o_nn = P.o_nn, o_valid = P.o_valid, o_pos = P.o_pos, o_scan = P.o_scan,
+                 o_new_id = P.o_new_id, o_nodes2 = P.o_nodes2, o_uparent = P.o_uparent, o_moves = P.o_moves, o_lock = P.o_lock, o_optstat = P.o_optstat,
+                 o_ccost = P.o_ccost, o_cdec = P.o_cdec;
+    (void)o_cbounds;
+    uint* cbounds = P.cbounds();
+    const uint n_tri = n;
+    const bool optimise = ds.optimise_rounds > 0 && !ds.fast_build && n_tri > 2;
+    const bool dp_collapse = ds.collapse_by_cost && !ds.fast_build && n_tri > 2;
     if (n_tri > 0) {
         TriRecord* unsorted = reinterpret_cast<TriRecord*>(base + o_unsorted);
         unsigned long long *keys = reinterpret_cast<unsigned long long*>(base + o_keys), *keys_sorted = reinterpret_cast<unsigned long long*>(base + o_keys_sorted);
@@ -1032,12 +1048,10 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
         int *parent_internal = reinterpret_cast<int*>(base + o_parent), *parent_leaf = reinterpret_cast<int*>(base + o_parent_leaf);
         uint* arrive = reinterpret_cast<uint*>(base + o_arrive);
         BvhNode* nodes2 = reinterpret_cast<BvhNode*>(base + o_nodes2);   // binary nodes: only the collapse input
-        const uint tblocks = (n_tri + BT - 1) / BT;
-        hipLaunchKernelGGL(k_pretransform, dim3(tblocks < 1024u ? tblocks : 1024u), dim3(BT), 0, stream, sv, ds.tri_prefix, ds.non_opaque, ds.alpha_base, ds.alpha_tris, unsorted, cbounds);
         const uint blocks = (n + BT - 1) / BT;
         hipLaunchKernelGGL(k_morton, dim3(blocks), dim3(BT), 0, stream, n, unsorted, cbounds, keys, vals);
         HIPCHK(rocprim::radix_sort_pairs(base + o_sort, sort_bytes, keys, keys_sorted, vals, vals_sorted, n, 0, 64, stream));
-        hipLaunchKernelGGL(k_gather_leaves, dim3(blocks), dim3(BT), 0, stream, n, unsorted, vals_sorted, ds.tris, leaf_box);
+        hipLaunchKernelGGL(k_gather_leaves, dim3(blocks), dim3(BT), 0, stream, n, unsorted, vals_sorted, out_tris, leaf_box);
         const size_t n_all = (size_t)n + (n > 1 ? n - 1 : 0);
         if (n > 1) {
             const uint iblocks = (n - 1 + BT - 1) / BT;
@@ -1141,21 +1155,68 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
                     hipLaunchKernelGGL(k_collapse_cost, dim3(blocks), dim3(BT), 0, stream, t, arrive, reinterpret_cast<float*>(base + o_ccost), reinterpret_cast<uint8_t*>(base + o_cdec));
                     dec = reinterpret_cast<const uint8_t*>(base + o_cdec);
                 }
-                hipLaunchKernelGGL(k_collapse4, dim3(iblocks), dim3(BT), 0, stream, n - 1, children, node_box, leaf_box, new_id, dec, ds.nodes4);
+                hipLaunchKernelGGL(k_collapse4, dim3(iblocks), dim3(BT), 0, stream, n - 1, children, node_box, leaf_box, new_id, dec, out_nodes);
             }
         }
         HIPCHK(hipGetLastError());
-        if (getenv("TRHIP_PAIR_LEAVES") && atoi(getenv("TRHIP_PAIR_LEAVES")) != 0 && n > 2) {
+        if (experiments && getenv("TRHIP_PAIR_LEAVES") && atoi(getenv("TRHIP_PAIR_LEAVES")) != 0 && n > 2) {
 #if TR_PAIR_LEAVES
             if (int rc = pair_leaves_postpass(ds, stream, n - 1, n)) return rc;
 #else
             return set_error("TRHIP_PAIR_LEAVES needs a library built with -DTR_PAIR_LEAVES=1 (the traversal has to know the pair references)");
 #endif
         }
-        if (const char* e = getenv("TRHIP_TREELET")) {
+        if (const char* e = experiments ? getenv("TRHIP_TREELET") : nullptr) {
             if (n > 2 && atoi(e) > 0) if (int rc = reorder_into_treelets(ds, stream, n - 1, n, (uint)atoi(e), !getenv("TRHIP_TREELET_KEEP_TRIS"))) return rc;
         }
     }
+    return 0;
+}
+
+static int build_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);
+static int refit_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);
+
+int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
+    if (ds.accel_strategy != TRHIP_AS_ALL_MERGED) return build_two_level(ds, stream, info);
+    const uint n_scene = ds.tri_count;
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, stream));
+    ds.accel_built = false;
+    ds.levels_valid = false;   // a new tree: the refit level lists are rebuilt on demand
+    SceneView sv = ds.view();
+    sv.tri_count = n_scene;
+    // Temporaries come out of one scratch arena that survives the call, and the outputs keep their allocation while the
+    // triangle count does not change: a rebuild (dynamic scenes) performs no allocation at all.
+    // n_tri = triangles = leaves; n_cap = what everything is sized for
+    const uint n_tri = n_scene;
+    const uint n_cap = n_tri;
+    uint n = n_tri;
+    const size_t n1 = n_cap > 1 ? n_cap - 1 : 0;     // inner nodes the buffers hold
+    if (ds.two_level) ds.free_accel();                // the outputs of a two-level build
+    TreePlan P;
+    if (int rc = plan_tree(ds, stream, n_cap, P)) return rc;
+    uint* cbounds = P.cbounds();
+    {
+        const uint init[32] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(cbounds, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    }
+    if (ds.accel_capacity != n_cap) {   // outputs
+        ds.free_accel();
+        if (n_cap > 0) HIPCHK(hipMalloc(&ds.tris, (size_t)n_cap * sizeof(TriRecord)));
+        if (n1 > 0) {
+            // traversal addresses a node's planes with 32-bit byte offsets (node << 7 | plane)
+            if ((uint64_t)n1 * sizeof(Bvh4Node) > 0xFFFFFFFFull) return set_error("trhip_scene_build_accel: more than 2^25 nodes");
+            HIPCHK(hipMalloc(&ds.nodes4, n1 * sizeof(Bvh4Node)));
+        }
+        ds.accel_capacity = n_cap;
+    }
+    if (n_tri > 0) {
+        TriRecord* unsorted = P.unsorted();
+        const uint tblocks = (n_tri + BT - 1) / BT;
+        hipLaunchKernelGGL(k_pretransform, dim3(tblocks < 1024u ? tblocks : 1024u), dim3(BT), 0, stream, sv, ds.tri_prefix, ds.non_opaque, ds.alpha_base, ds.alpha_tris, unsorted, cbounds);
+    }
+    if (int rc = build_tree(ds, stream, P, n, ds.tris, ds.nodes4, true)) return rc;
     ds.leaf_count = n;
     ds.node_count = n > 1 ? n - 1 : 0;
     ds.accel_tri_count = n_tri;
@@ -1178,6 +1239,10 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
     uint hb[6];
     HIPCHK(hipMemcpy(hb, cbounds, sizeof(hb), hipMemcpyDeviceToHost));
     for (int k = 0; k < 3; ++k) { ds.bounds_lo[k] = float_unflip(hb[k]); ds.bounds_hi[k] = float_unflip(hb[3 + k]); }
+    ds.layout = {};
+    ds.layout.strategy = TRHIP_AS_ALL_MERGED; ds.layout.blas_count = 1; ds.layout.blas_updated = 1;
+    ds.layout.node_bytes = (uint64_t)ds.node_count * sizeof(Bvh4Node); ds.layout.record_bytes = (uint64_t)n * sizeof(TriRecord);
+    ds.layout.blas_ms = ms;
     if (info) {
         info->triangle_count = n_tri;
         info->leaf_count = n;
@@ -1187,6 +1252,535 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
         info->build_ms = ms;
         for (int k = 0; k < 3; ++k) { info->bounds_min[k] = float_unflip(hb[k]); info->bounds_max[k] = float_unflip(hb[3 + k]); }
     }
+    return 0;
+}
+
+// =====================================================================================================================
+// Two-level structure (trhip_scene_set_accel_strategy): one BLAS per group of instances, built by build_tree into
+// the shared node and record arrays behind the TLAS slots, and a TLAS built by the same pipeline over the instances' world boxes (a box
+// record is a TriRecord with v0 = lo, v1 = hi, v2 = lo: every stage takes a record's box as min / max of its three vertices).
+namespace {
+
+// records of one BLAS.  `list` = the instances whose triangles it holds (prefix sums of their triangle counts in `prefix`); world: the
+// merged static BLAS, records as k_pretransform writes them; else one instance of the shared span, object-space positions as uploaded.
+__global__ __launch_bounds__(BT) void k_group_records(SceneView sv, const uint* list, const uint* prefix, uint n_list, uint n, int world,
+                                                      const uint8_t* non_opaque, const uint* alpha_base, AlphaTri* alpha_tris, TriRecord* out) {
+    const uint gid = blockIdx.x * BT + threadIdx.x;
+    if (gid >= n) return;
+    uint slot, prim;
+    locate_triangle(prefix, n_list, gid, slot, prim);
+    const uint inst = list[slot];
+    const MeshSpan sp = sv.obj_spans[inst];
+    const uint* ix = sv.indices + sp.index_offset + 3u * prim;
+    const Vertex* vb = sv.obj_vertices + sp.vertex_offset;
+    f3 p0 = vb[ix[0]].pos, p1 = vb[ix[1]].pos, p2 = vb[ix[2]].pos;
+    TriRecord t;
+    if (world) {
+        const m4 model = sv.instances[inst].model;
+        p0 = transform_point(model, p0); p1 = transform_point(model, p1); p2 = transform_point(model, p2);
+        t.inst_flags = inst | (non_opaque[inst] ? 0x80000000u : 0u);
+        t.alpha = non_opaque[inst] ? alpha_word(sv.instances[inst].mat, alpha_base[inst] + prim, alpha_tris, vb[ix[0]].uv, vb[ix[1]].uv, vb[ix[2]].uv) : 0u;
+    } else {
+        t.inst_flags = inst;     // the instance the refit reads the span from; the traversal takes the words from the TLAS leaf
+        t.alpha = 0u;
+    }
+    t.prim = prim;
+    t.v0[0] = p0.x; t.v0[1] = p0.y; t.v0[2] = p0.z;
+    t.v1[0] = p1.x; t.v1[1] = p1.y; t.v1[2] = p1.z;
+    t.v2[0] = p2.x; t.v2[1] = p2.y; t.v2[2] = p2.z;
+    out[gid] = t;
+}
+
+// the centroid and box bounds k_pretransform accumulates, for records that are already written
+__global__ __launch_bounds__(BT) void k_record_bounds(uint n, const TriRecord* recs, uint* cbounds) {
+    float cmin[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
+    float cmax[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+    float smin[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
+    float smax[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+    for (uint i = blockIdx.x * BT + threadIdx.x; i < n; i += gridDim.x * BT) {
+        const TriRecord t = recs[i];
+        for (int k = 0; k < 3; ++k) {
+            const float lo = fminf(fminf(t.v0[k], t.v1[k]), t.v2[k]), hi = fmaxf(fmaxf(t.v0[k], t.v1[k]), t.v2[k]);
+            const float c = (lo + hi) * 0.5f;
+            cmin[k] = fminf(cmin[k], c); cmax[k] = fmaxf(cmax[k], c); smin[k] = fminf(smin[k], lo); smax[k] = fmaxf(smax[k], hi);
+        }
+    }
+    __shared__ float s_red[BT / 64][12];
+    for (int k = 0; k < 3; ++k) {
+        float mn = cmin[k], mx = cmax[k], sn = smin[k], sx = smax[k];
+        for (int off = 32; off > 0; off >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, off)); mx = fmaxf(mx, __shfl_xor(mx, off));
+            sn = fminf(sn, __shfl_xor(sn, off)); sx = fmaxf(sx, __shfl_xor(sx, off));
+        }
+        if ((threadIdx.x & 63) == 0) { float* w = s_red[threadIdx.x >> 6]; w[k] = mn; w[3 + k] = mx; w[6 + k] = sn; w[9 + k] = sx; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int k = (int)threadIdx.x;
+        float mn = s_red[0][k], mx = s_red[0][3 + k], sn = s_red[0][6 + k], sx = s_red[0][9 + k];
+        for (int w = 1; w < BT / 64; ++w) { mn = fminf(mn, s_red[w][k]); mx = fmaxf(mx, s_red[w][3 + k]); sn = fminf(sn, s_red[w][6 + k]); sx = fmaxf(sx, s_red[w][9 + k]); }
+        if (mn <= mx) {
+            atomicMin(&cbounds[k], float_flip(mn)); atomicMax(&cbounds[3 + k], float_flip(mx));
+            atomicMin(&cbounds[16 + k], float_flip(sn)); atomicMax(&cbounds[19 + k], float_flip(sx));
+        }
+    }
+}
+
+// the AlphaTri records of every non-opaque instance (in a shared BLAS the record words do not carry them)
+__global__ __launch_bounds__(BT) void k_alpha_records(SceneView sv, const uint* tri_prefix, const uint8_t* non_opaque, const uint* alpha_base, AlphaTri* alpha_tris) {
+    const uint gid = blockIdx.x * BT + threadIdx.x;
+    if (gid >= sv.tri_count) return;
+    uint inst, prim;
+    locate_triangle(tri_prefix, sv.instance_count, gid, inst, prim);
+    if (!non_opaque[inst]) return;
+    const MeshSpan sp = sv.obj_spans[inst];
+    const uint* ix = sv.indices + sp.index_offset + 3u * prim;
+    const Vertex* vb = sv.obj_vertices + sp.vertex_offset;
+    (void)alpha_word(sv.instances[inst].mat, alpha_base[inst] + prim, alpha_tris, vb[ix[0]].uv, vb[ix[1]].uv, vb[ix[2]].uv);
+}
+
+// ... of the triangles of the instances in `list` (prefix sums of their triangle counts in `prefix`): a refit's stale records only
+__global__ __launch_bounds__(BT) void k_alpha_list(SceneView sv, const uint* list, const uint* prefix, uint n_list, uint n, const uint* alpha_base,
+                                                   AlphaTri* alpha_tris) {
+    const uint gid = blockIdx.x * BT + threadIdx.x;
+    if (gid >= n) return;
+    uint slot, prim;
+    locate_triangle(prefix, n_list, gid, slot, prim);
+    const uint inst = list[slot];
+    const MeshSpan sp = sv.obj_spans[inst];
+    const uint* ix = sv.indices + sp.index_offset + 3u * prim;
+    const Vertex* vb = sv.obj_vertices + sp.vertex_offset;
+    (void)alpha_word(sv.instances[inst].mat, alpha_base[inst] + prim, alpha_tris, vb[ix[0]].uv, vb[ix[1]].uv, vb[ix[2]].uv);
+}
+
+// a BLAS built at node 0 / record 0 moved to its place in the shared arrays
+__global__ __launch_bounds__(BT) void k_rebase(Bvh4Node* nodes, uint count, int node_off, int tri_off) {
+    const uint i = blockIdx.x * BT + threadIdx.x;
+    if (i >= count) return;
+    for (int c = 0; c < 4; ++c) {
+        const int ch = nodes[i].child[c];
+        if (ch == 0x7FFFFFFF) continue;
+        nodes[i].child[c] = ch >= 0 ? ch + node_off : ~(~ch + tri_off);
+    }
+}
+
+// the box of each BLAS root reference (a node: the union of its child boxes; a record: its triangle)
+__global__ __launch_bounds__(BT) void k_root_boxes(const Bvh4Node* nodes, const TriRecord* tris, const int* roots, uint n, float* out) {
+    const uint i = blockIdx.x * BT + threadIdx.x;
+    if (i >= n) return;
+    float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()}, hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+    const int r = roots[i];
+    if (r >= 0) {
+        const Bvh4Node& nd = nodes[r];
+        for (int c = 0; c < 4; ++c) {
+            if (nd.child[c] == 0x7FFFFFFF) continue;
+            lo[0] = fminf(lo[0], nd.lox[c]); lo[1] = fminf(lo[1], nd.loy[c]); lo[2] = fminf(lo[2], nd.loz[c]);
+            hi[0] = fmaxf(hi[0], nd.hix[c]); hi[1] = fmaxf(hi[1], nd.hiy[c]); hi[2] = fmaxf(hi[2], nd.hiz[c]);
+        }
+    } else {
+        const TriRecord& t = tris[~r];
+        for (int k = 0; k < 3; ++k) { lo[k] = fminf(fminf(t.v0[k], t.v1[k]), t.v2[k]); hi[k] = fmaxf(fmaxf(t.v0[k], t.v1[k]), t.v2[k]); }
+    }
+    for (int k = 0; k < 3; ++k) { out[6 * i + k] = lo[k]; out[6 * i + 3 + k] = hi[k]; }
+}
+
+// instance records in TLAS leaf order: a sorted box record's `prim` is the leaf's place in the build input
+__global__ __launch_bounds__(BT) void k_tlas_leaves(uint n, const TriRecord* sorted, const TlasLeaf* src, TlasLeaf* out) {
+    const uint i = blockIdx.x * BT + threadIdx.x;
+    if (i < n) out[i] = src[sorted[i].prim];
+}
+
+// object-space records of a shared BLAS after skinning (k_retransform without the transform)
+__global__ __launch_bounds__(BT) void k_retransform_obj(SceneView sv, uint n, TriRecord* tris) {
+    const uint i = blockIdx.x * BT + threadIdx.x;
+    if (i >= n) return;
+    TriRecord t = tris[i];
+    const MeshSpan sp = sv.obj_spans[t.inst_flags & 0x7FFFFFFFu];
+    const uint* ix = sv.indices + sp.index_offset + 3u * t.prim;
+    const Vertex* vb = sv.obj_vertices + sp.vertex_offset;
+    const f3 p0 = vb[ix[0]].pos, p1 = vb[ix[1]].pos, p2 = vb[ix[2]].pos;
+    t.v0[0] = p0.x; t.v0[1] = p0.y; t.v0[2] = p0.z;
+    t.v1[0] = p1.x; t.v1[1] = p1.y; t.v1[2] = p1.z;
+    t.v2[0] = p2.x; t.v2[1] = p2.y; t.v2[2] = p2.z;
+    tris[i] = t;
+}
+
+const uint kCboundsInit[32] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+bool is_identity(const m4& m) {
+    const float* a = &m.c[0].x;
+    for (int k = 0; k < 16; ++k) if (a[k] != ((k % 5 == 0) ? 1.0f : 0.0f)) return false;
+    return true;
+}
+
+// world -> object rows of an affine model matrix (column-major m4; the bottom row is taken as 0 0 0 1), inverted in double.  An exact
+// identity gives an exact identity, and TR_TLAS_IDENTITY then skips the transform altogether.
+void inverse_rows(const m4& m, float xf[12]) {
+    double a[3][3], t[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) a[r][c] = (double)(&m.c[c].x)[r];
+        t[r] = (double)(&m.c[3].x)[r];
+    }
+    double inv[3][3];
+    inv[0][0] = a[1][1] * a[2][2] - a[1][2] * a[2][1]; inv[0][1] = a[0][2] * a[2][1] - a[0][1] * a[2][2]; inv[0][2] = a[0][1] * a[1][2] - a[0][2] * a[1][1];
+    inv[1][0] = a[1][2] * a[2][0] - a[1][0] * a[2][2]; inv[1][1] = a[0][0] * a[2][2] - a[0][2] * a[2][0]; inv[1][2] = a[0][2] * a[1][0] - a[0][0] * a[1][2];
+    inv[2][0] = a[1][0] * a[2][1] - a[1][1] * a[2][0]; inv[2][1] = a[0][1] * a[2][0] - a[0][0] * a[2][1]; inv[2][2] = a[0][0] * a[1][1] - a[0][1] * a[1][0];
+    const double det = a[0][0] * inv[0][0] + a[0][1] * inv[1][0] + a[0][2] * inv[2][0];
+    for (int r = 0; r < 3; ++r) {
+        double o = 0.0;
+        for (int c = 0; c < 3; ++c) { const double v = inv[r][c] / det; xf[4 * r + c] = (float)v; o -= v * t[c]; }
+        xf[4 * r + 3] = (float)o;
+    }
+}
+
+int ensure_aux(DeviceScene& ds, size_t bytes) {
+    if (bytes <= ds.tl_aux_bytes) return 0;
+    if (ds.tl_aux) (void)hipFree(ds.tl_aux);
+    ds.tl_aux = nullptr; ds.tl_aux_bytes = 0;
+    HIPCHK(hipMalloc(&ds.tl_aux, bytes));
+    ds.tl_aux_bytes = bytes;
+    return 0;
+}
+
+// The TLAS over the current instance transforms: BLAS root boxes -> world boxes (on the host, in double, rounded outwards) -> build_tree
+// into node slots 0 .. L - 2 -> instance records in leaf order.
+int build_tlas(DeviceScene& ds, hipStream_t stream, const TreePlan& P) {
+    const uint nb = (uint)ds.blases.size(), L = ds.tlas_leaf_count;
+    const size_t o_boxes = ((size_t)nb * 4 + 255) & ~(size_t)255, o_sorted = o_boxes + (((size_t)nb * 24 + 255) & ~(size_t)255);
+    if (int rc = ensure_aux(ds, o_sorted + (size_t)L * sizeof(TriRecord))) return rc;
+    char* aux = static_cast<char*>(ds.tl_aux);
+    std::vector<int> roots(nb);
+    for (uint b = 0; b < nb; ++b) roots[b] = ds.blases[b].root;
+    std::vector<float> boxes((size_t)nb * 6);
+    if (nb) {
+        HIPCHK(hipMemcpyAsync(aux, roots.data(), (size_t)nb * 4, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_root_boxes, dim3((nb + BT - 1) / BT), dim3(BT), 0, stream, ds.nodes4, ds.tris, reinterpret_cast<const int*>(aux), nb,
+                           reinterpret_cast<float*>(aux + o_boxes));
+        HIPCHK(hipMemcpyAsync(boxes.data(), aux + o_boxes, (size_t)nb * 24, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    std::vector<TlasLeaf> leaves(L);
+    std::vector<TriRecord> recs(L);
+    for (uint j = 0; j < L; ++j) {
+        const uint inst = ds.tlas_src[j];
+        const int b = inst == 0xFFFFFFFFu ? 0 : ds.inst_blas[inst];
+        const float* bx = &boxes[(size_t)b * 6];
+        TlasLeaf& lf = leaves[j];
+        memset(&lf, 0, sizeof(lf));
+        lf.blas_root = ds.blases[b].root;
+        float lo[3] = {bx[0], bx[1], bx[2]}, hi[3] = {bx[3], bx[4], bx[5]};
+        const bool ident = inst == 0xFFFFFFFFu || is_identity(ds.host_instances[inst].model);
+        if (ident) {
+            lf.xf[0] = lf.xf[5] = lf.xf[10] = 1.0f;
+            lf.flags = TR_TLAS_IDENTITY;
+        } else {
+            const m4& m = ds.host_instances[inst].model;
+            inverse_rows(m, lf.xf);
+            double wlo[3] = {1e300, 1e300, 1e300}, whi[3] = {-1e300, -1e300, -1e300};
+            for (int c = 0; c < 8; ++c) {
+                const double p[3] = {(c & 1) ? bx[3] : bx[0], (c & 2) ? bx[4] : bx[1], (c & 4) ? bx[5] : bx[2]};
+                for (int r = 0; r < 3; ++r) {
+                    double w = (double)(&m.c[3].x)[r];
+                    for (int k = 0; k < 3; ++k) w += (double)(&m.c[k].x)[r] * p[k];
+                    wlo[r] = std::min(wlo[r], w); whi[r] = std::max(whi[r], w);
+                }
+            }
+            // outwards by a relative 2^-16 of the box's size and place: covers the rounding of the object-space ray (a few ulp of the
+            // coordinates involved), so that no hit of the BLAS lies outside the box the world ray is tested against
+            for (int r = 0; r < 3; ++r) {
+                const double pad = (std::fabs(wlo[r]) + std::fabs(whi[r]) + (whi[r] - wlo[r])) * (1.0 / 65536.0);
+                lo[r] = std::nextafter((float)(wlo[r] - pad), -INFINITY); hi[r] = std::nextafter((float)(whi[r] + pad), INFINITY);
+            }
+        }
+        if (inst == 0xFFFFFFFFu) { lf.inst_word = TR_INST_FROM_RECORD; lf.alpha_base = 0; }
+        else {
+            lf.inst_word = inst | (ds.host_non_opaque[inst] ? 0x80000000u : 0u);
+            lf.alpha_base = ds.host_non_opaque[inst] ? ds.host_alpha_base[inst] : 0u;
+        }
+        TriRecord& t = recs[j];
+        memset(&t, 0, sizeof(t));
+        for (int k = 0; k < 3; ++k) { t.v0[k] = lo[k]; t.v1[k] = hi[k]; t.v2[k] = lo[k]; }
+        t.prim = j;
+        for (int k = 0; k < 3; ++k) {    // trhip_accel_info bounds of a two-level structure: the union of the instances' world boxes
+            ds.bounds_lo[k] = j == 0 ? lo[k] : std::min(ds.bounds_lo[k], lo[k]);
+            ds.bounds_hi[k] = j == 0 ? hi[k] : std::max(ds.bounds_hi[k], hi[k]);
+        }
+    }
+    if (L == 0) { for (int k = 0; k < 3; ++k) ds.bounds_lo[k] = ds.bounds_hi[k] = 0.0f; return 0; }
+    if (L == 1) {   // the root is a node of one child, so that every two-level traversal starts at node 0
+        Bvh4Node root;
+        for (int c = 0; c < 4; ++c) {
+            root.lox[c] = root.loy[c] = root.loz[c] = INFINITY; root.hix[c] = root.hiy[c] = root.hiz[c] = -INFINITY;
+            root.child[c] = 0x7FFFFFFF; root.pad[c] = 0;
+        }
+        root.lox[0] = recs[0].v0[0]; root.loy[0] = recs[0].v0[1]; root.loz[0] = recs[0].v0[2];
+        root.hix[0] = recs[0].v1[0]; root.hiy[0] = recs[0].v1[1]; root.hiz[0] = recs[0].v1[2];
+        root.child[0] = ~0;
+        HIPCHK(hipMemcpyAsync(ds.nodes4, &root, sizeof(root), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(ds.tlas, leaves.data(), sizeof(TlasLeaf), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));      // `root` and `leaves` live on this stack
+        return 0;
+    }
+    HIPCHK(hipMemcpyAsync(ds.tlas_src_leaves, leaves.data(), (size_t)L * sizeof(TlasLeaf), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(P.unsorted(), recs.data(), (size_t)L * sizeof(TriRecord), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(P.cbounds(), kCboundsInit, sizeof(kCboundsInit), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));      // `leaves` and `recs` live in this function
+    const uint blocks = (L + BT - 1) / BT;
+    hipLaunchKernelGGL(k_record_bounds, dim3(blocks < 1024u ? blocks : 1024u), dim3(BT), 0, stream, L, P.unsorted(), P.cbounds());
+    TriRecord* sorted = reinterpret_cast<TriRecord*>(aux + o_sorted);
+    if (int rc = build_tree(ds, stream, P, L, sorted, ds.nodes4, false)) return rc;
+    hipLaunchKernelGGL(k_tlas_leaves, dim3(blocks), dim3(BT), 0, stream, L, sorted, ds.tlas_src_leaves, ds.tlas);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int extract_tri_lights(DeviceScene& ds, hipStream_t stream) {
+    ds.tri_light_count = 0;
+    if (ds.gather_emissive_triangles && ds.host_tri_light_count > 0) {
+        if (!ds.tri_lights) HIPCHK(hipMalloc(&ds.tri_lights, (size_t)ds.host_tri_light_count * sizeof(TriLight)));
+        HIPCHK(hipMemsetAsync(ds.tri_lights, 0, (size_t)ds.host_tri_light_count * sizeof(TriLight), stream));
+        ds.tri_light_count = ds.host_tri_light_count;
+        SceneView sv2 = ds.view();
+        hipLaunchKernelGGL(k_extract_tri_lights, dim3((ds.tri_count + BT - 1) / BT), dim3(BT), 0, stream, sv2, ds.tri_prefix, ds.tri_lights);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+void fill_info(const DeviceScene& ds, trhip_accel_info* info, float ms) {
+    if (!info) return;
+    memset(info, 0, sizeof(*info));
+    info->triangle_count = ds.tri_count; info->leaf_count = ds.leaf_count; info->node_count = ds.node_count; info->node_bytes = 112u;
+    info->tri_light_count = ds.tri_light_count; info->build_ms = ms;
+    for (int k = 0; k < 3; ++k) { info->bounds_min[k] = ds.bounds_lo[k]; info->bounds_max[k] = ds.bounds_hi[k]; }
+}
+
+struct Timer {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Timer() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+}  // namespace
+
+void mark_skinned(DeviceScene& ds, uint instance) {
+    if (!ds.two_level || instance >= ds.inst_blas.size() || ds.inst_blas[instance] < 0) return;
+    if (ds.host_non_opaque[instance]) ds.alpha_dirty[instance] = 1;
+    const int b = ds.inst_blas[instance];
+    if (ds.blases[b].world) ds.static_dirty = true;
+    else ds.blas_dirty[b] = 1;
+}
+
+static int build_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
+    Timer T;
+    for (hipEvent_t& x : T.e) HIPCHK(hipEventCreate(&x));
+    HIPCHK(hipEventRecord(T.e[0], stream));
+    ds.accel_built = false;
+    ds.levels_valid = false;
+    if (!ds.two_level) ds.free_accel();      // the outputs of an all-merged build
+    const uint NI = ds.instance_count;
+    const bool merge_static = ds.accel_strategy == TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH;
+    // grouping: a span key per instance; an instance is dynamic when marked, skinned, or on the span of a skinned instance
+    auto key = [&](uint i) { const MeshSpan& s = ds.host_spans[i]; return std::make_tuple(s.vertex_offset, s.vertex_count, s.index_offset, s.triangle_count); };
+    std::vector<std::tuple<uint, uint, uint, uint>> skinned_keys;
+    for (uint i = 0; i < NI && i < ds.skin_slots.size(); ++i) if (ds.skin_slots[i].source) skinned_keys.push_back(key(i));
+    std::vector<uint8_t> dyn(NI, 0);
+    for (uint i = 0; i < NI; ++i)
+        dyn[i] = (i < ds.dynamic_marks.size() && ds.dynamic_marks[i]) || std::find(skinned_keys.begin(), skinned_keys.end(), key(i)) != skinned_keys.end();
+    std::vector<DeviceScene::Blas> blases;
+    std::vector<std::vector<uint>> lists;
+    std::vector<int> inst_blas(NI, -1);
+    std::vector<uint> tlas_src;
+    std::vector<uint> static_list;
+    for (uint i = 0; i < NI; ++i) if (merge_static && !dyn[i] && ds.host_spans[i].triangle_count > 0) static_list.push_back(i);
+    if (!static_list.empty()) {
+        DeviceScene::Blas b = {};
+        b.world = true; b.rep = static_list[0];
+        for (uint i : static_list) { b.tri_count += ds.host_spans[i].triangle_count; inst_blas[i] = 0; }
+        blases.push_back(b); lists.push_back(static_list); tlas_src.push_back(0xFFFFFFFFu);
+    }
+    std::map<std::tuple<uint, uint, uint, uint>, int> by_span;
+    for (uint i = 0; i < NI; ++i) {
+        if (ds.host_spans[i].triangle_count == 0 || inst_blas[i] >= 0) continue;
+        auto it = by_span.find(key(i));
+        if (it == by_span.end()) {
+            DeviceScene::Blas b = {};
+            b.world = false; b.rep = i; b.tri_count = ds.host_spans[i].triangle_count;
+            it = by_span.emplace(key(i), (int)blases.size()).first;
+            blases.push_back(b); lists.push_back({i});
+        }
+        inst_blas[i] = it->second;
+        tlas_src.push_back(i);
+    }
+    const uint L = (uint)tlas_src.size();
+    const uint tlas_slots = L > 1 ? L - 1 : L;     // a TLAS of one leaf gets a root node of its own
+    size_t node_slots = tlas_slots, records = 0;
+    uint n_cap = L;
+    for (DeviceScene::Blas& b : blases) {
+        b.node_off = (uint)node_slots; b.tri_off = (uint)records;
+        b.node_slots = b.tri_count > 1 ? b.tri_count - 1 : 0;
+        b.root = b.node_slots ? (int)b.node_off : ~(int)b.tri_off;
+        node_slots += b.node_slots; records += b.tri_count;
+        n_cap = std::max(n_cap, b.tri_count);
+    }
+    if (node_slots * sizeof(Bvh4Node) > 0xFFFFFFFFull) return set_error("trhip_scene_build_accel: more than 2^25 nodes");
+    if (records > 0x7FFFFFF0ull) return set_error("trhip_scene_build_accel: too many triangle records");
+    // outputs (kept while their sizes do not change: a rebuild allocates nothing)
+    if (ds.node_capacity != node_slots || ds.tri_capacity != records || ds.tlas_capacity != L) {
+        ds.free_accel();
+        if (records) HIPCHK(hipMalloc(&ds.tris, records * sizeof(TriRecord)));
+        // node slots, then the TLAS leaf records (SceneView finds them behind node_count: common.h tlas_leaves)
+        const size_t leaf_bytes = (((size_t)L * sizeof(TlasLeaf) + sizeof(Bvh4Node) - 1) / sizeof(Bvh4Node)) * sizeof(Bvh4Node);
+        if (node_slots) HIPCHK(hipMalloc(&ds.nodes4, node_slots * sizeof(Bvh4Node) + leaf_bytes));
+        ds.tlas = reinterpret_cast<TlasLeaf*>(ds.nodes4 + node_slots);
+        if (L) HIPCHK(hipMalloc(&ds.tlas_src_leaves, (size_t)L * sizeof(TlasLeaf)));
+        ds.node_capacity = node_slots; ds.tri_capacity = records; ds.tlas_capacity = L;
+    }
+    ds.blases = blases; ds.inst_blas = inst_blas; ds.tlas_src = tlas_src; ds.tlas_leaf_count = L; ds.tlas_node_slots = tlas_slots;
+    ds.blas_dirty.assign(blases.size(), 0); ds.static_dirty = false; ds.alpha_dirty.assign(NI, 0);
+    ds.two_level = true;
+    TreePlan P;
+    if (int rc = plan_tree(ds, stream, n_cap, P)) return rc;
+    // the instance lists of the BLASes (prefix sums of their triangle counts behind them) in the aux buffer
+    size_t list_words = 0;
+    for (auto& l : lists) list_words += 2 * l.size() + 1;
+    if (int rc = ensure_aux(ds, list_words * 4)) return rc;
+    std::vector<uint> words;
+    words.reserve(list_words);
+    std::vector<size_t> list_at;
+    for (auto& l : lists) {
+        list_at.push_back(words.size());
+        words.insert(words.end(), l.begin(), l.end());
+        uint acc = 0;
+        words.push_back(0);
+        for (uint i : l) { acc += ds.host_spans[i].triangle_count; words.push_back(acc); }
+    }
+    uint* aux = static_cast<uint*>(ds.tl_aux);
+    if (!words.empty()) HIPCHK(hipMemcpyAsync(aux, words.data(), words.size() * 4, hipMemcpyHostToDevice, stream));
+    SceneView sv = ds.view();
+    sv.tri_count = ds.tri_count;
+    for (size_t g = 0; g < blases.size(); ++g) {
+        const DeviceScene::Blas& b = blases[g];
+        const uint nl = (uint)lists[g].size();
+        HIPCHK(hipMemcpyAsync(P.cbounds(), kCboundsInit, sizeof(kCboundsInit), hipMemcpyHostToDevice, stream));
+        const uint blocks = (b.tri_count + BT - 1) / BT;
+        hipLaunchKernelGGL(k_group_records, dim3(blocks), dim3(BT), 0, stream, sv, aux + list_at[g], aux + list_at[g] + nl, nl, b.tri_count, b.world ? 1 : 0,
+                           ds.non_opaque, ds.alpha_base, ds.alpha_tris, P.unsorted());
+        hipLaunchKernelGGL(k_record_bounds, dim3(blocks < 1024u ? blocks : 1024u), dim3(BT), 0, stream, b.tri_count, P.unsorted(), P.cbounds());
+        if (int rc = build_tree(ds, stream, P, b.tri_count, ds.tris + b.tri_off, ds.nodes4 + b.node_off, false)) return rc;
+        if (b.node_slots) hipLaunchKernelGGL(k_rebase, dim3((b.node_slots + BT - 1) / BT), dim3(BT), 0, stream, ds.nodes4 + b.node_off, b.node_slots, (int)b.node_off, (int)b.tri_off);
+        HIPCHK(hipGetLastError());
+    }
+    if (ds.alpha_count && ds.tri_count)
+        hipLaunchKernelGGL(k_alpha_records, dim3((ds.tri_count + BT - 1) / BT), dim3(BT), 0, stream, sv, ds.tri_prefix, ds.non_opaque, ds.alpha_base, ds.alpha_tris);
+    HIPCHK(hipEventRecord(T.e[1], stream));
+    if (int rc = build_tlas(ds, stream, P)) return rc;
+    ds.leaf_count = (uint)records;
+    ds.node_count = (uint)node_slots;
+    ds.accel_tri_count = ds.tri_count;
+    ds.accel_built = true;
+    if (int rc = extract_tri_lights(ds, stream)) return rc;
+    HIPCHK(hipEventRecord(T.e[2], stream));
+    HIPCHK(hipEventSynchronize(T.e[2]));
+    float ms_blas = 0, ms_tlas = 0;
+    HIPCHK(hipEventElapsedTime(&ms_blas, T.e[0], T.e[1]));
+    HIPCHK(hipEventElapsedTime(&ms_tlas, T.e[1], T.e[2]));
+    ds.layout = {};
+    ds.layout.strategy = ds.accel_strategy; ds.layout.blas_count = (uint)blases.size(); ds.layout.tlas_leaf_count = L;
+    ds.layout.blas_updated = (uint)blases.size();
+    ds.layout.node_bytes = (uint64_t)node_slots * sizeof(Bvh4Node);
+    ds.layout.record_bytes = (uint64_t)records * sizeof(TriRecord) + (uint64_t)L * sizeof(TlasLeaf);
+    ds.layout.blas_ms = ms_blas; ds.layout.tlas_ms = ms_tlas;
+    fill_info(ds, info, ms_blas + ms_tlas);
+    return 0;
+}
+
+// Level lists of the live nodes under `roots` (breadth-first), as refit_accel builds them for the whole tree
+static int node_levels(DeviceScene& ds, hipStream_t stream, const std::vector<uint>& roots, std::vector<uint>& offsets) {
+    offsets.assign(1, 0u);
+    if (roots.empty()) return 0;
+    const uint n1 = ds.node_count;
+    if (!ds.level_nodes) HIPCHK(hipMalloc(&ds.level_nodes, (size_t)n1 * 4));
+    if (!ds.node_bounds) HIPCHK(hipMalloc(&ds.node_bounds, (size_t)n1 * 24));
+    uint* counter = reinterpret_cast<uint*>(ds.node_bounds);      // the bounds are written afterwards, level by level
+    HIPCHK(hipMemcpyAsync(ds.level_nodes, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, stream));
+    uint begin = 0, count = (uint)roots.size();
+    while (count > 0) {
+        offsets.push_back(begin + count);
+        if (begin + count >= n1) break;
+        HIPCHK(hipMemsetAsync(counter, 0, 4, stream));
+        hipLaunchKernelGGL(k_expand_level, dim3((count + BT - 1) / BT), dim3(BT), 0, stream, count, ds.level_nodes + begin, ds.nodes4, ds.level_nodes + begin + count, counter);
+        uint next = 0;
+        HIPCHK(hipMemcpyAsync(&next, counter, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        begin += count; count = next;
+        if (offsets.size() > 4096) return set_error("trhip_scene_refit_accel: hierarchy too deep");
+    }
+    return 0;
+}
+
+static int refit_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
+    Timer T;
+    for (hipEvent_t& x : T.e) HIPCHK(hipEventCreate(&x));
+    HIPCHK(hipEventRecord(T.e[0], stream));
+    SceneView sv = ds.view();
+    sv.tri_count = ds.tri_count;
+    std::vector<uint> roots;
+    uint updated = 0;
+    for (size_t g = 0; g < ds.blases.size(); ++g) {
+        const DeviceScene::Blas& b = ds.blases[g];
+        if (!(b.world ? ds.static_dirty : ds.blas_dirty[g] != 0)) continue;
+        updated++;
+        const uint blocks = (b.tri_count + BT - 1) / BT;
+        if (b.world) hipLaunchKernelGGL(k_retransform, dim3(blocks), dim3(BT), 0, stream, sv, b.tri_count, ds.tris + b.tri_off, ds.alpha_base, ds.alpha_tris);
+        else hipLaunchKernelGGL(k_retransform_obj, dim3(blocks), dim3(BT), 0, stream, sv, b.tri_count, ds.tris + b.tri_off);
+        if (b.root >= 0) roots.push_back((uint)b.root);
+    }
+    if (!roots.empty()) {
+        std::vector<uint> offsets;
+        if (int rc = node_levels(ds, stream, roots, offsets)) return rc;
+        for (size_t l = offsets.size(); l-- > 1;) {
+            const uint lo = offsets[l - 1], cnt = offsets[l] - lo;
+            if (cnt) hipLaunchKernelGGL(k_refit_level, dim3((cnt + BT - 1) / BT), dim3(BT), 0, stream, cnt, ds.level_nodes + lo, ds.nodes4, ds.tris, ds.node_bounds);
+        }
+    }
+    {   // the any-hit records of the non-opaque instances whose material changed or whose mesh was skinned (a rigid move touches none)
+        std::vector<uint> list, prefix(1, 0u);
+        for (uint i = 0; i < ds.alpha_dirty.size(); ++i)
+            if (ds.alpha_dirty[i] && ds.host_spans[i].triangle_count) { list.push_back(i); prefix.push_back(prefix.back() + ds.host_spans[i].triangle_count); }
+        if (!list.empty()) {
+            const size_t words = list.size() + prefix.size();
+            if (words > ds.alpha_list_words) {
+                if (ds.alpha_list) (void)hipFree(ds.alpha_list);
+                ds.alpha_list = nullptr; ds.alpha_list_words = 0;
+                HIPCHK(hipMalloc(&ds.alpha_list, words * 4));
+                ds.alpha_list_words = words;
+            }
+            list.insert(list.end(), prefix.begin(), prefix.end());
+            HIPCHK(hipMemcpyAsync(ds.alpha_list, list.data(), words * 4, hipMemcpyHostToDevice, stream));
+            const uint n_list = (uint)(words - 1) / 2, n = prefix.back();
+            hipLaunchKernelGGL(k_alpha_list, dim3((n + BT - 1) / BT), dim3(BT), 0, stream, sv, ds.alpha_list, ds.alpha_list + n_list, n_list, n, ds.alpha_base,
+                               ds.alpha_tris);
+            HIPCHK(hipStreamSynchronize(stream));   // `list` lives in this block
+        }
+        std::fill(ds.alpha_dirty.begin(), ds.alpha_dirty.end(), 0);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(T.e[1], stream));
+    uint n_cap = ds.tlas_leaf_count;
+    TreePlan P;
+    if (int rc = plan_tree(ds, stream, n_cap, P)) return rc;
+    if (int rc = build_tlas(ds, stream, P)) return rc;
+    ds.accel_built = true;
+    if (int rc = extract_tri_lights(ds, stream)) return rc;
+    HIPCHK(hipEventRecord(T.e[2], stream));
+    HIPCHK(hipEventSynchronize(T.e[2]));
+    float ms_blas = 0, ms_tlas = 0;
+    HIPCHK(hipEventElapsedTime(&ms_blas, T.e[0], T.e[1]));
+    HIPCHK(hipEventElapsedTime(&ms_tlas, T.e[1], T.e[2]));
+    std::fill(ds.blas_dirty.begin(), ds.blas_dirty.end(), 0);
+    ds.static_dirty = false;
+    ds.layout.blas_updated = updated; ds.layout.blas_ms = ms_blas; ds.layout.tlas_ms = ms_tlas;
+    fill_info(ds, info, ms_blas + ms_tlas);
     return 0;
 }
 

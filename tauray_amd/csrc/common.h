@@ -196,6 +196,23 @@ static_assert(sizeof(AlphaTri) == 32, "alpha record layout");
 
 struct HitRecord { int instance_id, primitive_id; float u, v, t; };
 
+// Two-level structure (trhip_scene_set_accel_strategy != TRHIP_AS_ALL_MERGED).  `nodes4` holds the TLAS first
+// (root = node 0, also for a single leaf), then every BLAS, then the TLAS leaf records (tlas_leaves); `tris` holds the records of every
+// BLAS.  A TLAS leaf ~j names instance record j: the ray enters the BLAS at `blas_root` in the instance's object space.  In a BLAS shared by instances of one mesh
+// the records are object-space and their words other than the vertices and `prim` mean nothing: instance id, non-opaque bit and any-hit
+// record come from here.  The merged BLAS of the static instances (TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH) keeps world-space records
+// with their own words under an identity leaf (inst_word = TR_INST_FROM_RECORD).
+#define TR_INST_FROM_RECORD 0xFFFFFFFFu
+#define TR_TLAS_IDENTITY 1u
+struct alignas(64) TlasLeaf {
+    float xf[12];       // world -> object, three rows of (m0 m1 m2 | m3): object = row . (p, 1), direction = row . (d, 0)
+    int blas_root;      // >= 0 node, < 0 ~record
+    uint inst_word;     // instance id | bit 31 non-opaque, or TR_INST_FROM_RECORD
+    uint alpha_base;    // first AlphaTri record of the instance (non-opaque instances): the any-hit record is alpha_base + primitive
+    uint flags;         // TR_TLAS_IDENTITY: exact identity model matrix, the world ray is used as it is
+};
+static_assert(sizeof(TlasLeaf) == 64, "TLAS leaf layout");
+
 // Everything a kernel needs to see the scene (passed by value).
 struct SceneView {
     const Instance* instances;
@@ -225,5 +242,7 @@ struct SceneView {
     uint tri_count, node_count;
     uint wide_textures;          // some texture of the scene is TEXTURE_FORMAT_RGBA16
 };
+// The TLAS leaf records of a two-level structure: behind the node_count node slots in the same allocation (SceneView stays as it is)
+TR_HD const TlasLeaf* tlas_leaves(const SceneView& sv) { return reinterpret_cast<const TlasLeaf*>(sv.nodes4 + sv.node_count); }
 
 }  // namespace tr

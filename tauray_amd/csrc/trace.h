@@ -348,8 +348,15 @@ TR_DEV bool shadow_descend(const Hit4& h, LaneStack& stk, int* spill, int& node)
 // Closest hit over triangles (+ sphere lights), one ray per lane.  ALPHA_MODE 0: stochastic alpha keyed by `seed`
 // (shader/rt_common.rahit:15-24); 1: fixed cutoff 1e-4 (shader/rt_feature.rahit:17).
 template <int ALPHA_MODE, bool COUNT>
+TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
+                              int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow);
+template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
 TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
                            int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
+    if constexpr (TWO_LEVEL) {
+        trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, include_lights, seed, lds_stack, hit, st, overflow);
+        return;
+    }
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
     float best_t = tmax;
     bool found = false;
@@ -441,7 +448,10 @@ TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, floa
 // shadow_ray (shader/path_tracer.glsl:35-52) + rt_common_shadow.rahit/.rchit: product of (1 - alpha)
 // over non-opaque hits, 0 on the first opaque hit; lights are excluded (mask 0xFD).
 template <bool COUNT>
+TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow);
+template <bool COUNT, bool TWO_LEVEL = false>
 TR_DEV float trace_shadow4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow) {
+    if constexpr (TWO_LEVEL) return trace_shadow4_2l<COUNT>(sv, org, dir, tmin, tmax, lds_stack, st, overflow);
     float visibility = 1.0f;
     if (sv.tri_count == 0 || !ray_is_finite(org, dir)) return visibility;
     RayPre r = make_ray(org, dir);
@@ -483,6 +493,186 @@ TR_DEV float trace_shadow4(const SceneView& sv, f3 org, f3 dir, float tmin, floa
         }
         if (stk.sp == 0) break;
         node = stk.pop(spill);
+    }
+    overflow += stk.overflow ? 1 : 0;
+    return visibility;
+}
+
+// =====================================================================================================================
+// Two-level traversal: the instantiations with TWO_LEVEL = true.  The loop is the per-lane loop above; a TLAS
+// leaf is a node-phase step that moves the ray into the instance's object space and descends into its BLAS, with a sentinel on the stack
+// below the BLAS entries that brings the world ray back when it is popped.  The object-space ray is M^-1 (o, 1) and M^-1 (d, 0), not
+// renormalised: a point at distance t along it is the image of the world point at t, so t, the culling bound best_t and the candidate
+// order (t, instance, primitive) keep their meaning across instances.
+static_assert(!TR_PAIR_LEAVES && !TR_TRI_STRIDE64, "the two-level traversal supports neither TR_PAIR_LEAVES nor TR_TRI_STRIDE64");
+#define TR_BLAS_SENTINEL 0x7FFFFFFF   // the reference of an empty child slot, which no node phase ever pushes
+
+struct InstanceFrame { uint inst_word, alpha_base; };
+
+// The ray of TLAS leaf `leaf` in its BLAS: the world ray for an identity leaf, else M^-1 applied in a fixed order.
+TR_DEV int enter_instance(const SceneView& sv, int leaf, f3 org, f3 dir, const RayPre& rw, RayPre& r, InstanceFrame& fr) {
+    const TlasLeaf* L = tlas_leaves(sv) + leaf;
+    const f4* q = reinterpret_cast<const f4*>(L);
+    const f4 a = q[0], b = q[1], c = q[2];
+    const int4 w = *reinterpret_cast<const int4*>(q + 3);
+    fr.inst_word = (uint)w.y; fr.alpha_base = (uint)w.z;
+    if ((uint)w.w & TR_TLAS_IDENTITY) r = rw;
+    else {
+        const f3 o = F3(a.x * org.x + a.y * org.y + a.z * org.z + a.w, b.x * org.x + b.y * org.y + b.z * org.z + b.w,
+                        c.x * org.x + c.y * org.y + c.z * org.z + c.w);
+        const f3 d = F3(a.x * dir.x + a.y * dir.y + a.z * dir.z, b.x * dir.x + b.y * dir.y + b.z * dir.z, c.x * dir.x + c.y * dir.y + c.z * dir.z);
+        r = make_ray(o, d);
+    }
+    return w.x;
+}
+// the words of a BLAS record as the instance the ray is in sees them
+TR_DEV void instance_words(const InstanceFrame& fr, TriHit& tr) {
+    if (fr.inst_word == TR_INST_FROM_RECORD) return;
+    tr.inst_flags = fr.inst_word;
+    tr.alpha = 0x80000000u | (fr.alpha_base + tr.prim);
+}
+
+template <int ALPHA_MODE, bool COUNT>
+TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
+                              int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
+    hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
+    float best_t = tmax;
+    bool found = false;
+    uint best_inst = 0xFFFFFFFFu, best_prim = 0xFFFFFFFFu;
+    const RayPre rw = make_ray(org, dir);
+    RayPre r = rw;
+    const bool finite_ray = ray_is_finite(org, dir);
+    if (sv.tri_count > 0 && finite_ray) {
+        LaneStack stk;
+        int spill[TR_SPILL_STACK];
+        stk.init(lds_stack);
+        int node = 0;
+        bool in_blas = false;
+        InstanceFrame fr = {0u, 0u};
+        while (true) {
+            const bool at_tri = node < 0 && in_blas;
+#if TR_VOTE > 0
+            const int n_leaf = __popcll(__ballot(at_tri)), n_all = __popcll(__ballot(true));
+            const bool leaf_phase = n_leaf >= TR_VOTE || n_leaf == n_all;
+            if (at_tri != leaf_phase) continue;
+#endif
+            if (!at_tri) {
+                if (node >= 0) {
+                    Hit4 h;
+                    box4_intersect(r, sv.nodes4, node, tmin, best_t, h);
+                    if (COUNT) st.nodes++;
+                    TR_CE4(0, 1) TR_CE4(2, 3) TR_CE4(0, 2) TR_CE4(1, 3) TR_CE4(1, 2)
+                    if (h.t[0] < __builtin_huge_valf()) {
+                        const int m = (int)(h.t[1] < __builtin_huge_valf()) + (int)(h.t[2] < __builtin_huge_valf()) + (int)(h.t[3] < __builtin_huge_valf());
+                        stk.push_sorted(spill, m, h.c[1], h.c[2], h.c[3]);
+                        if (COUNT) st.maxsp = max(st.maxsp, (uint)stk.sp);
+                        node = h.c[0];
+                        continue;
+                    }
+                } else {    // TLAS leaf: into the instance
+                    stk.push(spill, TR_BLAS_SENTINEL);
+                    if (COUNT) st.maxsp = max(st.maxsp, (uint)stk.sp);
+                    node = enter_instance(sv, ~node, org, dir, rw, r, fr);
+                    in_blas = true;
+                    continue;
+                }
+            } else {
+                TriHit tr;
+                if (COUNT) st.tris++;
+                if (tri_intersect(r, sv.tris, (uint)~node, tmin, __builtin_huge_valf(), tr)) {
+                    instance_words(fr, tr);
+                    const float t = tr.t, bu = tr.bu, bv = tr.bv;
+                    const uint inst = tr.inst_flags & 0x7FFFFFFFu;
+                    const bool closer = t < best_t ||
+                        (t == best_t && found && (inst < best_inst || (inst == best_inst && tr.prim < best_prim)));
+                    if (closer && t < tmax) {
+                        bool accept = true;
+                        if (tr.inst_flags & 0x80000000u) {
+                            if (COUNT) st.alpha++;
+                            float a = candidate_alpha(sv, tr.alpha, bu, bv);
+                            float cutoff = ALPHA_MODE == 0 ? alpha_cutoff_hash(seed, (int)inst, (int)tr.prim) : 0.0001f;
+                            accept = !(a <= cutoff);
+                        }
+                        if (accept) {
+                            best_t = t; found = true; best_inst = inst; best_prim = tr.prim;
+                            hit.instance_id = (int)inst; hit.primitive_id = (int)tr.prim; hit.u = bu; hit.v = bv;
+                        }
+                    }
+                }
+            }
+            if (stk.sp == 0) break;
+            node = stk.pop(spill);
+            if (node == TR_BLAS_SENTINEL) {     // the BLAS is done: back to the world ray (below a sentinel lies a TLAS entry or nothing)
+                r = rw; in_blas = false;
+                if (stk.sp == 0) break;
+                node = stk.pop(spill);
+            }
+        }
+        overflow += stk.overflow ? 1 : 0;
+    }
+    if (include_lights && finite_ray) {
+        for (uint i = 0; i < sv.point_light_count; ++i) {
+            const PointLight& pl = sv.point_lights[i];
+            float radius = pl.radius;
+            if (radius == 0.0f) continue;
+            f3 oc = org - pl.pos;
+            float a = dot(dir, dir);
+            float b = 2.0f * dot(oc, dir);
+            float c = dot(oc, oc) - radius * radius;
+            float disc = b * b - 4.0f * a * c;
+            if (disc < 0) continue;
+            float hh = (-b - sqrtf(disc)) / (2.0f * a);
+            if (hh > 0 && hh > tmin && hh < best_t) {
+                best_t = hh; found = true;
+                hit.instance_id = -1; hit.primitive_id = (int)i; hit.u = hh; hit.v = 0;
+            }
+        }
+    }
+    hit.t = found ? best_t : -1.0f;
+}
+
+template <bool COUNT>
+TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow) {
+    float visibility = 1.0f;
+    if (sv.tri_count == 0 || !ray_is_finite(org, dir)) return visibility;
+    const RayPre rw = make_ray(org, dir);
+    RayPre r = rw;
+    LaneStack stk;
+    int spill[TR_SPILL_STACK];
+    stk.init(lds_stack);
+    int node = 0;
+    bool in_blas = false;
+    InstanceFrame fr = {0u, 0u};
+    while (true) {
+        if (node >= 0) {
+            Hit4 h;
+            box4_intersect(r, sv.nodes4, node, tmin, tmax, h);
+            if (COUNT) st.nodes++;
+            if (shadow_descend(h, stk, spill, node)) continue;
+        } else if (!in_blas) {
+            stk.push(spill, TR_BLAS_SENTINEL);
+            node = enter_instance(sv, ~node, org, dir, rw, r, fr);
+            in_blas = true;
+            continue;
+        } else {
+            TriHit tr;
+            if (COUNT) st.tris++;
+            if (tri_intersect(r, sv.tris, (uint)~node, tmin, tmax, tr)) {
+                instance_words(fr, tr);
+                if (!(tr.inst_flags & 0x80000000u)) { visibility = 0.0f; break; }
+                if (COUNT) st.alpha++;
+                float alpha = candidate_alpha(sv, tr.alpha, tr.bu, tr.bv);
+                visibility *= 1.0f - alpha;
+                if (visibility == 0.0f) break;
+            }
+        }
+        if (stk.sp == 0) break;
+        node = stk.pop(spill);
+        if (node == TR_BLAS_SENTINEL) {
+            r = rw; in_blas = false;
+            if (stk.sp == 0) break;
+            node = stk.pop(spill);
+        }
     }
     overflow += stk.overflow ? 1 : 0;
     return visibility;

@@ -246,10 +246,15 @@ TR_DEV void quad_inherited_leaf(int q, int& pend, QuadStack& qs, int& qnode, boo
 
 // Closest hit for the rays of one wave.  Every lane of the wave calls this (`valid` = the lane has a ray); parameters and
 // result as trace_closest4.
-template <int ALPHA_MODE, bool COUNT>
+// TWO_LEVEL: the two-level structure, traced by the per-lane loop to the end (trace.h trace_closest4_2l; no quad tail in this version).
+template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
 TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
                                 int* lds_stack, const QuadCtx& qc, HitRecord& hit, TraceStats& st, int& overflow) {
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
+    if constexpr (TWO_LEVEL) {
+        if (valid) trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, include_lights, seed, lds_stack, hit, st, overflow);
+        return;
+    }
     float best_t = tmax, best_u = 0.0f, best_v = 0.0f;
     uint best_inst = 0xFFFFFFFFu, best_prim = 0xFFFFFFFFu;   // none found yet
     RayPre r = make_ray(org, dir);
@@ -467,9 +472,10 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
 
 // Any-hit visibility for the shadow rays of one wave (trace_shadow4 with the quad-cooperative tail).  Every lane of the wave
 // calls this; returns the product of (1 - alpha) over the non-opaque hits, 0 after an opaque one.
-template <bool COUNT>
+template <bool COUNT, bool TWO_LEVEL = false>
 TR_DEV float trace_shadow_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, const QuadCtx& qc,
                                 TraceStats& st, int& overflow) {
+    if constexpr (TWO_LEVEL) return valid ? trace_shadow4_2l<COUNT>(sv, org, dir, tmin, tmax, lds_stack, st, overflow) : 1.0f;
     float visibility = 1.0f;
     bool live = valid && sv.tri_count > 0 && ray_is_finite(org, dir);
     RayPre r = make_ray(org, dir);

@@ -93,6 +93,14 @@ int main(int argc, char** argv)
                 if(renderer != "path-tracer" && renderer != "direct") throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct)");
             }
             else if(starts(a, "--dump-scene=")) dump_scene = val("--dump-scene=");
+            else if(starts(a, "--as-strategy="))     // scene_stage::options::group_strategy (src/options.hh:519-532); see trhip.h
+            {
+                const std::string v = val("--as-strategy=");
+                if(v == "all-merged") opt.scene.as_strategy = TRHIP_AS_ALL_MERGED;
+                else if(v == "per-material" || v == "per-model") opt.scene.as_strategy = TRHIP_AS_PER_MESH;   // an instance is one primitive
+                else if(v == "static-merged-dynamic-per-model") opt.scene.as_strategy = TRHIP_AS_STATIC_MERGED_DYNAMIC_PER_MESH;
+                else throw std::runtime_error("unknown --as-strategy=" + v + " (all-merged, per-material, per-model, static-merged-dynamic-per-model)");
+            }
             else if(starts(a, "--device-workloads="))
             {
                 std::string v = val("--device-workloads=");
@@ -191,6 +199,20 @@ int main(int argc, char** argv)
         if(animation_flag) animator.play(animation_name, false);
         const int64_t update_dt = (int64_t)std::floor(1000000.0 / framerate + 0.5);
         const bool animated = animation_flag && animator.is_playing();
+        if(animated && scene.animation)
+        {   // the instances placed by an animated node or one below it are dynamic (!static_transformable)
+            opt.scene.dynamic.assign(scene.instance_count(), 0);
+            std::vector<int> todo;
+            for(const auto& c: scene.animation->clips) todo.push_back(c.first);
+            while(!todo.empty())
+            {
+                const int n = todo.back(); todo.pop_back();
+                auto it = scene.animation->nodes.find(n);
+                if(it == scene.animation->nodes.end()) continue;
+                for(uint32_t i: it->second.instances) if(i < opt.scene.dynamic.size()) opt.scene.dynamic[i] = 1;
+                for(int c: it->second.children) todo.push_back(c);
+            }
+        }
         if(animated && !frames_given) { frames = std::numeric_limits<int>::max(); hopt.single_frame = false; }      // until the clip ends
         if(!dump_scene.empty())
         {
@@ -355,7 +377,7 @@ int main(int argc, char** argv)
         {
             direct_renderer::options dopt;
             static_cast<path_tracer_stage::options&>(dopt) = opt;
-            dopt.tonemap = opt.tonemap; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;
+            dopt.tonemap = opt.tonemap; dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;
             direct_renderer rr(devices, scene, size, dopt);
             return run(rr);
         }

@@ -23,7 +23,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (AccelInfoC, CountersC, DistributionC, PtOptionsC, SceneDescC, TimingsC, TonemapInfoC, TrhipError, check)
+from ._lib import (AccelInfoC, AccelLayoutC, CountersC, DistributionC, PtOptionsC, SceneDescC, TimingsC, TonemapInfoC, TrhipError, check)
 from .distribution import (DISTRIBUTION_DUPLICATE, DISTRIBUTION_SCANLINE, DISTRIBUTION_SHUFFLED_STRIPS, DistributionParams,
                            get_device_distribution_params, get_distribution_target_size)
 from .scene import SceneDesc, build_alias_table
@@ -198,12 +198,17 @@ class Context:
 class SceneStage:
     """scene_stage: uploads the flattened scene and builds the acceleration structure on the device."""
 
-    def __init__(self, ctx: Context, scene: Optional[SceneDesc] = None, fast_trace_rebuilds: bool = False):
+    def __init__(self, ctx: Context, scene: Optional[SceneDesc] = None, fast_trace_rebuilds: bool = False, as_strategy: int = 0,
+                 dynamic=None):
+        """`as_strategy`: trhip_scene_set_accel_strategy (0 all-merged, the default; 1 per-mesh; 2 static-merged-dynamic-per-mesh).
+        `dynamic`: per-instance marks (trhip_scene_set_dynamic_instances) of the scenes this stage is given, or None (all static)."""
         self.ctx = ctx
         self.scene = None
         self.accel = None
         # the first build of a scene is a static build (tree optimisation on); rebuilds after a change are fast builds unless asked
         self.fast_trace_rebuilds = fast_trace_rebuilds
+        self.as_strategy = int(as_strategy)
+        self.dynamic = None if dynamic is None else np.ascontiguousarray(np.asarray(dynamic).astype(np.uint8))
         if scene is not None:
             self.set_scene(scene)
 
@@ -246,6 +251,11 @@ class SceneStage:
             self.set_skin(sk.instance, sk.skins)
             self.skin(sk.instance, scene.joint_transforms(sk), refit=None)
         info = AccelInfoC()
+        check(L.trhip_scene_set_accel_strategy(self.ctx.h, self.as_strategy))
+        if self.dynamic is not None:
+            if len(self.dynamic) != len(inst):
+                raise ValueError(f"SceneStage: {len(self.dynamic)} dynamic marks for {len(inst)} instances")
+            check(L.trhip_scene_set_dynamic_instances(self.ctx.h, self.dynamic.ctypes.data, len(self.dynamic)))
         check(L.trhip_scene_set_build_mode(self.ctx.h, 0))
         check(L.trhip_scene_build_accel(self.ctx.h, C.byref(info)))
         self.accel = dict(triangle_count=info.triangle_count, node_count=info.node_count,
@@ -253,6 +263,13 @@ class SceneStage:
                           bounds_min=tuple(info.bounds_min), bounds_max=tuple(info.bounds_max),
                           node_bytes=info.node_bytes, leaf_count=info.leaf_count)
         return self.accel
+
+    def layout(self) -> dict:
+        """trhip_scene_get_accel_layout: strategy, BLAS count, TLAS leaves, BLASes the last build / refit touched, node and record bytes
+        of both levels, device ms of the last BLAS work and TLAS build."""
+        out = AccelLayoutC()
+        check(_lib.lib().trhip_scene_get_accel_layout(self.ctx.h, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in AccelLayoutC._fields_}
 
     def pose(self, node_globals: dict, refit: bool = True):
         """New global transforms of the joint nodes (an animation step of the caller's): every skinned mesh is skinned again
@@ -608,7 +625,7 @@ class RtRenderer:
 
     def __init__(self, ctx: Context, scene: SceneDesc, options: PtOptionsC, size, strategy=DISTRIBUTION_SCANLINE,
                  rank=0, world_size=1, viewports=1, tonemap: Optional[dict] = None, accumulate=False, use_torch=None,
-                 shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1):
+                 shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None):
         """`shard`: what the ranks divide among themselves - "pixels" (the reference's distribution strategies, partial frames
         stitched on rank 0), "views" (viewport v on rank v mod N; nothing is exchanged before output) or "samples" (every
         rank renders samples_per_pixel / N samples of every pixel; one reduce to rank 0).  SURVEY.md section 8(e).
@@ -616,7 +633,9 @@ class RtRenderer:
         transfer.LocalExchange shared by the ranks of one process (device-to-device copies on the default stream).
         `frames_per_launch`: B > 1 makes every render() call B consecutive frames (trhip_pt_set_frame_batch): the images grow B
         layer groups, frame-major, and everything after the path tracing - exchange, stitch, tonemap - handles the B frames in
-        one go.  For frames that do not accumulate; what the ranks of a pixel-sharded job use, whose launches are small."""
+        one go.  For frames that do not accumulate; what the ranks of a pixel-sharded job use, whose launches are small.
+        `as_strategy`, `dynamic`: the acceleration-structure strategy and dynamic marks of the scene stage (SceneStage; the C++
+        rt_renderer::options::scene)."""
         if shard not in ("pixels", "views", "samples"):
             raise ValueError("shard must be pixels, views or samples")
         if frames_in_flight < 1:
@@ -648,7 +667,7 @@ class RtRenderer:
         self.viewports = viewports
         self.strategy = DISTRIBUTION_DUPLICATE if (world_size == 1 or self.shard != "pixels") else strategy   # src/tauray.cc:519-521
         self.accumulate = accumulate
-        self.scene_update = SceneStage(ctx, scene)
+        self.scene_update = SceneStage(ctx, scene, as_strategy=as_strategy, dynamic=dynamic)
         if self.shard == "pixels":
             workloads = [1.0 / world_size] * world_size
             self.dists = self._device_dists(workloads)

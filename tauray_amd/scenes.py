@@ -125,6 +125,11 @@ class _Builder:
         self.voff += len(verts)
         self.ioff += len(idx)
 
+    def share(self, span, material, model):
+        """Another instance of the mesh of instance `span` (no vertex or index copy)."""
+        self.inst.append(S.make_instance(model, material))
+        self.spans.append(self.spans[span])
+
     def tri_count(self):
         return self.ioff // 3
 
@@ -138,7 +143,8 @@ def _load_teapot():
     return v, i
 
 
-def sponza_class(seed: int = 1, target_tris: int = 260_000, teapots: int = 0, width: int = 1920, height: int = 1080) -> S.SceneDesc:
+def sponza_class(seed: int = 1, target_tris: int = 260_000, teapots: int = 0, width: int = 1920, height: int = 1080,
+                 share_teapot_mesh: bool = False) -> S.SceneDesc:
     rng = np.random.default_rng(seed)
     b = _Builder()
     LX, LY, LZ = 30.0, 12.0, 14.0          # length (x), height (y), width (z)
@@ -215,6 +221,7 @@ def sponza_class(seed: int = 1, target_tris: int = 260_000, teapots: int = 0, wi
     # --- teapots
     if teapots:
         tv, ti = _load_teapot()
+        first_teapot = None
         for k in range(teapots):
             if k < 10:
                 m = S.make_material(albedo=tuple(rng.uniform(0.6, 1.0, 3)) + (1.0,), metallic=0.0, roughness=0.05,
@@ -229,7 +236,11 @@ def sponza_class(seed: int = 1, target_tris: int = 260_000, teapots: int = 0, wi
             ang = rng.uniform(0, 2 * math.pi)
             q = (0.0, math.sin(ang / 2), 0.0, math.cos(ang / 2))
             sc = float(rng.uniform(0.25, 0.5))
-            b.add(tv, ti, m, S.trs_matrix(pos, q, (sc, sc, sc)))
+            if share_teapot_mesh and first_teapot is not None:      # one span for every teapot: a mesh the two-level structures share
+                b.share(first_teapot, m, S.trs_matrix(pos, q, (sc, sc, sc)))
+            else:
+                first_teapot = len(b.inst)
+                b.add(tv, ti, m, S.trs_matrix(pos, q, (sc, sc, sc)))
 
     cam = S.Camera(projection=S.PROJ_PERSPECTIVE, fov=60.0, aspect=width / float(height), near=0.1, far=200.0)
     # camera at the -x end, 1.7 m above the floor, looking down the nave (+x): -Z of the camera maps to +X
@@ -250,9 +261,10 @@ def sponza_class(seed: int = 1, target_tris: int = 260_000, teapots: int = 0, wi
     return desc.finalize(True)
 
 
-def sponza_teapots(seed: int = 1, width: int = 1920, height: int = 1080) -> S.SceneDesc:
-    """~1.0 M triangles: the atrium at ~286k + 50 teapots x 14 280."""
-    return sponza_class(seed=seed, target_tris=1_000_000, teapots=50, width=width, height=height)
+def sponza_teapots(seed: int = 1, width: int = 1920, height: int = 1080, share_teapot_mesh: bool = False) -> S.SceneDesc:
+    """~1.0 M triangles: the atrium at ~286k + 50 teapots x 14 280.  `share_teapot_mesh`: the 50 teapots are instances of one span
+    (the same world-space triangles, 1/50 of the teapot vertices and indices)."""
+    return sponza_class(seed=seed, target_tris=1_000_000, teapots=50, width=width, height=height, share_teapot_mesh=share_teapot_mesh)
 
 
 def scene_hash(desc: S.SceneDesc) -> str:
