@@ -225,6 +225,32 @@ typedef struct trhip_accel_layout {
     float tlas_ms;                    /* device time of the last TLAS build (0 for all-merged) */
 } trhip_accel_layout;
 int trhip_scene_get_accel_layout(trhip_device* dev, trhip_accel_layout* out);
+/* Sphere lights in closest-hit rays.  The reference builds one AABB per point / spot light into a light BLAS under a TLAS instance of mask
+ * 1 << 1 (src/scene_stage.cc:1356-1387, 1456-1466) and intersects it with shader/rt_common_point_light.rint:11-17, shader/rt_common.glsl:36-51,
+ * so a closest-hit ray costs the logarithm of the light count.  Here the lights with radius != 0 get a 4-wide tree of their own, built on the
+ * device at trhip_scene_upload (and when the mode below first asks for it) and walked after the triangles; trhip_scene_update_lights refits
+ * it when the set of lights with a radius stays the same and rebuilds it otherwise, before it returns.  The tree lives behind the light
+ * records, independent of trhip_scene_build_accel and of the acceleration-structure strategy.  Hits are bit-identical in every mode.
+ *   TRHIP_LIGHT_ACCEL_AUTO (the default): the tree once at least `auto_threshold` lights have a radius, else the loop.
+ *   TRHIP_LIGHT_ACCEL_LOOP: every light in a loop, the cost growing with the light count (what this library did before).
+ *   TRHIP_LIGHT_ACCEL_TREE: the tree whenever a light has a radius.
+ * The mode is kept over uploads.  Until it is set, the environment variable TRHIP_LIGHT_ACCEL=auto|loop|tree chooses it (A/B tools). */
+#define TRHIP_LIGHT_ACCEL_AUTO 0
+#define TRHIP_LIGHT_ACCEL_LOOP 1
+#define TRHIP_LIGHT_ACCEL_TREE 2
+int trhip_scene_set_light_accel(trhip_device* dev, int mode);
+typedef struct trhip_light_accel_info {
+    int32_t requested;                /* TRHIP_LIGHT_ACCEL_*: what was set (or TRHIP_LIGHT_ACCEL chose) */
+    int32_t in_effect;                /* TRHIP_LIGHT_ACCEL_LOOP or TRHIP_LIGHT_ACCEL_TREE: what the closest-hit kernels run now */
+    uint32_t sphere_lights;           /* point / spot lights with radius != 0 */
+    uint32_t tree_lights;             /* leaves of the tree (0: no tree) */
+    uint32_t node_count;              /* 128-byte node slots of the tree */
+    uint32_t auto_threshold;          /* sphere lights from which TRHIP_LIGHT_ACCEL_AUTO uses the tree */
+    uint64_t tree_bytes;              /* header + node slots behind the light records */
+    float last_ms;                    /* host wall time of the last build or refit, device work included */
+    int32_t last_was_refit;           /* 1: the last tree update was a refit, 0: a build, -1: none since the upload */
+} trhip_light_accel_info;
+int trhip_scene_get_light_accel(trhip_device* dev, trhip_light_accel_info* out);
 /* copies the 64-byte tri_light records back to the host (test hook) */
 int trhip_scene_get_tri_lights(trhip_device* dev, void* out_host, uint32_t max_count);
 
@@ -394,6 +420,11 @@ typedef struct trhip_phase_counters {
     uint64_t closest_node_visits;     /* node visits of the closest-hit rays alone (trhip_counters::node_visits includes shadow rays) */
 } trhip_phase_counters;
 int trhip_pt_get_phase_counters(trhip_pt* pt, trhip_phase_counters* out);   /* synchronises the stream */
+/* Sphere-light work of the closest-hit rays (trhip_scene_set_light_accel), cumulative like trhip_counters, only counted while work counting
+ * is on and cleared by trhip_pt_reset_counters: ray-sphere tests, node visits of the light tree (0 under TRHIP_LIGHT_ACCEL_LOOP), and walks
+ * that ran out of their 16-entry stack and tested every light in the loop instead (same hits, the loop's cost). */
+typedef struct trhip_light_counters { uint64_t sphere_tests, node_visits, walk_fallbacks; } trhip_light_counters;
+int trhip_pt_get_light_counters(trhip_pt* pt, trhip_light_counters* out);   /* synchronises the stream */
 /* Peak vector-instruction issue rate of the device as it runs now: a loop of independent v_fma_f32 at eight waves per SIMD,
  * in 10^9 wave-level instructions per second (MI355X_MICROARCH.md: 2 cycles per wave64 instruction on a SIMD-32; the clock is
  * what the box sustains).  The peak of the VALU roofline in bench.py; about 2 ms of device time. */

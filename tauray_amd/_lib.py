@@ -49,6 +49,22 @@ class AccelLayoutC(C.Structure):
 AS_ALL_MERGED, AS_PER_MESH, AS_STATIC_MERGED_DYNAMIC_PER_MESH = 0, 1, 2
 
 
+class LightAccelInfoC(C.Structure):
+    """trhip_light_accel_info: the sphere-light mode and tree of the scene (include/trhip.h)."""
+    _fields_ = [("requested", C.c_int32), ("in_effect", C.c_int32), ("sphere_lights", C.c_uint32), ("tree_lights", C.c_uint32),
+                ("node_count", C.c_uint32), ("auto_threshold", C.c_uint32), ("tree_bytes", C.c_uint64), ("last_ms", C.c_float),
+                ("last_was_refit", C.c_int32)]
+
+
+class LightCountersC(C.Structure):
+    """trhip_light_counters: sphere tests, light-tree node visits and walks that fell back to the loop, of the closest-hit rays."""
+    _fields_ = [("sphere_tests", C.c_uint64), ("node_visits", C.c_uint64), ("walk_fallbacks", C.c_uint64)]
+
+
+# trhip_scene_set_light_accel
+LIGHT_ACCEL_AUTO, LIGHT_ACCEL_LOOP, LIGHT_ACCEL_TREE = 0, 1, 2
+
+
 class PtOptionsC(C.Structure):
     """== path_tracer_stage::options (reference src/path_tracer_stage.hh:13-30), flattened."""
     _fields_ = [
@@ -128,6 +144,9 @@ SYMBOLS = {
     "trhip_scene_set_accel_strategy": (_i, [_vp, _i]),
     "trhip_scene_set_dynamic_instances": (_i, [_vp, _vp, _u32]),
     "trhip_scene_get_accel_layout": (_i, [_vp, C.POINTER(AccelLayoutC)]),
+    "trhip_scene_set_light_accel": (_i, [_vp, _i]),
+    "trhip_scene_get_light_accel": (_i, [_vp, C.POINTER(LightAccelInfoC)]),
+    "trhip_pt_get_light_counters": (_i, [_vp, C.POINTER(LightCountersC)]),
     "trhip_stitch_batch": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, C.c_float, _vp]),
     "trhip_stream_create": (_i, [_vp, C.POINTER(C.c_void_p)]),
     "trhip_stream_destroy": (_i, [_vp, _vp]),

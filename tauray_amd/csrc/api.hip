@@ -44,7 +44,7 @@ __global__ __launch_bounds__(KB) void k_feature(SceneView sv, LaunchCtx L, int f
     HitRecord hit;
     TraceStats st = {};
     int overflow = 0;
-    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), false, 0u, s_stack + threadIdx.x, hit, st, overflow);
+    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), 0u, s_stack + threadIdx.x, hit, st, overflow);
     if (overflow) *overflow_flag = 1;
     f4 data = default_value;
     if (hit.instance_id >= 0) {
@@ -135,15 +135,26 @@ __global__ __launch_bounds__(KB) void k_query_closest(SceneView sv, uint n, cons
         const uint seed = (valid && seeds) ? seeds[i] : 0u;
         HitRecord hit;
 #if TR_QUAD_SWITCH > 0
-        if (seeds) trace_closest_wave4<0, false, TWO_LEVEL>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, seed, my_stack, qc, hit, st, overflow);
-        else trace_closest_wave4<1, false, TWO_LEVEL>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, 0u, my_stack, qc, hit, st, overflow);
+        if (seeds) trace_closest_wave4<0, false, TWO_LEVEL>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], seed, my_stack, qc, hit, st, overflow);
+        else trace_closest_wave4<1, false, TWO_LEVEL>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], 0u, my_stack, qc, hit, st, overflow);
 #else
         if (valid) {
-            if (seeds) trace_closest4<0, false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, seed, my_stack, hit, st, overflow);
-            else trace_closest4<1, false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], include_lights != 0, 0u, my_stack, hit, st, overflow);
+            if (seeds) trace_closest4<0, false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], seed, my_stack, hit, st, overflow);
+            else trace_closest4<1, false, TWO_LEVEL>(sv, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], 0u, my_stack, hit, st, overflow);
         }
 #endif
         if (valid) out[i] = hit;
+        if (valid && include_lights) {     // sphere lights after the triangles, the ray read again (trace_lanes.h closest_lane)
+            const float tri_t = hit.instance_id >= 0 ? hit.t : r[7];
+            uint ri = i;
+            asm volatile("" : "+v"(ri));
+            const float* q = rays + (size_t)ri * 8;
+            const f3 o = F3(q[0], q[1], q[2]), d = F3(q[4], q[5], q[6]);
+            if (ray_is_finite(o, d)) {
+                const LightHit lh = trace_sphere_lights<false>(sv, o, d, q[3], tri_t, my_stack, st);
+                if (lh.light >= 0) out[ri] = HitRecord{-1, lh.light, lh.t, 0.0f, lh.t};
+            }
+        }
     }
     if (overflow) *overflow_flag = 1;
 }
@@ -466,7 +477,12 @@ int trhip_scene_upload(trhip_device* dev, const trhip_scene_desc* d) {
     }
     if (upload_array(s.vertices, d->vertices, d->vertex_count)) return 1;
     if (upload_array(s.indices, d->indices, d->index_count)) return 1;
-    if (upload_array(s.point_lights, d->point_lights, d->point_light_count)) return 1;
+    if (d->point_light_count) {     // the light records, then the header and node slots of the sphere-light tree (common.h)
+        if (!d->point_lights) return set_error("trhip_scene_upload: missing point lights");
+        HIPCHK(hipMalloc(&s.point_lights, light_allocation_bytes(d->point_light_count)));
+        HIPCHK(hipMemcpy(s.point_lights, d->point_lights, (size_t)d->point_light_count * sizeof(PointLight), hipMemcpyHostToDevice));
+        s.host_point_lights.assign((const PointLight*)d->point_lights, (const PointLight*)d->point_lights + d->point_light_count);
+    }
     if (upload_array(s.directional_lights, d->directional_lights, d->directional_light_count)) return 1;
     if (upload_array(s.tex_infos, d->texture_infos, d->texture_count)) return 1;
     size_t texel_count = 0;
@@ -509,7 +525,7 @@ int trhip_scene_upload(trhip_device* dev, const trhip_scene_desc* d) {
     s.gather_emissive_triangles = d->gather_emissive_triangles;
     s.host_tri_light_count = d->gather_emissive_triangles ? tri_lights : 0;
     if (int rc = build_shade_tris(s, -1, nullptr)) return rc;
-    return 0;
+    return update_light_accel(s, true);
 }
 
 int trhip_scene_update_lights(trhip_device* dev, const void* point_lights, uint32_t point_light_count, const void* directional_lights,
@@ -522,7 +538,11 @@ int trhip_scene_update_lights(trhip_device* dev, const void* point_lights, uint3
     HIPCHK(hipDeviceSynchronize());
     if (point_light_count) HIPCHK(hipMemcpy(s.point_lights, point_lights, (size_t)point_light_count * sizeof(PointLight), hipMemcpyHostToDevice));
     if (directional_light_count) HIPCHK(hipMemcpy(s.directional_lights, directional_lights, (size_t)directional_light_count * sizeof(DirectionalLight), hipMemcpyHostToDevice));
-    return 0;
+    if (!point_light_count) return 0;
+    // unchanged records (an animated scene updates its lights every frame): the tree stands as it is
+    const bool moved = memcmp(s.host_point_lights.data(), point_lights, (size_t)point_light_count * sizeof(PointLight)) != 0;
+    s.host_point_lights.assign((const PointLight*)point_lights, (const PointLight*)point_lights + point_light_count);
+    return update_light_accel(s, moved);      // refit, or rebuild when a radius went to or from 0: a moved light is never missed
 }
 
 int trhip_scene_update_cameras(trhip_device* dev, const void* camera_data, uint32_t count) {
@@ -654,6 +674,32 @@ int trhip_scene_get_accel_layout(trhip_device* dev, trhip_accel_layout* out) {
     DEVCHK(dev);
     if (!out) return set_error("trhip_scene_get_accel_layout: null output");
     *out = dev->scene.layout;
+    return 0;
+}
+int trhip_scene_set_light_accel(trhip_device* dev, int mode) {
+    DEVCHK(dev);
+    if (mode < TRHIP_LIGHT_ACCEL_AUTO || mode > TRHIP_LIGHT_ACCEL_TREE)
+        return set_error("trhip_scene_set_light_accel: unknown mode " + std::to_string(mode) + " (0 auto, 1 loop, 2 tree)");
+    HIPCHK(hipDeviceSynchronize());
+    dev->scene.light_accel_requested = mode;
+    return update_light_accel(dev->scene, false);
+}
+int trhip_scene_get_light_accel(trhip_device* dev, trhip_light_accel_info* out) {
+    DEVCHK(dev);
+    if (!out) return set_error("trhip_scene_get_light_accel: null output");
+    const DeviceScene& s = dev->scene;
+    memset(out, 0, sizeof(*out));
+    out->requested = light_accel_requested(s);
+    if (out->requested < 0) return set_error("trhip_scene_get_light_accel: TRHIP_LIGHT_ACCEL is not auto, loop or tree");
+    out->in_effect = s.light_in_effect;
+    for (const PointLight& pl : s.host_point_lights) out->sphere_lights += pl.radius != 0.0f ? 1u : 0u;
+    const bool tree = s.light_in_effect == TRHIP_LIGHT_ACCEL_TREE;
+    out->tree_lights = tree ? (uint32_t)s.light_tree_set.size() : 0u;
+    out->node_count = tree ? s.light_tree_nodes : 0u;
+    out->auto_threshold = light_accel_auto_threshold();
+    out->tree_bytes = tree ? sizeof(LightTreeHeader) + (uint64_t)s.light_tree_nodes * sizeof(Bvh4Node) : 0u;
+    out->last_ms = s.light_ms;
+    out->last_was_refit = s.light_last_refit;
     return 0;
 }
 int trhip_scene_refit_accel(trhip_device* dev, trhip_accel_info* out) {
@@ -795,6 +841,12 @@ int trhip_pt_set_profiling(trhip_pt* pt, int count_work, int detailed_timing) {
     return 0;
 }
 int trhip_pt_get_counters(trhip_pt* pt, trhip_counters* out) { if (!pt) return set_error("null trhip_pt"); DEVCHK(pt->dev); return pt->stage->get_counters(out, pt->stage->last_stream); }
+int trhip_pt_get_light_counters(trhip_pt* pt, trhip_light_counters* out) {
+    if (!pt) return set_error("null trhip_pt");
+    if (!out) return set_error("trhip_pt_get_light_counters: null output");
+    DEVCHK(pt->dev);
+    return pt->stage->get_light_counters(out, pt->stage->last_stream);
+}
 int trhip_pt_reset_counters(trhip_pt* pt) { if (!pt) return set_error("null trhip_pt"); DEVCHK(pt->dev); HIPCHK(hipStreamSynchronize(pt->stage->last_stream)); return pt->stage->reset_counters(); }
 int trhip_pt_get_timings(trhip_pt* pt, trhip_timings* out) { if (!pt) return set_error("null trhip_pt"); DEVCHK(pt->dev); return pt->stage->get_timings(out); }
 int trhip_pt_get_program(trhip_pt* pt, trhip_program_info* out) { if (!pt) return set_error("null trhip_pt"); if (!out) return set_error("trhip_pt_get_program: null out"); DEVCHK(pt->dev); return pt->stage->get_program(out); }

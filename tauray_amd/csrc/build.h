@@ -96,6 +96,15 @@ struct DeviceScene {
     std::vector<uint8_t> host_non_opaque;
     void* tl_aux = nullptr;         // TLAS build: BLAS root references and boxes, sorted instance boxes
     size_t tl_aux_bytes = 0;
+    // ---- sphere-light tree (trhip_scene_set_light_accel): header and nodes behind the records in `point_lights`
+    int light_accel_requested = -1;             // TRHIP_LIGHT_ACCEL_*, -1 = not set (TRHIP_LIGHT_ACCEL, else AUTO); kept over uploads
+    int light_in_effect = TRHIP_LIGHT_ACCEL_LOOP;
+    std::vector<PointLight> host_point_lights;  // what the device holds
+    std::vector<uint> light_tree_set;           // the lights the tree was built over (radius != 0), ascending
+    std::vector<Bvh4Node> light_nodes;          // host copy of the tree's nodes (the refit rewrites their boxes)
+    uint light_tree_nodes = 0;
+    float light_ms = 0.0f;
+    int light_last_refit = -1;
 
     SceneView view() const {
         SceneView v;
@@ -140,9 +149,10 @@ struct DeviceScene {
         void* ptrs[] = {instances, spans, vertices, indices, point_lights, directional_lights, tex_infos, texels, envmap,
                         alias_table, cameras, prev_cameras, non_opaque, tri_prefix, world_spans, world_vertices, scratch, shade_tris, alpha_base, alpha_tris};
         for (void* p : ptrs) if (p) (void)hipFree(p);
-        const int strategy = accel_strategy;
+        const int strategy = accel_strategy, light_mode = light_accel_requested;
         *this = DeviceScene();
         accel_strategy = strategy;
+        light_accel_requested = light_mode;
     }
 };
 
@@ -151,6 +161,11 @@ int ensure_world_vertices(DeviceScene& ds, hipStream_t stream);
 int build_shade_tris(DeviceScene& ds, int instance, hipStream_t stream);   // instance < 0: every mesh (after an upload); else the mesh of that instance (after skinning)
 int skin_instance(DeviceScene& ds, uint instance, const float* joint_transforms, uint joint_count, hipStream_t stream);   // skinning.comp
 int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);   // same tree, new boxes (after trhip_scene_update_instances)   // pre_transform.comp per instance
-void mark_skinned(DeviceScene& ds, uint instance);   // the BLAS of the instance's span needs a refit (two-level structure)
+void mark_skinned(DeviceScene& ds, uint instance);
+// The sphere-light tree after an upload or trhip_scene_update_lights (`moved`: the records changed) or trhip_scene_set_light_accel: chooses
+// the mode in effect, then builds, refits or drops the tree so that the device matches ds.host_point_lights.  Synchronous.
+int update_light_accel(DeviceScene& ds, bool moved);
+uint light_accel_auto_threshold();
+int light_accel_requested(const DeviceScene& ds);   // the mode set, else TRHIP_LIGHT_ACCEL, else TRHIP_LIGHT_ACCEL_AUTO   // the BLAS of the instance's span needs a refit (two-level structure)
 
 }  // namespace tr

@@ -6,6 +6,8 @@
 // trhip_scene_refit_accel keeps the tree and recomputes its boxes level by level.  Also here: extract_tri_lights
 // (shader/extract_tri_lights.comp:17-54) and the pre-transformed vertex copy (shader/pre_transform.comp:26-42).
 #include <algorithm>
+#include <cctype>
+#include <chrono>
 #include <cmath>
 #include <map>
 #include <tuple>
@@ -1781,6 +1783,149 @@ static int refit_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info
     ds.static_dirty = false;
     ds.layout.blas_updated = updated; ds.layout.blas_ms = ms_blas; ds.layout.tlas_ms = ms_tlas;
     fill_info(ds, info, ms_blas + ms_tlas);
+    return 0;
+}
+
+}  // namespace tr
+
+// =====================================================================================================================
+// Sphere-light tree (trhip_scene_set_light_accel).  One box record per light with radius != 0 (v0 = lo, v1 = hi,
+// v2 = lo, prim = light index), built like the TLAS by build_tree, then leaf ~j (sorted record j) renamed ~light index.  The leaf box is
+// pos +- (r + TR_LIGHT_KAPPA (|pos|inf + r)), rounded outwards (trace.h: what makes the walk exact for the fp32 root).
+namespace tr {
+
+#ifndef TR_LIGHT_AUTO_THRESHOLD
+#define TR_LIGHT_AUTO_THRESHOLD 16      // sphere lights from which TRHIP_LIGHT_ACCEL_AUTO walks the tree: the smallest measured count at which it
+                                        // is not slower than the loop (profiles/r8/sphere_light_accel.txt)
+#endif
+uint light_accel_auto_threshold() { return TR_LIGHT_AUTO_THRESHOLD; }
+int light_accel_requested(const DeviceScene& ds) {
+    if (ds.light_accel_requested >= 0) return ds.light_accel_requested;
+    const char* e = getenv("TRHIP_LIGHT_ACCEL");
+    std::string v = e ? e : "";
+    for (char& c : v) c = (char)tolower((unsigned char)c);
+    if (v.empty() || v == "auto") return TRHIP_LIGHT_ACCEL_AUTO;
+    return v == "loop" ? TRHIP_LIGHT_ACCEL_LOOP : (v == "tree" ? TRHIP_LIGHT_ACCEL_TREE : -1);
+}
+
+namespace {
+
+void light_box(const PointLight& pl, float lo[3], float hi[3]) {
+    const double p[3] = {pl.pos.x, pl.pos.y, pl.pos.z}, r = std::fabs((double)pl.radius);
+    const double m = std::max(std::fabs(p[0]), std::max(std::fabs(p[1]), std::fabs(p[2])));
+    const double g = r + (double)TR_LIGHT_KAPPA * (m + r);
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = std::nextafter((float)(p[k] - g), -INFINITY);
+        hi[k] = std::nextafter((float)(p[k] + g), INFINITY);
+    }
+}
+
+// union of the children of `node`, written into its slots on the way (post-order); returns the node's box
+void refit_light_node(std::vector<Bvh4Node>& nodes, const std::vector<PointLight>& lights, int node, float lo[3], float hi[3]) {
+    for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+    Bvh4Node& nd = nodes[(size_t)node];
+    for (int c = 0; c < 4; ++c) {
+        const int ch = nd.child[c];
+        if (ch == 0x7FFFFFFF) continue;
+        float clo[3], chi[3];
+        if (ch < 0) light_box(lights[(size_t)~ch], clo, chi);
+        else refit_light_node(nodes, lights, ch, clo, chi);
+        nd.lox[c] = clo[0]; nd.loy[c] = clo[1]; nd.loz[c] = clo[2]; nd.hix[c] = chi[0]; nd.hiy[c] = chi[1]; nd.hiz[c] = chi[2];
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], clo[k]); hi[k] = std::max(hi[k], chi[k]); }
+    }
+}
+
+int write_light_header(DeviceScene& ds, uint use_tree) {
+    const uint n = ds.point_light_count;
+    const LightTreeHeader h = {use_tree, ds.light_tree_nodes, use_tree ? (uint)ds.light_tree_set.size() : 0u, 0u};
+    HIPCHK(hipMemcpy(reinterpret_cast<char*>(ds.point_lights) + (size_t)n * sizeof(PointLight), &h, sizeof(h), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int build_light_tree(DeviceScene& ds, hipStream_t stream) {
+    const uint L = (uint)ds.light_tree_set.size();
+    Bvh4Node* dst = const_cast<Bvh4Node*>(light_tree_nodes(ds.view()));
+    std::vector<TriRecord> recs(L);
+    for (uint j = 0; j < L; ++j) {
+        TriRecord& t = recs[j];
+        memset(&t, 0, sizeof(t));
+        float lo[3], hi[3];
+        light_box(ds.host_point_lights[ds.light_tree_set[j]], lo, hi);
+        for (int k = 0; k < 3; ++k) { t.v0[k] = lo[k]; t.v1[k] = hi[k]; t.v2[k] = lo[k]; }
+        t.prim = ds.light_tree_set[j];
+    }
+    std::vector<Bvh4Node>& nodes = ds.light_nodes;
+    if (L == 1) {   // the root is a node of one child, so that every walk starts at node 0
+        nodes.assign(1, Bvh4Node());
+        Bvh4Node& root = nodes[0];
+        for (int c = 0; c < 4; ++c) {
+            root.lox[c] = root.loy[c] = root.loz[c] = INFINITY; root.hix[c] = root.hiy[c] = root.hiz[c] = -INFINITY;
+            root.child[c] = 0x7FFFFFFF; root.pad[c] = 0;
+        }
+        root.lox[0] = recs[0].v0[0]; root.loy[0] = recs[0].v0[1]; root.loz[0] = recs[0].v0[2];
+        root.hix[0] = recs[0].v1[0]; root.hiy[0] = recs[0].v1[1]; root.hiz[0] = recs[0].v1[2];
+        root.child[0] = ~(int)recs[0].prim;
+    } else {
+        const uint saved_rounds = ds.build_rounds;      // what trhip_accel_info reports is the triangle build's
+        TreePlan P;
+        if (int rc = plan_tree(ds, stream, L, P)) return rc;
+        TriRecord* sorted = nullptr;
+        HIPCHK(hipMalloc(&sorted, (size_t)L * sizeof(TriRecord)));
+        HIPCHK(hipMemcpyAsync(P.unsorted(), recs.data(), (size_t)L * sizeof(TriRecord), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(P.cbounds(), kCboundsInit, sizeof(kCboundsInit), hipMemcpyHostToDevice, stream));
+        const uint blocks = (L + BT - 1) / BT;
+        hipLaunchKernelGGL(k_record_bounds, dim3(blocks < 1024u ? blocks : 1024u), dim3(BT), 0, stream, L, P.unsorted(), P.cbounds());
+        int rc = build_tree(ds, stream, P, L, sorted, dst, false);
+        ds.build_rounds = saved_rounds;
+        nodes.resize((size_t)L - 1);
+        std::vector<TriRecord> order(L);
+        if (rc == 0) {
+            hipError_t e = hipStreamSynchronize(stream);
+            if (e == hipSuccess) e = hipMemcpy(nodes.data(), dst, nodes.size() * sizeof(Bvh4Node), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(order.data(), sorted, (size_t)L * sizeof(TriRecord), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = set_error(std::string("light tree: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(sorted);
+        if (rc) return rc;
+        for (Bvh4Node& nd : nodes)      // leaf ~j of the sorted records -> ~light index (dead slots too: harmless, never reached)
+            for (int c = 0; c < 4; ++c)
+                if (nd.child[c] < 0) nd.child[c] = ~(int)order[(size_t)~nd.child[c]].prim;
+    }
+    ds.light_tree_nodes = (uint)nodes.size();
+    HIPCHK(hipMemcpy(dst, nodes.data(), nodes.size() * sizeof(Bvh4Node), hipMemcpyHostToDevice));
+    return 0;
+}
+
+}  // namespace
+
+int update_light_accel(DeviceScene& ds, bool moved) {
+    const uint n = ds.point_light_count;
+    std::vector<uint> set;
+    for (uint i = 0; i < n; ++i) if (ds.host_point_lights[i].radius != 0.0f) set.push_back(i);
+    const int requested = light_accel_requested(ds);
+    if (requested < 0) return set_error(std::string("TRHIP_LIGHT_ACCEL: unknown value '") + getenv("TRHIP_LIGHT_ACCEL") + "' (auto, loop or tree)");
+    const bool tree = !set.empty() && (requested == TRHIP_LIGHT_ACCEL_TREE || (requested == TRHIP_LIGHT_ACCEL_AUTO && set.size() >= light_accel_auto_threshold()));
+    ds.light_in_effect = tree ? TRHIP_LIGHT_ACCEL_TREE : TRHIP_LIGHT_ACCEL_LOOP;
+    if (n == 0) return 0;
+    if (!tree) {
+        ds.light_tree_set.clear(); ds.light_nodes.clear(); ds.light_tree_nodes = 0;
+        return write_light_header(ds, 0u);
+    }
+    const bool current = set == ds.light_tree_set && !ds.light_nodes.empty();
+    if (current && !moved) return write_light_header(ds, 1u);     // a mode change over a tree that is up to date
+    const auto t0 = std::chrono::steady_clock::now();
+    if (current) {      // same lights: new boxes in the same tree
+        float lo[3], hi[3];
+        refit_light_node(ds.light_nodes, ds.host_point_lights, 0, lo, hi);
+        HIPCHK(hipMemcpy(const_cast<Bvh4Node*>(light_tree_nodes(ds.view())), ds.light_nodes.data(), ds.light_nodes.size() * sizeof(Bvh4Node), hipMemcpyHostToDevice));
+        ds.light_last_refit = 1;
+    } else {
+        ds.light_tree_set = set;
+        if (int rc = build_light_tree(ds, nullptr)) { ds.light_tree_set.clear(); ds.light_nodes.clear(); ds.light_tree_nodes = 0; (void)write_light_header(ds, 0u); return rc; }
+        ds.light_last_refit = 0;
+    }
+    if (int rc = write_light_header(ds, 1u)) return rc;
+    ds.light_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 

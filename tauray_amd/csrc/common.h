@@ -245,4 +245,19 @@ struct SceneView {
 // The TLAS leaf records of a two-level structure: behind the node_count node slots in the same allocation (SceneView stays as it is)
 TR_HD const TlasLeaf* tlas_leaves(const SceneView& sv) { return reinterpret_cast<const TlasLeaf*>(sv.nodes4 + sv.node_count); }
 
+// Sphere-light tree (trhip_scene_set_light_accel).  The point-light allocation holds the point_light_count light
+// records, then this header, then - from the next 128-byte boundary - the 4-wide nodes of a tree over the lights with radius != 0
+// (root = node 0, leaf ~i = light record i).  use_tree = 0: the closest-hit kernels test every light in a loop instead.
+#define TR_LIGHT_KAPPA 0.001953125f     // box widening per unit of distance from the origin (the derivation: trace.h trace_sphere_lights)
+struct alignas(16) LightTreeHeader { uint use_tree, node_count, leaf_count, pad; };
+static_assert(sizeof(LightTreeHeader) == 16, "light tree header layout");
+TR_HD size_t light_tree_node_offset(uint point_light_count) { return ((size_t)point_light_count * sizeof(PointLight) + sizeof(LightTreeHeader) + 127) & ~(size_t)127; }
+TR_HD size_t light_allocation_bytes(uint point_light_count) {   // records, header and a node slot per light (a tree over n leaves has n - 1)
+    return light_tree_node_offset(point_light_count) + (size_t)(point_light_count > 1 ? point_light_count - 1 : 1) * sizeof(Bvh4Node);
+}
+TR_HD const LightTreeHeader* light_tree_header(const SceneView& sv) { return reinterpret_cast<const LightTreeHeader*>(sv.point_lights + sv.point_light_count); }
+TR_HD const Bvh4Node* light_tree_nodes(const SceneView& sv) {
+    return reinterpret_cast<const Bvh4Node*>(reinterpret_cast<const char*>(sv.point_lights) + light_tree_node_offset(sv.point_light_count));
+}
+
 }  // namespace tr

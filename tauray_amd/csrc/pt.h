@@ -26,6 +26,7 @@ public:
     int reset_counters();
     int get_timings(trhip_timings* out);
     int get_phase_counters(trhip_phase_counters* out, hipStream_t stream);
+    int get_light_counters(trhip_light_counters* out, hipStream_t stream);
     int get_program(trhip_program_info* out);
 
     DeviceScene* scene;

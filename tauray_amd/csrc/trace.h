@@ -252,6 +252,7 @@ struct TraceStats {
     uint ph_qnode, ph_qtri;   // phases of the quad-cooperative tail (trace_quad.h)
     uint ph_hist[8];          // per-lane node phases by live rays: 1-8, 9-16, ..., 57-64
     uint cnodes;              // node visits of closest-hit rays alone (`nodes` also counts the shadow rays of a fused launch)
+    uint ltests, lnodes, lfallbacks;   // sphere-light tests, light-tree node visits, walks that fell back to the loop (trhip_pt_get_light_counters)
 };
 
 // Candidate alpha of a non-opaque triangle: albedo_factor.a * texture alpha at the uv of the candidate hit
@@ -345,16 +346,140 @@ TR_DEV bool shadow_descend(const Hit4& h, LaneStack& stk, int* spill, int& node)
 #define TR_CE4(a, b) { const bool sw = h.t[b] < h.t[a]; const float ta = h.t[a], tb = h.t[b]; const int ca = h.c[a], cb = h.c[b]; \
                        h.t[a] = sw ? tb : ta; h.t[b] = sw ? ta : tb; h.c[a] = sw ? cb : ca; h.c[b] = sw ? ca : cb; }
 
-// Closest hit over triangles (+ sphere lights), one ray per lane.  ALPHA_MODE 0: stochastic alpha keyed by `seed`
+// =====================================================================================================================
+// Sphere lights (rt_common_point_light.rint:11-17 / .rchit:10-15, shader/rt_common.glsl:36-51), after the triangles: every point / spot
+// light with radius != 0 in a loop, or - LightTreeHeader::use_tree - a walk of the light tree.  Both give the loop's
+// result bit for bit: of the lights whose fp32 root hh satisfies hh > 0, hh > tmin and hh < best_t (the closest triangle, or tmax), the
+// smallest hh wins, the lowest index on equal hh; a triangle at the same t beats every light.
+//
+// The root as the reference computes it, in its operation order (no contraction: -ffp-contract=off).  NaN when the sphere is missed is
+// not needed: disc < 0 returns -1, which no test accepts.
+TR_DEV float sphere_light_root(f3 org, f3 dir, f3 pos, float radius) {
+    f3 oc = org - pos;
+    float a = dot(dir, dir);
+    float b = 2.0f * dot(oc, dir);
+    float c = dot(oc, oc) - radius * radius;
+    float disc = b * b - 4.0f * a * c;
+    if (disc < 0) return -1.0f;
+    return (-b - sqrtf(disc)) / (2.0f * a);
+}
+
+// Leaf boxes of the light tree are pos +- (r + TR_LIGHT_KAPPA (|pos|inf + r)), and a ray widens every box it tests by TR_LIGHT_KAPPA |org|inf
+// more.  Why that is enough: hh is not the geometric sphere's root.  With v = oc as computed (v = org - pos', |pos' - pos| <= eps |org - pos|
+// per component, eps = 2^-24), a = |d|^2 (1 + 3 eps), b = 2 (v.d + e_b), |e_b| <= 3 eps |v||d|, c = |v|^2 - r^2 + e_c, |e_c| <= 4 eps (|v|^2 + r^2),
+// the computed disc is the exact 4 |d|^2 (r^2 - dist^2) (dist: pos' to the ray's line) plus an error E with |E| <= 16 eps 4 |d|^2 (|v|^2 + r^2)
+// (b^2 and 4ac are both up to 4 |d|^2 (|v|^2 + r^2) and each carries a few eps of it; far from the light they nearly cancel, which is
+// why a ray that misses the sphere can still report a root).  The exact root of the quadratic with that disc lies on a sphere about pos' of
+// radius sqrt(r^2 + E / (4 |d|^2)) <= r + 4 sqrt(eps) (|v| + r); rounding b, the square root, the subtraction and the division moves the
+// point org + hh d along the ray by at most ~10 eps (|v| + r) more.  So |org + hh d - pos|_2 <= r + (4 sqrt(eps) + 11 eps)(|v|_2 + r), and
+// with |v|_2 <= sqrt(3) (1 + eps) (|org|inf + |pos|inf) every coordinate of the point is within r + 1.692e-3 (|org|inf + |pos|inf + r) of
+// pos.  TR_LIGHT_KAPPA (common.h) = 2^-9 = 1.953e-3 leaves 15 % for the rounding of the stored boxes (outwards on the host) and of the widened origins here.
+// A box that contains the exact point is entered no later than hh (1 + 3 eps) and left no earlier than hh (1 - 3 eps); TR_SLAB_PAD covers
+// both, so every light whose hh the loop would accept is reached (tests/test_sphere_light_accel.py checks it against the oracle).
+// The bound assumes |d|^2 and the products stay in fp32's normal range (ray directions of a frame are unit vectors).
+#define TR_LIGHT_STACK TR_LDS_STACK     // the walk keeps its stack in the lane's LDS column, free once the triangles are done
+
+// Candidate light i with root hh against the best so far: selects, not a branch.
+TR_DEV void consider_light(float hh, int i, float tmin, float& best_t, int& best_light) {
+    const bool take = hh > 0 && hh > tmin && (hh < best_t || (hh == best_t && best_light >= 0 && i < best_light));
+    best_t = take ? hh : best_t;
+    best_light = take ? i : best_light;
+}
+
+template <bool COUNT>
+TR_DEV void sphere_light_loop(const SceneView& sv, f3 org, f3 dir, float tmin, float& best_t, int& best_light, TraceStats& st) {
+    for (uint i = 0; i < sv.point_light_count; ++i) {
+        const PointLight& pl = sv.point_lights[i];
+        float radius = pl.radius;
+        if (radius == 0.0f) continue;
+        if (COUNT) st.ltests++;
+        consider_light(sphere_light_root(org, dir, pl.pos, radius), (int)i, tmin, best_t, best_light);
+    }
+}
+
+// The walk of the tree.  Kept lean - one child box at a time, no sorting network, a loop the compiler does not unroll, its ray derived from
+// org / dir rather than the traversal's RayPre - so that it needs few registers next to what the kernel keeps live (a walk with the
+// triangle loop's four-box test and sort added spills to the closest-hit kernels).  Lights are rarely hit, so the walk has little to gain
+// from visiting near children first.  `best_t` is the triangle result; returns the winning light (-1: none) and its hh in `t`.  A full
+// stack reports overflow = 1 and the caller runs the loop.
+struct LightWalk { float t; int light; uint tests, nodes, overflow; };
+template <bool COUNT>
+TR_DEV LightWalk light_tree_walk(const PointLight* lights, const Bvh4Node* nodes, f3 org, f3 dir, float tmin, float best_t, int* lds_stack) {
+    int best_light = -1;
+    uint tests = 0, visits = 0;
+    bool overflow = false;
+    // every box widened by w: near planes move towards the ray, far planes away from it (the sign of the direction picks which is which).
+    // The ray's own RayPre is not kept alive for this: its values are org / dir again, in another order.
+    const float w = TR_LIGHT_KAPPA * fmaxf(fmaxf(fabsf(org.x), fabsf(org.y)), fabsf(org.z));
+    const f3 ip = F3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+    const uint nk = ((__float_as_uint(ip.x) >> 31) << 4) | ((32u | ((__float_as_uint(ip.y) >> 31) << 4)) << 8) | ((64u | ((__float_as_uint(ip.z) >> 31) << 4)) << 16);
+    const char* base = reinterpret_cast<const char*>(nodes);
+    int sp = 0, node = 0;
+    while (true) {
+        if (node >= 0) {
+            if (COUNT) visits++;
+            const uint t = (uint)node << 7;
+#pragma unroll 1
+            for (uint k = 0; k < 4; ++k) {
+                const uint ax = t + (nk & 0xFFu) + 4u * k, ay = t + ((nk >> 8) & 0xFFu) + 4u * k, az = t + (nk >> 16) + 4u * k;
+                const float nx = *reinterpret_cast<const float*>(base + ax), fx = *reinterpret_cast<const float*>(base + (ax ^ 16u));
+                const float ny = *reinterpret_cast<const float*>(base + ay), fy = *reinterpret_cast<const float*>(base + (ay ^ 16u));
+                const float nz = *reinterpret_cast<const float*>(base + az), fz = *reinterpret_cast<const float*>(base + (az ^ 16u));
+                const int c = *reinterpret_cast<const int*>(base + t + 96u + 4u * k);
+                const float wx = copysignf(w, ip.x), wy = copysignf(w, ip.y), wz = copysignf(w, ip.z);
+                const float t0 = fmaxf(fmaxf((nx - (org.x + wx)) * ip.x, (ny - (org.y + wy)) * ip.y), fmaxf((nz - (org.z + wz)) * ip.z, tmin));
+                const float t1 = fminf(fminf(fminf((fx - (org.x - wx)) * ip.x, (fy - (org.y - wy)) * ip.y), (fz - (org.z - wz)) * ip.z), best_t) * TR_SLAB_PAD;
+                if (t0 <= t1) {     // empty slots hold an inverted box and never pass
+                    if (sp < TR_LIGHT_STACK) lds_stack[sp * TR_BLOCK] = c;
+                    overflow = overflow || sp >= TR_LIGHT_STACK;
+                    sp = sp < TR_LIGHT_STACK ? sp + 1 : sp;
+                }
+            }
+        } else {
+            const int i = ~node;
+            const PointLight& pl = lights[i];
+            if (COUNT) tests++;
+            if (pl.radius != 0.0f) consider_light(sphere_light_root(org, dir, pl.pos, pl.radius), i, tmin, best_t, best_light);
+        }
+        if (sp == 0) break;
+        --sp;
+        node = lds_stack[sp * TR_BLOCK];
+    }
+    return {best_t, best_light, tests, visits, overflow ? 1u : 0u};
+}
+
+// The sphere lights of a closest-hit ray whose triangles are done: `best_t` is the closest triangle's t, or tmax without one.  Returns the
+// winning light (-1: none, the triangle result stands) and its hh, which is the hit's t and u.  The kernels call this after the triangle
+// traversal has returned and its hit is stored, with the ray read again from memory: nothing of the walk or of the light result is live
+// across the triangle loops (run inside them, the walk cost those loops spills).  The caller checks that the ray is finite, as the
+// traversal does.
+struct LightHit { float t; int light; };
+template <bool COUNT>
+TR_DEV LightHit trace_sphere_lights(const SceneView& sv, f3 org, f3 dir, float tmin, float best_t, int* lds_stack, TraceStats& st) {
+    int best_light = -1;
+    if (sv.point_light_count == 0) return {best_t, best_light};
+    bool fallback = light_tree_header(sv)->use_tree == 0u;
+    if (!fallback) {
+        const LightWalk lw = light_tree_walk<COUNT>(sv.point_lights, light_tree_nodes(sv), org, dir, tmin, best_t, lds_stack);
+        best_t = lw.t; best_light = lw.light;
+        if (COUNT) { st.ltests += lw.tests; st.lnodes += lw.nodes; st.lfallbacks += lw.overflow; }
+        fallback = lw.overflow != 0u;
+    }
+    // no tree, or a walk that ran out of stack: the loop over every light (same rule, so a partial walk before it changes nothing)
+    if (fallback) sphere_light_loop<COUNT>(sv, org, dir, tmin, best_t, best_light, st);
+    return {best_t, best_light};
+}
+
+// Closest hit over triangles, one ray per lane (sphere lights: trace_sphere_lights, called after it).  ALPHA_MODE 0: stochastic alpha keyed by `seed`
 // (shader/rt_common.rahit:15-24); 1: fixed cutoff 1e-4 (shader/rt_feature.rahit:17).
 template <int ALPHA_MODE, bool COUNT>
-TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
+TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
                               int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow);
 template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
-TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
+TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
                            int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
     if constexpr (TWO_LEVEL) {
-        trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, include_lights, seed, lds_stack, hit, st, overflow);
+        trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, seed, lds_stack, hit, st, overflow);
         return;
     }
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
@@ -423,24 +548,6 @@ TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, floa
             node = stk.pop(spill);
         }
         overflow += stk.overflow ? 1 : 0;
-    }
-    if (include_lights && finite_ray) {
-        for (uint i = 0; i < sv.point_light_count; ++i) {
-            const PointLight& pl = sv.point_lights[i];
-            float radius = pl.radius;
-            if (radius == 0.0f) continue;
-            f3 oc = org - pl.pos;
-            float a = dot(dir, dir);
-            float b = 2.0f * dot(oc, dir);
-            float c = dot(oc, oc) - radius * radius;
-            float disc = b * b - 4.0f * a * c;
-            if (disc < 0) continue;
-            float hh = (-b - sqrtf(disc)) / (2.0f * a);
-            if (hh > 0 && hh > tmin && hh < best_t) {
-                best_t = hh; found = true;
-                hit.instance_id = -1; hit.primitive_id = (int)i; hit.u = hh; hit.v = 0;
-            }
-        }
     }
     hit.t = found ? best_t : -1.0f;
 }
@@ -533,7 +640,7 @@ TR_DEV void instance_words(const InstanceFrame& fr, TriHit& tr) {
 }
 
 template <int ALPHA_MODE, bool COUNT>
-TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
+TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
                               int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
     float best_t = tmax;
@@ -609,24 +716,6 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
             }
         }
         overflow += stk.overflow ? 1 : 0;
-    }
-    if (include_lights && finite_ray) {
-        for (uint i = 0; i < sv.point_light_count; ++i) {
-            const PointLight& pl = sv.point_lights[i];
-            float radius = pl.radius;
-            if (radius == 0.0f) continue;
-            f3 oc = org - pl.pos;
-            float a = dot(dir, dir);
-            float b = 2.0f * dot(oc, dir);
-            float c = dot(oc, oc) - radius * radius;
-            float disc = b * b - 4.0f * a * c;
-            if (disc < 0) continue;
-            float hh = (-b - sqrtf(disc)) / (2.0f * a);
-            if (hh > 0 && hh > tmin && hh < best_t) {
-                best_t = hh; found = true;
-                hit.instance_id = -1; hit.primitive_id = (int)i; hit.u = hh; hit.v = 0;
-            }
-        }
     }
     hit.t = found ? best_t : -1.0f;
 }

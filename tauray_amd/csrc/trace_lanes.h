@@ -28,13 +28,12 @@ TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffe
     // (path_tracer.glsl:387-403; DESIGN.md on the any-hit hash)
     for (int b = 0; b < bounce; ++b) pcg(misc.x);
     HitRecord hit;
-    const bool include_lights = !(P.opt.hide_lights && bounce == 0);
     const uint before = st.nodes;
 #if TR_QUAD_SWITCH > 0
-    trace_closest_wave4<0, COUNT, TWO_LEVEL>(sv, valid, F3(o), F3(d), bounce == 0 ? 0.0f : P.opt.min_ray_dist, __builtin_huge_valf(), include_lights, misc.x,
+    trace_closest_wave4<0, COUNT, TWO_LEVEL>(sv, valid, F3(o), F3(d), bounce == 0 ? 0.0f : P.opt.min_ray_dist, __builtin_huge_valf(), misc.x,
                                   lds_stack, qc, hit, st, overflow);
 #else
-    if (valid) trace_closest4<0, COUNT, TWO_LEVEL>(sv, F3(o), F3(d), bounce == 0 ? 0.0f : P.opt.min_ray_dist, __builtin_huge_valf(), include_lights,
+    if (valid) trace_closest4<0, COUNT, TWO_LEVEL>(sv, F3(o), F3(d), bounce == 0 ? 0.0f : P.opt.min_ray_dist, __builtin_huge_valf(),
                                         misc.x, lds_stack, hit, st, overflow);
 #endif
     if (COUNT) st.cnodes += st.nodes - before;      // every lane: in the quad tail lane 0 of a quad counts for the quad's ray
@@ -48,7 +47,19 @@ TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffe
             dbg[8] = o.w; dbg[9] = d.w;
         }
     }
+    const float tri_t = hit.instance_id >= 0 ? hit.t : __builtin_huge_valf();
     pb.hit[id] = make_int4(hit.instance_id, hit.primitive_id, __float_as_int(hit.u), __float_as_int(hit.v));
+    if (!(P.opt.hide_lights && bounce == 0)) {
+        // sphere lights (trace.h trace_sphere_lights) once the triangle hit is stored, with the ray read again: neither the registers that
+        // brought it to the traversal nor the hit are held across its loops for this (the asm keeps the compiler from reusing the first load)
+        uint rid = id;
+        asm volatile("" : "+v"(rid));
+        const f3 lo = F3(pb.org_pdf[rid]), ld = F3(pb.dir_reg[rid]);
+        if (ray_is_finite(lo, ld)) {
+            const LightHit lh = trace_sphere_lights<COUNT>(sv, lo, ld, bounce == 0 ? 0.0f : P.opt.min_ray_dist, tri_t, lds_stack, st);
+            if (lh.light >= 0) pb.hit[rid] = make_int4(-1, lh.light, __float_as_int(lh.t), 0);
+        }
+    }
     rays++;
     TL(tl_misc(qc.tl, 5, tl_now() - tl_chunk);)
 }
@@ -113,6 +124,7 @@ TR_DEV void flush_trace_counters(const PtParams& P, const PathBuffers& pb, int o
             st.ph_node += __shfl_xor(st.ph_node, off); st.ph_tri += __shfl_xor(st.ph_tri, off); st.ph_node16 += __shfl_xor(st.ph_node16, off);
             st.ph_node8 += __shfl_xor(st.ph_node8, off); st.lv_node16 += __shfl_xor(st.lv_node16, off);
             st.ph_qnode += __shfl_xor(st.ph_qnode, off); st.ph_qtri += __shfl_xor(st.ph_qtri, off); st.cnodes += __shfl_xor(st.cnodes, off);
+            st.ltests += __shfl_xor(st.ltests, off); st.lnodes += __shfl_xor(st.lnodes, off); st.lfallbacks += __shfl_xor(st.lfallbacks, off);
             for (int b = 0; b < 8; ++b) st.ph_hist[b] += __shfl_xor(st.ph_hist[b], off);
             st.maxsp = max(st.maxsp, (uint)__shfl_xor(st.maxsp, off)); max_vis = max(max_vis, (uint)__shfl_xor(max_vis, off));
         }
@@ -125,6 +137,7 @@ TR_DEV void flush_trace_counters(const PtParams& P, const PathBuffers& pb, int o
             add64(pb.counters, CNT_PH_NODE, st.ph_node); add64(pb.counters, CNT_PH_TRI, st.ph_tri); add64(pb.counters, CNT_PH_NODE16, st.ph_node16);
             add64(pb.counters, CNT_PH_NODE8, st.ph_node8); add64(pb.counters, CNT_LV_NODE16, st.lv_node16);
             add64(pb.counters, CNT_PH_QNODE, st.ph_qnode); add64(pb.counters, CNT_PH_QTRI, st.ph_qtri); add64(pb.counters, CNT_CNODES, st.cnodes);
+            add64(pb.counters, CNT_LTESTS, st.ltests); add64(pb.counters, CNT_LNODES, st.lnodes); add64(pb.counters, CNT_LFALLBACKS, st.lfallbacks);
             for (int b = 0; b < 8; ++b) add64(pb.counters, CNT_PH_HIST + 2 * b, st.ph_hist[b]);
             atomicMax(&pb.counters[CNT_MAXSP], st.maxsp); atomicMax(&pb.counters[CNT_MAXVIS], max_vis);
         }

@@ -248,11 +248,11 @@ TR_DEV void quad_inherited_leaf(int q, int& pend, QuadStack& qs, int& qnode, boo
 // result as trace_closest4.
 // TWO_LEVEL: the two-level structure, traced by the per-lane loop to the end (trace.h trace_closest4_2l; no quad tail in this version).
 template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
-TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, bool include_lights, uint seed,
+TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, uint seed,
                                 int* lds_stack, const QuadCtx& qc, HitRecord& hit, TraceStats& st, int& overflow) {
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
     if constexpr (TWO_LEVEL) {
-        if (valid) trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, include_lights, seed, lds_stack, hit, st, overflow);
+        if (valid) trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, seed, lds_stack, hit, st, overflow);
         return;
     }
     float best_t = tmax, best_u = 0.0f, best_v = 0.0f;
@@ -445,25 +445,6 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
 
     bool found = best_inst != 0xFFFFFFFFu;
     if (found) { hit.instance_id = (int)best_inst; hit.primitive_id = (int)best_prim; hit.u = best_u; hit.v = best_v; }
-    if (include_lights && finite_ray) {
-        // rt_common_point_light.rint:11-17 / .rchit:10-15, shader/rt_common.glsl:36-51
-        for (uint i = 0; i < sv.point_light_count; ++i) {
-            const PointLight& pl = sv.point_lights[i];
-            float radius = pl.radius;
-            if (radius == 0.0f) continue;
-            f3 oc = org - pl.pos;
-            float a = dot(dir, dir);
-            float b = 2.0f * dot(oc, dir);
-            float c = dot(oc, oc) - radius * radius;
-            float disc = b * b - 4.0f * a * c;
-            if (disc < 0) continue;
-            float hh = (-b - sqrtf(disc)) / (2.0f * a);
-            if (hh > 0 && hh > tmin && hh < best_t) {
-                best_t = hh; found = true;
-                hit.instance_id = -1; hit.primitive_id = (int)i; hit.u = hh; hit.v = 0;
-            }
-        }
-    }
     hit.t = found ? best_t : -1.0f;
 #ifdef TR_QUAD_DEBUG
     hit.u = dbg_u; hit.v = dbg_v;      // what the ray looked like when the wave switched to quads

@@ -23,7 +23,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (AccelInfoC, AccelLayoutC, CountersC, DistributionC, PtOptionsC, SceneDescC, TimingsC, TonemapInfoC, TrhipError, check)
+from ._lib import (AccelInfoC, AccelLayoutC, CountersC, DistributionC, LightAccelInfoC, LightCountersC, PtOptionsC, SceneDescC, TimingsC,
+                   TonemapInfoC, TrhipError, check)
 from .distribution import (DISTRIBUTION_DUPLICATE, DISTRIBUTION_SCANLINE, DISTRIBUTION_SHUFFLED_STRIPS, DistributionParams,
                            get_device_distribution_params, get_distribution_target_size)
 from .scene import SceneDesc, build_alias_table
@@ -271,6 +272,24 @@ class SceneStage:
         check(_lib.lib().trhip_scene_get_accel_layout(self.ctx.h, C.byref(out)))
         return {name: getattr(out, name) for name, _ in AccelLayoutC._fields_}
 
+    def set_light_accel(self, mode: int):
+        """trhip_scene_set_light_accel: how closest-hit rays find sphere lights - _lib.LIGHT_ACCEL_AUTO (the default), LIGHT_ACCEL_LOOP or
+        LIGHT_ACCEL_TREE.  Kept over scenes; builds or drops the light tree now.  Hits do not depend on the mode."""
+        check(_lib.lib().trhip_scene_set_light_accel(self.ctx.h, int(mode)))
+
+    def light_accel(self) -> dict:
+        """trhip_scene_get_light_accel: requested mode and mode in effect, lights with a radius, lights / nodes / bytes of the tree, the
+        AUTO threshold and the ms of the last tree build or refit (last_was_refit: 1 refit, 0 build, -1 none)."""
+        out = LightAccelInfoC()
+        check(_lib.lib().trhip_scene_get_light_accel(self.ctx.h, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in LightAccelInfoC._fields_}
+
+    def update_lights(self, point_lights: np.ndarray, directional_lights: Optional[np.ndarray] = None):
+        """trhip_scene_update_lights: new light records, same counts; the light tree is refit (or rebuilt) before this returns."""
+        pl = np.ascontiguousarray(point_lights)
+        dl = np.ascontiguousarray(self.scene.directional_lights if directional_lights is None else directional_lights)
+        check(_lib.lib().trhip_scene_update_lights(self.ctx.h, pl.ctypes.data if len(pl) else None, len(pl), dl.ctypes.data if len(dl) else None, len(dl)))
+
     def pose(self, node_globals: dict, refit: bool = True):
         """New global transforms of the joint nodes (an animation step of the caller's): every skinned mesh is skinned again
         and the acceleration structure updated."""
@@ -493,6 +512,13 @@ class PathTracerStage:
 
     def reset_counters(self):
         check(_lib.lib().trhip_pt_reset_counters(self.h))
+
+    def light_counters(self) -> dict:
+        """trhip_pt_get_light_counters: sphere tests, light-tree node visits and walks that fell back to the loop (stack full), of the
+        closest-hit rays (counted under count_work)."""
+        c = LightCountersC()
+        check(_lib.lib().trhip_pt_get_light_counters(self.h, C.byref(c)))
+        return {n: int(getattr(c, n)) for n, _ in LightCountersC._fields_}
 
     def timings(self) -> dict:
         t = TimingsC()

@@ -267,6 +267,40 @@ def sponza_teapots(seed: int = 1, width: int = 1920, height: int = 1080, share_t
     return sponza_class(seed=seed, target_tris=1_000_000, teapots=50, width=width, height=height, share_teapot_mesh=share_teapot_mesh)
 
 
+def sponza_lights(n_lights: int, seed: int = 1, width: int = 1920, height: int = 1080) -> S.SceneDesc:
+    """`sponza_class` plus `n_lights` point and spot lights, for the sphere-light tree (trhip_scene_set_light_accel).  Radii are
+    log-uniform in [1e-3, 0.2] inside the atrium; about one light in ten has radius 0 (no sphere: not hit, still sampled), about one in
+    four is a spotlight (they follow the point lights, `spotlight_base`), and up to four tiny lights (radius 1e-3 .. 1e-2) sit 100 to
+    1000 units outside the hall, where the fp32 sphere test reports hits well outside the sphere.  Light powers
+    are scaled by 1 / n_lights so that the image keeps its brightness.  Deterministic for (n_lights, seed)."""
+    desc = sponza_class(seed, 260_000, 0, width, height)
+    rng = np.random.default_rng([seed, n_lights, 0x11647])
+    LX, LY, LZ = 30.0, 12.0, 14.0
+    n_far = min(4, n_lights // 8)
+    n_spot = n_lights // 4
+    points, spots = [], []
+    for k in range(n_lights):
+        far = k >= n_lights - n_far
+        if far:
+            d = rng.normal(size=3)
+            pos = d / np.linalg.norm(d) * rng.uniform(100.0, 1000.0)
+            radius = float(np.exp(rng.uniform(math.log(1e-3), math.log(1e-2))))
+        else:
+            pos = np.array([rng.uniform(-LX / 2 + 0.3, LX / 2 - 0.3), rng.uniform(0.3, LY - 0.3), rng.uniform(-LZ / 2 + 0.3, LZ / 2 - 0.3)])
+            radius = 0.0 if rng.uniform() < 0.1 else float(np.exp(rng.uniform(math.log(1e-3), math.log(0.2))))
+        color = tuple(float(c) for c in rng.uniform(0.5, 1.0, 3) * (40.0 / max(n_lights, 1)))
+        if not far and k < n_spot:
+            d = rng.normal(size=3)
+            d[1] = -abs(d[1]) - 0.5
+            spots.append(S.make_spotlight(color, tuple(pos), tuple(d), radius, float(rng.uniform(20.0, 60.0)), float(rng.uniform(1.0, 8.0))))
+        else:
+            points.append(S.make_point_light(color, tuple(pos), radius))
+    desc.point_lights = np.concatenate(points + spots) if n_lights else np.zeros(0, dtype=S.POINT_LIGHT)
+    desc.spotlight_base = len(points)
+    desc.name = f"sponza_lights(n_lights={n_lights}, seed={seed})"
+    return desc
+
+
 def scene_hash(desc: S.SceneDesc) -> str:
     h = hashlib.sha256()
     for a in (desc.instances, desc.spans, desc.vertices, desc.indices, desc.directional_lights, desc.point_lights):
