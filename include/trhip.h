@@ -425,6 +425,22 @@ int trhip_pt_get_phase_counters(trhip_pt* pt, trhip_phase_counters* out);   /* s
  * that ran out of their 16-entry stack and tested every light in the loop instead (same hits, the loop's cost). */
 typedef struct trhip_light_counters { uint64_t sphere_tests, node_visits, walk_fallbacks; } trhip_light_counters;
 int trhip_pt_get_light_counters(trhip_pt* pt, trhip_light_counters* out);   /* synchronises the stream */
+/* The last bounce as a first-hit emitter query.  Every path ends at bounce max_bounces - 1, where a surface hit can
+ * only add the emission of what was hit, so the last ray of a path needs to know whether it escapes, whether the nearest thing along it is
+ * an emitter triangle, or that something else is in the way - and then neither what nor where.
+ *   TRHIP_TERMINAL_QUERY_AUTO (the default): the launches of that bounce are the query while the structure is all-merged, max_bounces >= 2,
+ *     the scene has at most `threshold` emitter triangles and no sphere light with a radius; otherwise, and under
+ *   TRHIP_TERMINAL_QUERY_OFF, they are the closest-hit launches of every other bounce.
+ * Frames, ray counts and surface-hit counts do not depend on the mode.  Until it is set, TRHIP_TERMINAL_QUERY=auto|off chooses it
+ * (A/B tools; any other value fails trhip_pt_render). */
+#define TRHIP_TERMINAL_QUERY_AUTO 0
+#define TRHIP_TERMINAL_QUERY_OFF 1
+int trhip_pt_set_terminal_query(trhip_pt* pt, int mode);
+/* in_effect: what the stage's next frame does.  blocked_rays / fallback_rays: rays of the query that ended at something in front of the
+ * nearest emitter, and rays it traced as ordinary closest hits because their path state fails the query's range check; cumulative like
+ * trhip_counters, only counted while work counting is on, cleared by trhip_pt_reset_counters. */
+typedef struct trhip_terminal_counters { uint64_t blocked_rays, fallback_rays; uint32_t in_effect, emitter_triangles, threshold, pad; } trhip_terminal_counters;
+int trhip_pt_get_terminal_counters(trhip_pt* pt, trhip_terminal_counters* out);   /* synchronises the stream */
 /* Peak vector-instruction issue rate of the device as it runs now: a loop of independent v_fma_f32 at eight waves per SIMD,
  * in 10^9 wave-level instructions per second (MI355X_MICROARCH.md: 2 cycles per wave64 instruction on a SIMD-32; the clock is
  * what the box sustains).  The peak of the VALU roofline in bench.py; about 2 ms of device time. */
@@ -449,6 +465,12 @@ int trhip_feature_render(trhip_device* dev, int feature, const trhip_distributio
  * entries of its quad tails per device): enqueue them on one stream, or order the streams with trhip_stream_wait. */
 int trhip_trace_closest(trhip_device* dev, uint32_t n, const void* rays_dev, const void* seeds_dev,
                         int include_lights, void* hits_dev, void* stream);
+/* The terminal query (trhip_pt_set_terminal_query) for a list of rays: hits as above, except that a ray with an accepted hit in front of
+ * its nearest accepted emitter triangle reports instance -2 and nothing else (blocked).  fallback: NULL, or one uint32 per ray, nonzero =
+ * trace this ray as an ordinary closest hit (what a frame does with a path outside the query's range check).  Fails unless the structure
+ * is all-merged and holds at most the threshold's emitter triangles; sphere lights are not looked at. */
+int trhip_trace_terminal(trhip_device* dev, uint32_t n, const void* rays_dev, const void* seeds_dev, const void* fallback_dev,
+                         void* hits_dev, void* stream);
 int trhip_trace_shadow(trhip_device* dev, uint32_t n, const void* rays_dev, void* visibility_dev, void* stream);
 
 /* ---- stitch_stage (src/stitch_stage.cc:128-196, shader/stitch_scanline.comp, stitch_shuffled_strips.comp).

@@ -65,6 +65,17 @@ class LightCountersC(C.Structure):
 LIGHT_ACCEL_AUTO, LIGHT_ACCEL_LOOP, LIGHT_ACCEL_TREE = 0, 1, 2
 
 
+class TerminalCountersC(C.Structure):
+    """trhip_terminal_counters: blocked and fallback rays of the terminal query, whether it is in effect, the emitter set's size."""
+    _fields_ = [("blocked_rays", C.c_uint64), ("fallback_rays", C.c_uint64), ("in_effect", C.c_uint32), ("emitter_triangles", C.c_uint32),
+                ("threshold", C.c_uint32), ("pad", C.c_uint32)]
+
+
+# trhip_pt_set_terminal_query
+TERMINAL_QUERY_AUTO, TERMINAL_QUERY_OFF = 0, 1
+HIT_BLOCKED = -2      # instance_id of a blocked ray in the hits of trhip_trace_terminal
+
+
 class PtOptionsC(C.Structure):
     """== path_tracer_stage::options (reference src/path_tracer_stage.hh:13-30), flattened."""
     _fields_ = [
@@ -147,6 +158,9 @@ SYMBOLS = {
     "trhip_scene_set_light_accel": (_i, [_vp, _i]),
     "trhip_scene_get_light_accel": (_i, [_vp, C.POINTER(LightAccelInfoC)]),
     "trhip_pt_get_light_counters": (_i, [_vp, C.POINTER(LightCountersC)]),
+    "trhip_pt_set_terminal_query": (_i, [_vp, _i]),
+    "trhip_pt_get_terminal_counters": (_i, [_vp, C.POINTER(TerminalCountersC)]),
+    "trhip_trace_terminal": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "trhip_stitch_batch": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, C.c_float, _vp]),
     "trhip_stream_create": (_i, [_vp, C.POINTER(C.c_void_p)]),
     "trhip_stream_destroy": (_i, [_vp, _vp]),

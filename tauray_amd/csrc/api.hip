@@ -158,6 +158,33 @@ __global__ __launch_bounds__(KB) void k_query_closest(SceneView sv, uint n, cons
     }
     if (overflow) *overflow_flag = 1;
 }
+// The terminal query (trace_quad.h trace_closest_wave4<.., TERMINAL>) for a list of rays
+__global__ __launch_bounds__(KB) void k_query_terminal(SceneView sv, uint n, const float* rays, const uint* seeds, const uint* fallback, HitRecord* out, uint* overflow_flag,
+                                                       int* qspill) {
+    __shared__ int s_stack_rows[TR_STACK_WORDS];
+    int* const s_stack = s_stack_rows + TR_STACK_ROW0;     // row -1 exists (LaneStack, trace.h)
+    __shared__ int s_owner[(KB / 64) * TR_OWNER_WORDS];
+    int* my_stack = s_stack + threadIdx.x;
+    QuadCtx qc;
+    qc.wave_stack = s_stack + (threadIdx.x & ~63u);
+    qc.owner_tab = s_owner + (threadIdx.x >> 6) * TR_OWNER_WORDS;
+    qc.spill = qspill + ((size_t)blockIdx.x * (KB / 64) + (threadIdx.x >> 6)) * (16u * TR_QSPILL);
+    int overflow = 0;
+    TraceStats st = {};
+    for (uint base = blockIdx.x * KB; base < n; base += gridDim.x * KB) {
+        const uint i = base + threadIdx.x;
+        const bool valid = i < n;
+        float r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (valid) for (int k = 0; k < 8; ++k) r[k] = rays[(size_t)i * 8 + k];
+        const uint seed = (valid && seeds) ? seeds[i] : 0u;
+        TerminalRay term = {valid && !(fallback && fallback[i] != 0u), false};
+        HitRecord hit;
+        if (seeds) trace_closest_wave4<0, false, false, true>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], seed, my_stack, qc, hit, st, overflow, &term);
+        else trace_closest_wave4<1, false, false, true>(sv, valid, F3(r[0], r[1], r[2]), F3(r[4], r[5], r[6]), r[3], r[7], 0u, my_stack, qc, hit, st, overflow, &term);
+        if (valid) out[i] = term.blocked ? HitRecord{TR_HIT_BLOCKED, -1, 0.0f, 0.0f, -1.0f} : hit;
+    }
+    if (overflow) *overflow_flag = 1;
+}
 template <bool TWO_LEVEL>
 __global__ __launch_bounds__(KB) void k_query_shadow(SceneView sv, uint n, const float* rays, float* out, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
@@ -847,6 +874,20 @@ int trhip_pt_get_light_counters(trhip_pt* pt, trhip_light_counters* out) {
     DEVCHK(pt->dev);
     return pt->stage->get_light_counters(out, pt->stage->last_stream);
 }
+int trhip_pt_set_terminal_query(trhip_pt* pt, int mode) {
+    if (!pt) return set_error("null trhip_pt");
+    if (mode != TRHIP_TERMINAL_QUERY_AUTO && mode != TRHIP_TERMINAL_QUERY_OFF)
+        return set_error("trhip_pt_set_terminal_query: unknown mode " + std::to_string(mode) + " (0 auto, 1 off)");
+    pt->stage->terminal_query = mode;
+    return 0;
+}
+int trhip_pt_get_terminal_counters(trhip_pt* pt, trhip_terminal_counters* out) {
+    if (!pt) return set_error("null trhip_pt");
+    if (!out) return set_error("trhip_pt_get_terminal_counters: null output");
+    DEVCHK(pt->dev);
+    if (pt->stage->terminal_query_in_effect() < 0) return set_error("trhip_pt_get_terminal_counters: TRHIP_TERMINAL_QUERY is not auto or off");
+    return pt->stage->get_terminal_counters(out, pt->stage->last_stream);
+}
 int trhip_pt_reset_counters(trhip_pt* pt) { if (!pt) return set_error("null trhip_pt"); DEVCHK(pt->dev); HIPCHK(hipStreamSynchronize(pt->stage->last_stream)); return pt->stage->reset_counters(); }
 int trhip_pt_get_timings(trhip_pt* pt, trhip_timings* out) { if (!pt) return set_error("null trhip_pt"); DEVCHK(pt->dev); return pt->stage->get_timings(out); }
 int trhip_pt_get_program(trhip_pt* pt, trhip_program_info* out) { if (!pt) return set_error("null trhip_pt"); if (!out) return set_error("trhip_pt_get_program: null out"); DEVCHK(pt->dev); return pt->stage->get_program(out); }
@@ -938,6 +979,20 @@ int trhip_trace_closest(trhip_device* dev, uint32_t n, const void* rays_dev, con
     if (!dev->qspill) HIPCHK(hipMalloc(&dev->qspill, (size_t)QUERY_BLOCKS * (KB / 64) * 16u * TR_QSPILL * sizeof(int)));
     hipLaunchKernelGGL(dev->scene.two_level ? k_query_closest<true> : k_query_closest<false>, dim3(blocks), dim3(KB), 0, (hipStream_t)stream, dev->scene.view(), n, (const float*)rays_dev,
                        (const uint*)seeds_dev, include_lights, (HitRecord*)hits_dev, dev->overflow_flag, dev->qspill);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int trhip_trace_terminal(trhip_device* dev, uint32_t n, const void* rays_dev, const void* seeds_dev, const void* fallback_dev, void* hits_dev, void* stream) {
+    DEVCHK(dev);
+    const DeviceScene& s = dev->scene;
+    if (!s.accel_built) return set_error("trhip_trace_terminal: call trhip_scene_build_accel first");
+    if (s.two_level || !s.tris) return set_error("trhip_trace_terminal: the terminal query walks an all-merged structure");
+    if (s.emitter_count > TR_EMITTER_MAX) return set_error("trhip_trace_terminal: " + std::to_string(s.emitter_count) + " emitter triangles, the query tests at most " + std::to_string(TR_EMITTER_MAX));
+    if (n == 0) return 0;
+    uint blocks = std::min((n + KB - 1) / KB, QUERY_BLOCKS);
+    if (!dev->qspill) HIPCHK(hipMalloc(&dev->qspill, (size_t)QUERY_BLOCKS * (KB / 64) * 16u * TR_QSPILL * sizeof(int)));
+    hipLaunchKernelGGL(k_query_terminal, dim3(blocks), dim3(KB), 0, (hipStream_t)stream, s.view(), n, (const float*)rays_dev, (const uint*)seeds_dev, (const uint*)fallback_dev,
+                       (HitRecord*)hits_dev, dev->overflow_flag, dev->qspill);
     HIPCHK(hipGetLastError());
     return 0;
 }

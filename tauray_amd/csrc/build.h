@@ -105,6 +105,9 @@ struct DeviceScene {
     uint light_tree_nodes = 0;
     float light_ms = 0.0f;
     int light_last_refit = -1;
+    uint sphere_light_count() const { uint c = 0; for (const PointLight& pl : host_point_lights) c += pl.radius != 0.0f ? 1u : 0u; return c; }
+    // ---- emitter set of the terminal query (common.h EmitterSet): behind the records in `tris`, all-merged structure only
+    uint emitter_count = 0xFFFFFFFFu;           // emitter triangles of the last build or refit; 0xFFFFFFFF = no set
 
     SceneView view() const {
         SceneView v;
@@ -131,6 +134,7 @@ struct DeviceScene {
         tlas = nullptr; tlas_src_leaves = nullptr; tlas_capacity = 0; node_capacity = 0; tri_capacity = 0; two_level = false;
         blases.clear(); inst_blas.clear(); tlas_src.clear(); blas_dirty.clear(); static_dirty = false;
         nodes = nullptr; nodes4 = nullptr; tris = nullptr; tri_lights = nullptr; node_count = 0; tri_light_count = 0; accel_built = false;
+        emitter_count = 0xFFFFFFFFu;
         accel_capacity = 0xFFFFFFFFu;
         if (level_nodes) (void)hipFree(level_nodes);
         if (node_bounds) (void)hipFree(node_bounds);

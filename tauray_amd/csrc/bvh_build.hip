@@ -499,6 +499,41 @@ __global__ __launch_bounds__(BT) void k_extract_tri_lights(SceneView sv, const u
     out[(uint)o.light_base_id + prim] = l;
 }
 
+// The emitter set of the terminal query (common.h EmitterSet), from the records the tree's leaves hold: which of
+// them belong to an instance that emits (or that tri-light sampling knows, whatever its emission), ...
+__global__ __launch_bounds__(BT) void k_emitter_gather(const Instance* instances, const TriRecord* tris, uint n, EmitterSet* es) {
+    const uint i = blockIdx.x * BT + threadIdx.x;
+    if (i >= n) return;
+    const Instance& o = instances[tris[i].inst_flags & 0x7FFFFFFFu];
+    const f4 e = o.mat.emission_factor;
+    if (!(e.x != 0.0f || e.y != 0.0f || e.z != 0.0f || o.light_base_id >= 0)) return;
+    const uint slot = atomicAdd(&es->count, 1u);
+    if (slot < TR_EMITTER_MAX) es->index[slot] = i;
+}
+// ... then, one thread: the list in ascending order and the union box of its triangles (exact minima and maxima of the records' vertices)
+__global__ void k_emitter_finish(const TriRecord* tris, EmitterSet* es) {
+    const uint c = es->count <= TR_EMITTER_MAX ? es->count : 0u;      // above the threshold the query does not run: an empty box
+    for (uint a = 1; a < c; ++a) {
+        const uint v = es->index[a];
+        uint b = a;
+        for (; b > 0 && es->index[b - 1] > v; --b) es->index[b] = es->index[b - 1];
+        es->index[b] = v;
+    }
+    float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()}, hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+    for (uint a = 0; a < c; ++a) {
+        const TriRecord& t = tris[es->index[a]];
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = fminf(fminf(lo[k], t.v0[k]), fminf(t.v1[k], t.v2[k]));
+            hi[k] = fmaxf(fmaxf(hi[k], t.v0[k]), fmaxf(t.v1[k], t.v2[k]));
+        }
+    }
+    for (int k = 0; k < 3; ++k)
+        for (int slot = 0; slot < 4; ++slot) {      // a Bvh4Node's planes: lo of axis k at 8 k, hi at 8 k + 4; the box sits in slot 0
+            es->planes[8 * k + slot] = slot == 0 ? lo[k] : __builtin_huge_valf();
+            es->planes[8 * k + 4 + slot] = slot == 0 ? hi[k] : -__builtin_huge_valf();
+        }
+}
+
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 }  // namespace
@@ -520,6 +555,20 @@ __global__ __launch_bounds__(BT) void k_pre_transform_vertices(uint vertex_count
     v.tangent = F4(t, v.tangent.w);
     if (det < 0) { v.normal = -v.normal; v.tangent = F4(-t.x, -t.y, -t.z, -v.tangent.w); }
     out[i] = v;
+}
+
+// After a build or a refit of the all-merged structure (an instance update makes one of the two necessary, so a changed material is seen)
+static int gather_emitters(DeviceScene& ds, hipStream_t stream) {
+    ds.emitter_count = 0xFFFFFFFFu;
+    if (!ds.tris || ds.leaf_count != ds.tri_count) return 0;
+    EmitterSet* es = reinterpret_cast<EmitterSet*>(ds.tris + ds.tri_count);
+    HIPCHK(hipMemsetAsync(es, 0, sizeof(EmitterSet), stream));
+    hipLaunchKernelGGL(k_emitter_gather, dim3((ds.tri_count + BT - 1) / BT), dim3(BT), 0, stream, ds.instances, ds.tris, ds.tri_count, es);
+    hipLaunchKernelGGL(k_emitter_finish, dim3(1), dim3(1), 0, stream, ds.tris, es);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&ds.emitter_count, &es->count, sizeof(uint), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
 }
 
 int ensure_world_vertices(DeviceScene& ds, hipStream_t stream) {
@@ -787,6 +836,7 @@ int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
         SceneView sv2 = ds.view();
         hipLaunchKernelGGL(k_extract_tri_lights, dim3((ds.tri_count + BT - 1) / BT), dim3(BT), 0, stream, sv2, ds.tri_prefix, ds.tri_lights);
     }
+    if (int rc = gather_emitters(ds, stream)) return rc;
     HIPCHK(hipEventRecord(e1, stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0;
@@ -1205,7 +1255,7 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
     }
     if (ds.accel_capacity != n_cap) {   // outputs
         ds.free_accel();
-        if (n_cap > 0) HIPCHK(hipMalloc(&ds.tris, (size_t)n_cap * sizeof(TriRecord)));
+        if (n_cap > 0) HIPCHK(hipMalloc(&ds.tris, (size_t)n_cap * sizeof(TriRecord) + sizeof(EmitterSet)));      // the emitter set sits behind the records
         if (n1 > 0) {
             // traversal addresses a node's planes with 32-bit byte offsets (node << 7 | plane)
             if ((uint64_t)n1 * sizeof(Bvh4Node) > 0xFFFFFFFFull) return set_error("trhip_scene_build_accel: more than 2^25 nodes");
@@ -1233,6 +1283,7 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
         hipLaunchKernelGGL(k_extract_tri_lights, dim3((n_tri + BT - 1) / BT), dim3(BT), 0, stream, sv2, ds.tri_prefix, ds.tri_lights);
         HIPCHK(hipGetLastError());
     }
+    if (int rc = gather_emitters(ds, stream)) return rc;
     HIPCHK(hipEventRecord(e1, stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0;

@@ -260,4 +260,19 @@ TR_HD const Bvh4Node* light_tree_nodes(const SceneView& sv) {
     return reinterpret_cast<const Bvh4Node*>(reinterpret_cast<const char*>(sv.point_lights) + light_tree_node_offset(sv.point_light_count));
 }
 
+
+// Emitter set of the terminal query (trhip_pt_set_terminal_query), all-merged structure only: behind the tri_count
+// records of the `tris` allocation.  An emitter triangle is a triangle of an instance whose emission_factor.xyz is not zero or whose
+// light_base_id is not negative - every triangle the last bounce of a path could collect light or a light pdf from.  `index` holds the
+// places of the first TR_EMITTER_MAX of them in SceneView::tris, ascending; `count` counts them all (the query runs only while count <=
+// TR_EMITTER_MAX).  `planes` is their union box in the first slot of a Bvh4Node's plane layout (the other slots are never read), so
+// that a ray picks its near and far planes with the byte offsets it walks the tree with; an empty set holds an inverted box.
+//
+// TR_EMITTER_MAX = 16: the issue's starting value.  The sweep that would set it (sponza_lights-style scenes with more emissive quads
+// until the query launch is slower than the closest-hit launch) has not been run; profiles/r9/terminal_query.txt says so.
+#define TR_EMITTER_MAX 16
+struct alignas(16) EmitterSet { float planes[24]; uint count, pad[3]; uint index[TR_EMITTER_MAX]; };
+static_assert(sizeof(EmitterSet) == 176 && sizeof(TriRecord) % 16 == 0, "emitter set layout");
+TR_HD const EmitterSet* emitter_set(const SceneView& sv) { return reinterpret_cast<const EmitterSet*>(sv.tris + sv.tri_count); }
+
 }  // namespace tr

@@ -27,7 +27,9 @@ public:
     int get_timings(trhip_timings* out);
     int get_phase_counters(trhip_phase_counters* out, hipStream_t stream);
     int get_light_counters(trhip_light_counters* out, hipStream_t stream);
+    int get_terminal_counters(trhip_terminal_counters* out, hipStream_t stream);
     int get_program(trhip_program_info* out);
+    int terminal_query_in_effect() const;
 
     DeviceScene* scene;
     trhip_pt_options opt;
@@ -46,6 +48,7 @@ public:
     uint frame_batch = 1;            // trhip_pt_set_frame_batch: consecutive frames per render() call
     int ieee_shading = -1;           // trhip_pt_set_shading_arithmetic: 1 = k_shade at IEEE fp32 for every option set, 0 = Vulkan-grade arithmetic for the command-line set, -1 = TRHIP_SHADE_FAST decides
     int specialize = -1;             // trhip_pt_set_specialization: 1 = a shading program compiled for this stage's option set (hipRTC / kernel cache), 0 = the general kernels, -1 = TRHIP_SPECIALIZE decides (default on)
+    int terminal_query = -1;         // trhip_pt_set_terminal_query: TRHIP_TERMINAL_QUERY_AUTO / _OFF, -1 = TRHIP_TERMINAL_QUERY decides (default auto)
     bool direct = false;             // direct_stage instead of path_tracer_stage (trhip_direct_create)
     hipStream_t last_stream = nullptr;
 

@@ -46,7 +46,7 @@ struct PathBuffers {
 // (measured: 0.83 ms instead of 0.56 ms for one k_shade launch of 2 M paths).
 enum { BC_QUEUE = 0, BC_SHADOW = 64, BC_CUR_CLOSEST = 128, BC_CUR_SHADOW = 192, BC_STRIDE = 256 };
 enum { CNT_OVERFLOW = 2, CNT_CLOSEST = 4, CNT_SHADOWRAYS = 6, CNT_NODES = 8, CNT_TRIS = 10, CNT_ALPHA = 12, CNT_SURF = 14, CNT_MAXVIS = 16, CNT_DBG = 17,
-       CNT_MAXSP = 30, CNT_CNODES = 32, CNT_PH_NODE = 34, CNT_PH_TRI = 36, CNT_PH_NODE16 = 38, CNT_PH_NODE8 = 40, CNT_LV_NODE16 = 42, CNT_PH_QNODE = 44, CNT_PH_QTRI = 46, CNT_PH_HIST = 48, CNT_LTESTS = 64, CNT_LNODES = 66, CNT_LFALLBACKS = 68, CNT_WORDS = 70 };   // statistics of a lane; queue lengths and work cursors live in PathBuffers::bounce
+       CNT_MAXSP = 30, CNT_CNODES = 32, CNT_PH_NODE = 34, CNT_PH_TRI = 36, CNT_PH_NODE16 = 38, CNT_PH_NODE8 = 40, CNT_LV_NODE16 = 42, CNT_PH_QNODE = 44, CNT_PH_QTRI = 46, CNT_PH_HIST = 48, CNT_LTESTS = 64, CNT_LNODES = 66, CNT_LFALLBACKS = 68, CNT_TQ_BLOCKED = 70, CNT_TQ_FALLBACK = 72, CNT_WORDS = 74 };   // statistics of a lane; queue lengths and work cursors live in PathBuffers::bounce
 
 struct PtParams {
     trhip_pt_options opt;

@@ -87,6 +87,27 @@ TR_DEV bool leaf_is_pair(uint complemented_ref) { return TR_PAIR_LEAVES && (comp
 #define TR_LEAF_MEMBERS(ref, more) constexpr uint member = 0;
 #endif
 
+// A ray of the terminal query (trace_quad.h trace_closest_wave4<.., TERMINAL>).  `early`: the ray may end at the first accepted candidate
+// that replaces its best so far (false: an ordinary closest hit, the per-ray fallback).  `blocked`: it did.
+struct TerminalRay { bool early, blocked; };
+// HitRecord::instance_id of a blocked ray in the output of k_query_terminal (a frame's blocked paths get no record at all)
+#define TR_HIT_BLOCKED (-2)
+
+// The per-ray fallback predicate.  A blocked path is dropped because its last k_shade pass would add exactly nothing: for a hit on a
+// triangle that is not in the emitter set, mat.emission, every light term and every light pdf are zero, so
+//     light = (attenuation / bsdf_pdf) * mis_weight * 0,      mis_weight = bsdf_pdf / ((0 * 0 + bsdf_pdf * bsdf_pdf) / bsdf_pdf)  (power heuristic)
+// which is +-0 - and not written - exactly when the two factors are finite.  With 2^-40 <= bsdf_pdf <= 2^40 the square stays in
+// [2^-80, 2^80] (no overflow to inf, no underflow to 0), mis_pdf is bsdf_pdf to a few ulps in either shading arithmetic and
+// mis_weight is 1 to a few ulps (balance heuristic and no MIS: exactly bsdf_pdf, weight 1); with |attenuation| <= 2^40 per
+// component the quotient is at most 2^80 (1 + a few ulps).  bsdf_pdf == 0 skips the division and the weight (mis_weight = 1), and
+// the attenuation bound alone keeps the product finite.  The comparisons are false for NaN, so a NaN in either sends the ray down
+// the fallback.  clamp_contribution_mul of a zero light returns 1.
+TR_DEV bool terminal_early_ok(float bsdf_pdf, f3 attenuation) {
+    const float lo = 9.094947017729282e-13f, hi = 1099511627776.0f;      // 2^-40, 2^40
+    const bool pdf_ok = bsdf_pdf == 0.0f || (bsdf_pdf >= lo && bsdf_pdf <= hi);
+    return pdf_ok && fabsf(attenuation.x) <= hi && fabsf(attenuation.y) <= hi && fabsf(attenuation.z) <= hi;
+}
+
 // What a triangle test hands back: the candidate and the words of the record behind the vertices.
 struct TriHit { float t, bu, bv; uint inst_flags, prim, alpha; };
 

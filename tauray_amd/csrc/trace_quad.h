@@ -22,6 +22,15 @@ namespace tr {
 #ifndef TR_QUAD_VOTE
 #define TR_QUAD_VOTE 4         // lanes holding a triangle at which the quads of a wave run a triangle phase (2 / 4 / 8 / 16 measured)
 #endif
+// Open choices of the terminal query (A/B in profiles/r9/terminal_query.txt).  TR_TERMINAL_SLOT_ORDER: its per-lane
+// loop descends in slot order like the shadow loop (1, measured 1.4 % of a frame faster) or nearest child first like the closest-hit loop
+// (0).  TR_TERMINAL_QUADS: the quad tail (1), or one ray per lane to the end (0, measured 1.3 % slower).
+#ifndef TR_TERMINAL_SLOT_ORDER
+#define TR_TERMINAL_SLOT_ORDER 1
+#endif
+#ifndef TR_TERMINAL_QUADS
+#define TR_TERMINAL_QUADS 1
+#endif
 #define TR_QSPILL TR_SPILL_STACK   // stack entries per quad beyond the LDS part: the per-lane loop's depth (deepest stack seen on the bench scenes: 26)
 static_assert(TR_QUAD_SWITCH <= 16, "a wave has sixteen quads");
 
@@ -247,9 +256,11 @@ TR_DEV void quad_inherited_leaf(int q, int& pend, QuadStack& qs, int& qnode, boo
 // Closest hit for the rays of one wave.  Every lane of the wave calls this (`valid` = the lane has a ray); parameters and
 // result as trace_closest4.
 // TWO_LEVEL: the two-level structure, traced by the per-lane loop to the end (trace.h trace_closest4_2l; no quad tail in this version).
-template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
+// TERMINAL: the first-hit emitter query of a path's last ray (trace.h TerminalRay; all-merged structure only).
+template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false, bool TERMINAL = false>
 TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, uint seed,
-                                int* lds_stack, const QuadCtx& qc, HitRecord& hit, TraceStats& st, int& overflow) {
+                                int* lds_stack, const QuadCtx& qc, HitRecord& hit, TraceStats& st, int& overflow, TerminalRay* term = nullptr) {
+    static_assert(!(TERMINAL && TWO_LEVEL), "the terminal query walks the all-merged structure");
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
     if constexpr (TWO_LEVEL) {
         if (valid) trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, seed, lds_stack, hit, st, overflow);
@@ -267,9 +278,22 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
     TL(const unsigned long long tl_enter = tl_now(), tl_wall0 = tl_wall();)
 
     // candidate of a triangle test against the lane's best so far (shader/rt_common.rahit:15-24 for non-opaque geometry)
-    auto consider = [&](const TriHit& tr, float t, float bu, float bv) {
+    // TERMINAL: returns whether the candidate replaced the best so far
+    auto consider = [&](const TriHit& tr, float t, float bu, float bv) -> bool {
         const uint inst = tr.inst_flags & 0x7FFFFFFFu;
         const bool closer = t < best_t || (t == best_t && best_inst != 0xFFFFFFFFu && (inst < best_inst || (inst == best_inst && tr.prim < best_prim)));
+        if constexpr (TERMINAL) {      // selects, not `if (accept)` (see the quad tail below)
+            bool accept = closer;
+            if (accept && (tr.inst_flags & 0x80000000u)) {
+                if (COUNT) st.alpha++;
+                const float a = candidate_alpha(sv, tr.alpha, bu, bv);
+                const float cutoff = ALPHA_MODE == 0 ? alpha_cutoff_hash(seed, (int)inst, (int)tr.prim) : 0.0001f;
+                accept = !(a <= cutoff);
+            }
+            best_t = accept ? t : best_t; best_u = accept ? bu : best_u; best_v = accept ? bv : best_v;
+            best_inst = accept ? inst : best_inst; best_prim = accept ? tr.prim : best_prim;
+            return accept;
+        }
         if (closer) {
             bool accept = true;
             if (tr.inst_flags & 0x80000000u) {
@@ -280,12 +304,38 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
             }
             if (accept) { best_t = t; best_inst = inst; best_prim = tr.prim; best_u = bu; best_v = bv; }
         }
+        return false;
     };
+
+    // ---- TERMINAL prelude: the nearest accepted emitter triangle becomes the best so far, i.e. the walk's culling bound and tie holder.
+    // The emitters' union box is one more box around those triangles, tested like a node's (TR_SLAB_PAD as there).  The loop over the
+    // list is wave-uniform; a lane outside the box sits it out.
+    bool early = false, blocked = false;
+    if constexpr (TERMINAL) {
+        early = term->early;
+        const EmitterSet* es = emitter_set(sv);
+        const uint n_emit = es->count;
+        if (n_emit > 0 && live) {
+            const char* base = reinterpret_cast<const char*>(es);
+            const float nx = *reinterpret_cast<const float*>(base + r.nkx), fx = *reinterpret_cast<const float*>(base + (r.nkx ^ 16u));
+            const float ny = *reinterpret_cast<const float*>(base + r.nky), fy = *reinterpret_cast<const float*>(base + (r.nky ^ 16u));
+            const float nz = *reinterpret_cast<const float*>(base + r.nkz), fz = *reinterpret_cast<const float*>(base + (r.nkz ^ 16u));
+            const float t0 = fmaxf(fmaxf((nx - r.op.x) * r.ip.x, (ny - r.op.y) * r.ip.y), fmaxf((nz - r.op.z) * r.ip.z, tmin));
+            const float t1 = fminf(fminf(fminf((fx - r.op.x) * r.ip.x, (fy - r.op.y) * r.ip.y), (fz - r.op.z) * r.ip.z), tmax) * TR_SLAB_PAD;
+            if (t0 <= t1) {
+                for (uint e = 0; e < n_emit; ++e) {
+                    TriHit tr;
+                    if (COUNT) st.tris++;
+                    if (tri_intersect(r, sv.tris, es->index[e], tmin, __builtin_huge_valf(), tr)) consider(tr, tr.t, tr.bu, tr.bv);
+                }
+            }
+        }
+    }
 
     // ---- one ray per lane while more than TR_QUAD_SWITCH rays are live
     while (true) {
         const unsigned long long act = __ballot(live);
-        if (__popcll(act) <= TR_QUAD_SWITCH) break;
+        if (__popcll(act) <= ((TERMINAL && !TR_TERMINAL_QUADS) ? 0 : TR_QUAD_SWITCH)) break;
         if (live) {
             const bool at_leaf = node < 0;
 #if TR_VOTE > 0
@@ -309,6 +359,8 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                     Hit4 h;
                     box4_intersect(r, sv.nodes4, node, tmin, best_t, h TL(, &tlp));
                     if (COUNT) st.nodes++;
+                    if constexpr (TERMINAL && TR_TERMINAL_SLOT_ORDER) descend = shadow_descend(h, stk, spill, node);
+                    else {
                     TR_CE4(0, 1) TR_CE4(2, 3) TR_CE4(0, 2) TR_CE4(1, 3) TR_CE4(1, 2)
                     TL(asm volatile("" : "+v"(h.t[0]), "+v"(h.t[1]), "+v"(h.t[2]), "+v"(h.t[3]), "+v"(h.c[0]), "+v"(h.c[1]), "+v"(h.c[2]), "+v"(h.c[3])); tlp.mark_a();)
                     if (h.t[0] < __builtin_huge_valf()) {
@@ -318,6 +370,7 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                         if (COUNT) st.maxsp = max(st.maxsp, (uint)stk.sp);
                         node = h.c[0];
                         descend = true;
+                    }
                     }
                 } else {
                     TriHit tr;
@@ -329,13 +382,17 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                     tlp.mark_b();
 #else
                     TR_LEAF_MEMBERS((uint)~node, true)
-                    if (tri_intersect(r, sv.tris, leaf_index((uint)~node) + member, tmin, __builtin_huge_valf(), tr)) consider(tr, tr.t, tr.bu, tr.bv);
+                    if (tri_intersect(r, sv.tris, leaf_index((uint)~node) + member, tmin, __builtin_huge_valf(), tr)) {
+                        const bool took = consider(tr, tr.t, tr.bu, tr.bv);
+                        if constexpr (TERMINAL) blocked = blocked || (took && early);      // something accepted lies in front of the nearest emitter
+                    }
 #endif
                 }
                 if (!descend) {
                     if (stk.sp == 0) live = false;
                     else node = stk.pop(spill);
                 }
+                if constexpr (TERMINAL) live = live && !blocked;
                 TL(tlp.end(qc.tl, leaf_phase ? TL_LT : TL_LN, tl_units, (tl_units - 1) >> 3, leaf_phase ? TL_LT_WAIT_HIST : TL_LN_WAIT_HIST);)
             }
         }
@@ -360,6 +417,8 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
         float qbest = lt;
         bool qlive = deal.has_ray;
         int pend = -1;      // triangle this lane has to test
+        const bool qearly = TERMINAL ? bperm(src, early ? 1 : 0) != 0 : false;
+        bool qblocked = false;
 #if TR_TAIL_PREFETCH
         int qpf = 0;
 #endif
@@ -373,6 +432,7 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
             const bool tri_phase = __popcll(__ballot(pend >= 0)) >= TR_QUAD_VOTE || __ballot(can_node) == 0;
             if (COUNT && (threadIdx.x & 63) == 0) { if (tri_phase) st.ph_qtri++; else st.ph_qnode++; }
             if (tri_phase) {
+                bool took = false;
                 if (pend >= 0) {
                     TL(TlPhase tlp; const int tl_units = __popcll(__ballot(true)); tlp.begin();)
                     TriHit tr;
@@ -393,10 +453,16 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                         // alpha branch overwrote) - found as Suzanne hits with t = inf, tools/ab_dump.py
                         lt = accept ? t : lt; lu = accept ? bu : lu; lv = accept ? bv : lv;
                         linst = accept ? inst : linst; lprim = accept ? tr.prim : lprim;
+                        if constexpr (TERMINAL) took = accept;
                     }
                     TL(tlp.end(qc.tl, TL_QT, tl_units, (tl_units - 1) >> 3, -1);)
                 }
                 pend = -1;
+                if constexpr (TERMINAL) {      // a lane of the quad replaced the best so far: the ray is blocked and ends here
+                    int z = took ? 1 : 0;
+                    z |= qrot1(z); z |= qrot2(z);
+                    if (z != 0 && qearly) { qblocked = true; qlive = false; }
+                }
                 float m = lt;
                 m = fminf(m, qrot1f(m)); m = fminf(m, qrot2f(m));
                 qbest = fminf(qbest, m);
@@ -439,7 +505,12 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
         const uint ri = (uint)bperm(back, (int)linst), rp = (uint)bperm(back, (int)lprim);
         const int ro = bperm(back, qo);
         if (live) { best_t = rt; best_u = ru; best_v = rv; best_inst = ri; best_prim = rp; overflow += ro; }
+        if constexpr (TERMINAL) {
+            const int rb = bperm(back, qblocked ? 1 : 0);
+            if (live) blocked = blocked || rb != 0;
+        }
     }
+    if constexpr (TERMINAL) term->blocked = blocked;
     overflow += stk.overflow ? 1 : 0;
     TL(tl_misc(qc.tl, 0, 1); tl_misc(qc.tl, 1, tl_now() - tl_enter); tl_misc(qc.tl, 4, tl_wall() - tl_wall0);)
 

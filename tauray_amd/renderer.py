@@ -23,7 +23,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (AccelInfoC, AccelLayoutC, CountersC, DistributionC, LightAccelInfoC, LightCountersC, PtOptionsC, SceneDescC, TimingsC,
+from ._lib import (AccelInfoC, AccelLayoutC, CountersC, DistributionC, LightAccelInfoC, LightCountersC, PtOptionsC, TerminalCountersC, SceneDescC, TimingsC,
                    TonemapInfoC, TrhipError, check)
 from .distribution import (DISTRIBUTION_DUPLICATE, DISTRIBUTION_SCANLINE, DISTRIBUTION_SHUFFLED_STRIPS, DistributionParams,
                            get_device_distribution_params, get_distribution_target_size)
@@ -397,6 +397,27 @@ class SceneStage:
                                              1 if include_lights else 0, d_hits.ptr, None))
         return d_hits.download((n,), hit_dtype)
 
+    def trace_terminal(self, rays: np.ndarray, seeds: Optional[np.ndarray] = None, fallback: Optional[np.ndarray] = None) -> np.ndarray:
+        """trhip_trace_terminal: the terminal query on explicit rays.  Hits as trace_closest without lights, except that a blocked ray
+        reports instance_id _lib.HIT_BLOCKED; fallback: nonzero = trace that ray as an ordinary closest hit."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(rays)
+        hit_dtype = np.dtype([("instance_id", "<i4"), ("primitive_id", "<i4"), ("bary_u", "<f4"), ("bary_v", "<f4"), ("t", "<f4")])
+        if n == 0:
+            return np.zeros(0, dtype=hit_dtype)
+        d_rays = self.ctx.alloc(rays.nbytes).upload(rays)
+        d_seeds = d_fb = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+            d_seeds = self.ctx.alloc(seeds.nbytes).upload(seeds)
+        if fallback is not None:
+            fallback = np.ascontiguousarray(fallback, dtype=np.uint32)
+            d_fb = self.ctx.alloc(fallback.nbytes).upload(fallback)
+        d_hits = self.ctx.alloc(n * 20)
+        check(_lib.lib().trhip_trace_terminal(self.ctx.h, n, d_rays.ptr, d_seeds.ptr if d_seeds else None, d_fb.ptr if d_fb else None,
+                                              d_hits.ptr, None))
+        return d_hits.download((n,), hit_dtype)
+
     def trace_shadow(self, rays: np.ndarray) -> np.ndarray:
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = len(rays)
@@ -519,6 +540,18 @@ class PathTracerStage:
         c = LightCountersC()
         check(_lib.lib().trhip_pt_get_light_counters(self.h, C.byref(c)))
         return {n: int(getattr(c, n)) for n, _ in LightCountersC._fields_}
+
+    def set_terminal_query(self, mode: int):
+        """trhip_pt_set_terminal_query: _lib.TERMINAL_QUERY_AUTO (the default: the last bounce is a first-hit emitter query where the
+        scene allows it) or TERMINAL_QUERY_OFF.  Frames and ray counts do not depend on the mode."""
+        check(_lib.lib().trhip_pt_set_terminal_query(self.h, mode))
+
+    def terminal_counters(self) -> dict:
+        """trhip_pt_get_terminal_counters: blocked_rays / fallback_rays of the terminal query (counted under count_work), in_effect,
+        emitter_triangles, threshold."""
+        c = TerminalCountersC()
+        check(_lib.lib().trhip_pt_get_terminal_counters(self.h, C.byref(c)))
+        return {n: int(getattr(c, n)) for n, _ in TerminalCountersC._fields_ if n != "pad"}
 
     def timings(self) -> dict:
         t = TimingsC()
