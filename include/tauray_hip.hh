@@ -22,6 +22,7 @@
 #include <fstream>
 #include <functional>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -479,6 +480,37 @@ public:
     options opt;
 };
 
+// bmfr_stage (src/bmfr_stage.{hh,cc}): the BMFR denoiser between the path tracer and the tonemap stage.  The reference's constructor
+// takes the current and the previous gbuffer; here the stage keeps last frame's normal / pos and its histories itself (trhip_bmfr_*),
+// so there is one gbuffer: the images trhip_pt_render_targets wrote, `layers` of them of `size`.  color is denoised in place.
+class bmfr_stage
+{
+public:
+    enum class bmfr_settings { DIFFUSE_ONLY = TRHIP_BMFR_DIFFUSE_ONLY, DIFFUSE_SPECULAR = TRHIP_BMFR_DIFFUSE_SPECULAR };
+    struct options
+    {
+        bmfr_settings settings = bmfr_settings::DIFFUSE_ONLY;
+        float noise_amount = 0.0f;      // 0 = the reference's 1e-2
+    };
+    bmfr_stage(device& dev, const trhip_bmfr_features& current_features, uvec2 size, uint32_t layers, const options& opt)
+    : dev(&dev), features(current_features), opt(opt)
+    {
+        const trhip_bmfr_options o = {(int32_t)opt.settings, opt.noise_amount};
+        check(trhip_bmfr_create(dev.h, &o, size.x, size.y, layers, &h));
+    }
+    bmfr_stage(const bmfr_stage&) = delete;
+    ~bmfr_stage() { trhip_bmfr_destroy(h); }
+    // stage::run: one frame on `stream`; frame_counter = context::get_frame_counter()
+    void run(uint32_t frame_counter, void* stream = nullptr) { check(trhip_bmfr_run(h, &features, frame_counter, stream)); }
+    void reset_history() { check(trhip_bmfr_reset_history(h)); }
+    trhip_bmfr_timings get_timings() { trhip_bmfr_timings t; check(trhip_bmfr_get_timings(h, &t)); return t; }
+
+    device* dev;
+    trhip_bmfr_features features;
+    options opt;
+    trhip_bmfr* h = nullptr;
+};
+
 class load_balancer
 {
 public:
@@ -533,6 +565,11 @@ public:
         // B * active_viewport_count layers, frame-major, and `display` B tonemapped frames.  For frames that do not accumulate.
         // Bigger launches: less of a frame is the tail of its kernels (the pipelined figure of bench.py uses two).
         int frames_per_launch = 1;
+        // --denoiser=bmfr (src/post_processing_renderer.cc:53-106): the path tracer also renders the gbuffer entries the stage reads, every
+        // frame is a fresh frame (the sample counter keeps counting), the stage runs between stitch and tonemap - which is then a stage of
+        // its own - and gets last frame's cameras as camera_pair.previous.  One device (or view shards): the feature targets of a pixel
+        // distribution over several devices would have to be gathered and stitched like colour, which is not built.
+        std::optional<bmfr_stage::options> bmfr;
     };
 
     // `devices`: HIP device index per logical device (repeat an index for --fake-devices); device 0 displays.
@@ -547,6 +584,14 @@ public:
         batch = (uint32_t)std::max(this->opt.frames_per_launch, 1);
         if(batch > 1 && this->opt.accumulate)
             throw std::runtime_error("rt_renderer: accumulating frames depend on each other, frames per launch must be 1");
+        if(this->opt.bmfr)
+        {
+            if(devices.size() > 1)
+                throw std::runtime_error("rt_renderer: a denoiser with a pixel distribution of count " + std::to_string(devices.size()) + " > 1 is not built: "
+                                         "the feature targets (diffuse, albedo, normal, pos, instance id, screen motion) would have to be gathered and stitched like colour");
+            if(this->opt.accumulate || batch > 1) throw std::runtime_error("rt_renderer: a denoised frame is a fresh frame: no accumulation, one frame per launch");
+            if(!std::is_same<Pipeline, path_tracer_stage>::value) throw std::runtime_error("rt_renderer: the denoiser reads the path tracer's diffuse target");
+        }
         per_device.resize(devices.size());
         std::vector<double> ratios(devices.size(), 1.0 / devices.size());
         double cumulative = 0;
@@ -587,17 +632,37 @@ public:
         // One device: nothing sits between the path tracer and the tonemap stage (no transfer, no stitch), and the stage writes the slot's
         // display image while it writes its colour target - the same bits without a second pass over the frame.  TRHIP_FUSED_TONEMAP=0: off.
         const char* fe = getenv("TRHIP_FUSED_TONEMAP");
-        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0);
+        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr;
+        if(this->opt.bmfr)
+        {
+            device& d0 = *per_device[0].dev;
+            const size_t px = size_t(size.x) * size.y * layers;
+            for(slot_data& sl: per_device[0].slots)
+            {
+                trhip_pt_targets& t = sl.targets;
+                t.color = sl.color;
+                t.diffuse = d0.alloc(px * 16); t.albedo = d0.alloc(px * 16); t.pos = d0.alloc(px * 16);
+                t.normal = d0.alloc(px * 8); t.screen_motion = d0.alloc(px * 8); t.instance_id = d0.alloc(px * 4);
+            }
+            const trhip_pt_targets& t0 = per_device[0].slots[0].targets;
+            bmfr = std::make_unique<bmfr_stage>(d0, trhip_bmfr_features{t0.color, t0.diffuse, t0.albedo, t0.normal, t0.pos, t0.screen_motion, t0.instance_id},
+                                                size, (uint32_t)layers, *this->opt.bmfr);
+            last_cameras = scene.cameras;
+            current_cameras = scene.cameras;
+        }
         fused_info.assign(frame_slots.size(), trhip_tonemap_info{-1, 0.0f, 0.0f, 0});     // what each slot's stage was last told: render() keeps it current
     }
 
     ~basic_rt_renderer()
     {
         finish_all();
+        bmfr.reset();
         for(size_t i = 0; i < per_device.size(); ++i)
             for(slot_data& sl: per_device[i].slots)
             {
                 sl.ray_tracer.reset();
+                for(void* p: {sl.targets.diffuse, sl.targets.albedo, sl.targets.pos, sl.targets.normal, sl.targets.screen_motion, sl.targets.instance_id})
+                    if(p) per_device[i].dev->free(p);
                 if(sl.gbuffer_copy) per_device[0].dev->free(sl.gbuffer_copy);
                 per_device[i].dev->free(sl.color);
                 per_device[i].dev->destroy_stream(sl.stream);
@@ -632,6 +697,8 @@ public:
     {
         finish_all();
         for(auto& d: per_device) d.scene_update->apply(s, rebuild);
+        current_cameras = s.cameras;
+        uploaded_previous_cameras = s.previous_cameras.empty() ? uploaded_previous_cameras : s.previous_cameras;
     }
 
     // rt_renderer::render (src/rt_renderer.cc:84-133): ray tracers -> transfers -> stitch -> tonemap.  Enqueues only.
@@ -660,7 +727,19 @@ public:
             if(frame_slots.size() > 1 || batch > 1) sl.ray_tracer->set_frame_counter(frame_index);   // one stage per slot: slot k renders frames k, k + N, ... (B at a time)
             if(i != 0)   // the slot's previous frame has been stitched on the display device: its receive buffer is free
                 check(trhip_stream_wait_peer(d.dev->h, sl.stream, display_device.h, display_stream));
-            sl.ray_tracer->run(sl.stream);
+            if(bmfr)
+            {   // camera_pair.previous = the cameras of the frame before this one
+                if(last_cameras != uploaded_previous_cameras)
+                {   // frames in flight read the cameras they were enqueued with: they finish before the record changes
+                    if(frame_slots.size() > 1) finish_all();
+                    d.scene_update->set_previous_cameras(last_cameras.data(), (uint32_t)(last_cameras.size() / 320));
+                    uploaded_previous_cameras = last_cameras;
+                }
+                last_cameras = current_cameras;
+                const uvec2 ts = get_distribution_target_size(d.dist);
+                check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
+            }
+            else sl.ray_tracer->run(sl.stream);
             if(i != 0) check(trhip_copy_peer(display_device.h, sl.gbuffer_copy, d.dev->h, sl.color, d.target_bytes(layers), sl.stream));
         }
         if(per_device.size() > 1)
@@ -680,7 +759,16 @@ public:
             stitch_blend_ratio = 1.0f;      // src/rt_renderer.cc:122
         }
         display = frame_slots[k].display;
-        if(!fused_tonemap) tonemap->run(per_device[0].slots[k].color, display, size, layers, display_stream);
+        void* post_stream = display_stream;
+        if(bmfr)
+        {   // the denoiser's history is one chain over the frames of all slots: it runs in frame order on the display device's default stream
+            if(frame_slots.size() > 1) { check(trhip_stream_wait(display_device.h, nullptr, display_stream)); post_stream = nullptr; }
+            const trhip_pt_targets& t = per_device[0].slots[k].targets;
+            bmfr->features = trhip_bmfr_features{t.color, t.diffuse, t.albedo, t.normal, t.pos, t.screen_motion, t.instance_id};
+            bmfr->run(frame_index, post_stream);
+        }
+        if(!fused_tonemap) tonemap->run(per_device[0].slots[k].color, display, size, layers, post_stream);
+        if(post_stream != display_stream) check(trhip_stream_wait(display_device.h, display_stream, nullptr));
         frame_index += batch;
         accumulated_frames++;
     }
@@ -723,6 +811,7 @@ public:
         std::unique_ptr<Pipeline> ray_tracer;
         void* color = nullptr;          // the device's (partial) colour target of this slot
         void* gbuffer_copy = nullptr;   // non-primary devices: where the partial lands on the display device
+        trhip_pt_targets targets = {};  // denoiser: the gbuffer entries next to `color`
     };
     struct per_device_data
     {
@@ -744,6 +833,8 @@ public:
     void* display = nullptr;          // frame_slots[current_slot].display
     size_t display_bytes = 0;
     std::unique_ptr<tonemap_stage> tonemap;
+    std::unique_ptr<bmfr_stage> bmfr;      // options.bmfr
+    std::vector<uint8_t> last_cameras, current_cameras, uploaded_previous_cameras;   // denoiser: camera_data of the last frame rendered / of the scene as it is / camera_pair.previous on the device
     bool fused_tonemap = false;
     std::vector<trhip_tonemap_info> fused_info;
     unsigned accumulated_frames = 0;

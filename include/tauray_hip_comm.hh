@@ -143,6 +143,9 @@ public:
     : rank(rank), nranks(nranks), size(size), opt(opt), dev(hip_device), scene_update(dev), hip_device(hip_device)
     {
         if(nranks < 1 || rank < 0 || rank >= nranks) throw std::runtime_error("process_rt_renderer: rank out of range");
+        if(this->opt.bmfr)
+            throw std::runtime_error("process_rt_renderer: a denoiser with a pixel distribution over the ranks of a job (count " + std::to_string(nranks) +
+                                     ") is not built: the feature targets would have to be gathered and stitched like colour; use rt_renderer on one device or view shards");
         if(nranks == 1) this->opt.distribution.strategy = DISTRIBUTION_DUPLICATE;   // src/tauray.cc:519-521
         const int n_slots = std::max(this->opt.max_frames_in_flight, 1);
         if(n_slots > 1 && this->opt.accumulate)

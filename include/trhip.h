@@ -499,6 +499,63 @@ int trhip_tonemap(trhip_device* dev, const void* in_dev, void* out_dev, uint32_t
  * second pass over the frame (a 1080p frame: 47 us after the last lane has finished).  NULL turns it off.  Path tracer stages only. */
 int trhip_pt_set_fused_tonemap(trhip_pt* pt, void* display_dev, const trhip_tonemap_info* info);
 
+/* ---- bmfr_stage (src/bmfr_stage.{hh,cc}, shader/bmfr_*.comp; --denoiser=bmfr, src/post_processing_renderer.cc:53-106): blockwise
+ * multi-order feature regression between the path tracer and the tonemap stage.  Per frame: (a) temporal accumulation of the noisy
+ * diffuse / specular light by reprojection through screen_motion, and the feature rows 1, n, p, p^2 of every 32 x 32 block of a grid
+ * that is shifted per frame; (b) a least-squares fit of the ten features to the noisy channels per block (Householder QR); (c) the
+ * fitted values per pixel; (d) temporal accumulation of the fitted values and colour = albedo * diffuse + specular.  csrc/bmfr.hip.
+ * The images are the targets of trhip_pt_render_targets (RGBA32F / RG32F / R32I, [layers][height][width]); every intermediate -
+ * histories of noisy and filtered values, last frame's normal and pos, feature rows, weights, min / max, accept bits - is fp32, owned
+ * by the stage and sized when it is created.  Deviations from the reference: the 16 block offsets are this
+ * stage's own table; the noise of the fit is a counter-based hash of (block-grid pixel, layer, feature, frame) instead of a
+ * per-thread stream; a pixel with instance_id < 0 is "no surface" like one whose pos is NaN (its colour passes through, its row
+ * stays out of the fit). */
+typedef struct trhip_bmfr trhip_bmfr;
+#define TRHIP_BMFR_DIFFUSE_ONLY 0          /* bmfr_stage::bmfr_settings: fit the diffuse light, pass the accumulated specular through */
+#define TRHIP_BMFR_DIFFUSE_SPECULAR 1      /* fit both */
+typedef struct trhip_bmfr_options {
+    int32_t settings;                 /* TRHIP_BMFR_DIFFUSE_ONLY (what --denoiser=bmfr selects) or TRHIP_BMFR_DIFFUSE_SPECULAR */
+    float noise_amount;               /* amplitude of the noise added to features 1-9 before the fit; 0 = the reference's 1e-2 */
+} trhip_bmfr_options;
+typedef struct trhip_bmfr_features {  /* the gbuffer entries the stage reads (src/bmfr_stage.cc:196-240) */
+    void* color;                      /* RGBA32F in: noisy, out: denoised */
+    void* diffuse;                    /* RGBA32F */
+    void* albedo;                     /* RGBA32F */
+    void* normal;                     /* RG32F   */
+    void* pos;                        /* RGBA32F */
+    void* screen_motion;              /* RG32F   */
+    void* instance_id;                /* R32I, may be NULL: then only a NaN pos marks "no surface" */
+} trhip_bmfr_features;
+typedef struct trhip_bmfr_timings {   /* the reference's timer names (src/bmfr_stage.cc), device ms of the last frame */
+    float preprocess_ms, fit_ms, weighted_sum_ms, accumulate_output_ms, total_ms;
+    uint32_t frames;                  /* frames run since the stage was created */
+} trhip_bmfr_timings;
+int trhip_bmfr_create(trhip_device* dev, const trhip_bmfr_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_bmfr** out); /* bmfr_stage ctor */
+void trhip_bmfr_destroy(trhip_bmfr* bmfr);
+/* bmfr_stage::run: one frame, asynchronous on `stream`, no synchronisation.  frame_counter (context::get_frame_counter) picks the block
+ * offset (frame_counter % 16) and seeds the noise.  Frames of one stage form one history: run them in frame order on one stream (or
+ * on streams ordered with trhip_stream_wait). */
+int trhip_bmfr_run(trhip_bmfr* bmfr, const trhip_bmfr_features* features, uint32_t frame_counter, void* stream);
+int trhip_bmfr_reset_history(trhip_bmfr* bmfr);   /* camera cut / new scene: the next frame has no history, like a new stage's first */
+int trhip_bmfr_get_timings(trhip_bmfr* bmfr, trhip_bmfr_timings* out);   /* waits for the last frame */
+/* Parity hooks, as trhip_trace_closest is for traceRayEXT.  trhip_bmfr_fit_blocks: the fit of (b) alone on `blocks` matrices
+ * [blocks][10 + channels][1024] (column-major per block: ten feature columns, already scaled and with noise, then the channels;
+ * channels = 3 or 6) -> weights [blocks][channels][10].  trhip_bmfr_download: a buffer of the stage as the last frame left it
+ * (synchronises the device); `bytes` must be the buffer's size. */
+int trhip_bmfr_fit_blocks(trhip_device* dev, uint32_t blocks, uint32_t channels, const float* matrix_dev, float* weights_dev, void* stream);
+#define TRHIP_BMFR_NOISY_DIFFUSE 0         /* RGBA32F [layers][h][w], a = history length */
+#define TRHIP_BMFR_NOISY_SPECULAR 1        /* RGBA32F */
+#define TRHIP_BMFR_FILTERED_DIFFUSE 2      /* RGBA32F, a = history length */
+#define TRHIP_BMFR_FILTERED_SPECULAR 3     /* RGBA32F, DIFFUSE_SPECULAR only */
+#define TRHIP_BMFR_FEATURE_ROWS 4          /* float [blocks][10 + channels][1024], unscaled, without noise; blocks = layers * (ceil(h/32)+1) * (ceil(w/32)+1) */
+#define TRHIP_BMFR_WEIGHTS 5               /* float [blocks][channels][10] */
+#define TRHIP_BMFR_MIN_MAX 6               /* float [blocks][6][2]: min, max of features 4-9 */
+#define TRHIP_BMFR_ACCEPT_BITS 7           /* uint8 [layers][h][w]: bits 0-3 the taps kept (tl, tr, bl, br), bit 4 no surface */
+#define TRHIP_BMFR_BLOCK_OFFSETS 8         /* int32 [16][2]: the table frame_counter % 16 indexes (needs no device) */
+#define TRHIP_BMFR_PREVIOUS_NORMAL 9       /* RG32F: the normal target of the last frame */
+#define TRHIP_BMFR_PREVIOUS_POS 10         /* RGBA32F: the pos target of the last frame, w = 1 where it had no surface */
+int trhip_bmfr_download(trhip_bmfr* bmfr, int which, void* host, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

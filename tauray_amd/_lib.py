@@ -124,6 +124,27 @@ class TonemapInfoC(C.Structure):
     _fields_ = [("op", C.c_int32), ("exposure", C.c_float), ("gamma", C.c_float), ("alpha_grid_background", C.c_int32)]
 
 
+class BmfrOptionsC(C.Structure):
+    """trhip_bmfr_options: bmfr_stage::options (settings) + the noise amplitude of the fit (0 = 1e-2)."""
+    _fields_ = [("settings", C.c_int32), ("noise_amount", C.c_float)]
+
+
+class BmfrFeaturesC(C.Structure):
+    """trhip_bmfr_features: the gbuffer entries the BMFR stage reads; color is also its output.  instance_id may be None."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "diffuse", "albedo", "normal", "pos", "screen_motion", "instance_id")]
+
+
+class BmfrTimingsC(C.Structure):
+    _fields_ = ([(n, C.c_float) for n in ("preprocess_ms", "fit_ms", "weighted_sum_ms", "accumulate_output_ms", "total_ms")]
+                + [("frames", C.c_uint32)])
+
+
+# trhip_bmfr_options::settings, trhip_bmfr_download
+BMFR_DIFFUSE_ONLY, BMFR_DIFFUSE_SPECULAR = 0, 1
+(BMFR_NOISY_DIFFUSE, BMFR_NOISY_SPECULAR, BMFR_FILTERED_DIFFUSE, BMFR_FILTERED_SPECULAR, BMFR_FEATURE_ROWS, BMFR_WEIGHTS, BMFR_MIN_MAX,
+ BMFR_ACCEPT_BITS, BMFR_BLOCK_OFFSETS, BMFR_PREVIOUS_NORMAL, BMFR_PREVIOUS_POS) = range(11)
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -203,6 +224,13 @@ SYMBOLS = {
     "trhip_trace_shadow": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "trhip_stitch": (_i, [_vp, C.POINTER(DistributionC), _vp, _u32, _u32, _vp, _u32, _f, _vp]),
     "trhip_tonemap": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, C.POINTER(TonemapInfoC), _vp]),
+    "trhip_bmfr_create": (_i, [_vp, C.POINTER(BmfrOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),
+    "trhip_bmfr_destroy": (None, [_vp]),
+    "trhip_bmfr_run": (_i, [_vp, C.POINTER(BmfrFeaturesC), _u32, _vp]),
+    "trhip_bmfr_reset_history": (_i, [_vp]),
+    "trhip_bmfr_get_timings": (_i, [_vp, C.POINTER(BmfrTimingsC)]),
+    "trhip_bmfr_fit_blocks": (_i, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "trhip_bmfr_download": (_i, [_vp, _i, _vp, C.c_size_t]),
 }
 
 _LIB = None

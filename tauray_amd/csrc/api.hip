@@ -284,6 +284,8 @@ struct trhip_pt {
     PtStage* stage;
 };
 
+namespace tr { int device_index(const trhip_device* dev) { return dev ? dev->hip_device : -1; } }   // for the stages of other translation units (bmfr.hip)
+
 #define DEVCHK(dev) do { if (!(dev)) return set_error("null trhip_device"); hipError_t e_ = hipSetDevice((dev)->hip_device); \
     if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)
 

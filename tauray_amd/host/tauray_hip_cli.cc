@@ -9,7 +9,7 @@
 //              [--filetype=exr|raw|none] [--format=rgb16|rgb32|rgba16|rgba32] [--tonemap=filmic|linear|gamma-correction|
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
-//              [--renderer=path-tracer|direct]
+//              [--renderer=path-tracer|direct] [--denoiser=none|bmfr]
 //              [--camera-grid=w,h,x,y --camera-recentering-distance=5 --camera-grid-roll=0]   (light-field grid, one file per view)
 //
 // One process per GPU (include/tauray_hip_comm.hh): start N copies with --process-count=N --process-rank=0..N-1 --device=<HIP index>
@@ -33,6 +33,18 @@
 using namespace tr;
 
 static bool starts(const std::string& s, const std::string& p) { return s.compare(0, p.size(), p) == 0; }
+
+static const char* const usage_text =
+    "usage: tauray_hip scene.glb|scene.gltf|scene.trsc [options]\n"
+    "  --width=W --height=H --headless=PREFIX --frames=N --warmup-frames=N --filetype=exr|raw|none --format=rgb16|rgb32|rgba16|rgba32\n"
+    "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
+    "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
+    "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
+    "  --tonemap=filmic|linear|gamma-correction|reinhard|reinhard-luminance --exposure=E --gamma=G\n"
+    "  --animation[=NAME] --framerate=F --accumulation --envmap=FILE --camera-grid=w,h,x,y -t --skip-nan-check\n"
+    "  --fake-devices=N | --devices=0,1,... --distribution-strategy=scanline|shuffled-strips --frames-in-flight=N --frames-per-launch=N\n"
+    "  --process-count=N --process-rank=R --device=D --comm-id=FILE [--comm-nonce=N] [--exchange=rccl|ipc] [--shard=views]\n"
+    "  --dump-scene=out.trsc\n";
 
 int main(int argc, char** argv)
 {
@@ -71,6 +83,15 @@ int main(int argc, char** argv)
             std::string a = argv[i];
             auto val = [&](const char* key) { return a.substr(std::strlen(key)); };
             if(a == "-t") timing = true;
+            else if(a == "--help" || a == "-h") { std::cout << usage_text; return 0; }
+            else if(starts(a, "--denoiser="))
+            {   // --denoiser (src/options.hh; src/tauray.cc:516-517): the post-processing chain between path tracer and tonemap
+                const std::string v = val("--denoiser=");
+                if(v == "bmfr") opt.bmfr = bmfr_stage::options{};
+                else if(v == "none") opt.bmfr.reset();
+                else if(v == "svgf") throw std::runtime_error("--denoiser=svgf: the SVGF denoiser is not built (--denoiser=none|bmfr)");
+                else throw std::runtime_error("--denoiser is none or bmfr, not " + v);
+            }
             else if(a == "--skip-nan-check") hopt.skip_nan_check = true;     // headless::options::skip_nan_check (src/headless.hh:74); with --filetype=none: no readback at all
             else if(a == "--accumulation") opt.accumulate = true;
             else if(a == "--pre-transform-vertices") opt.pre_transformed_vertices = true;
@@ -185,7 +206,7 @@ int main(int argc, char** argv)
             else if(starts(a, "--")) throw std::runtime_error("unknown option " + a);
             else scene_path = a;
         }
-        if(scene_path.empty()) throw std::runtime_error("usage: tauray_hip scene.glb|scene.trsc [options]");
+        if(scene_path.empty()) throw std::runtime_error(usage_text);
         if(devices.empty()) devices.assign((size_t)std::max(fake_devices, 1), 0);
 
         const bool is_glb = (scene_path.size() > 4 && scene_path.compare(scene_path.size() - 4, 4, ".glb") == 0) ||
@@ -375,6 +396,7 @@ int main(int argc, char** argv)
         };
         if(renderer == "direct")
         {
+            if(opt.bmfr) throw std::runtime_error("--denoiser=bmfr reads the path tracer's demodulated diffuse target: --renderer=path-tracer");
             direct_renderer::options dopt;
             static_cast<path_tracer_stage::options&>(dopt) = opt;
             dopt.tonemap = opt.tonemap; dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;

@@ -246,6 +246,8 @@ class SceneStage:
         d.gather_emissive_triangles = 1 if getattr(scene, "tri_light_count", 0) > 0 else 0
         check(L.trhip_scene_upload(self.ctx.h, C.byref(d)))
         self.scene = scene
+        self.camera_data = cams.copy()           # what the device renders with (update_cameras follows)
+        self.previous_camera_data = None         # camera_pair.previous as last set (None: the cameras themselves)
         # skinned meshes: the uploaded vertices are the bind pose; pose them with the file's rest pose before the build
         # (the reference runs skinning.comp on the first scene update, src/scene_stage.cc:1543-1567)
         for sk in getattr(scene, "skinned", []):
@@ -317,11 +319,17 @@ class SceneStage:
     def update_cameras(self, cameras):
         data = np.concatenate([c.pack() for c in cameras])
         check(_lib.lib().trhip_scene_update_cameras(self.ctx.h, data.ctypes.data, len(data)))
+        self.camera_data = data
 
     def set_previous_cameras(self, cameras):
         """camera_pair.previous per viewport (motion features, screen-motion target)."""
-        data = np.concatenate([c.pack() for c in cameras])
+        self.set_previous_camera_data(np.concatenate([c.pack() for c in cameras]))
+
+    def set_previous_camera_data(self, data: np.ndarray):
+        """The same from packed camera_data records (what `camera_data` held when an earlier frame was rendered)."""
+        data = np.ascontiguousarray(data)
         check(_lib.lib().trhip_scene_set_previous_cameras(self.ctx.h, data.ctypes.data, len(data)))
+        self.previous_camera_data = data.copy()
 
     def update_instances(self, instances: np.ndarray, refit: bool = False):
         """Dynamic scenes: new instance records (transforms / materials) for the same meshes, then a full rebuild of the
@@ -654,14 +662,101 @@ class TonemapStage:
         check(_lib.lib().trhip_tonemap(self.ctx.h, _ptr(src), _ptr(dst), width, height, layers, C.byref(self.info), stream))
 
 
+class BmfrStage:
+    """bmfr_stage(device&, gbuffer_target& current_features, gbuffer_target& prev_features, const options&) (src/bmfr_stage.{hh,cc}):
+    the BMFR denoiser between the path tracer and the tonemap stage.  The stage keeps last frame's normal / pos and its histories
+    itself (trhip_bmfr_*, include/trhip.h); `settings`: _lib.BMFR_DIFFUSE_ONLY (--denoiser=bmfr) or BMFR_DIFFUSE_SPECULAR."""
+
+    FEATURES = ("color", "diffuse", "albedo", "normal", "pos", "screen_motion", "instance_id")
+    # trhip_bmfr_download: name -> (code, numpy dtype, shape(stage))
+    BUFFERS = {
+        "noisy_diffuse": (_lib.BMFR_NOISY_DIFFUSE, np.float32, lambda s: (s.layers, s.size[1], s.size[0], 4)),
+        "noisy_specular": (_lib.BMFR_NOISY_SPECULAR, np.float32, lambda s: (s.layers, s.size[1], s.size[0], 4)),
+        "filtered_diffuse": (_lib.BMFR_FILTERED_DIFFUSE, np.float32, lambda s: (s.layers, s.size[1], s.size[0], 4)),
+        "filtered_specular": (_lib.BMFR_FILTERED_SPECULAR, np.float32, lambda s: (s.layers, s.size[1], s.size[0], 4)),
+        "feature_rows": (_lib.BMFR_FEATURE_ROWS, np.float32, lambda s: (s.blocks, 10 + s.channels, 1024)),
+        "weights": (_lib.BMFR_WEIGHTS, np.float32, lambda s: (s.blocks, s.channels, 10)),
+        "min_max": (_lib.BMFR_MIN_MAX, np.float32, lambda s: (s.blocks, 6, 2)),
+        "accept_bits": (_lib.BMFR_ACCEPT_BITS, np.uint8, lambda s: (s.layers, s.size[1], s.size[0])),
+        "block_offsets": (_lib.BMFR_BLOCK_OFFSETS, np.int32, lambda s: (16, 2)),
+        "previous_normal": (_lib.BMFR_PREVIOUS_NORMAL, np.float32, lambda s: (s.layers, s.size[1], s.size[0], 2)),
+        "previous_pos": (_lib.BMFR_PREVIOUS_POS, np.float32, lambda s: (s.layers, s.size[1], s.size[0], 4)),
+    }
+
+    def __init__(self, ctx: Context, size, layers=1, settings=_lib.BMFR_DIFFUSE_ONLY, noise_amount=0.0):
+        self.ctx, self.size, self.layers, self.settings = ctx, (int(size[0]), int(size[1])), int(layers), int(settings)
+        self.channels = 3 if self.settings == _lib.BMFR_DIFFUSE_ONLY else 6
+        self.block_grid = ((self.size[0] + 31) // 32 + 1, (self.size[1] + 31) // 32 + 1)
+        self.blocks = self.block_grid[0] * self.block_grid[1] * self.layers
+        self.h = None
+        opt = _lib.BmfrOptionsC(self.settings, float(noise_amount))
+        h = C.c_void_p()
+        check(_lib.lib().trhip_bmfr_create(getattr(ctx, "h", None), C.byref(opt), self.size[0], self.size[1], self.layers, C.byref(h)))
+        self.h = h.value
+
+    def run(self, targets: dict, frame_counter: int, stream=None):
+        """stage::run: denoises targets["color"] in place from the other gbuffer entries (device images of the stage's size)."""
+        unknown = set(targets) - set(self.FEATURES)
+        if unknown:
+            raise ValueError(f"BmfrStage: not a feature the stage reads: {sorted(unknown)}")
+        f = _lib.BmfrFeaturesC()
+        for name, buf in targets.items():
+            setattr(f, name, None if buf is None else _ptr(buf))
+        check(_lib.lib().trhip_bmfr_run(self.h, C.byref(f), int(frame_counter) & 0xFFFFFFFF, stream))
+
+    def reset_history(self):
+        check(_lib.lib().trhip_bmfr_reset_history(self.h))
+
+    def timings(self) -> dict:
+        """Device ms of the last frame's four kernels under the reference's timer names, their sum, and the frames run."""
+        t = _lib.BmfrTimingsC()
+        check(_lib.lib().trhip_bmfr_get_timings(self.h, C.byref(t)))
+        return {n: (int if n == "frames" else float)(getattr(t, n)) for n, _ in _lib.BmfrTimingsC._fields_}
+
+    def download(self, name: str) -> np.ndarray:
+        """A buffer of the stage as the last frame left it (trhip_bmfr_download; test hook)."""
+        code, dtype, shape = self.BUFFERS[name]
+        out = np.empty(shape(self), dtype=dtype)
+        check(_lib.lib().trhip_bmfr_download(self.h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().trhip_bmfr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fit_blocks(ctx: Context, matrices: np.ndarray) -> np.ndarray:
+    """trhip_bmfr_fit_blocks: the BMFR least-squares fit alone.  matrices [blocks][10 + channels][1024] (features scaled and with
+    noise, then 3 or 6 channels) -> weights [blocks][channels][10]."""
+    m = np.ascontiguousarray(matrices, dtype=np.float32)
+    if m.ndim != 3 or m.shape[2] != 1024 or m.shape[1] not in (13, 16):
+        raise ValueError("fit_blocks: matrices must be [blocks][13 or 16][1024]")
+    blocks, channels = m.shape[0], m.shape[1] - 10
+    if blocks == 0:
+        return np.zeros((0, channels, 10), np.float32)
+    d_m = ctx.alloc(m.nbytes).upload(m)
+    d_w = ctx.alloc(blocks * channels * 40)
+    check(_lib.lib().trhip_bmfr_fit_blocks(ctx.h, blocks, channels, d_m.ptr, d_w.ptr, None))
+    return d_w.download((blocks, channels, 10), np.float32)
+
+
 class _FrameSlot:
     """What one frame in flight owns: its stage (path buffers, counters), its images and the stream it is ordered on."""
 
     def __init__(self):
         self.pt = None
+        self.features = None     # denoiser: the gbuffer targets next to the colour target
         self.color = None
         self.display = None
         self.stream = None
+        self.frame = 0           # frame counter of the slot's last frame
         self.fused_info = None
 
 
@@ -684,7 +779,8 @@ class RtRenderer:
 
     def __init__(self, ctx: Context, scene: SceneDesc, options: PtOptionsC, size, strategy=DISTRIBUTION_SCANLINE,
                  rank=0, world_size=1, viewports=1, tonemap: Optional[dict] = None, accumulate=False, use_torch=None,
-                 shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None):
+                 shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None,
+                 denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY):
         """`shard`: what the ranks divide among themselves - "pixels" (the reference's distribution strategies, partial frames
         stitched on rank 0), "views" (viewport v on rank v mod N; nothing is exchanged before output) or "samples" (every
         rank renders samples_per_pixel / N samples of every pixel; one reduce to rank 0).  SURVEY.md section 8(e).
@@ -694,9 +790,26 @@ class RtRenderer:
         layer groups, frame-major, and everything after the path tracing - exchange, stitch, tonemap - handles the B frames in
         one go.  For frames that do not accumulate; what the ranks of a pixel-sharded job use, whose launches are small.
         `as_strategy`, `dynamic`: the acceleration-structure strategy and dynamic marks of the scene stage (SceneStage; the C++
-        rt_renderer::options::scene)."""
+        rt_renderer::options::scene).
+        `denoiser`: None, or "bmfr" (the reference's --denoiser=bmfr, src/post_processing_renderer.cc:53-106): the path tracer renders the
+        gbuffer entries the BMFR stage reads next to the colour target, every frame is a fresh frame of samples_per_pixel samples (the
+        sample counter keeps counting), and post_process runs the stage before the tonemap stage (which is then a stage of its own: the
+        fused tonemap is off).  The stage gets last frame's cameras as camera_pair.previous.  With frames in flight its history stays
+        one chain: it runs in frame order on the default stream.  `denoiser_settings`: _lib.BMFR_DIFFUSE_ONLY or BMFR_DIFFUSE_SPECULAR."""
         if shard not in ("pixels", "views", "samples"):
             raise ValueError("shard must be pixels, views or samples")
+        if denoiser not in (None, "none", "bmfr"):
+            raise ValueError(f"denoiser {denoiser!r}: only \"bmfr\" is built" + (" (svgf is not built)" if denoiser == "svgf" else ""))
+        denoiser = None if denoiser == "none" else denoiser
+        if denoiser is not None:
+            if world_size > 1 and shard != "views":
+                raise ValueError(f"denoiser with a {shard} distribution of count {world_size} > 1: the feature targets (diffuse, albedo, normal, pos, "
+                                 "instance id, screen motion) would have to be gathered and stitched like colour, which is not built; "
+                                 "use one device or shard=\"views\"")
+            if accumulate or frames_per_launch > 1:
+                raise ValueError("a denoised frame is a fresh frame: accumulate must be False and frames_per_launch 1")
+            if stage_cls is not None and stage_cls is not PathTracerStage:
+                raise ValueError("the denoiser reads the path tracer's demodulated diffuse target: stage_cls must be PathTracerStage")
         if frames_in_flight < 1:
             raise ValueError("frames_in_flight must be >= 1")
         if frames_in_flight > 1 and accumulate:
@@ -749,7 +862,10 @@ class RtRenderer:
         self.tonemap = TonemapStage(ctx, **(tonemap or {}))
         # rt_renderer on one device has nothing between path_tracer_stage and tonemap_stage: the stage writes the display image itself
         # (trhip_pt_set_fused_tonemap: the same bits without the second pass over the frame); TRHIP_FUSED_TONEMAP=0 keeps the stage
-        self.fused_tonemap = (world_size == 1 and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
+        self.denoiser = denoiser
+        self.bmfr = BmfrStage(ctx, self.size, viewports, denoiser_settings) if (denoiser == "bmfr" and viewports > 0) else None
+        self._last_cameras = None        # denoiser: the cameras the last frame was rendered with
+        self.fused_tonemap = (world_size == 1 and denoiser is None and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
                               and hasattr(_lib.lib(), "trhip_pt_set_fused_tonemap") and os.environ.get("TRHIP_FUSED_TONEMAP", "1") != "0")
         self.slots = []
         for k in range(frames_in_flight):
@@ -765,6 +881,9 @@ class RtRenderer:
                 slot.pt.set_frame_slots(frames_in_flight)    # the frames in flight fill the chip between them: the stage picks one lane (two with two slots)
                 slot.stream = ctx.create_stream()
             slot.color = self._alloc_color(viewports, tw, th)
+            if self.bmfr is not None:
+                slot.features = {n: ctx.alloc(viewports * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero()
+                                 for n in BmfrStage.FEATURES if n != "color"}
             if self.fused_tonemap:
                 slot.display = self._alloc_display(viewports)
                 slot.fused_info = None       # what the stage was last told (bytes of the tonemap info), None = off
@@ -811,6 +930,9 @@ class RtRenderer:
     def set_scene(self, scene: SceneDesc):
         self.sync()
         self.scene_update.set_scene(scene)
+        if self.bmfr is not None:
+            self.bmfr.reset_history()
+            self._last_cameras = None
 
     def program(self) -> dict:
         """The shading program of this rank's stage (PathTracerStage.program)."""
@@ -944,9 +1066,21 @@ class RtRenderer:
             slot.pt.reset_accumulated_samples()
         if self.frames_in_flight > 1 or self.frames_per_launch > 1:
             slot.pt.set_frame_counter(self.frame_index)      # one stage per slot: slot k renders frames k, k + F, ... (B at a time)
+        slot.frame = self.frame_index
         self.frame_index += self.frames_per_launch
         if self.viewports > 0:      # a view shard can be empty (more devices than views)
-            slot.pt.run(slot.color, self.viewports, stream if stream is not None else slot.stream)
+            if self.bmfr is not None:
+                cameras = self.scene_update.camera_data
+                prev = cameras if self._last_cameras is None else self._last_cameras
+                on_device = self.scene_update.previous_camera_data
+                if on_device is None or prev.tobytes() != on_device.tobytes():
+                    if self.frames_in_flight > 1:      # frames in flight read the cameras they were enqueued with
+                        self.sync()
+                    self.scene_update.set_previous_camera_data(prev)
+                self._last_cameras = cameras.copy()
+                slot.pt.run_targets(dict(slot.features, color=slot.color), self.viewports, stream if stream is not None else slot.stream)
+            else:
+                slot.pt.run(slot.color, self.viewports, stream if stream is not None else slot.stream)
 
     def transfer_and_stitch(self, own_slot=None):
         """device_transfer + stitch_stage over RCCL: gather partial frames on rank 0 (default stream).  `own_slot`: the display
@@ -970,7 +1104,14 @@ class RtRenderer:
         self.render_partial(tonemap=tonemap)
         slot = self.current
         if self.world_size == 1:
-            if tonemap and not self.fused_tonemap:
+            if self.bmfr is not None:
+                # the denoiser's history is one chain over the frames of all slots: it runs on the default stream, in frame order
+                if slot.stream is not None:
+                    self.ctx.stream_wait(None, slot.stream)
+                self.post_process(None, tonemap=tonemap)
+                if slot.stream is not None:
+                    self.ctx.stream_wait(slot.stream, None)
+            elif tonemap and not self.fused_tonemap:
                 self.post_process(slot.stream)       # the whole frame stays on its slot's stream
             self.accumulated_frames += 1
             return
@@ -985,8 +1126,8 @@ class RtRenderer:
             self.ctx.stream_wait(None, slot.stream)
         if self.shard == "views":
             # every rank finishes its own views (tonemap is per pixel); `gather_views` ships them to the writer on rank 0
-            if tonemap and self.viewports > 0:
-                self.post_process()
+            if (tonemap or self.bmfr is not None) and self.viewports > 0:
+                self.post_process(tonemap=tonemap)
             if gather_views:
                 from .transfer import gather_views_to_display
                 src = self.display if tonemap else self.color
@@ -1004,11 +1145,16 @@ class RtRenderer:
             self.ctx.stream_wait(slot.stream, None)
         self.accumulated_frames += 1
 
-    def post_process(self, stream=None):
+    def post_process(self, stream=None, tonemap=True):
+        """The post-processing chain of the last frame (src/post_processing_renderer.cc:53-106): denoiser, then tonemap."""
         w, h = self.size
         if self.viewports == 0:
             return
         slot = self.current
+        if self.bmfr is not None:
+            self.bmfr.run(dict(slot.features, color=slot.color), slot.frame, stream)
+        if not tonemap:
+            return
         if slot.display is None:
             slot.display = self._alloc_display(self.viewports)
         self.tonemap.run(slot.color, slot.display, w, h, self.viewports, stream)
@@ -1030,6 +1176,8 @@ class RtRenderer:
         if not self.slots:
             return
         self.sync()
+        if self.bmfr is not None:
+            self.bmfr.close()
         for slot in self.slots:
             slot.pt.close()
             if slot.stream is not None:
