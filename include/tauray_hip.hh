@@ -21,6 +21,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -511,6 +512,100 @@ public:
     trhip_bmfr* h = nullptr;
 };
 
+// The first-hit G-buffer of viewports that are not path traced (trhip_gbuffer_render): normal, pos and instance id of one ray through every
+// pixel centre for a list of viewports in one launch, as compact layers in list order.
+class gbuffer_stage
+{
+public:
+    gbuffer_stage(device& dev, uvec2 size, int projection, float min_ray_dist): dev(&dev), size(size), projection(projection), min_ray_dist(min_ray_dist) {}
+    void run(const std::vector<uint32_t>& viewports, const trhip_gbuffer_targets& targets, void* stream = nullptr)
+    {
+        check(trhip_gbuffer_render(dev->h, projection, viewports.data(), (uint32_t)viewports.size(), min_ray_dist, &targets, size.x, size.y, stream));
+    }
+    device* dev;
+    uvec2 size;
+    int projection;
+    float min_ray_dist;
+};
+
+// The active viewports of a sparse light field as arithmetic runs {base, stride, count} in list order - what set_shard expresses:
+// 0,4,8 is one run, 18..26 is one run, 0,1,5 is {0, 1, 2}, {5, 1, 1}.
+struct viewport_run { uint32_t base, stride, count; };
+inline std::vector<viewport_run> viewport_runs(const std::vector<uint32_t>& v)
+{
+    std::vector<viewport_run> runs;
+    for(size_t i = 0; i < v.size();)
+    {
+        uint32_t count = 1, stride = 1;
+        if(i + 1 < v.size() && v[i + 1] > v[i])
+        {
+            stride = v[i + 1] - v[i];
+            while(i + count < v.size() && v[i + count] > v[i + count - 1] && v[i + count] - v[i + count - 1] == stride) ++count;
+        }
+        runs.push_back({v[i], stride, count});
+        i += count;
+    }
+    return runs;
+}
+
+// A non-empty list of distinct viewports of the grid that leaves some to reproject (what both hosts refuse otherwise).
+inline void check_viewport_list(const std::vector<uint32_t>& v, size_t total, const std::string& what)
+{
+    if(v.empty()) throw std::runtime_error(what + ": the viewport list is empty");
+    for(uint32_t x: v) if(x >= total) throw std::runtime_error(what + ": viewport " + std::to_string(x) + " is out of range (the scene has " + std::to_string(total) + " viewports)");
+    for(size_t i = 0; i < v.size(); ++i) for(size_t j = 0; j < i; ++j) if(v[i] == v[j]) throw std::runtime_error(what + ": a viewport is listed twice");
+    if(v.size() >= total) throw std::runtime_error(what + ": the list names every viewport: there is nothing to reproject");
+}
+
+// spatial_reprojection_stage (src/spatial_reprojection_stage.{hh,cc}): fills the viewports that were not path traced from the ones that
+// were, through the G-buffer (trhip_spatial_reprojection_*).  `source_viewports`: the path-traced viewports in the order of the source
+// images' layers; the output holds every viewport in natural order.
+class spatial_reprojection_stage
+{
+public:
+    spatial_reprojection_stage(device& dev, uvec2 size, uint32_t total_viewports, const std::vector<uint32_t>& source_viewports)
+    : dev(&dev), sources(source_viewports)
+    {
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        const float default_value[4] = {nan, nan, nan, nan};      // src/spatial_reprojection_stage.cc: what nothing reprojects to
+        check(trhip_spatial_reprojection_create(dev.h, size.x, size.y, total_viewports, sources.data(), (uint32_t)sources.size(), default_value, &h));
+        for(uint32_t v = 0; v < total_viewports; ++v)
+            if(std::find(sources.begin(), sources.end(), v) == sources.end()) destinations.push_back(v);
+    }
+    spatial_reprojection_stage(const spatial_reprojection_stage&) = delete;
+    ~spatial_reprojection_stage() { trhip_spatial_reprojection_destroy(h); }
+    void run(const trhip_reprojection_images& source_images, const trhip_reprojection_images& destination_images, void* color_out, void* stream = nullptr)
+    {
+        check(trhip_spatial_reprojection_run(h, &source_images, &destination_images, color_out, stream));
+    }
+    trhip_reprojection_timings get_timings() { trhip_reprojection_timings t; check(trhip_spatial_reprojection_get_timings(h, &t)); return t; }
+
+    device* dev;
+    std::vector<uint32_t> sources, destinations;
+    trhip_spatial_reprojection* h = nullptr;
+};
+
+// temporal_reprojection_stage (src/temporal_reprojection_stage.{hh,cc}): color = mix(color, last frame's colour found through
+// screen_motion, temporal_ratio) on the path-traced layers; the stage keeps last frame's colour, normal and pos itself.
+class temporal_reprojection_stage
+{
+public:
+    struct options { float temporal_ratio = 0.75f; };
+    temporal_reprojection_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), opt(opt)
+    {
+        check(trhip_temporal_reprojection_create(dev.h, size.x, size.y, layers, opt.temporal_ratio, &h));
+    }
+    temporal_reprojection_stage(const temporal_reprojection_stage&) = delete;
+    ~temporal_reprojection_stage() { trhip_temporal_reprojection_destroy(h); }
+    void run(const trhip_reprojection_images& images, void* stream = nullptr) { check(trhip_temporal_reprojection_run(h, &images, stream)); }
+    void reset_history() { check(trhip_temporal_reprojection_reset_history(h)); }
+    trhip_reprojection_timings get_timings() { trhip_reprojection_timings t; check(trhip_temporal_reprojection_get_timings(h, &t)); return t; }
+
+    device* dev;
+    options opt;
+    trhip_temporal_reprojection* h = nullptr;
+};
+
 class load_balancer
 {
 public:
@@ -570,6 +665,13 @@ public:
         // its own - and gets last frame's cameras as camera_pair.previous.  One device (or view shards): the feature targets of a pixel
         // distribution over several devices would have to be gathered and stitched like colour, which is not built.
         std::optional<bmfr_stage::options> bmfr;
+        // --spatial-reprojection=i,j,... : only these viewports of active_viewport_count are path traced, as compact layers in list order
+        // with their own cameras and RNG streams; the others get a first-hit G-buffer pass and are filled by spatial_reprojection_stage.
+        // `display` holds every viewport in natural order; with `accumulate` the sources are the accumulators and the full image is
+        // rewritten every frame.  --temporal-reprojection=r (0 = off): temporal_reprojection_stage on the path-traced layers in front of it;
+        // its history is one chain in frame order, like the denoiser's.  One device, no denoiser, one frame per launch.
+        std::vector<uint32_t> spatial_reprojection;
+        float temporal_reprojection = 0.0f;
     };
 
     // `devices`: HIP device index per logical device (repeat an index for --fake-devices); device 0 displays.
@@ -592,11 +694,28 @@ public:
             if(this->opt.accumulate || batch > 1) throw std::runtime_error("rt_renderer: a denoised frame is a fresh frame: no accumulation, one frame per launch");
             if(!std::is_same<Pipeline, path_tracer_stage>::value) throw std::runtime_error("rt_renderer: the denoiser reads the path tracer's diffuse target");
         }
+        const bool spatial_on = !this->opt.spatial_reprojection.empty();
+        if(!(this->opt.temporal_reprojection >= 0.0f) || !(this->opt.temporal_reprojection < 1.0f))
+            throw std::runtime_error("rt_renderer: the temporal reprojection ratio must be in [0, 1) (0 = off)");
+        const bool temporal_on = this->opt.temporal_reprojection > 0.0f;
+        if(spatial_on) check_viewport_list(this->opt.spatial_reprojection, this->opt.active_viewport_count, "rt_renderer: spatial reprojection");
+        if(spatial_on || temporal_on)
+        {
+            const std::string which = spatial_on ? "spatial reprojection" : "temporal reprojection";
+            if(devices.size() > 1)
+                throw std::runtime_error("rt_renderer: " + which + " with a distribution of count " + std::to_string(devices.size()) + " > 1: the stages read the "
+                                         "G-buffer of whole viewports on one device, gathering it from several is not built; use one device");
+            if(this->opt.bmfr) throw std::runtime_error("rt_renderer: " + which + " together with a denoiser: a chain of reprojection and a denoiser is not built");
+            if(batch > 1) throw std::runtime_error("rt_renderer: " + which + ": a reprojected frame is one frame, frames per launch must be 1");
+            if(temporal_on && this->opt.accumulate) throw std::runtime_error("rt_renderer: temporal reprojection blends the previous frame into a fresh frame: no accumulation");
+        }
         per_device.resize(devices.size());
         std::vector<double> ratios(devices.size(), 1.0 / devices.size());
         double cumulative = 0;
+        output_layers = this->opt.active_viewport_count * batch;                                  // layers of `display`
+        if(spatial_on) this->opt.active_viewport_count = this->opt.spatial_reprojection.size();  // the path tracer's layers: the active viewports, compact
         const size_t layers = this->opt.active_viewport_count * batch;
-        display_bytes = size_t(size.x) * size.y * 16 * layers;
+        display_bytes = size_t(size.x) * size.y * 16 * output_layers;
         for(size_t i = 0; i < devices.size(); ++i)
         {
             per_device_data& d = per_device[i];
@@ -621,6 +740,23 @@ public:
                 sl.ray_tracer = std::make_unique<Pipeline>(*d.dev, *d.scene_update, sl.color, po);
                 if(n_slots > 1) { sl.ray_tracer->set_frame_slots(n_slots); }   // the frames in flight fill the chip between them
                 if(batch > 1) sl.ray_tracer->set_frame_batch(batch);
+                if(spatial_on)
+                {   // the list as arithmetic runs, one stage per run (usually one): layer l shows viewport list[l], its camera and its RNG stream
+                    uint32_t first = 0;
+                    for(const viewport_run& r: viewport_runs(this->opt.spatial_reprojection))
+                    {
+                        Pipeline* stage = sl.ray_tracer.get();
+                        if(!sl.runs.empty())
+                        {
+                            sl.extra_tracers.push_back(std::make_unique<Pipeline>(*d.dev, *d.scene_update, sl.color, po));
+                            stage = sl.extra_tracers.back().get();
+                            if(n_slots > 1) stage->set_frame_slots(n_slots);
+                        }
+                        stage->set_shard(r.base, r.stride);
+                        sl.runs.push_back({stage, first, r.count});
+                        first += r.count;
+                    }
+                }
                 if(i != 0) sl.gbuffer_copy = per_device[0].dev->alloc(d.max_bytes);   // receive buffer on the display device
             }
             d.dev->sync();
@@ -632,7 +768,7 @@ public:
         // One device: nothing sits between the path tracer and the tonemap stage (no transfer, no stitch), and the stage writes the slot's
         // display image while it writes its colour target - the same bits without a second pass over the frame.  TRHIP_FUSED_TONEMAP=0: off.
         const char* fe = getenv("TRHIP_FUSED_TONEMAP");
-        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr;
+        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr && !spatial_on && !temporal_on;
         if(this->opt.bmfr)
         {
             device& d0 = *per_device[0].dev;
@@ -650,6 +786,33 @@ public:
             last_cameras = scene.cameras;
             current_cameras = scene.cameras;
         }
+        if(spatial_on || temporal_on)
+        {
+            device& d0 = *per_device[0].dev;
+            const size_t layer_px = size_t(size.x) * size.y, px = layer_px * layers;
+            for(slot_data& sl: per_device[0].slots)
+            {
+                trhip_pt_targets& t = sl.targets;
+                t.color = sl.color;
+                t.pos = d0.alloc(px * 16); t.normal = d0.alloc(px * 8); t.instance_id = d0.alloc(px * 4);
+                if(temporal_on) t.screen_motion = d0.alloc(px * 8);
+                if(spatial_on) { sl.full = d0.alloc(display_bytes); check(trhip_memset(d0.h, sl.full, 0, display_bytes, nullptr)); }
+            }
+            if(temporal_on)
+            {
+                temporal = std::make_unique<temporal_reprojection_stage>(d0, size, (uint32_t)layers, temporal_reprojection_stage::options{this->opt.temporal_reprojection});
+                last_cameras = scene.cameras;
+                current_cameras = scene.cameras;
+            }
+            if(spatial_on)
+            {
+                spatial = std::make_unique<spatial_reprojection_stage>(d0, size, (uint32_t)output_layers, this->opt.spatial_reprojection);
+                gbuffer = std::make_unique<gbuffer_stage>(d0, size, this->opt.projection, this->opt.min_ray_dist);
+                const size_t dpx = layer_px * spatial->destinations.size();
+                destination_targets.normal = d0.alloc(dpx * 8); destination_targets.pos = d0.alloc(dpx * 16); destination_targets.instance_id = d0.alloc(dpx * 4);
+            }
+            d0.sync();
+        }
         fused_info.assign(frame_slots.size(), trhip_tonemap_info{-1, 0.0f, 0.0f, 0});     // what each slot's stage was last told: render() keeps it current
     }
 
@@ -657,10 +820,15 @@ public:
     {
         finish_all();
         bmfr.reset();
+        temporal.reset();
+        spatial.reset();
+        for(void* p: {destination_targets.normal, destination_targets.pos, destination_targets.instance_id}) if(p) per_device[0].dev->free(p);
         for(size_t i = 0; i < per_device.size(); ++i)
             for(slot_data& sl: per_device[i].slots)
             {
                 sl.ray_tracer.reset();
+                sl.extra_tracers.clear();
+                if(sl.full) per_device[i].dev->free(sl.full);
                 for(void* p: {sl.targets.diffuse, sl.targets.albedo, sl.targets.pos, sl.targets.normal, sl.targets.screen_motion, sl.targets.instance_id})
                     if(p) per_device[i].dev->free(p);
                 if(sl.gbuffer_copy) per_device[0].dev->free(sl.gbuffer_copy);
@@ -677,6 +845,7 @@ public:
             {
                 sl.ray_tracer->reset_accumulated_samples();
                 if(reset_sample_counter) sl.ray_tracer->reset_sample_counter();
+                for(auto& t: sl.extra_tracers) { t->reset_accumulated_samples(); if(reset_sample_counter) t->reset_sample_counter(); }
             }
         if(reset_sample_counter) frame_index = 0;
         accumulated_frames = 0;
@@ -707,6 +876,7 @@ public:
         const size_t k = (frame_index / batch) % frame_slots.size();
         current_slot = (int)k;
         const uint32_t layers = (uint32_t)opt.active_viewport_count * batch;
+        const bool reprojection = temporal || spatial;
         device& display_device = *per_device[0].dev;
         void* const display_stream = per_device[0].slots[k].stream;
         if(fused_tonemap)
@@ -725,9 +895,14 @@ public:
             slot_data& sl = d.slots[k];
             if(!opt.accumulate) sl.ray_tracer->reset_accumulated_samples();
             if(frame_slots.size() > 1 || batch > 1) sl.ray_tracer->set_frame_counter(frame_index);   // one stage per slot: slot k renders frames k, k + N, ... (B at a time)
+            for(auto& t: sl.extra_tracers)
+            {
+                if(!opt.accumulate) t->reset_accumulated_samples();
+                if(frame_slots.size() > 1) t->set_frame_counter(frame_index);
+            }
             if(i != 0)   // the slot's previous frame has been stitched on the display device: its receive buffer is free
                 check(trhip_stream_wait_peer(d.dev->h, sl.stream, display_device.h, display_stream));
-            if(bmfr)
+            if(bmfr || temporal)
             {   // camera_pair.previous = the cameras of the frame before this one
                 if(last_cameras != uploaded_previous_cameras)
                 {   // frames in flight read the cameras they were enqueued with: they finish before the record changes
@@ -736,9 +911,20 @@ public:
                     uploaded_previous_cameras = last_cameras;
                 }
                 last_cameras = current_cameras;
-                const uvec2 ts = get_distribution_target_size(d.dist);
-                check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
             }
+            const uvec2 ts = get_distribution_target_size(d.dist);
+            if(!sl.runs.empty())
+            {   // a viewport list: every run of it into its layers of the compact targets
+                const size_t layer_px = size_t(ts.x) * ts.y;
+                for(const run_data& r: sl.runs)
+                {
+                    trhip_pt_targets t = sl.targets;
+                    auto at = [&](void* p, size_t bytes_per_pixel) { return p ? static_cast<void*>(static_cast<char*>(p) + r.first * layer_px * bytes_per_pixel) : nullptr; };
+                    t.color = at(t.color, 16); t.pos = at(t.pos, 16); t.normal = at(t.normal, 8); t.instance_id = at(t.instance_id, 4); t.screen_motion = at(t.screen_motion, 8);
+                    check(trhip_pt_render_targets(r.stage->pt, &t, ts.x, ts.y, r.count, sl.stream));
+                }
+            }
+            else if(bmfr || reprojection) check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
             else sl.ray_tracer->run(sl.stream);
             if(i != 0) check(trhip_copy_peer(display_device.h, sl.gbuffer_copy, d.dev->h, sl.color, d.target_bytes(layers), sl.stream));
         }
@@ -760,14 +946,32 @@ public:
         }
         display = frame_slots[k].display;
         void* post_stream = display_stream;
+        if((bmfr || reprojection) && frame_slots.size() > 1)
+        {   // the denoiser's / temporal stage's history is one chain over the frames of all slots: it runs in frame order on the display device's
+            // default stream (and so does the spatial stage, whose destination G-buffer the slots share)
+            check(trhip_stream_wait(display_device.h, nullptr, display_stream)); post_stream = nullptr;
+        }
         if(bmfr)
-        {   // the denoiser's history is one chain over the frames of all slots: it runs in frame order on the display device's default stream
-            if(frame_slots.size() > 1) { check(trhip_stream_wait(display_device.h, nullptr, display_stream)); post_stream = nullptr; }
+        {
             const trhip_pt_targets& t = per_device[0].slots[k].targets;
             bmfr->features = trhip_bmfr_features{t.color, t.diffuse, t.albedo, t.normal, t.pos, t.screen_motion, t.instance_id};
             bmfr->run(frame_index, post_stream);
         }
-        if(!fused_tonemap) tonemap->run(per_device[0].slots[k].color, display, size, layers, post_stream);
+        const void* final_color = per_device[0].slots[k].color;
+        if(reprojection)
+        {
+            const slot_data& sl = per_device[0].slots[k];
+            const trhip_pt_targets& t = sl.targets;
+            if(temporal) temporal->run(trhip_reprojection_images{t.color, t.normal, t.pos, t.instance_id, t.screen_motion}, post_stream);
+            if(spatial)
+            {
+                gbuffer->run(spatial->destinations, destination_targets, post_stream);
+                spatial->run(trhip_reprojection_images{t.color, t.normal, t.pos, t.instance_id, nullptr},
+                             trhip_reprojection_images{nullptr, destination_targets.normal, destination_targets.pos, destination_targets.instance_id, nullptr}, sl.full, post_stream);
+                final_color = sl.full;
+            }
+        }
+        if(!fused_tonemap) tonemap->run(final_color, display, size, (uint32_t)output_layers, post_stream);
         if(post_stream != display_stream) check(trhip_stream_wait(display_device.h, display_stream, nullptr));
         frame_index += batch;
         accumulated_frames++;
@@ -811,8 +1015,13 @@ public:
         std::unique_ptr<Pipeline> ray_tracer;
         void* color = nullptr;          // the device's (partial) colour target of this slot
         void* gbuffer_copy = nullptr;   // non-primary devices: where the partial lands on the display device
-        trhip_pt_targets targets = {};  // denoiser: the gbuffer entries next to `color`
+        trhip_pt_targets targets = {};  // denoiser / reprojection: the gbuffer entries next to `color`
+        struct run { Pipeline* stage; uint32_t first, count; };
+        std::vector<run> runs;          // a viewport list: one stage per arithmetic run of it (ray_tracer is the first), its first layer and layer count
+        std::vector<std::unique_ptr<Pipeline>> extra_tracers;   // ... the stages of the runs after the first
+        void* full = nullptr;           // spatial reprojection: the colour of every viewport in natural order (`color` holds the sources)
     };
+    using run_data = typename slot_data::run;
     struct per_device_data
     {
         std::unique_ptr<device> dev;
@@ -834,6 +1043,11 @@ public:
     size_t display_bytes = 0;
     std::unique_ptr<tonemap_stage> tonemap;
     std::unique_ptr<bmfr_stage> bmfr;      // options.bmfr
+    std::unique_ptr<temporal_reprojection_stage> temporal;      // options.temporal_reprojection
+    std::unique_ptr<spatial_reprojection_stage> spatial;        // options.spatial_reprojection
+    std::unique_ptr<gbuffer_stage> gbuffer;
+    trhip_gbuffer_targets destination_targets = {};             // the G-buffer of the viewports that are reprojected, shared by the slots
+    size_t output_layers = 1;                                    // layers of `display` (every viewport; the path tracer renders opt.active_viewport_count)
     std::vector<uint8_t> last_cameras, current_cameras, uploaded_previous_cameras;   // denoiser: camera_data of the last frame rendered / of the scene as it is / camera_pair.previous on the device
     bool fused_tonemap = false;
     std::vector<trhip_tonemap_info> fused_info;

@@ -556,6 +556,73 @@ int trhip_bmfr_fit_blocks(trhip_device* dev, uint32_t blocks, uint32_t channels,
 #define TRHIP_BMFR_PREVIOUS_POS 10         /* RGBA32F: the pos target of the last frame, w = 1 where it had no surface */
 int trhip_bmfr_download(trhip_bmfr* bmfr, int which, void* host, size_t bytes);
 
+/* ---- sparse light fields (--spatial-reprojection=i,j,... / --temporal-reprojection=r; src/spatial_reprojection_stage.{hh,cc},
+ * src/temporal_reprojection_stage.{hh,cc}, shader/spatial_reprojection.comp, shader/temporal_reprojection.comp).  Only the listed
+ * viewports of a camera grid are path traced; the others are filled from them through the G-buffer.  csrc/reprojection.hip.
+ * Frame order: path tracer (the sources) -> temporal stage on the sources -> trhip_gbuffer_render (the other viewports) -> spatial stage
+ * -> tonemap.  All images are fp32 device images [layers][height][width]. */
+typedef struct trhip_gbuffer_targets {
+    void* normal;       /* RG32F, octahedral (math.glsl:480-485) */
+    void* pos;          /* RGBA32F, world space, w = 0 */
+    void* instance_id;  /* R32I, -1 = no surface */
+} trhip_gbuffer_targets;
+/* The first hit of one ray through every pixel centre of `count` viewports in one launch: compact layers [count][height][width] in the
+ * order of `viewports` (any order, repeats allowed); null targets are not written.  pos.xyz and instance_id are what
+ * trhip_feature_render features 3 and 9 give for that viewport with a duplicate distribution, bit for bit, normal is the packing of
+ * feature 1; a miss writes the ray origin, the packed -direction and -1, as the targets of trhip_pt_render_targets do.  Both
+ * acceleration-structure layouts. */
+int trhip_gbuffer_render(trhip_device* dev, int projection, const uint32_t* viewports, uint32_t count, float min_ray_dist,
+                         const trhip_gbuffer_targets* targets, uint32_t width, uint32_t height, void* stream);
+typedef struct trhip_reprojection_images {
+    void* color;         /* RGBA32F */
+    void* normal;        /* RG32F   */
+    void* pos;           /* RGBA32F */
+    void* instance_id;   /* R32I    */
+    void* screen_motion; /* RG32F, the temporal stage only */
+} trhip_reprojection_images;
+typedef struct trhip_reprojection_timings { float total_ms; uint32_t frames; } trhip_reprojection_timings;   /* device ms of the last frame's kernel */
+/* spatial_reprojection_stage.  Per output pixel of viewport v (natural order):
+ *   v is a source: its colour, bit for bit.
+ *   a destination with a surface: pos is projected with every source's view_proj (the scene's current cameras, read on the device when
+ *     the kernel runs).  The candidate is the source with the smallest z/w below 1 (ties: the first).  A try of source s takes the four
+ *     taps at floor(uv * size - 0.5), uv = (xy/w * 0.5 + 0.5, y -> 1 - y); a tap is kept when it is inside the image, has a surface,
+ *     dot(n_tap, n) > 0.99 and |pos - pos_tap|^2 < 0.01; the bilinear weights are renormalised over the kept taps and the try succeeds
+ *     when the kept weight exceeds 1e-5.  The candidate is tried first; if it fails the other sources are tried in list order, each only
+ *     if its depth is below the best accepted so far (below 1 while none is).  Nothing accepted: default_value (the hosts pass NaN).
+ *   a destination without a surface: the same pixel of the first source that has no surface there either, else default_value.
+ * Deviations from the reference: (1) the tap origin is floor(), where the reference truncates towards zero;
+ * (2) a source with w <= 0 is skipped; (3) "no surface" is a NaN pos or instance_id < 0, as in the BMFR stage; (4) the sources are named
+ * by a list and the output is in natural viewport order, instead of "the first N layers" and a reorder mask in the tonemap stage;
+ * (5) every image is fp32.  view_proj is used as it is: perspective and orthographic cameras. */
+typedef struct trhip_spatial_reprojection trhip_spatial_reprojection;
+int trhip_spatial_reprojection_create(trhip_device* dev, uint32_t width, uint32_t height, uint32_t total_viewports, const uint32_t* source_viewports,
+                                      uint32_t source_count, const float default_value[4], trhip_spatial_reprojection** out);
+void trhip_spatial_reprojection_destroy(trhip_spatial_reprojection* stage);
+/* sources: {color, normal, pos, instance_id} [source_count] layers in the order of source_viewports; destinations: {normal, pos,
+ * instance_id} of the other viewports in ascending order; color_out: RGBA32F [total_viewports][height][width].  Asynchronous on `stream`. */
+int trhip_spatial_reprojection_run(trhip_spatial_reprojection* stage, const trhip_reprojection_images* sources,
+                                   const trhip_reprojection_images* destinations, void* color_out, void* stream);
+int trhip_spatial_reprojection_get_timings(trhip_spatial_reprojection* stage, trhip_reprojection_timings* out);   /* waits for the last frame */
+/* Decision record, 8 bytes per pixel: u8 kind (0 none, 1 reprojected, 2 no-surface copy), u8 source slot, u8 keep bits (tl, tr, bl, br),
+ * u8 zero, i16 x 2 tap origin.  Spatial: [destinations][h][w]; temporal: [layers][h][w].  Downloads synchronise the device. */
+#define TRHIP_REPROJECTION_DECISIONS 0
+#define TRHIP_REPROJECTION_PREVIOUS_COLOR 1     /* temporal: RGBA32F, the colour the last frame left */
+#define TRHIP_REPROJECTION_PREVIOUS_NORMAL 2    /* temporal: RG32F */
+#define TRHIP_REPROJECTION_PREVIOUS_POS 3       /* temporal: RGBA32F, w = 1 where it had no surface */
+int trhip_spatial_reprojection_download(trhip_spatial_reprojection* stage, int which, void* host, size_t bytes);
+/* temporal_reprojection_stage, in front of the spatial stage on the path-traced layers: the taps above at screen_motion in the previous
+ * frame's normal / pos / colour, color = mix(color, reprojected, ratio); the pixel stays as it is when no tap is kept or the result has
+ * a NaN.  A no-surface pixel keeps its colour and is never a tap.  After the blend the frame's colour, normal and pos become the
+ * stage's history (two copies, ping-pong); the first frame after create or reset_history only stores it.  ratio in (0, 1). */
+typedef struct trhip_temporal_reprojection trhip_temporal_reprojection;
+int trhip_temporal_reprojection_create(trhip_device* dev, uint32_t width, uint32_t height, uint32_t layers, float ratio, trhip_temporal_reprojection** out);
+void trhip_temporal_reprojection_destroy(trhip_temporal_reprojection* stage);
+/* images: {color in/out, normal, pos, screen_motion, instance_id or NULL}.  Asynchronous on `stream`; frames of one stage form one history. */
+int trhip_temporal_reprojection_run(trhip_temporal_reprojection* stage, const trhip_reprojection_images* images, void* stream);
+int trhip_temporal_reprojection_reset_history(trhip_temporal_reprojection* stage);
+int trhip_temporal_reprojection_get_timings(trhip_temporal_reprojection* stage, trhip_reprojection_timings* out);
+int trhip_temporal_reprojection_download(trhip_temporal_reprojection* stage, int which, void* host, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,27 @@ BMFR_DIFFUSE_ONLY, BMFR_DIFFUSE_SPECULAR = 0, 1
  BMFR_ACCEPT_BITS, BMFR_BLOCK_OFFSETS, BMFR_PREVIOUS_NORMAL, BMFR_PREVIOUS_POS) = range(11)
 
 
+class GbufferTargetsC(C.Structure):
+    """trhip_gbuffer_targets: what trhip_gbuffer_render writes per viewport; None = not requested."""
+    _fields_ = [(n, C.c_void_p) for n in ("normal", "pos", "instance_id")]
+
+
+class ReprojectionImagesC(C.Structure):
+    """trhip_reprojection_images: the images a reprojection stage reads (and, for the temporal stage's colour, writes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "normal", "pos", "instance_id", "screen_motion")]
+
+
+class ReprojectionTimingsC(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("frames", C.c_uint32)]
+
+
+# trhip_*_reprojection_download; the kinds of a decision record
+REPROJECTION_DECISIONS, REPROJECTION_PREVIOUS_COLOR, REPROJECTION_PREVIOUS_NORMAL, REPROJECTION_PREVIOUS_POS = range(4)
+REPROJ_NONE, REPROJ_REPROJECTED, REPROJ_SKY_COPY = 0, 1, 2
+# the decision record: 8 bytes per pixel
+REPROJECTION_RECORD = [("kind", "u1"), ("slot", "u1"), ("bits", "u1"), ("zero", "u1"), ("ox", "<i2"), ("oy", "<i2")]
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -231,6 +252,18 @@ SYMBOLS = {
     "trhip_bmfr_get_timings": (_i, [_vp, C.POINTER(BmfrTimingsC)]),
     "trhip_bmfr_fit_blocks": (_i, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "trhip_bmfr_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_gbuffer_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _f, C.POINTER(GbufferTargetsC), _u32, _u32, _vp]),
+    "trhip_spatial_reprojection_create": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_u32), _u32, C.POINTER(_f), C.POINTER(_vp)]),
+    "trhip_spatial_reprojection_destroy": (None, [_vp]),
+    "trhip_spatial_reprojection_run": (_i, [_vp, C.POINTER(ReprojectionImagesC), C.POINTER(ReprojectionImagesC), _vp, _vp]),
+    "trhip_spatial_reprojection_get_timings": (_i, [_vp, C.POINTER(ReprojectionTimingsC)]),
+    "trhip_spatial_reprojection_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_temporal_reprojection_create": (_i, [_vp, _u32, _u32, _u32, _f, C.POINTER(_vp)]),
+    "trhip_temporal_reprojection_destroy": (None, [_vp]),
+    "trhip_temporal_reprojection_run": (_i, [_vp, C.POINTER(ReprojectionImagesC), _vp]),
+    "trhip_temporal_reprojection_reset_history": (_i, [_vp]),
+    "trhip_temporal_reprojection_get_timings": (_i, [_vp, C.POINTER(ReprojectionTimingsC)]),
+    "trhip_temporal_reprojection_download": (_i, [_vp, _i, _vp, C.c_size_t]),
 }
 
 _LIB = None

@@ -284,7 +284,9 @@ struct trhip_pt {
     PtStage* stage;
 };
 
-namespace tr { int device_index(const trhip_device* dev) { return dev ? dev->hip_device : -1; } }   // for the stages of other translation units (bmfr.hip)
+namespace tr { int device_index(const trhip_device* dev) { return dev ? dev->hip_device : -1; } }   // for the stages of other translation units (bmfr.hip, reprojection.hip)
+namespace tr { DeviceScene* device_scene(trhip_device* dev) { return dev ? &dev->scene : nullptr; } }
+namespace tr { uint* device_overflow_flag(trhip_device* dev) { return dev ? dev->overflow_flag : nullptr; } }
 
 #define DEVCHK(dev) do { if (!(dev)) return set_error("null trhip_device"); hipError_t e_ = hipSetDevice((dev)->hip_device); \
     if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)

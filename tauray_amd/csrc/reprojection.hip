@@ -1,0 +1,517 @@
+// Sparse light fields for gfx950: the first-hit G-buffer pass of viewports that are not path traced (k_gbuffer), spatial_reprojection_stage
+// (src/spatial_reprojection_stage.{hh,cc}, shader/spatial_reprojection.comp restated: k_spatial_reprojection) and
+// temporal_reprojection_stage (src/temporal_reprojection_stage.{hh,cc}, shader/temporal_reprojection.comp restated:
+// k_temporal_reprojection), with the entry points trhip_gbuffer_render, trhip_spatial_reprojection_* and trhip_temporal_reprojection_*
+// of include/trhip.h.  Layouts: reprojection.h.  Everything is fp32 and evaluated without contraction in a fixed order, no atomics: two
+// runs of the same inputs give the same bits.  Built with the flags of api.hip, so that k_gbuffer computes what k_feature computes.
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "reprojection.h"
+#include "taps.h"
+#include "pt.h"
+#include "trace.h"
+
+namespace tr {
+namespace {
+
+#define RP_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+#define RP_DEVCHK(idx) do { hipError_t e_ = hipSetDevice(idx); if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)
+
+constexpr int KB = TR_BLOCK;
+constexpr int GBUFFER_CHUNK = 64;      // viewports of one k_gbuffer launch (the list travels in the kernel arguments)
+static_assert(REPROJ_TILE * REPROJ_TILE == KB, "a workgroup is one tile");
+
+struct ViewportList { uint v[GBUFFER_CHUNK]; };
+
+TR_DEV f2 octahedral_pack(f3 n) {        // math.glsl:480-485, as write_first_hit_gbuffer (path_tracer.hip) evaluates it
+    const f3 nn = n / (fabsf(n.x) + fabsf(n.y) + fabsf(n.z));
+    return nn.z >= 0.0f ? F2(nn.x, nn.y)
+                        : F2((1 - fabsf(nn.y)) * ((nn.x >= 0.0f ? 1.0f : 0.0f) * 2 - 1), (1 - fabsf(nn.x)) * ((nn.y >= 0.0f ? 1.0f : 0.0f) * 2 - 1));
+}
+
+// Pixel of a thread: a workgroup is a 16 x 16 tile of layer blockIdx.z, a wave an 8 x 8 quarter of it (coherent primary rays, shared tap lines).
+TR_DEV void tile_pixel(int& x, int& y) {
+    const uint t = threadIdx.x, wave = t >> 6, k = t & 63u;
+    x = (int)(blockIdx.x * REPROJ_TILE + ((wave & 1u) << 3) + (k & 7u));
+    y = (int)(blockIdx.y * REPROJ_TILE + ((wave >> 1) << 3) + (k >> 3));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The primary hit of k_feature (api.hip) for `count` viewports at once: pos = feature 3, instance id = feature 9, normal = the packing of
+// feature 1; a miss writes the ray origin, the packed -direction and -1, as the path tracer's targets do (k_first_hit_gbuffer).
+template <bool TWO_LEVEL>
+__global__ __launch_bounds__(KB) void k_gbuffer(SceneView sv, LaunchCtx L, int projection, ViewportList list, float min_ray_dist,
+                                                f2* normal, f4* pos, int* instance_id, uint* overflow_flag) {
+    __shared__ int s_stack_rows[TR_STACK_WORDS];
+    int* const s_stack = s_stack_rows + TR_STACK_ROW0;
+    int px, py;
+    tile_pixel(px, py);
+    if ((uint)px >= L.launch_w || (uint)py >= L.launch_h) return;
+    const uint layer = blockIdx.z;
+    const CameraData cam = sv.cameras[list.v[layer]];
+    f3 origin, dir;
+    get_screen_camera_ray(L, px, py, cam, projection, false, F2(0), F2(0.5f), origin, dir);
+    const f3 ray_origin = projection == 2 ? origin : F3(cam.origin);
+    HitRecord hit;
+    TraceStats st = {};
+    int overflow = 0;
+    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), 0u, s_stack + threadIdx.x, hit, st, overflow);
+    if (overflow) *overflow_flag = 1;
+    f3 p = ray_origin, n = -dir;
+    int id = -1;
+    if (hit.instance_id >= 0) {
+        SurfacePoint v;
+        SampledMaterial mat;
+        shade_surface(sv, hit.instance_id, hit.primitive_id, hit.u, hit.v, dir, ray_origin, false, 0, false, v, mat);
+        p = v.pos; n = v.mapped_normal; id = hit.instance_id;
+    }
+    const size_t pix = ((size_t)layer * L.launch_h + (uint)py) * L.launch_w + (uint)px;
+    if (normal) normal[pix] = octahedral_pack(n);
+    if (pos) pos[pix] = F4(p, 0.0f);
+    if (instance_id) instance_id[pix] = id;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The tap logic both stages share (tap_position, tap_weights: taps.h; the success threshold there is REPROJ_MIN_WEIGHT).
+
+struct TapSource {      // one layer of G-buffer and colour that taps are taken from
+    const f4* color; const f2* normal; const f4* pos; const int* instance_id;      // instance_id may be null
+    bool pos_w_marks;   // a history layer: pos.w != 0 = no surface
+};
+
+TR_DEV bool no_surface(const f4 p, const int* ids, size_t pix, bool pos_w_marks) {
+    if (pos_w_marks) return p.w != 0.0f;
+    return any_nan(F3(p)) || (ids && ids[pix] < 0);
+}
+
+// Keep bits of the four taps at (tx, ty): inside the image, a surface, dot(n_tap, n) > 0.99, |pos - pos_tap|^2 < 0.01.
+TR_DEV uint keep_taps(const TapSource& S, int w, int h, int tx, int ty, f3 n, f3 p) {
+    uint bits = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = tx + (k & 1), y = ty + (k >> 1);
+        if (x < 0 || y < 0 || x >= w || y >= h) continue;
+        const size_t s = (size_t)y * w + x;
+        const f4 pp = S.pos[s];
+        if (no_surface(pp, S.instance_id, s, S.pos_w_marks)) continue;
+        const f3 d = p - F3(pp);
+        if (dot(octahedral_unpack(S.normal[s]), n) > REPROJ_NORMAL_COS && dot(d, d) < REPROJ_DISTANCE_SQ) bits |= 1u << k;
+    }
+    return bits;
+}
+
+TR_DEV f4 blend_taps(const f4* img, int w, int tx, int ty, uint bits, const float cw[4]) {
+    f4 r = F4(0.0f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f4 t = F4(0.0f);
+        if (bits & (1u << k)) t = img[(size_t)(ty + (k >> 1)) * w + (tx + (k & 1))];
+        r = r + t * cw[k];
+    }
+    return r;
+}
+
+// One try: the taps of `S` around uv.  True when the kept weight exceeds 1e-5; then `out` is the blended colour.
+TR_DEV bool try_taps(const TapSource& S, int w, int h, f2 uv, f3 n, f3 p, f4& out, uint& bits, int& tx, int& ty) {
+    float qx, qy;
+    tap_position(uv, w, h, tx, ty, qx, qy);
+    bits = keep_taps(S, w, h, tx, ty, n, p);
+    float cw[4];
+    if (!(tap_weights(qx, qy, bits, cw) > REPROJ_MIN_WEIGHT)) return false;
+    out = blend_taps(S.color, w, tx, ty, bits, cw);
+    return true;
+}
+
+TR_DEV ReprojRecord make_record(int kind, int slot, uint bits, int tx, int ty) {
+    ReprojRecord r;
+    r.kind = (uint8_t)kind; r.slot = (uint8_t)slot; r.bits = (uint8_t)bits; r.zero = 0; r.ox = (int16_t)tx; r.oy = (int16_t)ty;
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------------------
+struct SpatialParams {
+    int w, h, total, sources;
+    const CameraData* cameras;      // the scene's current cameras, [total] at least
+    const int* source_viewport;     // [sources]
+    const int* layer_of;            // [total]: >= 0: source slot; < 0: destination layer -(v + 1)
+    const f4* src_color; const f2* src_normal; const f4* src_pos; const int* src_id;
+    const f2* dst_normal; const f4* dst_pos; const int* dst_id;
+    f4* out;
+    f4 default_value;
+    ReprojRecord* record;           // [total - sources][h][w]
+};
+
+// Depth of world position p under source s and its screen position; false: behind the camera plane (w <= 0) or not in front of the far plane.
+TR_DEV bool project_to_source(const SpatialParams& P, int s, f3 p, float& depth, f2& uv) {
+    const f4 c = mul(P.cameras[P.source_viewport[s]].view_proj, F4(p, 1.0f));      // s is wave-uniform: the matrix arrives through scalar loads
+    if (!(c.w > 0.0f)) return false;
+    depth = c.z / c.w;
+    uv = F2((c.x / c.w) * 0.5f + 0.5f, (c.y / c.w) * 0.5f + 0.5f);
+    return depth < 1.0f;
+}
+
+// One thread per output pixel; blockIdx.z = viewport in natural order.
+__global__ __launch_bounds__(KB) void k_spatial_reprojection(SpatialParams P) {
+    int x, y;
+    tile_pixel(x, y);
+    if (x >= P.w || y >= P.h) return;
+    const int vp = (int)blockIdx.z;
+    const size_t layer_px = (size_t)P.w * P.h, in_layer = (size_t)y * P.w + x;
+    const int lo = P.layer_of[vp];
+    f4* const out = P.out + (size_t)vp * layer_px + in_layer;
+    if (lo >= 0) { *out = P.src_color[(size_t)lo * layer_px + in_layer]; return; }
+    const size_t dpix = (size_t)(-(lo + 1)) * layer_px + in_layer;
+    const f4 pp = P.dst_pos[dpix];
+    f4 result = P.default_value;
+    ReprojRecord rec = make_record(REPROJ_NONE, 0, 0, 0, 0);
+    if (no_surface(pp, P.dst_id, dpix, false)) {
+        for (int s = 0; s < P.sources; ++s) {
+            const size_t spix = (size_t)s * layer_px + in_layer;
+            if (no_surface(P.src_pos[spix], P.src_id, spix, false)) { result = P.src_color[spix]; rec = make_record(REPROJ_SKY_COPY, s, 0, 0, 0); break; }
+        }
+    } else {
+        const f3 p = F3(pp), n = octahedral_unpack(P.dst_normal[dpix]);
+        // the candidate: the source that sees the point nearest (smallest z / w below 1; ties go to the first)
+        int cand = -1;
+        float cand_depth = 1.0f;
+        for (int s = 0; s < P.sources; ++s) {
+            float depth; f2 uv;
+            if (project_to_source(P, s, p, depth, uv) && depth < cand_depth) { cand = s; cand_depth = depth; }
+        }
+        // the candidate first; if it fails, the others in order, each only if it is nearer than the best accepted so far
+        float best = 1.0f;
+        for (int i = (cand >= 0 ? -1 : 0); i < P.sources; ++i) {
+            const int s = i < 0 ? cand : i;
+            if (i >= 0 && s == cand) continue;
+            float depth; f2 uv;
+            if (!project_to_source(P, s, p, depth, uv) || !(depth < best)) continue;
+            const TapSource S = {P.src_color + (size_t)s * layer_px, P.src_normal + (size_t)s * layer_px, P.src_pos + (size_t)s * layer_px,
+                                 P.src_id ? P.src_id + (size_t)s * layer_px : nullptr, false};
+            f4 c; uint bits; int tx, ty;
+            if (try_taps(S, P.w, P.h, uv, n, p, c, bits, tx, ty)) {
+                result = c; best = depth; rec = make_record(REPROJ_REPROJECTED, s, bits, tx, ty);
+                if (i < 0) break;
+            }
+        }
+    }
+    *out = result;
+    P.record[dpix] = rec;
+}
+
+// ---------------------------------------------------------------------------------------------------
+struct TemporalParams {
+    int w, h, layers, have_history;
+    float ratio;
+    f4* color; const f2* normal; const f4* pos; const f2* motion; const int* instance_id;
+    const f4* color_prev; const f2* normal_prev; const f4* pos_prev;      // pos.w = 1: no surface
+    f4* color_cur; f2* normal_cur; f4* pos_cur;
+    ReprojRecord* record;
+};
+
+__global__ __launch_bounds__(KB) void k_temporal_reprojection(TemporalParams P) {
+    int x, y;
+    tile_pixel(x, y);
+    if (x >= P.w || y >= P.h) return;
+    const size_t layer_px = (size_t)P.w * P.h, base = (size_t)blockIdx.z * layer_px, pix = base + (size_t)y * P.w + x;
+    const f4 pp = P.pos[pix];
+    const f2 packed = P.normal[pix];
+    const bool nosurf = no_surface(pp, P.instance_id, pix, false);
+    f4 col = P.color[pix];
+    ReprojRecord rec = make_record(REPROJ_NONE, 0, 0, 0, 0);
+    if (P.have_history && !nosurf) {
+        const TapSource S = {P.color_prev + base, P.normal_prev + base, P.pos_prev + base, nullptr, true};
+        f4 c; uint bits; int tx, ty;
+        if (try_taps(S, P.w, P.h, P.motion[pix], octahedral_unpack(packed), F3(pp), c, bits, tx, ty)) {
+            const f4 blended = mix4(col, c, P.ratio);
+            if (!(isnan(blended.x) || isnan(blended.y) || isnan(blended.z) || isnan(blended.w))) {
+                col = blended;
+                P.color[pix] = col;
+                rec = make_record(REPROJ_REPROJECTED, 0, bits, tx, ty);
+            }
+        }
+    }
+    P.color_cur[pix] = col;
+    P.normal_cur[pix] = packed;
+    P.pos_cur[pix] = F4(pp.x, pp.y, pp.z, nosurf ? 1.0f : 0.0f);
+    P.record[pix] = rec;
+}
+
+dim3 tile_grid(uint w, uint h, uint layers) { return dim3((w + REPROJ_TILE - 1) / REPROJ_TILE, (h + REPROJ_TILE - 1) / REPROJ_TILE, layers); }
+
+int check_size(const char* who, uint32_t w, uint32_t h, uint32_t layers) {
+    if (w == 0 || h == 0 || layers == 0) return set_error(std::string(who) + ": zero width, height or layer count");
+    if (w > 16384 || h > 16384 || layers > 4096) return set_error(std::string(who) + ": image too large");      // the record's tap origin is int16
+    return 0;
+}
+
+}  // namespace
+}  // namespace tr
+
+using namespace tr;
+
+struct trhip_spatial_reprojection {
+    trhip_device* dev = nullptr;
+    int hip_device = 0;
+    uint32_t w = 0, h = 0, total = 0, sources = 0;
+    f4 default_value = {0, 0, 0, 0};
+    int* source_viewport = nullptr;      // device
+    int* layer_of = nullptr;             // device
+    ReprojRecord* record = nullptr;
+    hipEvent_t ev[2] = {};
+    uint32_t frames = 0;
+    size_t record_count() const { return (size_t)(total - sources) * w * h; }
+};
+
+struct trhip_temporal_reprojection {
+    int hip_device = 0;
+    uint32_t w = 0, h = 0, layers = 0;
+    float ratio = 0;
+    int cur = 0;                         // the history a frame reads; it writes cur ^ 1
+    bool have_history = false;
+    f4* color[2] = {};
+    f2* normal[2] = {};
+    f4* pos[2] = {};
+    ReprojRecord* record = nullptr;
+    hipEvent_t ev[2] = {};
+    uint32_t frames = 0;
+    size_t pixels() const { return (size_t)w * h * layers; }
+};
+
+static void spatial_release(trhip_spatial_reprojection* s) {
+    if (s->source_viewport) (void)hipFree(s->source_viewport);
+    if (s->layer_of) (void)hipFree(s->layer_of);
+    if (s->record) (void)hipFree(s->record);
+    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+static void temporal_release(trhip_temporal_reprojection* t) {
+    for (int i = 0; i < 2; ++i) {
+        if (t->color[i]) (void)hipFree(t->color[i]);
+        if (t->normal[i]) (void)hipFree(t->normal[i]);
+        if (t->pos[i]) (void)hipFree(t->pos[i]);
+    }
+    if (t->record) (void)hipFree(t->record);
+    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+    delete t;
+}
+
+extern "C" {
+
+int trhip_gbuffer_render(trhip_device* dev, int projection, const uint32_t* viewports, uint32_t count, float min_ray_dist,
+                         const trhip_gbuffer_targets* targets, uint32_t width, uint32_t height, void* stream) {
+    if (!dev) return set_error("trhip_gbuffer_render: null trhip_device (no HIP device: there is no CPU fallback)");
+    if (!targets) return set_error("trhip_gbuffer_render: null targets");
+    if (count == 0) return 0;
+    if (!viewports) return set_error("trhip_gbuffer_render: null viewport list");
+    if (check_size("trhip_gbuffer_render", width, height, count)) return 1;
+    RP_DEVCHK(device_index(dev));
+    DeviceScene* scene = device_scene(dev);
+    if (!scene->accel_built) return set_error("trhip_gbuffer_render: call trhip_scene_build_accel first");
+    for (uint32_t i = 0; i < count; ++i)
+        if (viewports[i] >= scene->camera_count) return set_error("trhip_gbuffer_render: viewport " + std::to_string(viewports[i]) + " out of range");
+    LaunchCtx L{};      // a duplicate distribution of the whole image: what trhip_feature_render launches for it
+    L.size_x = width; L.size_y = height; L.strategy = 0; L.index = 0; L.count = 1; L.primary = 1; L.launch_w = width; L.launch_h = height;
+    const size_t layer_px = (size_t)width * height;
+    for (uint32_t first = 0; first < count; first += GBUFFER_CHUNK) {
+        const uint32_t n = std::min<uint32_t>(GBUFFER_CHUNK, count - first);
+        ViewportList list{};
+        for (uint32_t i = 0; i < n; ++i) list.v[i] = viewports[first + i];
+        f2* normal = targets->normal ? (f2*)targets->normal + first * layer_px : nullptr;
+        f4* pos = targets->pos ? (f4*)targets->pos + first * layer_px : nullptr;
+        int* ids = targets->instance_id ? (int*)targets->instance_id + first * layer_px : nullptr;
+        hipLaunchKernelGGL(scene->two_level ? k_gbuffer<true> : k_gbuffer<false>, tile_grid(width, height, n), dim3(KB), 0, (hipStream_t)stream, scene->view(), L,
+                           projection, list, min_ray_dist, normal, pos, ids, device_overflow_flag(dev));
+    }
+    RP_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int trhip_spatial_reprojection_create(trhip_device* dev, uint32_t width, uint32_t height, uint32_t total_viewports, const uint32_t* source_viewports,
+                                      uint32_t source_count, const float default_value[4], trhip_spatial_reprojection** out) {
+    if (!out) return set_error("trhip_spatial_reprojection_create: null out");
+    *out = nullptr;
+    if (check_size("trhip_spatial_reprojection_create", width, height, total_viewports)) return 1;
+    if (!source_viewports || source_count == 0) return set_error("trhip_spatial_reprojection_create: no source viewports");
+    if (source_count >= total_viewports) return set_error("trhip_spatial_reprojection_create: every viewport is a source: nothing to reproject");
+    if (source_count > (uint32_t)REPROJ_MAX_SOURCES) return set_error("trhip_spatial_reprojection_create: more than 255 source viewports");
+    if (!default_value) return set_error("trhip_spatial_reprojection_create: null default_value");
+    std::vector<int> layer_of(total_viewports, -1), src(source_count);
+    for (uint32_t i = 0; i < source_count; ++i) {
+        const uint32_t v = source_viewports[i];
+        if (v >= total_viewports) return set_error("trhip_spatial_reprojection_create: source viewport " + std::to_string(v) + " out of range (" + std::to_string(total_viewports) + " viewports)");
+        if (layer_of[v] >= 0) return set_error("trhip_spatial_reprojection_create: source viewport " + std::to_string(v) + " listed twice");
+        layer_of[v] = (int)i; src[i] = (int)v;
+    }
+    int d = 0;
+    for (uint32_t v = 0; v < total_viewports; ++v) if (layer_of[v] < 0) layer_of[v] = -(d++ + 1);
+    if (!dev) return set_error("trhip_spatial_reprojection_create: null trhip_device (no HIP device: there is no CPU fallback)");
+    RP_DEVCHK(device_index(dev));
+    trhip_spatial_reprojection* s = new trhip_spatial_reprojection;
+    s->dev = dev; s->hip_device = device_index(dev);
+    s->w = width; s->h = height; s->total = total_viewports; s->sources = source_count;
+    s->default_value = F4(default_value[0], default_value[1], default_value[2], default_value[3]);
+    hipError_t e = hipMalloc((void**)&s->source_viewport, src.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(s->source_viewport, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->layer_of, layer_of.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(s->layer_of, layer_of.data(), layer_of.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->record, s->record_count() * sizeof(ReprojRecord));
+    if (e == hipSuccess) e = hipMemset(s->record, 0, s->record_count() * sizeof(ReprojRecord));
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&s->ev[i]);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { spatial_release(s); return set_error(std::string("trhip_spatial_reprojection_create: ") + hipGetErrorString(e)); }
+    *out = s;
+    return 0;
+}
+
+void trhip_spatial_reprojection_destroy(trhip_spatial_reprojection* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->hip_device);
+    (void)hipDeviceSynchronize();
+    spatial_release(s);
+}
+
+int trhip_spatial_reprojection_run(trhip_spatial_reprojection* s, const trhip_reprojection_images* sources, const trhip_reprojection_images* destinations,
+                                   void* color_out, void* stream) {
+    if (!s) return set_error("trhip_spatial_reprojection_run: null stage");
+    if (!sources || !destinations || !color_out) return set_error("trhip_spatial_reprojection_run: null images");
+    if (!sources->color || !sources->normal || !sources->pos || !sources->instance_id)
+        return set_error("trhip_spatial_reprojection_run: the sources need color, normal, pos and instance_id");
+    if (!destinations->normal || !destinations->pos || !destinations->instance_id)
+        return set_error("trhip_spatial_reprojection_run: the destinations need normal, pos and instance_id");
+    RP_DEVCHK(s->hip_device);
+    DeviceScene* scene = device_scene(s->dev);
+    if (scene->camera_count < s->total || !scene->cameras)
+        return set_error("trhip_spatial_reprojection_run: the scene has " + std::to_string(scene->camera_count) + " cameras, the stage " + std::to_string(s->total) + " viewports");
+    SpatialParams P{};
+    P.w = (int)s->w; P.h = (int)s->h; P.total = (int)s->total; P.sources = (int)s->sources;
+    P.cameras = scene->cameras; P.source_viewport = s->source_viewport; P.layer_of = s->layer_of;
+    P.src_color = (const f4*)sources->color; P.src_normal = (const f2*)sources->normal; P.src_pos = (const f4*)sources->pos; P.src_id = (const int*)sources->instance_id;
+    P.dst_normal = (const f2*)destinations->normal; P.dst_pos = (const f4*)destinations->pos; P.dst_id = (const int*)destinations->instance_id;
+    P.out = (f4*)color_out; P.default_value = s->default_value; P.record = s->record;
+    hipStream_t st = (hipStream_t)stream;
+    RP_HIPCHK(hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(k_spatial_reprojection, tile_grid(s->w, s->h, s->total), dim3(KB), 0, st, P);
+    RP_HIPCHK(hipEventRecord(s->ev[1], st));
+    RP_HIPCHK(hipGetLastError());
+    s->frames += 1;
+    return 0;
+}
+
+int trhip_spatial_reprojection_get_timings(trhip_spatial_reprojection* s, trhip_reprojection_timings* out) {
+    if (!s || !out) return set_error("trhip_spatial_reprojection_get_timings: null argument");
+    memset(out, 0, sizeof(*out));
+    out->frames = s->frames;
+    if (s->frames == 0) return 0;
+    RP_DEVCHK(s->hip_device);
+    RP_HIPCHK(hipEventSynchronize(s->ev[1]));
+    RP_HIPCHK(hipEventElapsedTime(&out->total_ms, s->ev[0], s->ev[1]));
+    return 0;
+}
+
+int trhip_spatial_reprojection_download(trhip_spatial_reprojection* s, int which, void* host, size_t bytes) {
+    if (!s || !host) return set_error("trhip_spatial_reprojection_download: null argument");
+    if (which != TRHIP_REPROJECTION_DECISIONS) return set_error("trhip_spatial_reprojection_download: unknown buffer");
+    const size_t size = s->record_count() * sizeof(ReprojRecord);
+    if (bytes != size) return set_error("trhip_spatial_reprojection_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
+    RP_DEVCHK(s->hip_device);
+    RP_HIPCHK(hipDeviceSynchronize());
+    RP_HIPCHK(hipMemcpy(host, s->record, size, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int trhip_temporal_reprojection_create(trhip_device* dev, uint32_t width, uint32_t height, uint32_t layers, float ratio, trhip_temporal_reprojection** out) {
+    if (!out) return set_error("trhip_temporal_reprojection_create: null out");
+    *out = nullptr;
+    if (check_size("trhip_temporal_reprojection_create", width, height, layers)) return 1;
+    if (!(ratio > 0.0f) || !(ratio < 1.0f)) return set_error("trhip_temporal_reprojection_create: ratio must be in (0, 1)");
+    if (!dev) return set_error("trhip_temporal_reprojection_create: null trhip_device (no HIP device: there is no CPU fallback)");
+    RP_DEVCHK(device_index(dev));
+    trhip_temporal_reprojection* t = new trhip_temporal_reprojection;
+    t->hip_device = device_index(dev);
+    t->w = width; t->h = height; t->layers = layers; t->ratio = ratio;
+    const size_t px = t->pixels();
+    hipError_t e = hipSuccess;
+    auto alloc = [&](auto*& p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc((void**)&p, bytes); if (e == hipSuccess) e = hipMemset(p, 0, bytes); } };
+    for (int i = 0; i < 2; ++i) { alloc(t->color[i], px * sizeof(f4)); alloc(t->normal[i], px * sizeof(f2)); alloc(t->pos[i], px * sizeof(f4)); }
+    alloc(t->record, px * sizeof(ReprojRecord));
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&t->ev[i]);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { temporal_release(t); return set_error(std::string("trhip_temporal_reprojection_create: ") + hipGetErrorString(e)); }
+    *out = t;
+    return 0;
+}
+
+void trhip_temporal_reprojection_destroy(trhip_temporal_reprojection* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->hip_device);
+    (void)hipDeviceSynchronize();
+    temporal_release(t);
+}
+
+int trhip_temporal_reprojection_reset_history(trhip_temporal_reprojection* t) {
+    if (!t) return set_error("trhip_temporal_reprojection_reset_history: null stage");
+    t->have_history = false;
+    return 0;
+}
+
+int trhip_temporal_reprojection_run(trhip_temporal_reprojection* t, const trhip_reprojection_images* images, void* stream) {
+    if (!t) return set_error("trhip_temporal_reprojection_run: null stage");
+    if (!images) return set_error("trhip_temporal_reprojection_run: null images");
+    if (!images->color || !images->normal || !images->pos || !images->screen_motion)
+        return set_error("trhip_temporal_reprojection_run: color, normal, pos and screen_motion are required (only instance_id may be null)");
+    RP_DEVCHK(t->hip_device);
+    TemporalParams P{};
+    P.w = (int)t->w; P.h = (int)t->h; P.layers = (int)t->layers; P.have_history = t->have_history ? 1 : 0; P.ratio = t->ratio;
+    P.color = (f4*)images->color; P.normal = (const f2*)images->normal; P.pos = (const f4*)images->pos; P.motion = (const f2*)images->screen_motion;
+    P.instance_id = (const int*)images->instance_id;
+    const int c = t->cur, nx = c ^ 1;
+    P.color_prev = t->color[c]; P.normal_prev = t->normal[c]; P.pos_prev = t->pos[c];
+    P.color_cur = t->color[nx]; P.normal_cur = t->normal[nx]; P.pos_cur = t->pos[nx];
+    P.record = t->record;
+    hipStream_t st = (hipStream_t)stream;
+    RP_HIPCHK(hipEventRecord(t->ev[0], st));
+    hipLaunchKernelGGL(k_temporal_reprojection, tile_grid(t->w, t->h, t->layers), dim3(KB), 0, st, P);
+    RP_HIPCHK(hipEventRecord(t->ev[1], st));
+    RP_HIPCHK(hipGetLastError());
+    t->cur = nx;
+    t->have_history = true;
+    t->frames += 1;
+    return 0;
+}
+
+int trhip_temporal_reprojection_get_timings(trhip_temporal_reprojection* t, trhip_reprojection_timings* out) {
+    if (!t || !out) return set_error("trhip_temporal_reprojection_get_timings: null argument");
+    memset(out, 0, sizeof(*out));
+    out->frames = t->frames;
+    if (t->frames == 0) return 0;
+    RP_DEVCHK(t->hip_device);
+    RP_HIPCHK(hipEventSynchronize(t->ev[1]));
+    RP_HIPCHK(hipEventElapsedTime(&out->total_ms, t->ev[0], t->ev[1]));
+    return 0;
+}
+
+int trhip_temporal_reprojection_download(trhip_temporal_reprojection* t, int which, void* host, size_t bytes) {
+    if (!t || !host) return set_error("trhip_temporal_reprojection_download: null argument");
+    const size_t px = t->pixels();
+    const void* src = nullptr;
+    size_t size = 0;
+    const int c = t->cur;      // what the last frame wrote
+    switch (which) {
+        case TRHIP_REPROJECTION_DECISIONS: src = t->record; size = px * sizeof(ReprojRecord); break;
+        case TRHIP_REPROJECTION_PREVIOUS_COLOR: src = t->color[c]; size = px * sizeof(f4); break;
+        case TRHIP_REPROJECTION_PREVIOUS_NORMAL: src = t->normal[c]; size = px * sizeof(f2); break;
+        case TRHIP_REPROJECTION_PREVIOUS_POS: src = t->pos[c]; size = px * sizeof(f4); break;
+        default: return set_error("trhip_temporal_reprojection_download: unknown buffer");
+    }
+    if (bytes != size) return set_error("trhip_temporal_reprojection_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
+    RP_DEVCHK(t->hip_device);
+    RP_HIPCHK(hipDeviceSynchronize());
+    RP_HIPCHK(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@
 //              [--filetype=exr|raw|none] [--format=rgb16|rgb32|rgba16|rgba32] [--tonemap=filmic|linear|gamma-correction|
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
-//              [--renderer=path-tracer|direct] [--denoiser=none|bmfr]
+//              [--renderer=path-tracer|direct] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--camera-grid=w,h,x,y --camera-recentering-distance=5 --camera-grid-roll=0]   (light-field grid, one file per view)
 //
 // One process per GPU (include/tauray_hip_comm.hh): start N copies with --process-count=N --process-rank=0..N-1 --device=<HIP index>
@@ -40,6 +40,9 @@ static const char* const usage_text =
     "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
     "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
     "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
+    "  --spatial-reprojection=i,j,...   sparse light field: only the listed viewports of --camera-grid are path traced, the others are\n"
+    "                         filled from them through the G-buffer (one file per view, in natural view order; one device, no denoiser)\n"
+    "  --temporal-reprojection=r        blend the previous frame, found through screen motion, into the path-traced views: r in (0, 1)\n"
     "  --tonemap=filmic|linear|gamma-correction|reinhard|reinhard-luminance --exposure=E --gamma=G\n"
     "  --animation[=NAME] --framerate=F --accumulation --envmap=FILE --camera-grid=w,h,x,y -t --skip-nan-check\n"
     "  --fake-devices=N | --devices=0,1,... --distribution-strategy=scanline|shuffled-strips --frames-in-flight=N --frames-per-launch=N\n"
@@ -91,6 +94,21 @@ int main(int argc, char** argv)
                 else if(v == "none") opt.bmfr.reset();
                 else if(v == "svgf") throw std::runtime_error("--denoiser=svgf: the SVGF denoiser is not built (--denoiser=none|bmfr)");
                 else throw std::runtime_error("--denoiser is none or bmfr, not " + v);
+            }
+            else if(starts(a, "--spatial-reprojection="))
+            {   // --spatial-reprojection (src/options.hh; src/tauray.cc:301-305): the active viewports
+                std::stringstream ss(val("--spatial-reprojection=")); std::string tok;
+                while(std::getline(ss, tok, ','))
+                {
+                    if(tok.empty() || tok.find_first_not_of("0123456789") != std::string::npos) throw std::runtime_error("--spatial-reprojection=i,j,...: viewport indices, not " + tok);
+                    opt.spatial_reprojection.push_back((uint32_t)std::stoul(tok));
+                }
+                if(opt.spatial_reprojection.empty()) throw std::runtime_error("--spatial-reprojection=i,j,...: the viewport list is empty");
+            }
+            else if(starts(a, "--temporal-reprojection="))
+            {
+                opt.temporal_reprojection = std::stof(val("--temporal-reprojection="));
+                if(!(opt.temporal_reprojection >= 0.0f) || !(opt.temporal_reprojection < 1.0f)) throw std::runtime_error("--temporal-reprojection=r: the ratio must be in [0, 1) (0 = off)");
             }
             else if(a == "--skip-nan-check") hopt.skip_nan_check = true;     // headless::options::skip_nan_check (src/headless.hh:74); with --filetype=none: no readback at all
             else if(a == "--accumulation") opt.accumulate = true;
@@ -265,6 +283,19 @@ int main(int argc, char** argv)
 
         opt.max_frames_in_flight = frames_in_flight;
         opt.frames_per_launch = frames_per_launch;
+        if(!opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)
+        {   // what rt_renderer refuses, said before a device is touched
+            const std::string which = !opt.spatial_reprojection.empty() ? "--spatial-reprojection" : "--temporal-reprojection";
+            if(!opt.spatial_reprojection.empty()) check_viewport_list(opt.spatial_reprojection, viewports, "--spatial-reprojection");
+            if(devices.size() > 1 || process_count > 0 || shard_views)
+                throw std::runtime_error(which + " with several devices or processes: the stages read the G-buffer of whole viewports on one device, "
+                                         "gathering it from several is not built; use one device");
+            if(opt.bmfr) throw std::runtime_error(which + " together with --denoiser=bmfr: a chain of reprojection and a denoiser is not built");
+            if(frames_per_launch > 1) throw std::runtime_error(which + ": a reprojected frame is one frame, --frames-per-launch must be 1");
+            if(opt.temporal_reprojection > 0.0f && opt.accumulate) throw std::runtime_error("--temporal-reprojection blends the previous frame into a fresh frame: no --accumulation");
+            // a viewport that nothing reprojects to holds NaN (src/tauray.cc:301-305)
+            if(!opt.spatial_reprojection.empty()) hopt.skip_nan_check = true;
+        }
         hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
         if(shard_views)
         {   // view shards: viewport v belongs to rank v mod N; every rank renders, tonemaps and saves its own
@@ -400,6 +431,7 @@ int main(int argc, char** argv)
             direct_renderer::options dopt;
             static_cast<path_tracer_stage::options&>(dopt) = opt;
             dopt.tonemap = opt.tonemap; dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;
+            dopt.spatial_reprojection = opt.spatial_reprojection; dopt.temporal_reprojection = opt.temporal_reprojection;
             direct_renderer rr(devices, scene, size, dopt);
             return run(rr);
         }

@@ -747,11 +747,190 @@ def fit_blocks(ctx: Context, matrices: np.ndarray) -> np.ndarray:
     return d_w.download((blocks, channels, 10), np.float32)
 
 
+class _LayerView:
+    """Layers [first, ...) of a device image (what a stage that renders a run of the viewport list writes)."""
+
+    def __init__(self, image, byte_offset):
+        self.image, self.byte_offset = image, int(byte_offset)
+
+    def data_ptr(self):
+        return _ptr(self.image) + self.byte_offset
+
+
+def viewport_runs(viewports):
+    """A viewport list as arithmetic runs [(base, stride, count), ...] in list order - what trhip_pt_set_shard expresses: 0,4,8 is one
+    run, 18..26 is one run, 0,1,5 is (0, 1, 2), (5, 1, 1)."""
+    runs, i, v = [], 0, [int(x) for x in viewports]
+    while i < len(v):
+        count, stride = 1, 1
+        if i + 1 < len(v) and v[i + 1] > v[i]:
+            stride = v[i + 1] - v[i]
+            while i + count < len(v) and v[i + count] - v[i + count - 1] == stride:
+                count += 1
+        runs.append((v[i], stride, count))
+        i += count
+    return runs
+
+
+def check_viewport_list(viewports, total, what="spatial_reprojection"):
+    """The active viewports of a sparse light field: a non-empty list of distinct viewports of the grid that leaves some to reproject."""
+    v = [int(x) for x in viewports]
+    if not v:
+        raise ValueError(f"{what}: the viewport list is empty")
+    bad = [x for x in v if x < 0 or x >= total]
+    if bad:
+        raise ValueError(f"{what}: viewport {bad[0]} is out of range (the scene has {total} viewports)")
+    if len(set(v)) != len(v):
+        raise ValueError(f"{what}: a viewport is listed twice")
+    if len(v) >= total:
+        raise ValueError(f"{what}: the list names every viewport: there is nothing to reproject")
+    return v
+
+
+class GbufferStage:
+    """The first-hit G-buffer of viewports that are not path traced (trhip_gbuffer_render): normal, pos and instance id of one ray through
+    every pixel centre, for a list of viewports in one launch, as compact layers in list order."""
+
+    TARGETS = ("normal", "pos", "instance_id")
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, size, projection=0, min_ray_dist=1e-4):
+        self.ctx, self.ss, self.size = ctx, scene_stage, (int(size[0]), int(size[1]))
+        self.projection, self.min_ray_dist = int(projection), float(min_ray_dist)
+
+    def alloc_targets(self, layers) -> dict:
+        w, h = self.size
+        return {n: self.ctx.alloc(max(layers, 1) * w * h * PathTracerStage.TARGETS[n][0] * 4).zero() for n in self.TARGETS}
+
+    def run(self, viewports, targets: dict, stream=None):
+        unknown = set(targets) - set(self.TARGETS)
+        if unknown:
+            raise ValueError(f"GbufferStage: not a target the pass writes: {sorted(unknown)}")
+        t = _lib.GbufferTargetsC()
+        for name, buf in targets.items():
+            setattr(t, name, None if buf is None else _ptr(buf))
+        v = (C.c_uint32 * max(len(viewports), 1))(*[int(x) for x in viewports])
+        check(_lib.lib().trhip_gbuffer_render(self.ctx.h, self.projection, v, len(viewports), self.min_ray_dist, C.byref(t), self.size[0], self.size[1], stream))
+
+
+def _reprojection_images(images: dict, allowed, who):
+    unknown = set(images) - set(allowed)
+    if unknown:
+        raise ValueError(f"{who}: not an image the stage reads: {sorted(unknown)}")
+    f = _lib.ReprojectionImagesC()
+    for name, buf in images.items():
+        setattr(f, name, None if buf is None else _ptr(buf))
+    return f
+
+
+def _reprojection_timings(fn, h) -> dict:
+    t = _lib.ReprojectionTimingsC()
+    check(fn(h, C.byref(t)))
+    return {"total_ms": float(t.total_ms), "frames": int(t.frames)}
+
+
+class SpatialReprojectionStage:
+    """spatial_reprojection_stage (src/spatial_reprojection_stage.{hh,cc}): fills the viewports that were not path traced from the ones
+    that were, through the G-buffer (trhip_spatial_reprojection_*, include/trhip.h).  `source_viewports`: the path-traced viewports, in the
+    order of the source images' layers; the output holds every viewport in natural order."""
+
+    SOURCES = ("color", "normal", "pos", "instance_id")
+    DESTINATIONS = ("normal", "pos", "instance_id")
+
+    def __init__(self, ctx: Context, size, total_viewports, source_viewports, default_value=(np.nan,) * 4):
+        self.ctx, self.size, self.total = ctx, (int(size[0]), int(size[1])), int(total_viewports)
+        self.sources = [int(v) for v in source_viewports]
+        self.destinations = [v for v in range(self.total) if v not in set(self.sources)]
+        self.h = None
+        src = (C.c_uint32 * max(len(self.sources), 1))(*[v & 0xFFFFFFFF for v in self.sources])
+        dv = (C.c_float * 4)(*default_value)
+        h = C.c_void_p()
+        check(_lib.lib().trhip_spatial_reprojection_create(getattr(ctx, "h", None), self.size[0], self.size[1], max(self.total, 0), src, len(self.sources), dv, C.byref(h)))
+        self.h = h.value
+
+    def run(self, sources: dict, destinations: dict, color_out, stream=None):
+        s = _reprojection_images(sources, self.SOURCES, "SpatialReprojectionStage")
+        d = _reprojection_images(destinations, self.DESTINATIONS, "SpatialReprojectionStage")
+        check(_lib.lib().trhip_spatial_reprojection_run(self.h, C.byref(s), C.byref(d), _ptr(color_out), stream))
+
+    def timings(self) -> dict:
+        return _reprojection_timings(_lib.lib().trhip_spatial_reprojection_get_timings, self.h)
+
+    def decisions(self) -> np.ndarray:
+        """The decision record of the last frame, [destinations][h][w] (fields kind, slot, bits, ox, oy; test hook)."""
+        out = np.empty((len(self.destinations), self.size[1], self.size[0]), dtype=np.dtype(_lib.REPROJECTION_RECORD))
+        check(_lib.lib().trhip_spatial_reprojection_download(self.h, _lib.REPROJECTION_DECISIONS, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().trhip_spatial_reprojection_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TemporalReprojectionStage:
+    """temporal_reprojection_stage (src/temporal_reprojection_stage.{hh,cc}): blends last frame's colour, found through screen_motion, into
+    the path-traced layers: color = mix(color, reprojected, ratio) (trhip_temporal_reprojection_*, include/trhip.h).  The stage keeps last
+    frame's colour, normal and pos itself."""
+
+    IMAGES = ("color", "normal", "pos", "screen_motion", "instance_id")
+    BUFFERS = {"previous_color": (_lib.REPROJECTION_PREVIOUS_COLOR, 4), "previous_normal": (_lib.REPROJECTION_PREVIOUS_NORMAL, 2),
+               "previous_pos": (_lib.REPROJECTION_PREVIOUS_POS, 4)}
+
+    def __init__(self, ctx: Context, size, layers=1, ratio=0.75):
+        self.ctx, self.size, self.layers, self.ratio = ctx, (int(size[0]), int(size[1])), int(layers), float(ratio)
+        self.h = None
+        h = C.c_void_p()
+        check(_lib.lib().trhip_temporal_reprojection_create(getattr(ctx, "h", None), self.size[0], self.size[1], max(self.layers, 0), self.ratio, C.byref(h)))
+        self.h = h.value
+
+    def run(self, images: dict, stream=None):
+        """stage::run: blends into images["color"] in place."""
+        f = _reprojection_images(images, self.IMAGES, "TemporalReprojectionStage")
+        check(_lib.lib().trhip_temporal_reprojection_run(self.h, C.byref(f), stream))
+
+    def reset_history(self):
+        check(_lib.lib().trhip_temporal_reprojection_reset_history(self.h))
+
+    def timings(self) -> dict:
+        return _reprojection_timings(_lib.lib().trhip_temporal_reprojection_get_timings, self.h)
+
+    def decisions(self) -> np.ndarray:
+        out = np.empty((self.layers, self.size[1], self.size[0]), dtype=np.dtype(_lib.REPROJECTION_RECORD))
+        check(_lib.lib().trhip_temporal_reprojection_download(self.h, _lib.REPROJECTION_DECISIONS, out.ctypes.data, out.nbytes))
+        return out
+
+    def download(self, name: str) -> np.ndarray:
+        """The history the last frame left (test hook)."""
+        code, ch = self.BUFFERS[name]
+        out = np.empty((self.layers, self.size[1], self.size[0], ch), np.float32)
+        check(_lib.lib().trhip_temporal_reprojection_download(self.h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().trhip_temporal_reprojection_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _FrameSlot:
     """What one frame in flight owns: its stage (path buffers, counters), its images and the stream it is ordered on."""
 
     def __init__(self):
         self.pt = None
+        self.runs = None         # a viewport list: [(stage, first layer, layers)], one stage per arithmetic run of the list (self.pt is the first)
+        self.full = None         # spatial reprojection: the colour of every viewport in natural order (self.color holds the sources)
         self.features = None     # denoiser: the gbuffer targets next to the colour target
         self.color = None
         self.display = None
@@ -780,7 +959,7 @@ class RtRenderer:
     def __init__(self, ctx: Context, scene: SceneDesc, options: PtOptionsC, size, strategy=DISTRIBUTION_SCANLINE,
                  rank=0, world_size=1, viewports=1, tonemap: Optional[dict] = None, accumulate=False, use_torch=None,
                  shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None,
-                 denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY):
+                 denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY, spatial_reprojection=None, temporal_reprojection=0.0):
         """`shard`: what the ranks divide among themselves - "pixels" (the reference's distribution strategies, partial frames
         stitched on rank 0), "views" (viewport v on rank v mod N; nothing is exchanged before output) or "samples" (every
         rank renders samples_per_pixel / N samples of every pixel; one reduce to rank 0).  SURVEY.md section 8(e).
@@ -795,7 +974,13 @@ class RtRenderer:
         gbuffer entries the BMFR stage reads next to the colour target, every frame is a fresh frame of samples_per_pixel samples (the
         sample counter keeps counting), and post_process runs the stage before the tonemap stage (which is then a stage of its own: the
         fused tonemap is off).  The stage gets last frame's cameras as camera_pair.previous.  With frames in flight its history stays
-        one chain: it runs in frame order on the default stream.  `denoiser_settings`: _lib.BMFR_DIFFUSE_ONLY or BMFR_DIFFUSE_SPECULAR."""
+        one chain: it runs in frame order on the default stream.  `denoiser_settings`: _lib.BMFR_DIFFUSE_ONLY or BMFR_DIFFUSE_SPECULAR.
+        `spatial_reprojection`: None, or the list of active viewports of a sparse light field (the reference's --spatial-reprojection=i,j,...):
+        only these are path traced, as compact layers in list order with their own cameras and RNG streams; the others get a first-hit
+        G-buffer pass and are filled by SpatialReprojectionStage.  color / display then hold every viewport in natural order, the fused
+        tonemap is off, and with `accumulate` the sources are the accumulators and the full image is rewritten every frame.
+        `temporal_reprojection`: 0, or the ratio of TemporalReprojectionStage (--temporal-reprojection=r), which runs on the path-traced layers
+        in front of the spatial stage; its history is one chain in frame order, like the denoiser's."""
         if shard not in ("pixels", "views", "samples"):
             raise ValueError("shard must be pixels, views or samples")
         if denoiser not in (None, "none", "bmfr"):
@@ -810,6 +995,22 @@ class RtRenderer:
                 raise ValueError("a denoised frame is a fresh frame: accumulate must be False and frames_per_launch 1")
             if stage_cls is not None and stage_cls is not PathTracerStage:
                 raise ValueError("the denoiser reads the path tracer's demodulated diffuse target: stage_cls must be PathTracerStage")
+        temporal_reprojection = float(temporal_reprojection or 0.0)
+        if not (0.0 <= temporal_reprojection < 1.0):
+            raise ValueError(f"temporal_reprojection {temporal_reprojection!r}: the ratio must be in [0, 1) (0 = off)")
+        if spatial_reprojection is not None:
+            spatial_reprojection = check_viewport_list(spatial_reprojection, viewports)
+        if spatial_reprojection is not None or temporal_reprojection > 0.0:
+            which = "spatial_reprojection" if spatial_reprojection is not None else "temporal_reprojection"
+            if world_size > 1:
+                raise ValueError(f"{which} with a {shard} distribution of count {world_size} > 1: the stages read the G-buffer of whole viewports on one "
+                                 "device, gathering it from several is not built; use one device")
+            if denoiser is not None:
+                raise ValueError(f"{which} together with denoiser={denoiser!r}: a chain of reprojection and a denoiser is not built")
+            if frames_per_launch > 1:
+                raise ValueError(f"{which}: a reprojected frame is one frame: frames_per_launch must be 1")
+            if temporal_reprojection > 0.0 and accumulate:
+                raise ValueError("temporal_reprojection blends the previous frame into a fresh frame: accumulate must be False")
         if frames_in_flight < 1:
             raise ValueError("frames_in_flight must be >= 1")
         if frames_in_flight > 1 and accumulate:
@@ -833,6 +1034,9 @@ class RtRenderer:
         if self.shard == "views":
             from .transfer import shard_viewports
             viewports = len(shard_viewports(viewports, rank, world_size))
+        self.spatial_sources = spatial_reprojection
+        if spatial_reprojection is not None:
+            viewports = len(spatial_reprojection)           # the path tracer's layers: the active viewports, compact, in list order
         self.frames_per_launch = frames_per_launch
         self.frame_viewports = viewports                    # layers of one frame
         viewports = viewports * frames_per_launch           # layers of one launch: every buffer, transfer, stitch and tonemap below
@@ -865,12 +1069,29 @@ class RtRenderer:
         self.denoiser = denoiser
         self.bmfr = BmfrStage(ctx, self.size, viewports, denoiser_settings) if (denoiser == "bmfr" and viewports > 0) else None
         self._last_cameras = None        # denoiser: the cameras the last frame was rendered with
-        self.fused_tonemap = (world_size == 1 and denoiser is None and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
+        self.output_viewports = self.total_viewports if spatial_reprojection is not None else viewports      # layers of color / display
+        self.temporal = (TemporalReprojectionStage(ctx, self.size, viewports, temporal_reprojection)
+                         if (temporal_reprojection > 0.0 and viewports > 0) else None)
+        self.spatial = self.gbuffer = self.destination_targets = None
+        if spatial_reprojection is not None:
+            self.spatial = SpatialReprojectionStage(ctx, self.size, self.total_viewports, spatial_reprojection)
+            self.gbuffer = GbufferStage(ctx, self.scene_update, self.size, options.projection, options.min_ray_dist)
+            self.destination_targets = self.gbuffer.alloc_targets(len(self.spatial.destinations))
+        reprojection = self.spatial is not None or self.temporal is not None
+        self.fused_tonemap = (world_size == 1 and denoiser is None and not reprojection and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
                               and hasattr(_lib.lib(), "trhip_pt_set_fused_tonemap") and os.environ.get("TRHIP_FUSED_TONEMAP", "1") != "0")
         self.slots = []
         for k in range(frames_in_flight):
             slot = _FrameSlot()
             slot.pt = (stage_cls or PathTracerStage)(ctx, self.scene_update, options, self.dist)   # rt_renderer<Pipeline>: path_tracer_stage or direct_stage
+            if spatial_reprojection is not None:
+                # the list as arithmetic runs, one stage per run (usually one): layer l shows viewport list[l], its camera and its RNG stream
+                slot.runs, first = [], 0
+                for base, stride, count in viewport_runs(spatial_reprojection):
+                    stage = slot.pt if not slot.runs else (stage_cls or PathTracerStage)(ctx, self.scene_update, options, self.dist)
+                    stage.set_shard(viewport_base=base, viewport_stride=stride)
+                    slot.runs.append((stage, first, count))
+                    first += count
             if self.shard == "views":
                 slot.pt.set_shard(viewport_base=rank, viewport_stride=world_size)
             elif self.shard == "samples":
@@ -884,6 +1105,11 @@ class RtRenderer:
             if self.bmfr is not None:
                 slot.features = {n: ctx.alloc(viewports * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero()
                                  for n in BmfrStage.FEATURES if n != "color"}
+            elif reprojection:
+                names = ("normal", "pos", "instance_id") + (("screen_motion",) if self.temporal is not None else ())
+                slot.features = {n: ctx.alloc(max(viewports, 1) * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero() for n in names}
+            if self.spatial is not None:
+                slot.full = self._alloc_color(self.output_viewports, tw, th)
             if self.fused_tonemap:
                 slot.display = self._alloc_display(viewports)
                 slot.fused_info = None       # what the stage was last told (bytes of the tonemap info), None = off
@@ -902,7 +1128,11 @@ class RtRenderer:
 
     @property
     def color(self):
-        return self.current.color
+        return self.current.full if self.spatial is not None else self.current.color
+
+    def _stages(self, slot):
+        """The path tracer stages of a slot: one, or one per arithmetic run of the viewport list."""
+        return [slot.pt] if slot.runs is None else [stage for stage, _, _ in slot.runs]
 
     @property
     def display(self):
@@ -932,6 +1162,9 @@ class RtRenderer:
         self.scene_update.set_scene(scene)
         if self.bmfr is not None:
             self.bmfr.reset_history()
+            self._last_cameras = None
+        if self.temporal is not None:
+            self.temporal.reset_history()
             self._last_cameras = None
 
     def program(self) -> dict:
@@ -976,37 +1209,42 @@ class RtRenderer:
 
     def reset_accumulation(self, reset_sample_counter=False):
         for slot in self.slots:
-            slot.pt.reset_accumulated_samples()
-            if reset_sample_counter:
-                slot.pt.reset_sample_counter()
+            for pt in self._stages(slot):
+                pt.reset_accumulated_samples()
+                if reset_sample_counter:
+                    pt.reset_sample_counter()
         if reset_sample_counter:
             self.frame_index = 0
         self.accumulated_frames = 0
 
     def set_profiling(self, count_work=False, detailed_timing=False):
         for slot in self.slots:
-            slot.pt.set_profiling(count_work, detailed_timing)
+            for pt in self._stages(slot):
+                pt.set_profiling(count_work, detailed_timing)
 
     def reset_counters(self):
         self.sync()
         for slot in self.slots:
-            slot.pt.reset_counters()
+            for pt in self._stages(slot):
+                pt.reset_counters()
 
     def counters(self) -> dict:
         """Work counters summed over the frame slots."""
         self.sync()
         total = {}
         for slot in self.slots:
-            for k, v in slot.pt.counters().items():
-                total[k] = max(total.get(k, 0), v) if k == "stack_overflows" else total.get(k, 0) + v
+            for pt in self._stages(slot):
+                for k, v in pt.counters().items():
+                    total[k] = max(total.get(k, 0), v) if k == "stack_overflows" else total.get(k, 0) + v
         return total
 
     def timings(self) -> dict:
         self.sync()
         total = {}
         for slot in self.slots:
-            for k, v in slot.pt.timings().items():
-                total[k] = total.get(k, 0) + v
+            for pt in self._stages(slot):
+                for k, v in pt.timings().items():
+                    total[k] = total.get(k, 0) + v
         return total
 
     def phase_counters(self) -> dict:
@@ -1021,7 +1259,7 @@ class RtRenderer:
         """The "path tracing" timer the load balancer reads (src/load_balancer.cc:17,25): the last frame of every slot, averaged.
         Waits for the slots."""
         self.sync()
-        t = [slot.pt.timings()["path_tracing_ms"] for slot in self.slots]
+        t = [sum(pt.timings()["path_tracing_ms"] for pt in self._stages(slot)) for slot in self.slots]
         return sum(t) / len(t)
 
     def set_device_workloads(self, ratios):
@@ -1062,14 +1300,15 @@ class RtRenderer:
         self.current = slot
         if self.fused_tonemap:
             self._sync_fused_tonemap(slot, tonemap)
-        if not self.accumulate:
-            slot.pt.reset_accumulated_samples()
-        if self.frames_in_flight > 1 or self.frames_per_launch > 1:
-            slot.pt.set_frame_counter(self.frame_index)      # one stage per slot: slot k renders frames k, k + F, ... (B at a time)
+        for pt in self._stages(slot):
+            if not self.accumulate:
+                pt.reset_accumulated_samples()
+            if self.frames_in_flight > 1 or self.frames_per_launch > 1:
+                pt.set_frame_counter(self.frame_index)       # one stage per slot: slot k renders frames k, k + F, ... (B at a time)
         slot.frame = self.frame_index
         self.frame_index += self.frames_per_launch
         if self.viewports > 0:      # a view shard can be empty (more devices than views)
-            if self.bmfr is not None:
+            if self.bmfr is not None or self.temporal is not None:
                 cameras = self.scene_update.camera_data
                 prev = cameras if self._last_cameras is None else self._last_cameras
                 on_device = self.scene_update.previous_camera_data
@@ -1078,7 +1317,14 @@ class RtRenderer:
                         self.sync()
                     self.scene_update.set_previous_camera_data(prev)
                 self._last_cameras = cameras.copy()
-                slot.pt.run_targets(dict(slot.features, color=slot.color), self.viewports, stream if stream is not None else slot.stream)
+            st = stream if stream is not None else slot.stream
+            if slot.runs is not None:
+                tw, th = self.target_size
+                for pt, first, count in slot.runs:
+                    pt.run_targets({n: _LayerView(b, first * tw * th * PathTracerStage.TARGETS[n][0] * 4)
+                                    for n, b in dict(slot.features, color=slot.color).items()}, count, st)
+            elif slot.features is not None:
+                slot.pt.run_targets(dict(slot.features, color=slot.color), self.viewports, st)
             else:
                 slot.pt.run(slot.color, self.viewports, stream if stream is not None else slot.stream)
 
@@ -1104,8 +1350,9 @@ class RtRenderer:
         self.render_partial(tonemap=tonemap)
         slot = self.current
         if self.world_size == 1:
-            if self.bmfr is not None:
-                # the denoiser's history is one chain over the frames of all slots: it runs on the default stream, in frame order
+            if self.bmfr is not None or self.temporal is not None or self.spatial is not None:
+                # the denoiser's / temporal stage's history is one chain over the frames of all slots: it runs on the default stream, in frame
+                # order (and so does the spatial stage, whose destination G-buffer the slots share)
                 if slot.stream is not None:
                     self.ctx.stream_wait(None, slot.stream)
                 self.post_process(None, tonemap=tonemap)
@@ -1153,11 +1400,17 @@ class RtRenderer:
         slot = self.current
         if self.bmfr is not None:
             self.bmfr.run(dict(slot.features, color=slot.color), slot.frame, stream)
+        if self.temporal is not None:
+            self.temporal.run(dict(slot.features, color=slot.color), stream)
+        if self.spatial is not None:
+            self.gbuffer.run(self.spatial.destinations, self.destination_targets, stream)
+            self.spatial.run({n: (slot.color if n == "color" else slot.features[n]) for n in SpatialReprojectionStage.SOURCES},
+                             self.destination_targets, slot.full, stream)
         if not tonemap:
             return
         if slot.display is None:
-            slot.display = self._alloc_display(self.viewports)
-        self.tonemap.run(slot.color, slot.display, w, h, self.viewports, stream)
+            slot.display = self._alloc_display(self.output_viewports)
+        self.tonemap.run(slot.full if self.spatial is not None else slot.color, slot.display, w, h, self.output_viewports, stream)
 
     def download(self, which="color") -> np.ndarray:
         """The most recent frame's partial colour target or tonemapped display image."""
@@ -1170,16 +1423,18 @@ class RtRenderer:
         if self.use_torch:
             self._torch.cuda.synchronize()
             return buf.cpu().numpy()
-        return buf.download((self.viewports, th, tw, 4), np.float32)
+        return buf.download((self.output_viewports, th, tw, 4), np.float32)
 
     def close(self):
         if not self.slots:
             return
         self.sync()
-        if self.bmfr is not None:
-            self.bmfr.close()
+        for stage in (self.bmfr, self.temporal, self.spatial):
+            if stage is not None:
+                stage.close()
         for slot in self.slots:
-            slot.pt.close()
+            for pt in self._stages(slot):
+                pt.close()
             if slot.stream is not None:
                 self.ctx.destroy_stream(slot.stream)
                 slot.stream = None
