@@ -852,181 +852,6 @@ int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
     return 0;
 }
 
-// Experiment (TRHIP_TREELET=<nodes per treelet>, off by default; profiles/r5/treelet_order_ab.txt): the live 4-wide nodes laid out treelet by
-// treelet - a treelet is grown from its root by always opening the hit-likeliest (largest) child box until it holds the given number of
-// nodes, its nodes are stored side by side, the subtrees hanging off it follow depth-first - and the triangle records in the order the new
-// node array refers to them, so the leaves of a node are neighbours in memory.  Dead lines (binary nodes the collapse adopted away) drop
-// out.  A host pass over a downloaded tree: build time is not the point of the experiment.  Hits do not depend on the layout.
-static int reorder_into_treelets(DeviceScene& ds, hipStream_t stream, uint n_nodes, uint n_tris, uint treelet_nodes, bool reorder_tris) {
-    if (n_nodes == 0 || n_tris == 0) return 0;
-    HIPCHK(hipStreamSynchronize(stream));
-    std::vector<Bvh4Node> nodes(n_nodes), out_nodes;
-    std::vector<TriRecord> tris(n_tris), out_tris;
-    HIPCHK(hipMemcpy(nodes.data(), ds.nodes4, (size_t)n_nodes * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tris.data(), ds.tris, (size_t)n_tris * sizeof(TriRecord), hipMemcpyDeviceToHost));
-    std::vector<int> new_id(n_nodes, -1);
-    std::vector<uint> order;            // old node ids in their new order
-    order.reserve(n_nodes);
-    std::vector<uint> roots = {0u};     // stack of treelet roots
-    auto area = [&](const Bvh4Node& nd, int c) {
-        const float dx = nd.hix[c] - nd.lox[c], dy = nd.hiy[c] - nd.loy[c], dz = nd.hiz[c] - nd.loz[c];
-        return dx * dy + dy * dz + dz * dx;
-    };
-    std::vector<std::pair<float, uint>> heap;
-    while (!roots.empty()) {
-        const uint root = roots.back(); roots.pop_back();
-        heap.clear();
-        heap.push_back({__builtin_huge_valf(), root});
-        uint taken = 0;
-        std::vector<uint> rest;
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end());
-            const uint nd = heap.back().second; heap.pop_back();
-            if (taken >= treelet_nodes) { rest.push_back(nd); continue; }
-            new_id[nd] = (int)order.size(); order.push_back(nd); taken++;
-            for (int c = 0; c < 4; ++c) {
-                const int ch = nodes[nd].child[c];
-                if (ch >= 0 && ch != 0x7FFFFFFF) { heap.push_back({area(nodes[nd], c), (uint)ch}); std::push_heap(heap.begin(), heap.end()); }
-            }
-        }
-        // the subtrees below the treelet, the largest box last so that it is laid out next
-        for (size_t k = rest.size(); k-- > 0;) roots.push_back(rest[k]);
-    }
-    out_nodes.resize(n_nodes);
-    std::vector<int> new_tri(n_tris, -1);
-    uint next_tri = 0;
-    for (size_t k = 0; k < order.size(); ++k) {
-        Bvh4Node nd = nodes[order[k]];
-        for (int c = 0; c < 4; ++c) {
-            const int ch = nd.child[c];
-            if (ch == 0x7FFFFFFF) continue;
-            if (ch >= 0) nd.child[c] = new_id[ch];
-            else if (reorder_tris) { const uint t = (uint)~ch; if (new_tri[t] < 0) new_tri[t] = (int)next_tri++; nd.child[c] = ~new_tri[t]; }
-        }
-        out_nodes[k] = nd;
-    }
-    for (size_t k = order.size(); k < n_nodes; ++k) { out_nodes[k] = nodes[0]; }   // never referenced
-    HIPCHK(hipMemcpy(ds.nodes4, out_nodes.data(), (size_t)n_nodes * sizeof(Bvh4Node), hipMemcpyHostToDevice));
-    if (reorder_tris) {
-        out_tris.resize(n_tris);
-        for (uint t = 0; t < n_tris; ++t) { if (new_tri[t] < 0) new_tri[t] = (int)next_tri++; out_tris[new_tri[t]] = tris[t]; }
-        HIPCHK(hipMemcpy(ds.tris, out_tris.data(), (size_t)n_tris * sizeof(TriRecord), hipMemcpyHostToDevice));
-    }
-    if (getenv("TRHIP_DEBUG")) fprintf(stderr, "[trhip] treelet layout: %zu live nodes of %u in treelets of %u, triangles %s\n", order.size(), n_nodes, treelet_nodes, reorder_tris ? "in node order" : "as built");
-    return 0;
-}
-
-// Experiment (TRHIP_PAIR_LEAVES=1 with a library built -DTR_PAIR_LEAVES=1; profiles/r5/pair_leaves_ab.txt): leaves of two triangles.
-// A host pass over the finished 4-wide tree, bottom-up: the leaf slots of a node are paired (the two whose union box is smallest first), a
-// pair takes one slot - reference ~(first | 1 << 30), its triangles adjacent in the record array - and the slots that frees are filled by
-// adopting the children of inner children that fit, which removes those nodes and a level of the walk above them.  Nodes and records are
-// then renumbered in depth-first order.  Refit does not understand pair references: the experiment is for static scenes.
-static int pair_leaves_postpass(DeviceScene& ds, hipStream_t stream, uint n_nodes, uint n_tris) {
-    if (n_nodes == 0 || n_tris < 2) return 0;
-    HIPCHK(hipStreamSynchronize(stream));
-    std::vector<Bvh4Node> nodes(n_nodes);
-    std::vector<TriRecord> tris(n_tris);
-    HIPCHK(hipMemcpy(nodes.data(), ds.nodes4, (size_t)n_nodes * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tris.data(), ds.tris, (size_t)n_tris * sizeof(TriRecord), hipMemcpyDeviceToHost));
-    struct Slot { float lo[3], hi[3]; int kind; int a, b; };      // kind 0 inner node a, 1 triangle a, 2 pair (a, b)
-    std::vector<std::vector<Slot>> slots(n_nodes);
-    std::vector<char> live(n_nodes, 0), dead(n_nodes, 0);
-    {   // live nodes: reachable from the root
-        std::vector<uint> st = {0u};
-        while (!st.empty()) {
-            const uint nd = st.back(); st.pop_back();
-            live[nd] = 1;
-            for (int c = 0; c < 4; ++c) {
-                const int ch = nodes[nd].child[c];
-                if (ch == 0x7FFFFFFF) continue;
-                Slot sl;
-                sl.lo[0] = nodes[nd].lox[c]; sl.lo[1] = nodes[nd].loy[c]; sl.lo[2] = nodes[nd].loz[c];
-                sl.hi[0] = nodes[nd].hix[c]; sl.hi[1] = nodes[nd].hiy[c]; sl.hi[2] = nodes[nd].hiz[c];
-                sl.kind = ch >= 0 ? 0 : 1; sl.a = ch >= 0 ? ch : ~ch; sl.b = -1;
-                slots[nd].push_back(sl);
-                if (ch >= 0) st.push_back((uint)ch);
-            }
-        }
-    }
-    auto area_of = [](const float* lo, const float* hi) { const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2]; return dx * dy + dy * dz + dz * dx; };
-    size_t pairs = 0, adopted = 0;
-    for (uint k = n_nodes; k-- > 0;) {      // children sit behind their parents (depth-first order): bottom-up
-        if (!live[k]) continue;
-        std::vector<Slot>& S = slots[k];
-        while (true) {      // pair leaf slots, cheapest union first
-            int bi = -1, bj = -1; float best = __builtin_huge_valf();
-            for (size_t i = 0; i < S.size(); ++i) for (size_t j = i + 1; j < S.size(); ++j) {
-                if (S[i].kind != 1 || S[j].kind != 1) continue;
-                float lo[3], hi[3];
-                for (int a = 0; a < 3; ++a) { lo[a] = std::min(S[i].lo[a], S[j].lo[a]); hi[a] = std::max(S[i].hi[a], S[j].hi[a]); }
-                const float ar = area_of(lo, hi);
-                if (ar < best) { best = ar; bi = (int)i; bj = (int)j; }
-            }
-            if (bi < 0) break;
-            for (int a = 0; a < 3; ++a) { S[bi].lo[a] = std::min(S[bi].lo[a], S[bj].lo[a]); S[bi].hi[a] = std::max(S[bi].hi[a], S[bj].hi[a]); }
-            S[bi].kind = 2; S[bi].b = S[bj].a;
-            S.erase(S.begin() + bj);
-            pairs++;
-        }
-        while (true) {      // adopt the children of an inner child that fit into the free slots, largest box first
-            int pick = -1; float best = -1.0f;
-            for (size_t i = 0; i < S.size(); ++i) {
-                if (S[i].kind != 0) continue;
-                const std::vector<Slot>& C = slots[(size_t)S[i].a];
-                if (S.size() - 1 + C.size() > 4) continue;
-                const float ar = area_of(S[i].lo, S[i].hi);
-                if (ar > best) { best = ar; pick = (int)i; }
-            }
-            if (pick < 0) break;
-            const int child = S[pick].a;
-            const std::vector<Slot> C = slots[(size_t)child];
-            S.erase(S.begin() + pick);
-            S.insert(S.end(), C.begin(), C.end());
-            dead[(size_t)child] = 1;
-            adopted++;
-        }
-    }
-    // renumber depth-first
-    std::vector<int> new_id(n_nodes, -1);
-    std::vector<uint> order;
-    {
-        std::vector<uint> st = {0u};
-        while (!st.empty()) {
-            const uint nd = st.back(); st.pop_back();
-            new_id[nd] = (int)order.size(); order.push_back(nd);
-            for (size_t i = slots[nd].size(); i-- > 0;) if (slots[nd][i].kind == 0) st.push_back((uint)slots[nd][i].a);
-        }
-    }
-    std::vector<Bvh4Node> out_nodes(n_nodes, nodes[0]);
-    std::vector<TriRecord> out_tris(n_tris);
-    uint next_tri = 0;
-    for (size_t k = 0; k < order.size(); ++k) {
-        Bvh4Node nd;
-        const std::vector<Slot>& S = slots[order[k]];
-        for (int c = 0; c < 4; ++c) {
-            nd.pad[c] = 0;
-            if ((size_t)c >= S.size()) {
-                nd.lox[c] = nd.loy[c] = nd.loz[c] = __builtin_huge_valf(); nd.hix[c] = nd.hiy[c] = nd.hiz[c] = -__builtin_huge_valf(); nd.child[c] = 0x7FFFFFFF;
-                continue;
-            }
-            const Slot& sl = S[(size_t)c];
-            nd.lox[c] = sl.lo[0]; nd.loy[c] = sl.lo[1]; nd.loz[c] = sl.lo[2]; nd.hix[c] = sl.hi[0]; nd.hiy[c] = sl.hi[1]; nd.hiz[c] = sl.hi[2];
-            if (sl.kind == 0) nd.child[c] = new_id[(size_t)sl.a];
-            else {
-                out_tris[next_tri] = tris[(size_t)sl.a];
-                if (sl.kind == 2) { out_tris[next_tri + 1] = tris[(size_t)sl.b]; nd.child[c] = ~(int)(next_tri | 0x40000000u); next_tri += 2; }
-                else { nd.child[c] = ~(int)next_tri; next_tri += 1; }
-            }
-        }
-        out_nodes[k] = nd;
-    }
-    if (next_tri != n_tris) return set_error("pair leaves: " + std::to_string(next_tri) + " of " + std::to_string(n_tris) + " triangles referenced");
-    HIPCHK(hipMemcpy(ds.nodes4, out_nodes.data(), (size_t)n_nodes * sizeof(Bvh4Node), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ds.tris, out_tris.data(), (size_t)n_tris * sizeof(TriRecord), hipMemcpyHostToDevice));
-    fprintf(stderr, "[trhip] pair leaves: %zu pairs, %zu nodes adopted away, %zu live nodes of %u\n", pairs, adopted, order.size(), n_nodes);
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // One tree over n records: the scratch plan (sized for up to n_cap leaves; the arena survives the call) and the pipeline from the
 // unsorted records + their centroid bounds to sorted records and 4-wide nodes.  trhip_scene_build_accel runs it once over every world
@@ -1076,7 +901,7 @@ static int plan_tree(DeviceScene& ds, hipStream_t stream, uint n_cap, TreePlan& 
     return 0;
 }
 
-static int build_tree(DeviceScene& ds, hipStream_t stream, const TreePlan& P, uint n, TriRecord* out_tris, Bvh4Node* out_nodes, bool experiments) {
+static int build_tree(DeviceScene& ds, hipStream_t stream, const TreePlan& P, uint n, TriRecord* out_tris, Bvh4Node* out_nodes) {
     char* base = P.base;
     size_t sort_bytes = P.sort_bytes, scan_bytes = P.scan_bytes;
     const size_t o_cbounds = P.o_cbounds, o_unsorted = P.o_unsorted, o_keys = P.o_keys, o_keys_sorted = P.o_keys_sorted, o_vals = P.o_vals,
@@ -1211,16 +1036,6 @@ static int build_tree(DeviceScene& ds, hipStream_t stream, const TreePlan& P, ui
             }
         }
         HIPCHK(hipGetLastError());
-        if (experiments && getenv("TRHIP_PAIR_LEAVES") && atoi(getenv("TRHIP_PAIR_LEAVES")) != 0 && n > 2) {
-#if TR_PAIR_LEAVES
-            if (int rc = pair_leaves_postpass(ds, stream, n - 1, n)) return rc;
-#else
-            return set_error("TRHIP_PAIR_LEAVES needs a library built with -DTR_PAIR_LEAVES=1 (the traversal has to know the pair references)");
-#endif
-        }
-        if (const char* e = experiments ? getenv("TRHIP_TREELET") : nullptr) {
-            if (n > 2 && atoi(e) > 0) if (int rc = reorder_into_treelets(ds, stream, n - 1, n, (uint)atoi(e), !getenv("TRHIP_TREELET_KEEP_TRIS"))) return rc;
-        }
     }
     return 0;
 }
@@ -1268,7 +1083,7 @@ int build_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info) {
         const uint tblocks = (n_tri + BT - 1) / BT;
         hipLaunchKernelGGL(k_pretransform, dim3(tblocks < 1024u ? tblocks : 1024u), dim3(BT), 0, stream, sv, ds.tri_prefix, ds.non_opaque, ds.alpha_base, ds.alpha_tris, unsorted, cbounds);
     }
-    if (int rc = build_tree(ds, stream, P, n, ds.tris, ds.nodes4, true)) return rc;
+    if (int rc = build_tree(ds, stream, P, n, ds.tris, ds.nodes4)) return rc;
     ds.leaf_count = n;
     ds.node_count = n > 1 ? n - 1 : 0;
     ds.accel_tri_count = n_tri;
@@ -1581,7 +1396,7 @@ int build_tlas(DeviceScene& ds, hipStream_t stream, const TreePlan& P) {
     const uint blocks = (L + BT - 1) / BT;
     hipLaunchKernelGGL(k_record_bounds, dim3(blocks < 1024u ? blocks : 1024u), dim3(BT), 0, stream, L, P.unsorted(), P.cbounds());
     TriRecord* sorted = reinterpret_cast<TriRecord*>(aux + o_sorted);
-    if (int rc = build_tree(ds, stream, P, L, sorted, ds.nodes4, false)) return rc;
+    if (int rc = build_tree(ds, stream, P, L, sorted, ds.nodes4)) return rc;
     hipLaunchKernelGGL(k_tlas_leaves, dim3(blocks), dim3(BT), 0, stream, L, sorted, ds.tlas_src_leaves, ds.tlas);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1719,7 +1534,7 @@ static int build_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info
         hipLaunchKernelGGL(k_group_records, dim3(blocks), dim3(BT), 0, stream, sv, aux + list_at[g], aux + list_at[g] + nl, nl, b.tri_count, b.world ? 1 : 0,
                            ds.non_opaque, ds.alpha_base, ds.alpha_tris, P.unsorted());
         hipLaunchKernelGGL(k_record_bounds, dim3(blocks < 1024u ? blocks : 1024u), dim3(BT), 0, stream, b.tri_count, P.unsorted(), P.cbounds());
-        if (int rc = build_tree(ds, stream, P, b.tri_count, ds.tris + b.tri_off, ds.nodes4 + b.node_off, false)) return rc;
+        if (int rc = build_tree(ds, stream, P, b.tri_count, ds.tris + b.tri_off, ds.nodes4 + b.node_off)) return rc;
         if (b.node_slots) hipLaunchKernelGGL(k_rebase, dim3((b.node_slots + BT - 1) / BT), dim3(BT), 0, stream, ds.nodes4 + b.node_off, b.node_slots, (int)b.node_off, (int)b.tri_off);
         HIPCHK(hipGetLastError());
     }
@@ -1926,7 +1741,7 @@ int build_light_tree(DeviceScene& ds, hipStream_t stream) {
         HIPCHK(hipMemcpyAsync(P.cbounds(), kCboundsInit, sizeof(kCboundsInit), hipMemcpyHostToDevice, stream));
         const uint blocks = (L + BT - 1) / BT;
         hipLaunchKernelGGL(k_record_bounds, dim3(blocks < 1024u ? blocks : 1024u), dim3(BT), 0, stream, L, P.unsorted(), P.cbounds());
-        int rc = build_tree(ds, stream, P, L, sorted, dst, false);
+        int rc = build_tree(ds, stream, P, L, sorted, dst);
         ds.build_rounds = saved_rounds;
         nodes.resize((size_t)L - 1);
         std::vector<TriRecord> order(L);

@@ -172,11 +172,8 @@ TR_DEV void correct_lobes_for_normal_map(f3 sample_dir, f3 geometric_normal, Lob
 }
 
 // One bounce of evaluate_ray (path_tracer.glsl:385-498) for every live path of the queue.
-#ifndef TR_SHADE_NOLOOP
-#define TR_SHADE_NOLOOP 0       // 1: one pass per thread instead of the persistent loop (an experiment: profiles/r6/shade_noloop_ab.txt)
-#endif
 #ifndef TR_SHADE_WAVES
-#define TR_SHADE_WAVES (TR_SHADE_NOLOOP ? 4 : 3)
+#define TR_SHADE_WAVES 3
 #endif
 #ifndef TR_SHADE_LAST_WAVES
 #define TR_SHADE_LAST_WAVES 5   // the last bounce only collects emission: no light or BSDF sampling, no queue appends
@@ -456,15 +453,11 @@ TR_DEV void shade_bounce(const SceneView& sv_, const PtParams& P_, const PathBuf
 #if TR_SHADE_TIMELINE
     stl_begin();
 #endif
-    // A persistent grid that strides over the queue.  -DTR_SHADE_NOLOOP=1 (an experiment, profiles/r6/shade_noloop_ab.txt): one pass per thread,
-    // launched with a thread per queue slot - the kernel alone is 28 % faster (126 registers, nothing hoisted, nothing spilled), but a grid of
-    // one-pass blocks gives its slots away to the other lanes' persistent trace kernels as its blocks finish, and whole frames lose 1-5 %.
-#if TR_SHADE_NOLOOP
-    for (uint qi = blockIdx.x * KB + threadIdx.x, once = 1; once && qi < n_round; once = 0) {
-#else
+    // A persistent grid that strides over the queue.  (Measured against one pass per thread, launched with a thread per queue slot:
+    // profiles/r6/shade_noloop_ab.txt - the kernel alone is 28 % faster (126 registers, nothing hoisted, nothing spilled), but a grid of
+    // one-pass blocks gives its slots away to the other lanes' persistent trace kernels as its blocks finish, and whole frames lose 1-5 %.)
     for (uint qi = blockIdx.x * KB + threadIdx.x; qi < n_round; qi += gridDim.x * KB) {
-#endif
-#if TR_SHADE_FRESH_ARGS && !TR_SHADE_NOLOOP
+#if TR_SHADE_FRESH_ARGS
         // Every pass of the loop reads the scene view and the parameters afresh, through a pointer to the kernel-argument segment the
         // optimiser cannot see through.  Round 6 (profiles/r6/shade_phase_timeline.txt, shade_noloop_ab.txt): around this loop the compiler
         // hoisted everything invariant - reciprocals of the light counts and of the environment's size, the pieces of uniform divisions -
@@ -568,11 +561,32 @@ TR_DEV void raygen_paths(const SceneView& sv, const PtParams& P_, const PathBuff
 template <typename S = SpecGeneral>
 __global__ __launch_bounds__(KB) void k_raygen(SceneView sv, PtParams P, PathBuffers pb) { raygen_paths<S>(sv, P, pb); }
 
+// ShadeKernArgs against a kernel that calls shade_bounce: the kernel takes exactly (SceneView, PtParams, PathBuffers, int, const uint*,
+// uint*, uint*) by value, and in the kernel-argument segment each of them lies at the end of the one before it, rounded up to its own
+// alignment - which is where ShadeKernArgs has its member.  Stated behind every such kernel (here and in shade_spec.hip): their
+// signatures are pinned.  An argument added, dropped or moved has to be added, dropped or moved in ShadeKernArgs and in this check
+// too, or shade_bounce reads something else through TR_SHADE_FRESH_ARGS.
+constexpr unsigned long long kernarg_next(unsigned long long off, unsigned long long size, unsigned long long align) { return (off + size + align - 1) / align * align; }
+#define TR_KERNARG_OFF(m) __builtin_offsetof(ShadeKernArgs, m)
+#define TR_ASSERT_SHADE_KERNARGS(kernel) \
+    static_assert(__is_same(decltype(&kernel), void (*)(SceneView, PtParams, PathBuffers, int, const uint*, uint*, uint*)), \
+                  #kernel " does not have the signature ShadeKernArgs mirrors"); \
+    static_assert(TR_KERNARG_OFF(sv) == 0 && \
+                  TR_KERNARG_OFF(P) == kernarg_next(TR_KERNARG_OFF(sv), sizeof(SceneView), alignof(PtParams)) && \
+                  TR_KERNARG_OFF(pb) == kernarg_next(TR_KERNARG_OFF(P), sizeof(PtParams), alignof(PathBuffers)) && \
+                  TR_KERNARG_OFF(bounce) == kernarg_next(TR_KERNARG_OFF(pb), sizeof(PathBuffers), alignof(int)) && \
+                  TR_KERNARG_OFF(queue) == kernarg_next(TR_KERNARG_OFF(bounce), sizeof(int), alignof(const uint*)) && \
+                  TR_KERNARG_OFF(bc) == kernarg_next(TR_KERNARG_OFF(queue), sizeof(const uint*), alignof(uint*)) && \
+                  TR_KERNARG_OFF(next_queue) == kernarg_next(TR_KERNARG_OFF(bc), sizeof(uint*), alignof(uint*)) && \
+                  sizeof(ShadeKernArgs) == TR_KERNARG_OFF(next_queue) + sizeof(uint*), \
+                  "ShadeKernArgs is not the argument layout of " #kernel)
+
 template <bool COUNT, bool LAST, typename S = SpecGeneral>
 __global__ __launch_bounds__(KB, LAST ? TR_SHADE_LAST_WAVES : TR_SHADE_WAVES) void k_shade(SceneView sv, PtParams P, PathBuffers pb, int bounce, const uint* queue,
                                               uint* bc, uint* next_queue) {
     shade_bounce<COUNT, LAST, S>(sv, P, pb, bounce, queue, bc, next_queue);
 }
+TR_ASSERT_SHADE_KERNARGS((k_shade<false, false>));     // the signature is pinned: see above
 
 }  // namespace
 

@@ -23,11 +23,13 @@ extern "C" __global__ __launch_bounds__(KB, TR_SHADE_WAVES) void trhip_spec_shad
                                                                                   uint* next_queue) {
     shade_bounce<TR_SPEC_COUNT != 0, false, SpecMacros>(sv, P, pb, bounce, queue, bc, next_queue);
 }
+TR_ASSERT_SHADE_KERNARGS(trhip_spec_shade);         // the signature is pinned: shade_kernel.h, in front of k_shade
 
 extern "C" __global__ __launch_bounds__(KB, TR_SHADE_LAST_WAVES) void trhip_spec_shade_last(SceneView sv, PtParams P, PathBuffers pb, int bounce, const uint* queue,
                                                                                             uint* bc, uint* next_queue) {
     shade_bounce<TR_SPEC_COUNT != 0, true, SpecMacros>(sv, P, pb, bounce, queue, bc, next_queue);
 }
+TR_ASSERT_SHADE_KERNARGS(trhip_spec_shade_last);
 
 #endif
 

@@ -74,19 +74,6 @@ TR_DEV bool ray_is_finite(f3 o, f3 d) {
            (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f);
 }
 
-// Experiment -DTR_PAIR_LEAVES=1 (bvh_build.hip pair_leaves_postpass): a leaf reference ~(index | 1 << 30) names two records, index and index + 1.
-#ifndef TR_PAIR_LEAVES
-#define TR_PAIR_LEAVES 0
-#endif
-TR_DEV uint leaf_index(uint complemented_ref) { return TR_PAIR_LEAVES ? (complemented_ref & 0x3FFFFFFFu) : complemented_ref; }
-TR_DEV bool leaf_is_pair(uint complemented_ref) { return TR_PAIR_LEAVES && (complemented_ref & 0x40000000u) != 0; }
-// in front of the `if (tri_intersect(... leaf_index(ref) + member ...))` of a leaf: once, or once per member of a pair
-#if TR_PAIR_LEAVES
-#define TR_LEAF_MEMBERS(ref, more) for (uint member = 0; member <= (leaf_is_pair(ref) ? 1u : 0u) && (more); ++member)
-#else
-#define TR_LEAF_MEMBERS(ref, more) constexpr uint member = 0;
-#endif
-
 // A ray of the terminal query (trace_quad.h trace_closest_wave4<.., TERMINAL>).  `early`: the ray may end at the first accepted candidate
 // that replaces its best so far (false: an ordinary closest hit, the per-ray fallback).  `blocked`: it did.
 struct TerminalRay { bool early, blocked; };
@@ -114,26 +101,8 @@ struct TriHit { float t, bu, bv; uint inst_flags, prim, alpha; };
 // Watertight test (Woop, Benthin, Wald 2013), no culling, of triangle record `index`.  Plain IEEE fp32 without
 // contraction: the shared-edge guarantee needs both products of each edge function
 // rounded, and the CPU oracle evaluates exactly the same expression tree.  The nine vertex components are taken in the ray's order.
-// Wave priority around the fetch of a phase (an experiment, -DTR_SETPRIO=1: low while a phase issues its loads, high from there to the
-// next phase's loads; =2: the other way round; profiles/r5/setprio_ab.txt).  Off: no instruction.
-#ifndef TR_SETPRIO
-#define TR_SETPRIO 0
-#endif
-#if TR_SETPRIO == 1
-#define TR_PRIO_BEGIN() __builtin_amdgcn_s_setprio(0)
-#define TR_PRIO_ISSUED() __builtin_amdgcn_s_setprio(2)
-#elif TR_SETPRIO == 2
-#define TR_PRIO_BEGIN() __builtin_amdgcn_s_setprio(2)
-#define TR_PRIO_ISSUED() __builtin_amdgcn_s_setprio(0)
-#else
-#define TR_PRIO_BEGIN()
-#define TR_PRIO_ISSUED()
-#endif
-
 TR_DEV bool tri_intersect(const RayPre& r, const TriRecord* tris, uint index, float tmin, float tmax, TriHit& o TL(, TlPhase* tlp = nullptr)) {
 #pragma clang fp contract(off)
-    TR_PRIO_BEGIN();
-#ifndef TR_TRI_FETCH_DWORDS
     // The record is three 16-byte loads - what a lane's L1 pays for is accesses, not bytes - and every component is picked out of the three
     // registers of its vertex with two selects (18 selects per test).  Round 5 measured both ways of not branching over the axes
     // (profiles/r5/triangle_fetch_ab.txt): nine 4-byte loads at per-lane offsets 4 kx / 4 ky / 4 kz cost no vector instruction at all and ten
@@ -141,24 +110,12 @@ TR_DEV bool tri_intersect(const RayPre& r, const TriRecord* tris, uint index, fl
     // (0.65 of its access rate), the VALUs are not (0.43).
     const f4* p = reinterpret_cast<const f4*>(reinterpret_cast<const char*>(tris) + (size_t)index * (uint)sizeof(TriRecord));
     const f4 q0 = p[0], q1 = p[1], q2 = p[2];       // x0 y0 z0 x1 | y1 z1 x2 y2 | z2 inst prim alpha
-    TR_PRIO_ISSUED();
     o.inst_flags = __float_as_uint(q2.y); o.prim = __float_as_uint(q2.z); o.alpha = __float_as_uint(q2.w);
     const uint kx4 = tri_component_offset(r.nkx), ky4 = tri_component_offset(r.nky), kz4 = tri_component_offset(r.nkz);
     auto pick = [](float x, float y, float z, uint k4) { const float xy = k4 == 4u ? y : x; return k4 == 8u ? z : xy; };
     const float v0x = pick(q0.x, q0.y, q0.z, kx4), v1x = pick(q0.w, q1.x, q1.y, kx4), v2x = pick(q1.z, q1.w, q2.x, kx4);
     const float v0y = pick(q0.x, q0.y, q0.z, ky4), v1y = pick(q0.w, q1.x, q1.y, ky4), v2y = pick(q1.z, q1.w, q2.x, ky4);
     const float v0z = pick(q0.x, q0.y, q0.z, kz4), v1z = pick(q0.w, q1.x, q1.y, kz4), v2z = pick(q1.z, q1.w, q2.x, kz4);
-#else
-    // variant for the A/B: nine 4-byte loads at per-lane offsets, no select
-    const char* base = reinterpret_cast<const char*>(tris);
-    const uint rec = index * (uint)sizeof(TriRecord);
-    const uint ox = rec + tri_component_offset(r.nkx), oy = rec + tri_component_offset(r.nky), oz = rec + tri_component_offset(r.nkz);
-    const float v0x = *reinterpret_cast<const float*>(base + (size_t)ox), v1x = *reinterpret_cast<const float*>(base + (size_t)ox + 12), v2x = *reinterpret_cast<const float*>(base + (size_t)ox + 24);
-    const float v0y = *reinterpret_cast<const float*>(base + (size_t)oy), v1y = *reinterpret_cast<const float*>(base + (size_t)oy + 12), v2y = *reinterpret_cast<const float*>(base + (size_t)oy + 24);
-    const float v0z = *reinterpret_cast<const float*>(base + (size_t)oz), v1z = *reinterpret_cast<const float*>(base + (size_t)oz + 12), v2z = *reinterpret_cast<const float*>(base + (size_t)oz + 24);
-    const uint* tail = reinterpret_cast<const uint*>(base + (size_t)rec + 36);
-    o.inst_flags = tail[0]; o.prim = tail[1]; o.alpha = tail[2];
-#endif
     TL(if (tlp) tlp->loads_issued();)
     const float Akz = v0z - r.op.z, Bkz = v1z - r.op.z, Ckz = v2z - r.op.z;
     const float Ax = (v0x - r.op.x) - r.Sx * Akz, Ay = (v0y - r.op.y) - r.Sy * Akz;
@@ -339,9 +296,7 @@ TR_DEV void box4_test(const RayPre& r, const Node4Data& d, float tmin, float tma
 }
 TR_DEV void box4_intersect(const RayPre& r, const Bvh4Node* nodes, int node, float tmin, float tmax, Hit4& h TL(, TlPhase* tlp = nullptr)) {
     Node4Data d;
-    TR_PRIO_BEGIN();
     box4_load(r, nodes, node, d);
-    TR_PRIO_ISSUED();
     TL(if (tlp) tlp->loads_issued();)
     box4_test(r, d, tmin, tmax, h);
 }
@@ -491,148 +446,12 @@ TR_DEV LightHit trace_sphere_lights(const SceneView& sv, f3 org, f3 dir, float t
     return {best_t, best_light};
 }
 
-// Closest hit over triangles, one ray per lane (sphere lights: trace_sphere_lights, called after it).  ALPHA_MODE 0: stochastic alpha keyed by `seed`
-// (shader/rt_common.rahit:15-24); 1: fixed cutoff 1e-4 (shader/rt_feature.rahit:17).
-template <int ALPHA_MODE, bool COUNT>
-TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
-                              int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow);
-template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
-TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
-                           int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
-    if constexpr (TWO_LEVEL) {
-        trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, seed, lds_stack, hit, st, overflow);
-        return;
-    }
-    hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
-    float best_t = tmax;
-    bool found = false;
-    uint best_inst = 0xFFFFFFFFu, best_prim = 0xFFFFFFFFu;
-    RayPre r = make_ray(org, dir);
-    const bool finite_ray = ray_is_finite(org, dir);
-    if (sv.tri_count > 0 && finite_ray) {
-        LaneStack stk;
-        int spill[TR_SPILL_STACK];
-        stk.init(lds_stack);
-        int node = sv.node_count > 0 ? 0 : -1;   // single-triangle scene: leaf ~0 == -1
-        while (true) {
-#if TR_VOTE > 0
-            const bool at_leaf = node < 0;
-            const int n_leaf = __popcll(__ballot(at_leaf)), n_all = __popcll(__ballot(true));
-            const bool leaf_phase = n_leaf >= TR_VOTE || n_leaf == n_all;
-            if (at_leaf != leaf_phase) continue;
-#endif
-            if (COUNT) {
-                const unsigned long long m = __ballot(true), mn = __ballot(node >= 0);
-                if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) {
-                    if (mn) { st.ph_node++; if (__popcll(m) <= 16) { st.ph_node16++; st.lv_node16 += (uint)__popcll(mn); } if (__popcll(m) <= 8) st.ph_node8++; }
-                    else st.ph_tri++;
-                }
-            }
-            if (node >= 0) {
-                Hit4 h;
-                box4_intersect(r, sv.nodes4, node, tmin, best_t, h);
-                if (COUNT) st.nodes++;
-                TR_CE4(0, 1) TR_CE4(2, 3) TR_CE4(0, 2) TR_CE4(1, 3) TR_CE4(1, 2)
-                if (h.t[0] < __builtin_huge_valf()) {
-                    // sorted: the hit children come first, so the number of further hits says which of c[1..3] go onto the stack
-                    const int m = (int)(h.t[1] < __builtin_huge_valf()) + (int)(h.t[2] < __builtin_huge_valf()) + (int)(h.t[3] < __builtin_huge_valf());
-                    stk.push_sorted(spill, m, h.c[1], h.c[2], h.c[3]);
-                    if (COUNT) st.maxsp = max(st.maxsp, (uint)stk.sp);
-                    node = h.c[0];
-                    continue;
-                }
-            } else {
-                TriHit tr;
-                if (COUNT) st.tris++;
-                TR_LEAF_MEMBERS((uint)~node, true)
-                if (tri_intersect(r, sv.tris, leaf_index((uint)~node) + member, tmin, __builtin_huge_valf(), tr)) {
-                    const float t = tr.t, bu = tr.bu, bv = tr.bv;
-                    const uint inst = tr.inst_flags & 0x7FFFFFFFu;
-                    const bool closer = t < best_t ||
-                        (t == best_t && found && (inst < best_inst || (inst == best_inst && tr.prim < best_prim)));
-                    if (closer && t < tmax) {
-                        bool accept = true;
-                        if (tr.inst_flags & 0x80000000u) {
-                            if (COUNT) st.alpha++;
-                            float a = candidate_alpha(sv, tr.alpha, bu, bv);
-                            float cutoff = ALPHA_MODE == 0 ? alpha_cutoff_hash(seed, (int)inst, (int)tr.prim) : 0.0001f;
-                            accept = !(a <= cutoff);
-                        }
-                        if (accept) {
-                            best_t = t; found = true; best_inst = inst; best_prim = tr.prim;
-                            hit.instance_id = (int)inst; hit.primitive_id = (int)tr.prim; hit.u = bu; hit.v = bv;
-                        }
-                    }
-                }
-            }
-            if (stk.sp == 0) break;
-            node = stk.pop(spill);
-        }
-        overflow += stk.overflow ? 1 : 0;
-    }
-    hit.t = found ? best_t : -1.0f;
-}
-
-// shadow_ray (shader/path_tracer.glsl:35-52) + rt_common_shadow.rahit/.rchit: product of (1 - alpha)
-// over non-opaque hits, 0 on the first opaque hit; lights are excluded (mask 0xFD).
-template <bool COUNT>
-TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow);
-template <bool COUNT, bool TWO_LEVEL = false>
-TR_DEV float trace_shadow4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow) {
-    if constexpr (TWO_LEVEL) return trace_shadow4_2l<COUNT>(sv, org, dir, tmin, tmax, lds_stack, st, overflow);
-    float visibility = 1.0f;
-    if (sv.tri_count == 0 || !ray_is_finite(org, dir)) return visibility;
-    RayPre r = make_ray(org, dir);
-    LaneStack stk;
-    int spill[TR_SPILL_STACK];
-    stk.init(lds_stack);
-    int node = sv.node_count > 0 ? 0 : -1;   // single-triangle scene: leaf ~0 == -1
-    while (true) {
-        if (node >= 0) {
-            Hit4 h;
-            box4_intersect(r, sv.nodes4, node, tmin, tmax, h);
-            if (COUNT) st.nodes++;
-            if (shadow_descend(h, stk, spill, node)) continue;
-        } else {
-            TriHit tr;
-            if (COUNT) st.tris++;
-#if TR_PAIR_LEAVES
-            bool occluded = false;
-            for (uint member = 0; member <= (leaf_is_pair((uint)~node) ? 1u : 0u) && !occluded; ++member)
-            if (tri_intersect(r, sv.tris, leaf_index((uint)~node) + member, tmin, tmax, tr)) {
-                if (!(tr.inst_flags & 0x80000000u)) { visibility = 0.0f; occluded = true; }
-                else {
-                    if (COUNT) st.alpha++;
-                    float alpha = candidate_alpha(sv, tr.alpha, tr.bu, tr.bv);
-                    visibility *= 1.0f - alpha;
-                    if (visibility == 0.0f) occluded = true;
-                }
-            }
-            if (occluded) break;
-#else
-            if (tri_intersect(r, sv.tris, (uint)~node, tmin, tmax, tr)) {
-                if (!(tr.inst_flags & 0x80000000u)) { visibility = 0.0f; break; }
-                if (COUNT) st.alpha++;
-                float alpha = candidate_alpha(sv, tr.alpha, tr.bu, tr.bv);
-                visibility *= 1.0f - alpha;
-                if (visibility == 0.0f) break;
-            }
-#endif
-        }
-        if (stk.sp == 0) break;
-        node = stk.pop(spill);
-    }
-    overflow += stk.overflow ? 1 : 0;
-    return visibility;
-}
-
 // =====================================================================================================================
-// Two-level traversal: the instantiations with TWO_LEVEL = true.  The loop is the per-lane loop above; a TLAS
-// leaf is a node-phase step that moves the ray into the instance's object space and descends into its BLAS, with a sentinel on the stack
-// below the BLAS entries that brings the world ray back when it is popped.  The object-space ray is M^-1 (o, 1) and M^-1 (d, 0), not
-// renormalised: a point at distance t along it is the image of the world point at t, so t, the culling bound best_t and the candidate
-// order (t, instance, primitive) keep their meaning across instances.
-static_assert(!TR_PAIR_LEAVES && !TR_TRI_STRIDE64, "the two-level traversal supports neither TR_PAIR_LEAVES nor TR_TRI_STRIDE64");
+// Two-level structures: what the per-lane loops below do with TWO_LEVEL = true.  A TLAS leaf is a node-phase step
+// that moves the ray into the instance's object space and descends into its BLAS, with a sentinel on the stack below the BLAS entries
+// that brings the world ray back when it is popped.  The object-space ray is M^-1 (o, 1) and M^-1 (d, 0), not renormalised: a point at
+// distance t along it is the image of the world point at t, so t, the culling bound best_t and the candidate order (t, instance,
+// primitive) keep their meaning across instances.
 #define TR_BLAS_SENTINEL 0x7FFFFFFF   // the reference of an empty child slot, which no node phase ever pushes
 
 struct InstanceFrame { uint inst_word, alpha_base; };
@@ -660,9 +479,12 @@ TR_DEV void instance_words(const InstanceFrame& fr, TriHit& tr) {
     tr.alpha = 0x80000000u | (fr.alpha_base + tr.prim);
 }
 
-template <int ALPHA_MODE, bool COUNT>
-TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
-                              int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
+// Closest hit over triangles, one ray per lane (sphere lights: trace_sphere_lights, called after it).  ALPHA_MODE 0: stochastic alpha keyed by `seed`
+// (shader/rt_common.rahit:15-24); 1: fixed cutoff 1e-4 (shader/rt_feature.rahit:17).  One loop for both structure kinds: a one-level
+// ray starts inside "its BLAS" (the whole tree) and never leaves it, a two-level ray starts in the TLAS.
+template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false>
+TR_DEV void trace_closest4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, uint seed,
+                           int* lds_stack, HitRecord& hit, TraceStats& st, int& overflow) {
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
     float best_t = tmax;
     bool found = false;
@@ -674,8 +496,8 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
         LaneStack stk;
         int spill[TR_SPILL_STACK];
         stk.init(lds_stack);
-        int node = 0;
-        bool in_blas = false;
+        int node = TWO_LEVEL ? 0 : (sv.node_count > 0 ? 0 : -1);   // one level, single-triangle scene: leaf ~0 == -1
+        bool in_blas = !TWO_LEVEL;
         InstanceFrame fr = {0u, 0u};
         while (true) {
             const bool at_tri = node < 0 && in_blas;
@@ -684,6 +506,13 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
             const bool leaf_phase = n_leaf >= TR_VOTE || n_leaf == n_all;
             if (at_tri != leaf_phase) continue;
 #endif
+            if (COUNT && !TWO_LEVEL) {
+                const unsigned long long m = __ballot(true), mn = __ballot(node >= 0);
+                if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) {
+                    if (mn) { st.ph_node++; if (__popcll(m) <= 16) { st.ph_node16++; st.lv_node16 += (uint)__popcll(mn); } if (__popcll(m) <= 8) st.ph_node8++; }
+                    else st.ph_tri++;
+                }
+            }
             if (!at_tri) {
                 if (node >= 0) {
                     Hit4 h;
@@ -691,13 +520,14 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
                     if (COUNT) st.nodes++;
                     TR_CE4(0, 1) TR_CE4(2, 3) TR_CE4(0, 2) TR_CE4(1, 3) TR_CE4(1, 2)
                     if (h.t[0] < __builtin_huge_valf()) {
+                        // sorted: the hit children come first, so the number of further hits says which of c[1..3] go onto the stack
                         const int m = (int)(h.t[1] < __builtin_huge_valf()) + (int)(h.t[2] < __builtin_huge_valf()) + (int)(h.t[3] < __builtin_huge_valf());
                         stk.push_sorted(spill, m, h.c[1], h.c[2], h.c[3]);
                         if (COUNT) st.maxsp = max(st.maxsp, (uint)stk.sp);
                         node = h.c[0];
                         continue;
                     }
-                } else {    // TLAS leaf: into the instance
+                } else if constexpr (TWO_LEVEL) {    // TLAS leaf: into the instance
                     stk.push(spill, TR_BLAS_SENTINEL);
                     if (COUNT) st.maxsp = max(st.maxsp, (uint)stk.sp);
                     node = enter_instance(sv, ~node, org, dir, rw, r, fr);
@@ -708,7 +538,7 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
                 TriHit tr;
                 if (COUNT) st.tris++;
                 if (tri_intersect(r, sv.tris, (uint)~node, tmin, __builtin_huge_valf(), tr)) {
-                    instance_words(fr, tr);
+                    if constexpr (TWO_LEVEL) instance_words(fr, tr);
                     const float t = tr.t, bu = tr.bu, bv = tr.bv;
                     const uint inst = tr.inst_flags & 0x7FFFFFFFu;
                     const bool closer = t < best_t ||
@@ -730,10 +560,12 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
             }
             if (stk.sp == 0) break;
             node = stk.pop(spill);
-            if (node == TR_BLAS_SENTINEL) {     // the BLAS is done: back to the world ray (below a sentinel lies a TLAS entry or nothing)
-                r = rw; in_blas = false;
-                if (stk.sp == 0) break;
-                node = stk.pop(spill);
+            if constexpr (TWO_LEVEL) {
+                if (node == TR_BLAS_SENTINEL) {     // the BLAS is done: back to the world ray (below a sentinel lies a TLAS entry or nothing)
+                    r = rw; in_blas = false;
+                    if (stk.sp == 0) break;
+                    node = stk.pop(spill);
+                }
             }
         }
         overflow += stk.overflow ? 1 : 0;
@@ -741,8 +573,10 @@ TR_DEV void trace_closest4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
     hit.t = found ? best_t : -1.0f;
 }
 
-template <bool COUNT>
-TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow) {
+// shadow_ray (shader/path_tracer.glsl:35-52) + rt_common_shadow.rahit/.rchit: product of (1 - alpha)
+// over non-opaque hits, 0 on the first opaque hit; lights are excluded (mask 0xFD).
+template <bool COUNT, bool TWO_LEVEL = false>
+TR_DEV float trace_shadow4(const SceneView& sv, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, TraceStats& st, int& overflow) {
     float visibility = 1.0f;
     if (sv.tri_count == 0 || !ray_is_finite(org, dir)) return visibility;
     const RayPre rw = make_ray(org, dir);
@@ -750,8 +584,8 @@ TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
     LaneStack stk;
     int spill[TR_SPILL_STACK];
     stk.init(lds_stack);
-    int node = 0;
-    bool in_blas = false;
+    int node = TWO_LEVEL ? 0 : (sv.node_count > 0 ? 0 : -1);   // one level, single-triangle scene: leaf ~0 == -1
+    bool in_blas = !TWO_LEVEL;
     InstanceFrame fr = {0u, 0u};
     while (true) {
         if (node >= 0) {
@@ -759,16 +593,18 @@ TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
             box4_intersect(r, sv.nodes4, node, tmin, tmax, h);
             if (COUNT) st.nodes++;
             if (shadow_descend(h, stk, spill, node)) continue;
-        } else if (!in_blas) {
-            stk.push(spill, TR_BLAS_SENTINEL);
-            node = enter_instance(sv, ~node, org, dir, rw, r, fr);
-            in_blas = true;
-            continue;
+        } else if (!in_blas) {      // TLAS leaf: into the instance (a one-level ray is never outside)
+            if constexpr (TWO_LEVEL) {
+                stk.push(spill, TR_BLAS_SENTINEL);
+                node = enter_instance(sv, ~node, org, dir, rw, r, fr);
+                in_blas = true;
+                continue;
+            }
         } else {
             TriHit tr;
             if (COUNT) st.tris++;
             if (tri_intersect(r, sv.tris, (uint)~node, tmin, tmax, tr)) {
-                instance_words(fr, tr);
+                if constexpr (TWO_LEVEL) instance_words(fr, tr);
                 if (!(tr.inst_flags & 0x80000000u)) { visibility = 0.0f; break; }
                 if (COUNT) st.alpha++;
                 float alpha = candidate_alpha(sv, tr.alpha, tr.bu, tr.bv);
@@ -778,10 +614,12 @@ TR_DEV float trace_shadow4_2l(const SceneView& sv, f3 org, f3 dir, float tmin, f
         }
         if (stk.sp == 0) break;
         node = stk.pop(spill);
-        if (node == TR_BLAS_SENTINEL) {
-            r = rw; in_blas = false;
-            if (stk.sp == 0) break;
-            node = stk.pop(spill);
+        if constexpr (TWO_LEVEL) {
+            if (node == TR_BLAS_SENTINEL) {
+                r = rw; in_blas = false;
+                if (stk.sp == 0) break;
+                node = stk.pop(spill);
+            }
         }
     }
     overflow += stk.overflow ? 1 : 0;

@@ -110,7 +110,7 @@ TR_DEV QuadCtx make_quad_ctx(int* s_stack, int* s_owner, const PathBuffers& pb T
 template <bool COUNT, bool TWO_LEVEL, typename CONTRIB, typename LOBES>
 TR_DEV void shadow_ray(const SceneView& sv, const PtParams& P, const PathBuffers& pb, bool valid, f4 o, f4 d, CONTRIB&& contrib, LOBES&& lobes, int* lds_stack, const QuadCtx& qc,
                        TraceStats& st, int& overflow, uint& rays) {
-#if TR_QUAD_SWITCH > 0 && !defined(TR_NO_SHADOW_QUADS)
+#if TR_QUAD_SWITCH > 0
     float vis = trace_shadow_wave4<COUNT, TWO_LEVEL>(sv, valid, F3(o), F3(d), P.opt.min_ray_dist, o.w, lds_stack, qc, st, overflow);
 #else
     float vis = 1.0f;

@@ -68,73 +68,28 @@ TR_DEV void wave_sync_lds() {   // LDS writes of this wave are visible to its ot
 }
 
 // What the four lanes of a quad share about their ray (same values in all four) plus the lane's own candidate.
-#ifndef TR_QUAD_FETCH
-#define TR_QUAD_FETCH 0
-#endif
 struct QuadRay {
     RayPre r;        // the ray as its owner kept it (trace.h)
     float tmin;
-#if TR_QUAD_FETCH
-    uint off_a, off_b;     // byte offsets inside a node of the two 16-byte chunks this lane fetches for its quad (quad_child_box)
-#endif
 };
-
-// 4 x 4 transpose inside a quad: lane i comes in with row i in (r0 .. r3) and leaves with column i.  Two butterfly stages of
-// quad-permute DPP reads (lane ^ 1, lane ^ 2), four selects + two reads per register pair: 16 vector instructions.
-TR_DEV void quad_transpose(int q, float& r0, float& r1, float& r2, float& r3) {
-    const bool odd = (q & 1) != 0, hi = (q & 2) != 0;
-    auto swap1 = [&](float& a, float& b) {      // with lane ^ 1
-        const float t = __int_as_float(quad_perm<0xB1>(__float_as_int(odd ? a : b)));
-        a = odd ? t : a; b = odd ? b : t;
-    };
-    auto swap2 = [&](float& a, float& b) {      // with lane ^ 2
-        const float t = __int_as_float(quad_perm<0x4E>(__float_as_int(hi ? a : b)));
-        a = hi ? t : a; b = hi ? b : t;
-    };
-    swap1(r0, r1); swap1(r2, r3);
-    swap2(r0, r2); swap2(r1, r3);
-}
 
 // Box of child q of `node` against the quad's ray; returns the child reference, `hit` and the entry distance.
 // A lane reads the seven words of its child out of seven different 16-byte chunks of the node: 28 L1 accesses per quad and node.
-// -DTR_QUAD_FETCH=1 (round 5, measured, not adopted: profiles/r5/quad_fetch_ab.txt) lets the quad fetch the node together instead - lane q
-// loads two whole chunks, eight accesses per quad, and two 4 x 4 transposes hand every lane the column of its child: 32 vector
-// instructions for 20 accesses.  Closest-hit +2 %, frames +1 %: the tail's phases serve few rays, its L1 accesses are few either way,
-// and the 32 instructions sit on the critical path of the last rays of a wave.  (The same trade in the triangle test - selects for
-// accesses - won, because those phases run with full waves.)
-// -DTR_TAIL_PREFETCH=1 (an experiment of round 6, profiles/r6/tail_prefetch_ab.txt): a quad lane whose child is an inner node that was hit
-// touches that child's cache line right away (one dword, `pf`), so that the line is on its way while the quad sorts its hits and updates its
-// stack; the value is consumed here, behind the next phase's own loads (older loads return first: no extra wait).
-#ifndef TR_TAIL_PREFETCH
-#define TR_TAIL_PREFETCH 0
-#endif
-TR_DEV int quad_child_box(const QuadRay& r, const Bvh4Node* nodes, int node, int q, float tmax, bool& hit, float& t0 TL(, TlPhase* tlp = nullptr), int pf = 0) {
+// Round 5 measured letting the quad fetch the node together instead (eight accesses and two 4 x 4 transposes; closest-hit +2 %,
+// profiles/r5/quad_fetch_ab.txt), round 6 a prefetch of the hit inner child's line (+1.5 %, profiles/r6/tail_prefetch_ab.txt): both
+// live in experiments/r12_retired_switches.patch.
+TR_DEV int quad_child_box(const QuadRay& r, const Bvh4Node* nodes, int node, int q, float tmax, bool& hit, float& t0 TL(, TlPhase* tlp = nullptr)) {
     float nx, fx, ny, fy, nz, fz;
     int c;
     {
         const char* base = reinterpret_cast<const char*>(nodes);
-#if TR_QUAD_FETCH
-        const uint t = (uint)node << 7;
-        const f4 a = *reinterpret_cast<const f4*>(base + (size_t)(t | r.off_a));
-        const f4 b = *reinterpret_cast<const f4*>(base + (size_t)(t | r.off_b));
-        TL(if (tlp) tlp->loads_issued();)
-        float a0 = a.x, a1 = a.y, a2 = a.z, a3 = a.w, b0 = b.x, b1 = b.y, b2 = b.z, b3 = b.w;
-        quad_transpose(q, a0, a1, a2, a3);      // rows: near x, far x, near y, far y
-        quad_transpose(q, b0, b1, b2, b3);      // rows: near z, far z, references, references
-        nx = a0; fx = a1; ny = a2; fy = a3; nz = b0; fz = b1;
-        c = __float_as_int(b2);
-#else
         const uint t = ((uint)node << 7) | ((uint)q << 2);
         const uint ax = t | r.r.nkx, ay = t | r.r.nky, az = t | r.r.nkz;
         nx = *reinterpret_cast<const float*>(base + (size_t)ax); fx = *reinterpret_cast<const float*>(base + (size_t)(ax ^ 16u));
         ny = *reinterpret_cast<const float*>(base + (size_t)ay); fy = *reinterpret_cast<const float*>(base + (size_t)(ay ^ 16u));
         nz = *reinterpret_cast<const float*>(base + (size_t)az); fz = *reinterpret_cast<const float*>(base + (size_t)(az ^ 16u));
         c = *reinterpret_cast<const int*>(base + (size_t)t + 96);
-#if TR_TAIL_PREFETCH
-        asm volatile("" : : "v"(pf));
-#endif
         TL(if (tlp) tlp->loads_issued();)
-#endif
     }
     // the arithmetic of box4_intersect for one child
     const float tx0 = (nx - r.r.op.x) * r.r.ip.x, tx1 = (fx - r.r.op.x) * r.r.ip.x;
@@ -143,9 +98,7 @@ TR_DEV int quad_child_box(const QuadRay& r, const Bvh4Node* nodes, int node, int
     t0 = fmaxf(fmaxf(tx0, ty0), fmaxf(tz0, r.tmin));
     const float t1 = fminf(fminf(fminf(tx1, ty1), tz1), tmax) * TR_SLAB_PAD;
     hit = t0 <= t1;
-#if !TR_QUAD_FETCH
     asm volatile("" : "+v"(c));
-#endif
     return c;
 }
 
@@ -212,13 +165,6 @@ TR_DEV QuadDeal quad_deal(unsigned long long act, bool live, const RayPre& r, fl
     const uint packed = (uint)bperm(src, (int)(r.nkx | (r.nky << 8) | (r.nkz << 16)));
     qr.r.nkx = packed & 0xFFu; qr.r.nky = (packed >> 8) & 0xFFu; qr.r.nkz = (packed >> 16) & 0xFFu;
     qr.tmin = bpermf(src, tmin);
-#if TR_QUAD_FETCH
-    {   // which two chunks of a node this lane fetches for its quad: lane 0 near x + near z, 1 far x + far z, 2 near y + references, 3 far y + references
-        const uint flip = (uint)(d.q & 1) << 4;
-        qr.off_a = ((d.q & 2) ? qr.r.nky : qr.r.nkx) ^ flip;
-        qr.off_b = (d.q & 2) ? 96u : (qr.r.nkz ^ flip);
-    }
-#endif
     qnode = bperm(src, node);
     qs.lds = qc.wave_stack + owner;
     qs.glob = qc.spill + d.qd * TR_QSPILL;
@@ -255,7 +201,7 @@ TR_DEV void quad_inherited_leaf(int q, int& pend, QuadStack& qs, int& qnode, boo
 
 // Closest hit for the rays of one wave.  Every lane of the wave calls this (`valid` = the lane has a ray); parameters and
 // result as trace_closest4.
-// TWO_LEVEL: the two-level structure, traced by the per-lane loop to the end (trace.h trace_closest4_2l; no quad tail in this version).
+// TWO_LEVEL: the two-level structure, traced by the per-lane loop to the end (trace.h trace_closest4<.., true>; no quad tail in this version).
 // TERMINAL: the first-hit emitter query of a path's last ray (trace.h TerminalRay; all-merged structure only).
 template <int ALPHA_MODE, bool COUNT, bool TWO_LEVEL = false, bool TERMINAL = false>
 TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, uint seed,
@@ -263,7 +209,7 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
     static_assert(!(TERMINAL && TWO_LEVEL), "the terminal query walks the all-merged structure");
     hit.instance_id = -1; hit.primitive_id = -1; hit.u = 0; hit.v = 0; hit.t = -1.0f;
     if constexpr (TWO_LEVEL) {
-        if (valid) trace_closest4_2l<ALPHA_MODE, COUNT>(sv, org, dir, tmin, tmax, seed, lds_stack, hit, st, overflow);
+        if (valid) trace_closest4<ALPHA_MODE, COUNT, true>(sv, org, dir, tmin, tmax, seed, lds_stack, hit, st, overflow);
         return;
     }
     float best_t = tmax, best_u = 0.0f, best_v = 0.0f;
@@ -381,8 +327,7 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                     if (tl_hit) { tlp.alpha = (tr.inst_flags & 0x80000000u) != 0 && (tr.t < best_t || tr.t == best_t); consider(tr, tr.t, tr.bu, tr.bv); }
                     tlp.mark_b();
 #else
-                    TR_LEAF_MEMBERS((uint)~node, true)
-                    if (tri_intersect(r, sv.tris, leaf_index((uint)~node) + member, tmin, __builtin_huge_valf(), tr)) {
+                    if (tri_intersect(r, sv.tris, (uint)~node, tmin, __builtin_huge_valf(), tr)) {
                         const bool took = consider(tr, tr.t, tr.bu, tr.bv);
                         if constexpr (TERMINAL) blocked = blocked || (took && early);      // something accepted lies in front of the nearest emitter
                     }
@@ -419,9 +364,6 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
         int pend = -1;      // triangle this lane has to test
         const bool qearly = TERMINAL ? bperm(src, early ? 1 : 0) != 0 : false;
         bool qblocked = false;
-#if TR_TAIL_PREFETCH
-        int qpf = 0;
-#endif
         TL(tl_misc(qc.tl, 2, tl_now() - tl_deal);)
         while (true) {
             int w = pend >= 0 ? 1 : 0;
@@ -437,8 +379,7 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                     TL(TlPhase tlp; const int tl_units = __popcll(__ballot(true)); tlp.begin();)
                     TriHit tr;
                     if (COUNT) st.tris++;
-                    TR_LEAF_MEMBERS((uint)pend, true)
-                    if (tri_intersect(qr.r, sv.tris, leaf_index((uint)pend) + member, qr.tmin, __builtin_huge_valf(), tr TL(, &tlp))) {
+                    if (tri_intersect(qr.r, sv.tris, (uint)pend, qr.tmin, __builtin_huge_valf(), tr TL(, &tlp))) {
                         const float t = tr.t, bu = tr.bu, bv = tr.bv;
                         const uint inst = tr.inst_flags & 0x7FFFFFFFu;
                         bool accept = t < lt || (t == lt && linst != 0xFFFFFFFFu && (inst < linst || (inst == linst && tr.prim < lprim)));
@@ -471,16 +412,9 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                 bool hitb; float t0;
                 TL(TlPhase tlp; const int tl_units = __popcll(__ballot(true)) >> 2; tlp.begin();)
                 const int q = quad_lane();
-#if TR_TAIL_PREFETCH
-                const int c = quad_child_box(qr, sv.nodes4, qnode, q, qbest, hitb, t0 TL(, &tlp), qpf);
-#else
                 const int c = quad_child_box(qr, sv.nodes4, qnode, q, qbest, hitb, t0 TL(, &tlp));
-#endif
                 if (COUNT && q == 0) st.nodes++;
                 const bool inner = hitb && c >= 0;
-#if TR_TAIL_PREFETCH
-                if (inner) qpf = *reinterpret_cast<const int*>(reinterpret_cast<const char*>(sv.nodes4) + ((size_t)(uint)c << 7) + 96);
-#endif
                 if (hitb && c < 0) pend = ~c;
                 // order of the inner children that were hit: entry distance, ties by slot (two low mantissa bits carry the slot)
                 quad_descend(inner, inner ? ((__float_as_uint(t0) & ~3u) | (uint)q) : 0xFFFFFFFFu, c, qs, qnode, qlive);
@@ -527,7 +461,7 @@ TR_DEV void trace_closest_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
 template <bool COUNT, bool TWO_LEVEL = false>
 TR_DEV float trace_shadow_wave4(const SceneView& sv, bool valid, f3 org, f3 dir, float tmin, float tmax, int* lds_stack, const QuadCtx& qc,
                                 TraceStats& st, int& overflow) {
-    if constexpr (TWO_LEVEL) return valid ? trace_shadow4_2l<COUNT>(sv, org, dir, tmin, tmax, lds_stack, st, overflow) : 1.0f;
+    if constexpr (TWO_LEVEL) return valid ? trace_shadow4<COUNT, true>(sv, org, dir, tmin, tmax, lds_stack, st, overflow) : 1.0f;
     float visibility = 1.0f;
     bool live = valid && sv.tri_count > 0 && ray_is_finite(org, dir);
     RayPre r = make_ray(org, dir);
@@ -558,8 +492,7 @@ TR_DEV float trace_shadow_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
             } else {
                 TriHit tr;
                 if (COUNT) st.tris++;
-                TR_LEAF_MEMBERS((uint)~node, live)
-                if (tri_intersect(r, sv.tris, leaf_index((uint)~node) + member, tmin, tmax, tr)) {
+                if (tri_intersect(r, sv.tris, (uint)~node, tmin, tmax, tr)) {
                     if (!(tr.inst_flags & 0x80000000u)) { visibility = 0.0f; live = false; }
                     else {
                         if (COUNT) st.alpha++;
@@ -598,8 +531,7 @@ TR_DEV float trace_shadow_wave4(const SceneView& sv, bool valid, f3 org, f3 dir,
                 if (pend >= 0) {
                     TriHit tr;
                     if (COUNT) st.tris++;
-                    TR_LEAF_MEMBERS((uint)pend, true)
-                    if (tri_intersect(qr.r, sv.tris, leaf_index((uint)pend) + member, qr.tmin, qtmax, tr)) {
+                    if (tri_intersect(qr.r, sv.tris, (uint)pend, qr.tmin, qtmax, tr)) {
                         if (!(tr.inst_flags & 0x80000000u)) lvis = 0.0f;
                         else {
                             if (COUNT) st.alpha++;
