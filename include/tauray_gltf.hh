@@ -236,11 +236,36 @@ struct instance { int32_t light_base_id, sh_grid_index; uint32_t pad; float shad
 struct directional_light { float color[3]; int32_t shadow_map_index; float dir[3]; float dir_cutoff; };
 struct point_light { float color[3], dir[3], pos[3], radius, dir_cutoff, dir_falloff, cutoff_radius, spot_radius; int32_t shadow_map_index, padding; };
 struct camera_data { float view[16], view_inverse[16], view_proj[16], proj_inverse[16], origin[4], dof_params[4], projection_info[4], pan[4]; };
+#pragma pack(pop)
 
 //---------------------------------------------------------------------------------------------------------------------
 // A camera as the file describes it + camera::write_uniform_buffer (src/camera.cc:431-478) with the aspect ratio
 // set_camera_params forces (src/tauray.cc:68-110)
-struct gltf_camera { mat4d transform; bool perspective; double fov, aspect, near, far; double ortho[6]; double pan[2] = {0, 0}; };
+struct gltf_camera
+{
+    mat4d transform; bool perspective; double fov, aspect, near, far; double ortho[6]; double pan[2] = {0, 0};
+    // camera::set_jitter / step_jitter / get_jitter (src/camera.cc:480-498): sub-pixel offsets of a perspective projection, one per frame
+    std::vector<std::array<float, 2>> jitter_sequence;
+    unsigned jitter_index = 0;
+    void set_jitter(const std::vector<std::array<float, 2>>& seq) { jitter_sequence = seq; jitter_index = 0; }
+    void step_jitter() { if(!jitter_sequence.empty()) jitter_index = (jitter_index + 1) % (unsigned)jitter_sequence.size(); }
+    std::array<float, 2> get_jitter() const { return jitter_sequence.empty() ? std::array<float, 2>{0.0f, 0.0f} : jitter_sequence[jitter_index]; }
+};
+
+// halton / get_camera_jitter_sequence (src/math.cc:293-328): Halton points 1..length in bases 2 and 3, mapped to (v * 2 - 1) / resolution
+inline float halton(int index, int base)
+{
+    float f = 1.0f, r = 0.0f;
+    while(index > 0) { f = f / (float)base; r = r + f * (float)(index % base); index = index / base; }
+    return r;
+}
+inline std::vector<std::array<float, 2>> get_camera_jitter_sequence(int length, uint32_t width, uint32_t height)
+{
+    std::vector<std::array<float, 2>> seq((size_t)(length > 0 ? length : 0));
+    for(int i = 0; i < length; ++i)
+        seq[(size_t)i] = {(halton(i + 1, 2) * 2.0f - 1.0f) / (float)width, (halton(i + 1, 3) * 2.0f - 1.0f) / (float)height};
+    return seq;
+}
 
 inline camera_data pack_camera(gltf_camera& c, double aspect)
 {
@@ -263,6 +288,12 @@ inline camera_data pack_camera(gltf_camera& c, double aspect)
         cd.dof_params[0] = 1.0f;
         proj.m[0][2] = c.pan[0]; proj.m[1][2] = c.pan[1];      // camera::set_pan (src/camera.cc:375-381): the off-axis shift of a light-field view
         cd.pan[0] = (float)c.pan[0]; cd.pan[1] = (float)c.pan[1];
+        if(!c.jitter_sequence.empty())
+        {   // src/camera.cc:377-381, 454-461
+            const std::array<float, 2> j = c.get_jitter();
+            proj.m[0][2] += (double)j[0]; proj.m[1][2] += (double)j[1];
+            cd.pan[0] += j[0]; cd.pan[1] += j[1]; cd.pan[2] += j[0]; cd.pan[3] += j[1];
+        }
     }
     else
     {
@@ -279,12 +310,22 @@ inline camera_data pack_camera(gltf_camera& c, double aspect)
     to_glm(view, cd.view);
     to_glm(c.transform, cd.view_inverse);
     to_glm(mul(proj, view), cd.view_proj);
-    to_glm(inverse(proj), cd.proj_inverse);
+    if(c.perspective && !c.jitter_sequence.empty())
+    {   // a jittered projection [[a, 0, px, 0], [0, b, py, 0], [0, 0, c, d], [0, 0, -1, 0]] is inverted in closed form, operation for operation
+        // as the Python host does it: both hosts then pack the same bytes
+        mat4d inv{};
+        inv.m[0][0] = 1.0 / proj.m[0][0]; inv.m[1][1] = 1.0 / proj.m[1][1];
+        inv.m[0][3] = proj.m[0][2] / proj.m[0][0]; inv.m[1][3] = proj.m[1][2] / proj.m[1][1];
+        inv.m[2][3] = -1.0; inv.m[3][2] = 1.0 / proj.m[2][3]; inv.m[3][3] = proj.m[2][2] / proj.m[2][3];
+        to_glm(inv, cd.proj_inverse);
+    }
+    else to_glm(inverse(proj), cd.proj_inverse);
     for(int k = 0; k < 4; ++k) cd.origin[k] = (float)c.transform.m[k][3];
     for(int k = 0; k < 4; ++k) cd.projection_info[k] = (float)info[k];
     return cd;
 }
 
+#pragma pack(push, 4)
 struct mesh_span { uint32_t vertex_offset, vertex_count, index_offset, triangle_count; };
 struct texture_info { uint32_t width, height, texel_offset, format; };      // offset in 4-byte words; format 0 = RGBA8, 1 = RGBA16 (include/trhip.h)
 #pragma pack(pop)
@@ -1081,6 +1122,29 @@ inline uint32_t generate_cameras(scene_data& s, int grid_w, int grid_h, double d
     std::memcpy(s.cameras.data(), packed.data(), s.cameras.size());
     s.previous_cameras.clear();
     return (uint32_t)packed.size();
+}
+
+//---------------------------------------------------------------------------------------------------------------------
+// set_camera_jitter (src/scene.cc:14-18) and the jitter step of update(scene, dt) (src/scene.cc:228) for scenes load_glb made: every
+// camera gets the sequence / steps it, and scene_data::cameras is packed again (scene_animator::update packs with the cameras' jitter too).
+inline void repack_cameras(scene_data& s)
+{
+    using namespace gltf_detail;
+    camera_data* cams = reinterpret_cast<camera_data*>(s.cameras.data());
+    for(size_t ci = 0; ci < s.animation->cameras.size() && (ci + 1) * sizeof(camera_data) <= s.cameras.size(); ++ci)
+        cams[ci] = pack_camera(s.animation->cameras[ci], s.animation->aspect);
+}
+inline void set_camera_jitter(scene_data& s, const std::vector<std::array<float, 2>>& seq)
+{
+    if(!s.animation || s.animation->cameras.empty()) throw std::runtime_error("set_camera_jitter: the scene has no camera description to jitter (load it from a glTF file)");
+    for(auto& c: s.animation->cameras) c.set_jitter(seq);
+    repack_cameras(s);
+}
+inline void step_camera_jitter(scene_data& s)
+{
+    if(!s.animation) return;
+    for(auto& c: s.animation->cameras) c.step_jitter();
+    repack_cameras(s);
 }
 
 //---------------------------------------------------------------------------------------------------------------------

@@ -606,6 +606,36 @@ public:
     trhip_temporal_reprojection* h = nullptr;
 };
 
+// taa_stage (src/taa_stage.{hh,cc}): temporal antialiasing behind the tonemap stage (trhip_taa_*): this frame's display-space colour is
+// blended into the stage's history, found through screen_motion with the cameras' jitter (camera_data::pan.zw) removed and clipped to the
+// 3 x 3 neighbourhood's k-DOP.  The stage keeps its two history images itself and reads the device scene's cameras / previous cameras.
+class taa_stage
+{
+public:
+    struct options
+    {
+        float blending_ratio = 0.125f;      // alpha: the weight of the new frame, 1 / the length of the jitter sequence
+        float gamma = 2.2f;                 // the tonemap stage's (src/post_processing_renderer.cc:215)
+        bool edge_dilation = true, anti_shimmer = false;      // src/options.hh:406-411
+        uint32_t base_camera_index = 0;
+        int projection = 0;
+    };
+    taa_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), opt(opt)
+    {
+        const trhip_taa_options o = {opt.blending_ratio, opt.gamma, opt.edge_dilation ? 1 : 0, opt.anti_shimmer ? 1 : 0, opt.base_camera_index, opt.projection};
+        check(trhip_taa_create(dev.h, &o, size.x, size.y, layers, &h));
+    }
+    taa_stage(const taa_stage&) = delete;
+    ~taa_stage() { trhip_taa_destroy(h); }
+    void run(const trhip_taa_images& images, void* stream = nullptr) { check(trhip_taa_run(h, &images, stream)); }
+    void reset_history() { check(trhip_taa_reset_history(h)); }
+    trhip_taa_timings get_timings() { trhip_taa_timings t; check(trhip_taa_get_timings(h, &t)); return t; }
+
+    device* dev;
+    options opt;
+    trhip_taa* h = nullptr;
+};
+
 class load_balancer
 {
 public:
@@ -672,6 +702,13 @@ public:
         // its history is one chain in frame order, like the denoiser's.  One device, no denoiser, one frame per launch.
         std::vector<uint32_t> spatial_reprojection;
         float temporal_reprojection = 0.0f;
+        // --taa=N (src/post_processing_renderer.cc:62, 99-100, 202-224): taa_stage behind the tonemap stage with alpha = 1 / N and the tonemap
+        // stage's gamma; the path tracer also renders screen_motion, pos and instance_id, every frame is a fresh frame and the stage gets last
+        // frame's cameras - with last frame's jitter - as camera_pair.previous.  The caller gives the scene's cameras the jitter sequence
+        // (set_camera_jitter) and steps it before every frame (step_camera_jitter, then update_cameras or update_scene).  One device, no
+        // reprojection stages, one frame per launch; its history is one chain in frame order, like the denoiser's.
+        struct taa_options { int sequence_length = 8; bool edge_dilation = true, anti_shimmer = false; };
+        std::optional<taa_options> taa;
     };
 
     // `devices`: HIP device index per logical device (repeat an index for --fake-devices); device 0 displays.
@@ -708,6 +745,20 @@ public:
             if(this->opt.bmfr) throw std::runtime_error("rt_renderer: " + which + " together with a denoiser: a chain of reprojection and a denoiser is not built");
             if(batch > 1) throw std::runtime_error("rt_renderer: " + which + ": a reprojected frame is one frame, frames per launch must be 1");
             if(temporal_on && this->opt.accumulate) throw std::runtime_error("rt_renderer: temporal reprojection blends the previous frame into a fresh frame: no accumulation");
+        }
+        if(this->opt.taa)
+        {
+            if(this->opt.taa->sequence_length < 1) throw std::runtime_error("rt_renderer: taa: the length of the jitter sequence must be positive");
+            if(devices.size() > 1)
+                throw std::runtime_error("rt_renderer: taa with a pixel distribution of count " + std::to_string(devices.size()) + " > 1: the stage reads screen motion, "
+                                         "pos and instance id of whole viewports on one device, gathering them from several is not built; use one device");
+            if(this->opt.accumulate) throw std::runtime_error("rt_renderer: taa blends a fresh, jittered frame into its history: no accumulation");
+            if(batch > 1) throw std::runtime_error("rt_renderer: taa: an antialiased frame is one frame (the jitter steps between frames), frames per launch must be 1");
+            if(spatial_on || temporal_on) throw std::runtime_error("rt_renderer: taa together with spatial / temporal reprojection: a chain of reprojection and taa is not built");
+            if(this->opt.projection == 2)
+                throw std::runtime_error("rt_renderer: taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
+                                         "which an equirectangular camera does not have");
+            if(!std::is_same<Pipeline, path_tracer_stage>::value) throw std::runtime_error("rt_renderer: taa reads the path tracer's screen_motion target");
         }
         per_device.resize(devices.size());
         std::vector<double> ratios(devices.size(), 1.0 / devices.size());
@@ -768,7 +819,7 @@ public:
         // One device: nothing sits between the path tracer and the tonemap stage (no transfer, no stitch), and the stage writes the slot's
         // display image while it writes its colour target - the same bits without a second pass over the frame.  TRHIP_FUSED_TONEMAP=0: off.
         const char* fe = getenv("TRHIP_FUSED_TONEMAP");
-        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr && !spatial_on && !temporal_on;
+        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr && !spatial_on && !temporal_on && !this->opt.taa;
         if(this->opt.bmfr)
         {
             device& d0 = *per_device[0].dev;
@@ -813,6 +864,27 @@ public:
             }
             d0.sync();
         }
+        if(this->opt.taa)
+        {
+            device& d0 = *per_device[0].dev;
+            const size_t px = size_t(size.x) * size.y * layers;
+            for(slot_data& sl: per_device[0].slots)
+            {
+                trhip_pt_targets& t = sl.targets;
+                t.color = sl.color;
+                if(!t.pos) t.pos = d0.alloc(px * 16);
+                if(!t.screen_motion) t.screen_motion = d0.alloc(px * 8);
+                if(!t.instance_id) t.instance_id = d0.alloc(px * 4);
+            }
+            taa_input = d0.alloc(display_bytes);
+            taa_stage::options to;
+            to.blending_ratio = 1.0f / (float)this->opt.taa->sequence_length; to.gamma = this->opt.tonemap.gamma;
+            to.edge_dilation = this->opt.taa->edge_dilation; to.anti_shimmer = this->opt.taa->anti_shimmer; to.projection = this->opt.projection;
+            taa = std::make_unique<taa_stage>(d0, size, (uint32_t)layers, to);
+            last_cameras = scene.cameras;
+            current_cameras = scene.cameras;
+            d0.sync();
+        }
         fused_info.assign(frame_slots.size(), trhip_tonemap_info{-1, 0.0f, 0.0f, 0});     // what each slot's stage was last told: render() keeps it current
     }
 
@@ -822,6 +894,8 @@ public:
         bmfr.reset();
         temporal.reset();
         spatial.reset();
+        taa.reset();
+        if(taa_input) per_device[0].dev->free(taa_input);
         for(void* p: {destination_targets.normal, destination_targets.pos, destination_targets.instance_id}) if(p) per_device[0].dev->free(p);
         for(size_t i = 0; i < per_device.size(); ++i)
             for(slot_data& sl: per_device[i].slots)
@@ -870,6 +944,14 @@ public:
         uploaded_previous_cameras = s.previous_cameras.empty() ? uploaded_previous_cameras : s.previous_cameras;
     }
 
+    // Only the cameras changed (the jitter of a still scene stepped): scene_data::cameras go to every device.
+    void update_cameras(const scene_data& s)
+    {
+        finish_all();
+        for(auto& d: per_device) d.scene_update->update_cameras(s.cameras.data(), (uint32_t)(s.cameras.size() / 320));
+        current_cameras = s.cameras;
+    }
+
     // rt_renderer::render (src/rt_renderer.cc:84-133): ray tracers -> transfers -> stitch -> tonemap.  Enqueues only.
     void render()
     {
@@ -902,7 +984,7 @@ public:
             }
             if(i != 0)   // the slot's previous frame has been stitched on the display device: its receive buffer is free
                 check(trhip_stream_wait_peer(d.dev->h, sl.stream, display_device.h, display_stream));
-            if(bmfr || temporal)
+            if(bmfr || temporal || taa)
             {   // camera_pair.previous = the cameras of the frame before this one
                 if(last_cameras != uploaded_previous_cameras)
                 {   // frames in flight read the cameras they were enqueued with: they finish before the record changes
@@ -924,7 +1006,7 @@ public:
                     check(trhip_pt_render_targets(r.stage->pt, &t, ts.x, ts.y, r.count, sl.stream));
                 }
             }
-            else if(bmfr || reprojection) check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
+            else if(bmfr || reprojection || taa) check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
             else sl.ray_tracer->run(sl.stream);
             if(i != 0) check(trhip_copy_peer(display_device.h, sl.gbuffer_copy, d.dev->h, sl.color, d.target_bytes(layers), sl.stream));
         }
@@ -946,7 +1028,7 @@ public:
         }
         display = frame_slots[k].display;
         void* post_stream = display_stream;
-        if((bmfr || reprojection) && frame_slots.size() > 1)
+        if((bmfr || reprojection || taa) && frame_slots.size() > 1)
         {   // the denoiser's / temporal stage's history is one chain over the frames of all slots: it runs in frame order on the display device's
             // default stream (and so does the spatial stage, whose destination G-buffer the slots share)
             check(trhip_stream_wait(display_device.h, nullptr, display_stream)); post_stream = nullptr;
@@ -971,7 +1053,12 @@ public:
                 final_color = sl.full;
             }
         }
-        if(!fused_tonemap) tonemap->run(final_color, display, size, (uint32_t)output_layers, post_stream);
+        if(!fused_tonemap) tonemap->run(final_color, taa ? taa_input : display, size, (uint32_t)output_layers, post_stream);
+        if(taa)
+        {
+            const trhip_pt_targets& t = per_device[0].slots[k].targets;
+            taa->run(trhip_taa_images{taa_input, display, t.screen_motion, t.pos, t.instance_id}, post_stream);
+        }
         if(post_stream != display_stream) check(trhip_stream_wait(display_device.h, display_stream, nullptr));
         frame_index += batch;
         accumulated_frames++;
@@ -1046,6 +1133,8 @@ public:
     std::unique_ptr<temporal_reprojection_stage> temporal;      // options.temporal_reprojection
     std::unique_ptr<spatial_reprojection_stage> spatial;        // options.spatial_reprojection
     std::unique_ptr<gbuffer_stage> gbuffer;
+    std::unique_ptr<taa_stage> taa;                             // options.taa
+    void* taa_input = nullptr;                                  // the tonemap stage's output when taa runs behind it (the stage writes `display`)
     trhip_gbuffer_targets destination_targets = {};             // the G-buffer of the viewports that are reprojected, shared by the slots
     size_t output_layers = 1;                                    // layers of `display` (every viewport; the path tracer renders opt.active_viewport_count)
     std::vector<uint8_t> last_cameras, current_cameras, uploaded_previous_cameras;   // denoiser: camera_data of the last frame rendered / of the scene as it is / camera_pair.previous on the device

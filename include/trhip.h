@@ -623,6 +623,62 @@ int trhip_temporal_reprojection_reset_history(trhip_temporal_reprojection* stage
 int trhip_temporal_reprojection_get_timings(trhip_temporal_reprojection* stage, trhip_reprojection_timings* out);
 int trhip_temporal_reprojection_download(trhip_temporal_reprojection* stage, int which, void* host, size_t bytes);
 
+/* ---- taa_stage (--taa=N; src/taa_stage.{hh,cc}, shader/taa.comp): temporal antialiasing behind the tonemap stage, the last stage of
+ * denoiser -> tonemap -> taa (src/post_processing_renderer.cc:79-106).  csrc/taa.hip, one kernel per frame; the order of operations is
+ * pinned in csrc/taa.h.  The hosts give every camera a sub-pixel jitter sequence (pan.zw of camera_data holds the frame's jitter); per
+ * output pixel p of layer z, with camera pair (cameras, previous cameras)[base_camera_index + z] of the device's scene as it is when the
+ * kernel runs:
+ *   1. col = src[p]; map(c) = c^gamma per rgb channel (exp2(gamma * log2(c)), c <= 0 -> 0), under anti_shimmer then c > 1e-5 ? log(c) : -10
+ *   2. the ranges of the mapped 3 x 3 window along the 11 axes of the reference's 22-DOP, widened by 1e-5
+ *   3. edge_dilation: the window pixel nearest to the camera (depth = dot(pos - origin, forward), strict <, x outer, y inner)
+ *   4. motion = screen_motion of that pixel; where it has no surface and the camera is perspective, the previous camera's projection of
+ *      the primary ray direction through the centre of p
+ *   5. motion += (previous.pan.zw - current.pan.zw) / 2; uv = (motion.x, 1 - motion.y) - offset / size; outside [0, 1 + 2 / size]:
+ *      dst = history = col
+ *   6. the history at uv through the reference's bicubic filter (Catmull-Rom, twelve clamped-to-edge texels), max(., 0)
+ *   7. map(history) is clipped towards map(col) onto the k-DOP, mixed with map(col) by alpha, unmapped; alpha passes through from src.
+ *      alpha is 1 on the first frame and after reset_history.
+ * Deviations from the reference: (1) the two history images are fp32 (fp16 there); (2) the depth comes from the pos
+ * target instead of a depth target; (3) "no surface" is instance_id < 0 (without instance_id: a NaN screen_motion, as in the shader, and
+ * every pixel has a depth); (4) a neighbour outside the image is skipped in the depth search (the reference clamps the depth read but then
+ * reads screen_motion out of bounds there); (5) the fraction of the bicubic filter's bilinear fetches is used as computed instead of
+ * going through a texture coordinate (which loses about 1e-4 of it at 1920 columns); (6) an orthographic miss keeps its written motion
+ * (the previous camera's projection of the ray origin; the reference's formula divides by w = 0 there); (7) the unused `rounding` push
+ * constant is dropped; (8) a NaN position counts as reprojected outside.  A NaN in one axis of the clip (0 * inf where a large colour
+ * absorbs the 1e-5) is dropped by fminf / fmaxf instead of deciding the clip. */
+typedef struct trhip_taa trhip_taa;
+typedef struct trhip_taa_options {
+    float alpha;                      /* weight of the new frame, in (0, 1]; the hosts pass 1 / sequence length */
+    float gamma;                      /* of the colour map; the hosts pass the tonemap stage's */
+    int32_t edge_dilation, anti_shimmer;
+    uint32_t base_camera_index;       /* layer z reads camera pair base_camera_index + z */
+    int32_t projection;               /* 0 perspective, 1 orthographic; 2 (equirectangular) is refused */
+} trhip_taa_options;
+typedef struct trhip_taa_images {
+    const void* src;                  /* RGBA32F display-space colour */
+    void* dst;                        /* RGBA32F; may equal src (then it is copied from the new history after the kernel), else must not overlap it */
+    const void* screen_motion;        /* RG32F */
+    const void* pos;                  /* RGBA32F, required with edge_dilation */
+    const void* instance_id;          /* R32I, may be NULL */
+} trhip_taa_images;
+typedef struct trhip_taa_timings {    /* the reference's timer, device ms of the last frame */
+    float total_ms;
+    uint32_t frames;                  /* frames run since the stage was created */
+    char name[64];                    /* "temporal antialiasing (N viewports)" */
+} trhip_taa_timings;
+/* Refuses width, height or layers of 0, alpha outside (0, 1] and projection 2. */
+int trhip_taa_create(trhip_device* dev, const trhip_taa_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_taa** out);
+void trhip_taa_destroy(trhip_taa* stage);
+/* One frame: one kernel between two events on `stream`, no synchronisation.  Frames of one stage form one history: run them in frame
+ * order on one stream (or on streams ordered with trhip_stream_wait). */
+int trhip_taa_run(trhip_taa* stage, const trhip_taa_images* images, void* stream);
+int trhip_taa_reset_history(trhip_taa* stage);   /* camera cut / new scene: the next frame passes through, like a new stage's first */
+int trhip_taa_get_timings(trhip_taa* stage, trhip_taa_timings* out);   /* waits for the last frame */
+#define TRHIP_TAA_HISTORY 0           /* RGBA32F [layers][h][w]: what the next frame will read */
+#define TRHIP_TAA_DECISIONS 1         /* uint8 [layers][h][w]: bits 0-3 the dilation offset as (x + 1) * 3 + (y + 1), bit 4 reprojected outside
+                                         (passed through), bit 5 no surface */
+int trhip_taa_download(trhip_taa* stage, int which, void* host, size_t bytes);   /* synchronises the device */
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,26 @@ REPROJ_NONE, REPROJ_REPROJECTED, REPROJ_SKY_COPY = 0, 1, 2
 REPROJECTION_RECORD = [("kind", "u1"), ("slot", "u1"), ("bits", "u1"), ("zero", "u1"), ("ox", "<i2"), ("oy", "<i2")]
 
 
+class TaaOptionsC(C.Structure):
+    """trhip_taa_options."""
+    _fields_ = [("alpha", C.c_float), ("gamma", C.c_float), ("edge_dilation", C.c_int32), ("anti_shimmer", C.c_int32),
+                ("base_camera_index", C.c_uint32), ("projection", C.c_int32)]
+
+
+class TaaImagesC(C.Structure):
+    """trhip_taa_images."""
+    _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "screen_motion", "pos", "instance_id")]
+
+
+class TaaTimingsC(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("frames", C.c_uint32), ("name", C.c_char * 64)]
+
+
+# trhip_taa_download; the bits of a decision byte
+TAA_HISTORY, TAA_DECISIONS = 0, 1
+TAA_DECISION_OFFSET_MASK, TAA_DECISION_OUTSIDE, TAA_DECISION_NO_SURFACE = 0x0F, 0x10, 0x20
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -264,6 +284,12 @@ SYMBOLS = {
     "trhip_temporal_reprojection_reset_history": (_i, [_vp]),
     "trhip_temporal_reprojection_get_timings": (_i, [_vp, C.POINTER(ReprojectionTimingsC)]),
     "trhip_temporal_reprojection_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_taa_create": (_i, [_vp, C.POINTER(TaaOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),
+    "trhip_taa_destroy": (None, [_vp]),
+    "trhip_taa_run": (_i, [_vp, C.POINTER(TaaImagesC), _vp]),
+    "trhip_taa_reset_history": (_i, [_vp]),
+    "trhip_taa_get_timings": (_i, [_vp, C.POINTER(TaaTimingsC)]),
+    "trhip_taa_download": (_i, [_vp, _i, _vp, C.c_size_t]),
 }
 
 _LIB = None

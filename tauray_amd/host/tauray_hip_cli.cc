@@ -10,6 +10,7 @@
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
 //              [--renderer=path-tracer|direct] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
+//              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
 //              [--camera-grid=w,h,x,y --camera-recentering-distance=5 --camera-grid-roll=0]   (light-field grid, one file per view)
 //
 // One process per GPU (include/tauray_hip_comm.hh): start N copies with --process-count=N --process-rank=0..N-1 --device=<HIP index>
@@ -43,6 +44,9 @@ static const char* const usage_text =
     "  --spatial-reprojection=i,j,...   sparse light field: only the listed viewports of --camera-grid are path traced, the others are\n"
     "                         filled from them through the G-buffer (one file per view, in natural view order; one device, no denoiser)\n"
     "  --temporal-reprojection=r        blend the previous frame, found through screen motion, into the path-traced views: r in (0, 1)\n"
+    "  --taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]   temporal antialiasing behind the tonemap stage: the cameras step through a\n"
+    "                         jitter sequence of N sub-pixel offsets, every frame is blended into a history with weight 1 / N (edge\n"
+    "                         dilation on, anti-shimmer off by default; one device; works with --animation, --headless, --denoiser=bmfr)\n"
     "  --tonemap=filmic|linear|gamma-correction|reinhard|reinhard-luminance --exposure=E --gamma=G\n"
     "  --animation[=NAME] --framerate=F --accumulation --envmap=FILE --camera-grid=w,h,x,y -t --skip-nan-check\n"
     "  --fake-devices=N | --devices=0,1,... --distribution-strategy=scanline|shuffled-strips --frames-in-flight=N --frames-per-launch=N\n"
@@ -109,6 +113,28 @@ int main(int argc, char** argv)
             {
                 opt.temporal_reprojection = std::stof(val("--temporal-reprojection="));
                 if(!(opt.temporal_reprojection >= 0.0f) || !(opt.temporal_reprojection < 1.0f)) throw std::runtime_error("--temporal-reprojection=r: the ratio must be in [0, 1) (0 = off)");
+            }
+            else if(starts(a, "--taa="))
+            {   // --taa (src/options.hh:406-411): sequence_length, edge_dilation = true, anti_shimmer = false
+                std::stringstream ss(val("--taa=")); std::string tok;
+                rt_renderer::options::taa_options t;
+                bool first = true;
+                auto on_off = [&](const std::string& v) { if(v == "on" || v == "true" || v == "1") return true; if(v == "off" || v == "false" || v == "0") return false;
+                                                          throw std::runtime_error("--taa: " + v + " is neither on nor off"); };
+                while(std::getline(ss, tok, ','))
+                {
+                    if(first)
+                    {
+                        if(tok.empty() || tok.find_first_not_of("0123456789") != std::string::npos || std::stoul(tok) < 1) throw std::runtime_error("--taa=N: the length of the jitter sequence, not " + tok);
+                        t.sequence_length = (int)std::stoul(tok);
+                        first = false;
+                    }
+                    else if(starts(tok, "edge-dilation=")) t.edge_dilation = on_off(tok.substr(14));
+                    else if(starts(tok, "anti-shimmer=")) t.anti_shimmer = on_off(tok.substr(13));
+                    else throw std::runtime_error("--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off], not " + tok);
+                }
+                if(first) throw std::runtime_error("--taa=N: the length of the jitter sequence is missing");
+                opt.taa = t;
             }
             else if(a == "--skip-nan-check") hopt.skip_nan_check = true;     // headless::options::skip_nan_check (src/headless.hh:74); with --filetype=none: no readback at all
             else if(a == "--accumulation") opt.accumulate = true;
@@ -296,6 +322,18 @@ int main(int argc, char** argv)
             // a viewport that nothing reprojects to holds NaN (src/tauray.cc:301-305)
             if(!opt.spatial_reprojection.empty()) hopt.skip_nan_check = true;
         }
+        if(opt.taa)
+        {   // what rt_renderer refuses, said before a device is touched
+            if(devices.size() > 1 || process_count > 0 || shard_views)
+                throw std::runtime_error("--taa with several devices or processes: the stage reads screen motion, pos and instance id of whole viewports on one device, "
+                                         "gathering them from several is not built; use one device");
+            if(opt.accumulate) throw std::runtime_error("--taa blends a fresh, jittered frame into its history: no --accumulation");
+            if(frames_per_launch > 1) throw std::runtime_error("--taa: an antialiased frame is one frame (the jitter steps between frames), --frames-per-launch must be 1");
+            if(!opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f) throw std::runtime_error("--taa together with spatial / temporal reprojection: a chain of reprojection and taa is not built");
+            if(opt.projection == 2) throw std::runtime_error("--taa with equirectangular cameras is not built");
+            if(renderer != "path-tracer") throw std::runtime_error("--taa reads the path tracer's screen_motion target: --renderer=path-tracer");
+            set_camera_jitter(scene, gltf_detail::get_camera_jitter_sequence(opt.taa->sequence_length, size.x, size.y));      // src/tauray.cc:816
+        }
         hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
         if(shard_views)
         {   // view shards: viewport v belongs to rank v mod N; every rank renders, tonemaps and saves its own
@@ -360,7 +398,7 @@ int main(int argc, char** argv)
             if(workloads.size() != rr.per_device.size()) throw std::runtime_error("--device-workloads needs one ratio per device");
             rr.set_device_workloads(workloads);
         }
-        if((frames_in_flight > 1 || frames_per_launch > 1) && !animated)
+        if((frames_in_flight > 1 || frames_per_launch > 1) && !animated && !opt.taa)
         {   // frame f renders while the frames before it are read back, compressed and written (the reference overlaps
             // its save workers with the next frames the same way, src/headless.cc:349-422); with --frames-per-launch=B a slot
             // holds B consecutive frames, frame-major in its display image
@@ -405,8 +443,10 @@ int main(int argc, char** argv)
                 if(!frames_given && !animator.is_playing()) break;
                 animator.update(f == 0 ? 0 : update_dt);
                 if(!frames_given && !animator.is_playing()) break;
+                if(opt.taa) step_camera_jitter(scene);      // scene::update steps the jitter with the animation (src/scene.cc:228)
                 rr.update_scene(scene, f % 3 == 2);      // an acceleration-structure update, every third frame a fast rebuild
             }
+            else if(opt.taa) { step_camera_jitter(scene); rr.update_cameras(scene); }
             auto t0 = std::chrono::high_resolution_clock::now();
             rr.reset_accumulation();                   // offline frames: accumulation reset, sample counter kept (src/tauray.cc:1101)
             rr.render();
@@ -428,6 +468,7 @@ int main(int argc, char** argv)
         if(renderer == "direct")
         {
             if(opt.bmfr) throw std::runtime_error("--denoiser=bmfr reads the path tracer's demodulated diffuse target: --renderer=path-tracer");
+            if(opt.taa) throw std::runtime_error("--taa reads the path tracer's screen_motion target: --renderer=path-tracer");
             direct_renderer::options dopt;
             static_cast<path_tracer_stage::options&>(dopt) = opt;
             dopt.tonemap = opt.tonemap; dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;

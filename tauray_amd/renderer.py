@@ -924,6 +924,71 @@ class TemporalReprojectionStage:
             pass
 
 
+class TaaStage:
+    """taa_stage (src/taa_stage.{hh,cc}): temporal antialiasing behind the tonemap stage (trhip_taa_*, include/trhip.h).  The stage keeps
+    its two history images itself and reads the scene's cameras and previous cameras (with their jitter in pan.zw) on the device.
+    `options`: alpha (weight of the new frame, 1 / sequence length), gamma (the tonemap stage's), edge_dilation, anti_shimmer,
+    base_camera_index, projection."""
+
+    IMAGES = ("src", "dst", "screen_motion", "pos", "instance_id")
+    DEFAULTS = dict(alpha=0.125, gamma=2.2, edge_dilation=True, anti_shimmer=False, base_camera_index=0, projection=0)
+
+    def __init__(self, ctx: Context, size, layers=1, options: Optional[dict] = None):
+        unknown = set(options or {}) - set(self.DEFAULTS)
+        if unknown:
+            raise ValueError(f"TaaStage: not an option of the stage: {sorted(unknown)}")
+        self.options = dict(self.DEFAULTS, **(options or {}))
+        self.ctx, self.size, self.layers = ctx, (int(size[0]), int(size[1])), int(layers)
+        self.h = None
+        o = self.options
+        opt = _lib.TaaOptionsC(float(o["alpha"]), float(o["gamma"]), int(bool(o["edge_dilation"])), int(bool(o["anti_shimmer"])),
+                               int(o["base_camera_index"]), int(o["projection"]))
+        h = C.c_void_p()
+        check(_lib.lib().trhip_taa_create(getattr(ctx, "h", None), C.byref(opt), max(self.size[0], 0), max(self.size[1], 0), max(self.layers, 0), C.byref(h)))
+        self.h = h.value
+
+    def run(self, images: dict, stream=None):
+        """stage::run: images["dst"] = this frame's images["src"] blended into the stage's history (dst may be src)."""
+        unknown = set(images) - set(self.IMAGES)
+        if unknown:
+            raise ValueError(f"TaaStage: not an image the stage reads: {sorted(unknown)}")
+        f = _lib.TaaImagesC()
+        for name, buf in images.items():
+            setattr(f, name, None if buf is None else _ptr(buf))
+        check(_lib.lib().trhip_taa_run(self.h, C.byref(f), stream))
+
+    def reset_history(self):
+        check(_lib.lib().trhip_taa_reset_history(self.h))
+
+    def timings(self) -> dict:
+        """The reference's timer: its name, device ms of the last frame, frames run."""
+        t = _lib.TaaTimingsC()
+        check(_lib.lib().trhip_taa_get_timings(self.h, C.byref(t)))
+        return {"name": t.name.decode(), "total_ms": float(t.total_ms), "frames": int(t.frames)}
+
+    def download(self, name: str) -> np.ndarray:
+        """"history": RGBA32F, what the next frame will read; "decisions": the decision byte per pixel (test hooks)."""
+        if name == "history":
+            code, out = _lib.TAA_HISTORY, np.empty((self.layers, self.size[1], self.size[0], 4), np.float32)
+        elif name == "decisions":
+            code, out = _lib.TAA_DECISIONS, np.empty((self.layers, self.size[1], self.size[0]), np.uint8)
+        else:
+            raise KeyError(name)
+        check(_lib.lib().trhip_taa_download(self.h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().trhip_taa_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _FrameSlot:
     """What one frame in flight owns: its stage (path buffers, counters), its images and the stream it is ordered on."""
 
@@ -959,7 +1024,8 @@ class RtRenderer:
     def __init__(self, ctx: Context, scene: SceneDesc, options: PtOptionsC, size, strategy=DISTRIBUTION_SCANLINE,
                  rank=0, world_size=1, viewports=1, tonemap: Optional[dict] = None, accumulate=False, use_torch=None,
                  shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None,
-                 denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY, spatial_reprojection=None, temporal_reprojection=0.0):
+                 denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY, spatial_reprojection=None, temporal_reprojection=0.0,
+                 taa=0, taa_edge_dilation=True, taa_anti_shimmer=False):
         """`shard`: what the ranks divide among themselves - "pixels" (the reference's distribution strategies, partial frames
         stitched on rank 0), "views" (viewport v on rank v mod N; nothing is exchanged before output) or "samples" (every
         rank renders samples_per_pixel / N samples of every pixel; one reduce to rank 0).  SURVEY.md section 8(e).
@@ -980,7 +1046,13 @@ class RtRenderer:
         G-buffer pass and are filled by SpatialReprojectionStage.  color / display then hold every viewport in natural order, the fused
         tonemap is off, and with `accumulate` the sources are the accumulators and the full image is rewritten every frame.
         `temporal_reprojection`: 0, or the ratio of TemporalReprojectionStage (--temporal-reprojection=r), which runs on the path-traced layers
-        in front of the spatial stage; its history is one chain in frame order, like the denoiser's."""
+        in front of the spatial stage; its history is one chain in frame order, like the denoiser's.
+        `taa`: 0, or the length N of the camera jitter sequence of temporal antialiasing (the reference's --taa=N): every camera of the scene
+        gets the Halton sequence of get_camera_jitter_sequence(N, size) and steps it once per frame before it is packed
+        (scene::update), the path tracer renders screen_motion, pos and instance_id next to the colour target, and TaaStage (alpha =
+        1 / N, gamma = the tonemap stage's; `taa_edge_dilation`, `taa_anti_shimmer`: the reference's defaults) runs after the tonemap
+        stage, in frame order on the default stream like the denoiser's history chain; the fused tonemap is off.  Every frame is a
+        fresh frame.  With denoiser="bmfr" or without."""
         if shard not in ("pixels", "views", "samples"):
             raise ValueError("shard must be pixels, views or samples")
         if denoiser not in (None, "none", "bmfr"):
@@ -1011,6 +1083,26 @@ class RtRenderer:
                 raise ValueError(f"{which}: a reprojected frame is one frame: frames_per_launch must be 1")
             if temporal_reprojection > 0.0 and accumulate:
                 raise ValueError("temporal_reprojection blends the previous frame into a fresh frame: accumulate must be False")
+        taa = int(taa or 0)
+        if taa < 0:
+            raise ValueError(f"taa {taa!r}: the length of the jitter sequence must be positive (0 = off)")
+        if taa:
+            if world_size > 1 and shard != "views":
+                raise ValueError(f"taa with a {shard} distribution of count {world_size} > 1: the stage reads screen motion, pos and instance id of whole "
+                                 "viewports on one device, gathering them from several is not built; use one device or shard=\"views\"")
+            if world_size > 1 and shard == "views" and max(viewports - rank + world_size - 1, 0) // world_size > 1:
+                raise ValueError("taa with shard=\"views\": more than one viewport per device is not built (the stage reads consecutive cameras)")
+            if accumulate:
+                raise ValueError("taa blends a fresh, jittered frame into its history: accumulate must be False")
+            if frames_per_launch > 1:
+                raise ValueError("taa: an antialiased frame is one frame (the jitter steps between frames): frames_per_launch must be 1")
+            if spatial_reprojection is not None or temporal_reprojection > 0.0:
+                raise ValueError("taa together with spatial_reprojection / temporal_reprojection: a chain of reprojection and taa is not built")
+            if options.projection == 2:
+                raise ValueError("taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
+                                 "which an equirectangular camera does not have")
+            if stage_cls is not None and stage_cls is not PathTracerStage:
+                raise ValueError("taa reads the path tracer's screen_motion target: stage_cls must be PathTracerStage")
         if frames_in_flight < 1:
             raise ValueError("frames_in_flight must be >= 1")
         if frames_in_flight > 1 and accumulate:
@@ -1078,7 +1170,20 @@ class RtRenderer:
             self.gbuffer = GbufferStage(ctx, self.scene_update, self.size, options.projection, options.min_ray_dist)
             self.destination_targets = self.gbuffer.alloc_targets(len(self.spatial.destinations))
         reprojection = self.spatial is not None or self.temporal is not None
-        self.fused_tonemap = (world_size == 1 and denoiser is None and not reprojection and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
+        self.taa = self.taa_input = None
+        self.taa_length = taa
+        if taa and viewports > 0:
+            from .scene import get_camera_jitter_sequence
+            seq = get_camera_jitter_sequence(taa, self.size)
+            for cam in scene.cameras:
+                cam.set_jitter(seq)
+            self.scene_update.update_cameras(scene.cameras)
+            base = rank if self.shard == "views" else 0       # a view shard's stage reads its first camera; TaaStage strides by one
+            self.taa = TaaStage(ctx, self.size, viewports, dict(alpha=1.0 / taa, gamma=self.tonemap.info.gamma, edge_dilation=taa_edge_dilation,
+                                                                anti_shimmer=taa_anti_shimmer, base_camera_index=base, projection=options.projection))
+            self.taa_input = self._alloc_display(viewports)     # the tonemap stage's output; the stage writes the display image
+            self._last_cameras = self.scene_update.camera_data.copy()      # the first frame's camera_pair.previous: the cameras before their first step
+        self.fused_tonemap = (world_size == 1 and denoiser is None and not reprojection and not taa and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
                               and hasattr(_lib.lib(), "trhip_pt_set_fused_tonemap") and os.environ.get("TRHIP_FUSED_TONEMAP", "1") != "0")
         self.slots = []
         for k in range(frames_in_flight):
@@ -1105,8 +1210,9 @@ class RtRenderer:
             if self.bmfr is not None:
                 slot.features = {n: ctx.alloc(viewports * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero()
                                  for n in BmfrStage.FEATURES if n != "color"}
-            elif reprojection:
-                names = ("normal", "pos", "instance_id") + (("screen_motion",) if self.temporal is not None else ())
+            elif reprojection or self.taa is not None:
+                names = ("screen_motion", "pos", "instance_id") if self.taa is not None else \
+                        ("normal", "pos", "instance_id") + (("screen_motion",) if self.temporal is not None else ())
                 slot.features = {n: ctx.alloc(max(viewports, 1) * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero() for n in names}
             if self.spatial is not None:
                 slot.full = self._alloc_color(self.output_viewports, tw, th)
@@ -1166,6 +1272,14 @@ class RtRenderer:
         if self.temporal is not None:
             self.temporal.reset_history()
             self._last_cameras = None
+        if self.taa is not None:
+            from .scene import get_camera_jitter_sequence
+            seq = get_camera_jitter_sequence(self.taa_length, self.size)
+            for cam in scene.cameras:
+                cam.set_jitter(seq)
+            self.scene_update.update_cameras(scene.cameras)
+            self.taa.reset_history()
+            self._last_cameras = self.scene_update.camera_data.copy()
 
     def program(self) -> dict:
         """The shading program of this rank's stage (PathTracerStage.program)."""
@@ -1308,7 +1422,15 @@ class RtRenderer:
         slot.frame = self.frame_index
         self.frame_index += self.frames_per_launch
         if self.viewports > 0:      # a view shard can be empty (more devices than views)
-            if self.bmfr is not None or self.temporal is not None:
+            if self.taa is not None:
+                # scene::update (src/scene.cc:228): every camera steps its jitter before it is packed
+                if self.frames_in_flight > 1:
+                    self.sync()
+                cams = self.scene_update.scene.cameras
+                for cam in cams:
+                    cam.step_jitter()
+                self.scene_update.update_cameras(cams)
+            if self.bmfr is not None or self.temporal is not None or self.taa is not None:
                 cameras = self.scene_update.camera_data
                 prev = cameras if self._last_cameras is None else self._last_cameras
                 on_device = self.scene_update.previous_camera_data
@@ -1350,7 +1472,7 @@ class RtRenderer:
         self.render_partial(tonemap=tonemap)
         slot = self.current
         if self.world_size == 1:
-            if self.bmfr is not None or self.temporal is not None or self.spatial is not None:
+            if self.bmfr is not None or self.temporal is not None or self.spatial is not None or self.taa is not None:
                 # the denoiser's / temporal stage's history is one chain over the frames of all slots: it runs on the default stream, in frame
                 # order (and so does the spatial stage, whose destination G-buffer the slots share)
                 if slot.stream is not None:
@@ -1410,7 +1532,11 @@ class RtRenderer:
             return
         if slot.display is None:
             slot.display = self._alloc_display(self.output_viewports)
-        self.tonemap.run(slot.full if self.spatial is not None else slot.color, slot.display, w, h, self.output_viewports, stream)
+        self.tonemap.run(slot.full if self.spatial is not None else slot.color, slot.display if self.taa is None else self.taa_input, w, h,
+                         self.output_viewports, stream)
+        if self.taa is not None:
+            self.taa.run(dict(src=self.taa_input, dst=slot.display, screen_motion=slot.features["screen_motion"], pos=slot.features["pos"],
+                              instance_id=slot.features["instance_id"]), stream)
 
     def download(self, which="color") -> np.ndarray:
         """The most recent frame's partial colour target or tonemapped display image."""
@@ -1429,7 +1555,10 @@ class RtRenderer:
         if not self.slots:
             return
         self.sync()
-        for stage in (self.bmfr, self.temporal, self.spatial):
+        if self.taa is not None and self.scene_update.scene is not None:
+            for cam in self.scene_update.scene.cameras:      # the caller's cameras get their jitter from this renderer: it goes with it
+                cam.set_jitter([])
+        for stage in (self.bmfr, self.temporal, self.spatial, self.taa):
             if stage is not None:
                 stage.close()
         for slot in self.slots:

@@ -110,6 +110,20 @@ def perspective_matrix(fov_deg, aspect, near, far):
     return m
 
 
+def perspective_matrix_inverse(p):
+    """The inverse of [[a, 0, px, 0], [0, b, py, 0], [0, 0, c, d], [0, 0, -1, 0]] (perspective_matrix with a pan), in closed form."""
+    a, b, px, py, c, d = p[0, 0], p[1, 1], p[0, 2], p[1, 2], p[2, 2], p[2, 3]
+    m = np.zeros((4, 4))
+    m[0, 0] = 1.0 / a
+    m[1, 1] = 1.0 / b
+    m[0, 3] = px / a
+    m[1, 3] = py / b
+    m[2, 3] = -1.0
+    m[3, 2] = 1.0 / d
+    m[3, 3] = c / d
+    return m
+
+
 def ortho_matrix(l, r, b, t, n, f):
     m = np.eye(4)
     m[0, 0] = 2 / (r - l); m[1, 1] = 2 / (t - b); m[2, 2] = -2 / (f - n)
@@ -130,6 +144,21 @@ class Camera:
     focus: tuple = (1.0, 0.0, 0.0, 0.0)     # dof_params
     ortho: tuple = (-1, 1, -1, 1, 0, 100)   # l r b t n f
     equirect_fov: tuple = (360.0, 180.0)
+    jitter_sequence: tuple = ()             # camera::set_jitter: sub-pixel offsets of the projection, one per frame (perspective only)
+    jitter_index: int = 0
+
+    def set_jitter(self, seq):
+        """camera::set_jitter (src/camera.cc:480-484): the sequence step_jitter walks; an empty one turns jitter off."""
+        self.jitter_sequence = tuple((float(np.float32(x)), float(np.float32(y))) for x, y in seq)      # vec2: float32 values
+        self.jitter_index = 0
+
+    def step_jitter(self):
+        """camera::step_jitter (src/camera.cc:486-493): once per frame, before the camera is packed."""
+        if self.jitter_sequence:
+            self.jitter_index = (self.jitter_index + 1) % len(self.jitter_sequence)
+
+    def get_jitter(self):
+        return self.jitter_sequence[self.jitter_index] if self.jitter_sequence else (0.0, 0.0)
 
     def set_aspect(self, aspect):
         # src/camera.cc:166-186
@@ -154,6 +183,10 @@ class Camera:
             p = perspective_matrix(self.fov, self.aspect, self.near, self.far)
             p[0, 2] = self.fov_offset[0]
             p[1, 2] = self.fov_offset[1]
+            if self.jitter_sequence:        # src/camera.cc:377-381
+                j = self.get_jitter()
+                p[0, 2] += j[0]
+                p[1, 2] += j[1]
             return p
         if self.projection == PROJ_ORTHOGRAPHIC:
             return ortho_matrix(*self.ortho)
@@ -192,11 +225,35 @@ class Camera:
             return out
         proj = self.projection_matrix()
         out["view_proj"][0] = to_glm(proj @ view)
-        out["proj_inverse"][0] = to_glm(np.linalg.inv(proj))
+        jittered = bool(self.jitter_sequence) and self.projection == PROJ_PERSPECTIVE
+        # a jittered projection is inverted in closed form, operation for operation as the C++ host does it: both hosts then pack the same bytes
+        out["proj_inverse"][0] = to_glm(perspective_matrix_inverse(proj) if jittered else np.linalg.inv(proj))
         out["dof_params"][0] = self.focus if self.projection == PROJ_PERSPECTIVE else (0, 0, 0, 0)
         out["projection_info"][0] = self.projection_info()
         out["pan"][0] = (self.fov_offset[0], self.fov_offset[1], 0, 0) if self.projection == PROJ_PERSPECTIVE else (0, 0, 0, 0)
+        if self.jitter_sequence and self.projection == PROJ_PERSPECTIVE:      # src/camera.cc:454-461 (perspective only: camera::refresh jitters no other matrix)
+            j = np.array(self.get_jitter() * 2, dtype=np.float32)
+            out["pan"][0] = out["pan"][0] + j
         return out
+
+
+def halton(index: int, base: int) -> float:
+    """halton (src/math.cc:293-305), in float32 like the reference."""
+    f, r = np.float32(1.0), np.float32(0.0)
+    while index > 0:
+        f = np.float32(f / np.float32(base))
+        r = np.float32(r + f * np.float32(index % base))
+        index //= base
+    return float(r)
+
+
+def get_camera_jitter_sequence(length: int, size) -> list:
+    """get_camera_jitter_sequence (src/math.cc:307-328): Halton points 1..length in bases 2 and 3, mapped to (v * 2 - 1) / resolution."""
+    out = []
+    for i in range(int(length)):
+        v = (np.float32(halton(i + 1, 2)), np.float32(halton(i + 1, 3)))
+        out.append(tuple(float((np.float32(c) * np.float32(2.0) - np.float32(1.0)) / np.float32(r)) for c, r in zip(v, size)))
+    return out
 
 
 def generate_camera_grid(cam: Camera, grid_w: int, grid_h: int, dx: float, dy: float,
