@@ -247,6 +247,7 @@ struct gltf_camera
     // camera::set_jitter / step_jitter / get_jitter (src/camera.cc:480-498): sub-pixel offsets of a perspective projection, one per frame
     std::vector<std::array<float, 2>> jitter_sequence;
     unsigned jitter_index = 0;
+    bool closed_form_inverse = false;      // looking_glass_cameras: proj_inverse in closed form, jittered or not (the bytes of the Python host)
     void set_jitter(const std::vector<std::array<float, 2>>& seq) { jitter_sequence = seq; jitter_index = 0; }
     void step_jitter() { if(!jitter_sequence.empty()) jitter_index = (jitter_index + 1) % (unsigned)jitter_sequence.size(); }
     std::array<float, 2> get_jitter() const { return jitter_sequence.empty() ? std::array<float, 2>{0.0f, 0.0f} : jitter_sequence[jitter_index]; }
@@ -310,7 +311,7 @@ inline camera_data pack_camera(gltf_camera& c, double aspect)
     to_glm(view, cd.view);
     to_glm(c.transform, cd.view_inverse);
     to_glm(mul(proj, view), cd.view_proj);
-    if(c.perspective && !c.jitter_sequence.empty())
+    if(c.perspective && (!c.jitter_sequence.empty() || c.closed_form_inverse))
     {   // a jittered projection [[a, 0, px, 0], [0, b, py, 0], [0, 0, c, d], [0, 0, -1, 0]] is inverted in closed form, operation for operation
         // as the Python host does it: both hosts then pack the same bytes
         mat4d inv{};
@@ -680,6 +681,8 @@ struct gltf_animation
     std::vector<int> roots;
     std::map<int, std::map<std::string, clip>> clips;     // node -> animation_pool (std::map: alphabetical)
     std::vector<gltf_detail::gltf_camera> cameras;
+    std::vector<gltf_detail::mat4d> camera_rig;     // looking_glass_cameras: the views' transforms under the first camera's node (empty: no rig)
+    gltf_detail::mat4d camera_rig_frame = gltf_detail::mat4d::identity();      // ... and that node's global transform, the rig's reference frame
     std::vector<skin> skins;
     double aspect = 1.0;
 };
@@ -1125,6 +1128,73 @@ inline uint32_t generate_cameras(scene_data& s, int grid_w, int grid_h, double d
 }
 
 //---------------------------------------------------------------------------------------------------------------------
+// The Looking Glass output (`--display=looking-glass`, src/looking_glass.{hh,cc}) without the device: the panel's calibration as
+// `--lkg-calibration` gives it (options::calibration_data; src/looking_glass.cc:216-242) and the camera rig of looking_glass::setup_cameras
+// (src/looking_glass.cc:62-88).  The values are the float numbers the command line holds; corrected_pitch and tilt are evaluated at double
+// from them and rounded to float once, like everything of the rig: the Python host (tauray_amd/looking_glass.py) does the same operations
+// in the same order, so both hosts pack the same bytes.
+struct looking_glass_calibration
+{
+    float pitch = 0, slope = 1, center = 0, view_cone = 0;
+    bool invert = false;
+    float dpi = 1;
+    uint32_t screen_w = 1, screen_h = 1;
+    float corrected_pitch() const { return (float)((double)screen_w / (double)dpi * (double)pitch * std::sin(std::atan(std::fabs((double)slope)))); }
+    float tilt() const { return (float)((double)screen_h / ((double)screen_w * (double)slope)); }
+    void check() const
+    {
+        if(screen_w < 1 || screen_h < 1) throw std::runtime_error("looking_glass_calibration: the screen size must be positive");
+        if(!(dpi > 0.0f) || slope == 0.0f || !std::isfinite(pitch) || !std::isfinite(slope) || !std::isfinite(center) || !std::isfinite(view_cone) || !std::isfinite(dpi))
+            throw std::runtime_error("looking_glass_calibration: DPI must be positive, the slope non-zero and every value finite");
+    }
+};
+
+// Replaces scene_data::cameras by the rig: `viewports` panned perspective cameras (vfov = 2 atan(1 / (2 relative_dist)), aspect = the
+// panel's, near 0.01, far 300) under the reference frame, which is the scene's first camera; the rig follows the animation of that
+// camera's node (gltf_animation::camera_rig, scene_animator::update).  Returns the number of viewports.  For scenes load_glb made.
+inline uint32_t looking_glass_cameras(scene_data& s, uint32_t viewports, double midplane, double depthiness, double relative_dist, const looking_glass_calibration& cal)
+{
+    using namespace gltf_detail;
+    if(!s.animation || s.animation->cameras.empty()) throw std::runtime_error("looking_glass_cameras: the scene has no camera to hang the rig on");
+    if(viewports < 1) throw std::runtime_error("looking_glass_cameras: the rig needs at least one view");
+    cal.check();
+    constexpr double PI = 3.14159265358979323846;
+    constexpr double rig_near = 0.01, rig_far = 300.0;
+    // a scene that already carries a rig keeps its reference frame
+    const mat4d frame = s.animation->camera_rig.empty() ? s.animation->cameras[0].transform : s.animation->camera_rig_frame;
+    const double vfov = 2.0 * std::atan(1.0 / (2.0 * relative_dist)) * 180.0 / PI;
+    const double aspect = (double)cal.screen_w / (double)cal.screen_h;
+    std::vector<gltf_camera> rig;
+    std::vector<mat4d> locals;
+    std::vector<camera_data> packed;
+    for(uint32_t i = 0; i < viewports; ++i)
+    {
+        const double offset = (((double)i + 0.5) / (double)viewports) * 2.0 - 1.0;
+        const double angle = offset * (double)cal.view_cone * depthiness;
+        const double pan = -std::tan(angle * (PI / 180.0));
+        // dir = P * (0, 0, 1, 1) with P the panned projection: (pan, 0, P[2][2] + P[2][3], -1); dir /= dir.z
+        const double zc = -(rig_far + rig_near) / (rig_far - rig_near) + -(2.0 * rig_far * rig_near) / (rig_far - rig_near);
+        gltf_camera cam{};
+        cam.perspective = true; cam.fov = vfov; cam.aspect = aspect; cam.near = rig_near; cam.far = rig_far;
+        cam.pan[0] = pan; cam.pan[1] = 0.0;
+        cam.closed_form_inverse = true;
+        mat4d local = mat4d::identity();
+        local.m[0][3] = midplane * (pan / zc); local.m[1][3] = midplane * (0.0 / zc); local.m[2][3] = midplane * 1.0;
+        cam.transform = mul(frame, local);
+        packed.push_back(pack_camera(cam, aspect));
+        rig.push_back(cam);
+        locals.push_back(local);
+    }
+    s.animation->cameras = rig;
+    s.animation->camera_rig = locals; s.animation->camera_rig_frame = frame;
+    s.animation->aspect = aspect;
+    s.cameras.resize(packed.size() * sizeof(camera_data));
+    std::memcpy(s.cameras.data(), packed.data(), s.cameras.size());
+    s.previous_cameras.clear();
+    return viewports;
+}
+
+//---------------------------------------------------------------------------------------------------------------------
 // set_camera_jitter (src/scene.cc:14-18) and the jitter step of update(scene, dt) (src/scene.cc:228) for scenes load_glb made: every
 // camera gets the sequence / steps it, and scene_data::cameras is packed again (scene_animator::update packs with the cameras' jitter too).
 inline void repack_cameras(scene_data& s)
@@ -1217,7 +1287,15 @@ public:
             const mat4d glob = mul(parent, node.local());
             globals[n] = glob;
             for(uint32_t i: node.instances) { to_glm(glob, inst[i].model); to_glm(transpose(inverse(glob)), inst[i].model_normal); }
-            for(uint32_t ci: node.cameras) anim->cameras[ci].transform = glob;
+            for(uint32_t ci: node.cameras)
+            {
+                if(anim->camera_rig.empty()) anim->cameras[ci].transform = glob;
+                else if(ci == 0)      // a Looking Glass rig hangs under the first camera's frame and replaces every camera of the file
+                {
+                    anim->camera_rig_frame = glob;
+                    for(size_t v = 0; v < anim->camera_rig.size() && v < anim->cameras.size(); ++v) anim->cameras[v].transform = mul(glob, anim->camera_rig[v]);
+                }
+            }
             for(const gltf_animation::node::light& l: node.lights)
             {   // get_global_direction / get_global_position as in load_glb; colours, radii and cone angles do not move
                 double coln[3], direction[3];

@@ -636,6 +636,42 @@ public:
     trhip_taa* h = nullptr;
 };
 
+// looking_glass_composition_stage (src/looking_glass_composition_stage.{hh,cc}): the last stage of a light-field chain (trhip_lkg_*): the
+// views of `src` (RGBA32F [views][view_size.y][view_size.x], display space) are interleaved, sub-pixel by sub-pixel, into the one image of
+// `output_size` a lenticular panel shows - as RGBA32F and / or as the reference's 8 bits.  pitch, tilt and center are the reference's
+// corrected_pitch, tilt and center (looking_glass_calibration of tauray_gltf.hh computes them).  The stage has no history.
+class looking_glass_composition_stage
+{
+public:
+    struct options
+    {
+        uint32_t viewport_count = 48;       // 1..255
+        float pitch = 0.0f, tilt = 0.0f, center = 0.0f;
+        bool invert = false;
+        bool record_view_indices = false;   // keep the view of every sub-pixel for download_view_indices (a test hook)
+    };
+    looking_glass_composition_stage(device& dev, uvec2 view_size, uvec2 output_size, const options& opt): dev(&dev), view_size(view_size), output_size(output_size), opt(opt)
+    {
+        const trhip_lkg_options o = {opt.viewport_count, opt.pitch, opt.tilt, opt.center, opt.invert ? 1 : 0, opt.record_view_indices ? 1 : 0};
+        check(trhip_lkg_create(dev.h, &o, view_size.x, view_size.y, output_size.x, output_size.y, &h));
+    }
+    looking_glass_composition_stage(const looking_glass_composition_stage&) = delete;
+    ~looking_glass_composition_stage() { trhip_lkg_destroy(h); }
+    void run(const void* src, void* dst, void* dst_rgba8 = nullptr, void* stream = nullptr) { check(trhip_lkg_run(h, src, dst, dst_rgba8, stream)); }
+    trhip_lkg_timings get_timings() { trhip_lkg_timings t; check(trhip_lkg_get_timings(h, &t)); return t; }
+    std::vector<uint8_t> download_view_indices()
+    {
+        std::vector<uint8_t> out(size_t(output_size.x) * output_size.y * 4);
+        check(trhip_lkg_download(h, TRHIP_LKG_VIEW_INDICES, out.data(), out.size()));
+        return out;
+    }
+
+    device* dev;
+    uvec2 view_size, output_size;
+    options opt;
+    trhip_lkg* h = nullptr;
+};
+
 class load_balancer
 {
 public:
@@ -709,6 +745,12 @@ public:
         // reprojection stages, one frame per launch; its history is one chain in frame order, like the denoiser's.
         struct taa_options { int sequence_length = 8; bool edge_dilation = true, anti_shimmer = false; };
         std::optional<taa_options> taa;
+        // --display=looking-glass: looking_glass_composition_stage at the very end, behind tonemap and taa; `size` is the size of one view,
+        // active_viewport_count the rig's view count (before a viewport list compacts it) and `composed` / `composed8` the panel's image.
+        // The caller sets the cameras up (looking_glass_cameras of tauray_gltf.hh).  One device - the views would have to be gathered
+        // first -, one frame per launch; works with the reprojection stages, the denoiser, taa and an animated scene.
+        struct looking_glass_options { looking_glass_composition_stage::options stage; uvec2 output_size{0, 0}; };
+        std::optional<looking_glass_options> looking_glass;
     };
 
     // `devices`: HIP device index per logical device (repeat an index for --fake-devices); device 0 displays.
@@ -759,6 +801,17 @@ public:
                 throw std::runtime_error("rt_renderer: taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
                                          "which an equirectangular camera does not have");
             if(!std::is_same<Pipeline, path_tracer_stage>::value) throw std::runtime_error("rt_renderer: taa reads the path tracer's screen_motion target");
+        }
+        if(this->opt.looking_glass)
+        {
+            if(devices.size() > 1)
+                throw std::runtime_error("rt_renderer: a Looking Glass output with a pixel distribution of count " + std::to_string(devices.size()) + " > 1: the composition "
+                                         "stage reads every view of the light field on one device, the views would have to be gathered first, which is not built; use one device");
+            if(batch > 1) throw std::runtime_error("rt_renderer: a Looking Glass output: a composed frame is one frame, frames per launch must be 1");
+            if(this->opt.projection != 0) throw std::runtime_error("rt_renderer: a Looking Glass output: the rig's cameras are perspective cameras");
+            if(this->opt.looking_glass->stage.viewport_count != this->opt.active_viewport_count)
+                throw std::runtime_error("rt_renderer: a Looking Glass output of " + std::to_string(this->opt.looking_glass->stage.viewport_count) + " views over " +
+                                         std::to_string(this->opt.active_viewport_count) + " viewports");
         }
         per_device.resize(devices.size());
         std::vector<double> ratios(devices.size(), 1.0 / devices.size());
@@ -819,7 +872,15 @@ public:
         // One device: nothing sits between the path tracer and the tonemap stage (no transfer, no stitch), and the stage writes the slot's
         // display image while it writes its colour target - the same bits without a second pass over the frame.  TRHIP_FUSED_TONEMAP=0: off.
         const char* fe = getenv("TRHIP_FUSED_TONEMAP");
-        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr && !spatial_on && !temporal_on && !this->opt.taa;
+        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr && !spatial_on && !temporal_on && !this->opt.taa && !this->opt.looking_glass;
+        if(this->opt.looking_glass)
+        {
+            device& d0 = *per_device[0].dev;
+            const uvec2 os = this->opt.looking_glass->output_size;
+            lkg = std::make_unique<looking_glass_composition_stage>(d0, size, os, this->opt.looking_glass->stage);
+            for(frame_slot& fs: frame_slots) { fs.composed = d0.alloc(size_t(os.x) * os.y * 16); fs.composed8 = d0.alloc(size_t(os.x) * os.y * 4); }
+            composed = frame_slots[0].composed; composed8 = frame_slots[0].composed8;
+        }
         if(this->opt.bmfr)
         {
             device& d0 = *per_device[0].dev;
@@ -895,6 +956,7 @@ public:
         temporal.reset();
         spatial.reset();
         taa.reset();
+        lkg.reset();
         if(taa_input) per_device[0].dev->free(taa_input);
         for(void* p: {destination_targets.normal, destination_targets.pos, destination_targets.instance_id}) if(p) per_device[0].dev->free(p);
         for(size_t i = 0; i < per_device.size(); ++i)
@@ -909,7 +971,12 @@ public:
                 per_device[i].dev->free(sl.color);
                 per_device[i].dev->destroy_stream(sl.stream);
             }
-        for(frame_slot& fs: frame_slots) per_device[0].dev->free(fs.display);
+        for(frame_slot& fs: frame_slots)
+        {
+            per_device[0].dev->free(fs.display);
+            if(fs.composed) per_device[0].dev->free(fs.composed);
+            if(fs.composed8) per_device[0].dev->free(fs.composed8);
+        }
     }
 
     void reset_accumulation(bool reset_sample_counter = false)
@@ -1059,6 +1126,11 @@ public:
             const trhip_pt_targets& t = per_device[0].slots[k].targets;
             taa->run(trhip_taa_images{taa_input, display, t.screen_motion, t.pos, t.instance_id}, post_stream);
         }
+        if(lkg)
+        {
+            composed = frame_slots[k].composed; composed8 = frame_slots[k].composed8;
+            lkg->run(display, composed, composed8, post_stream);
+        }
         if(post_stream != display_stream) check(trhip_stream_wait(display_device.h, display_stream, nullptr));
         frame_index += batch;
         accumulated_frames++;
@@ -1119,7 +1191,7 @@ public:
         size_t target_bytes(size_t layers) const { const uvec2 ts = get_distribution_target_size(dist); return size_t(ts.x) * ts.y * 16 * layers; }
     };
     std::vector<per_device_data> per_device;
-    struct frame_slot { void* display = nullptr; };   // tonemapped RGBA32F on the display device
+    struct frame_slot { void* display = nullptr; void* composed = nullptr; void* composed8 = nullptr; };   // tonemapped RGBA32F on the display device; a Looking Glass output: the panel's image
     std::vector<frame_slot> frame_slots;   // options.max_frames_in_flight of them (at least one)
     int current_slot = -1;
     uint32_t batch = 1;                    // options.frames_per_launch
@@ -1134,6 +1206,9 @@ public:
     std::unique_ptr<spatial_reprojection_stage> spatial;        // options.spatial_reprojection
     std::unique_ptr<gbuffer_stage> gbuffer;
     std::unique_ptr<taa_stage> taa;                             // options.taa
+    std::unique_ptr<looking_glass_composition_stage> lkg;       // options.looking_glass
+    void* composed = nullptr;                                   // frame_slots[current_slot].composed: RGBA32F [output_size.y][output_size.x]
+    void* composed8 = nullptr;                                  // ... and the same frame as uint8 [..][..][4]
     void* taa_input = nullptr;                                  // the tonemap stage's output when taa runs behind it (the stage writes `display`)
     trhip_gbuffer_targets destination_targets = {};             // the G-buffer of the viewports that are reprojected, shared by the slots
     size_t output_layers = 1;                                    // layers of `display` (every viewport; the path tracer renders opt.active_viewport_count)

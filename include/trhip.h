@@ -679,6 +679,42 @@ int trhip_taa_get_timings(trhip_taa* stage, trhip_taa_timings* out);   /* waits 
                                          (passed through), bit 5 no surface */
 int trhip_taa_download(trhip_taa* stage, int which, void* host, size_t bytes);   /* synchronises the device */
 
+/* ---- looking_glass_composition_stage (--display=looking-glass; src/looking_glass_composition_stage.{hh,cc},
+ * shader/looking_glass_composition.comp): the last stage of a light-field chain.  It interleaves the N views, sub-pixel by sub-pixel, into
+ * the one image a lenticular panel shows.  csrc/looking_glass.hip, one kernel per frame; the order of operations is pinned in
+ * csrc/looking_glass.h.  Per output pixel p:
+ *   1. calibration = (pitch, tilt * pitch, pitch / (3 * out_w), -center), every component negated under invert (computed by the host, in float)
+ *   2. uv = (p + 0.5) / out_size; uvf = (uv.x, 1 - uv.y)
+ *   3. per channel c = 0, 1, 2: d = ((uvf.x * cal.x + uvf.y * cal.y) + c * cal.z) + cal.w; view = clamp(int(floor(fract(d) * N)), 0, N - 1)
+ *   4. out[c] = channel c of that view, sampled bilinearly with clamp to edge at the unflipped uv (the shader flips y twice)
+ *   5. alpha = 1; dst_rgba8 = uint8(clamp(c, 0, 1) * 255 + 0.5) per channel and 255 for alpha
+ * Deviations from the reference: (1) the views are fp32 where the reference's are B8G8R8A8: dst_rgba8 is the reference's
+ * output format (in r, g, b, a order), the fp32 dst is extra; (2) the bilinear weights are fp32 where Vulkan's sampler uses 8-bit fixed
+ * point; (3) a NaN or a negative input passes through to dst and is clamped in dst_rgba8 (a NaN gives 0). */
+typedef struct trhip_lkg trhip_lkg;
+typedef struct trhip_lkg_options {
+    uint32_t viewport_count;          /* 1..255 */
+    float pitch, tilt, center;        /* the reference's corrected_pitch, tilt, center (src/looking_glass.cc:240-241) */
+    int32_t invert;
+    int32_t record_view_indices;      /* keep a uint8[4] per output pixel for trhip_lkg_download */
+} trhip_lkg_options;
+typedef struct trhip_lkg_timings {    /* the reference's timer, device ms of the last frame */
+    float total_ms;
+    uint32_t frames;                  /* frames run since the stage was created */
+    char name[64];                    /* "looking glass composition" */
+} trhip_lkg_timings;
+/* Refuses a view or output size of 0 or with an extent above 16384, a viewport_count of 0 or above 255 and a pitch, tilt or center that is
+ * not finite. */
+int trhip_lkg_create(trhip_device* dev, const trhip_lkg_options* opt, uint32_t view_w, uint32_t view_h, uint32_t out_w, uint32_t out_h, trhip_lkg** out);
+void trhip_lkg_destroy(trhip_lkg* stage);
+/* One frame: src RGBA32F [views][view_h][view_w] in display space; dst RGBA32F [out_h][out_w] or NULL; dst_rgba8 uint8 [out_h][out_w][4] or
+ * NULL (not both NULL).  One kernel between two events on `stream`, no synchronisation.  The stage has no history: it may run on a frame
+ * slot's own stream. */
+int trhip_lkg_run(trhip_lkg* stage, const void* src, void* dst, void* dst_rgba8, void* stream);
+int trhip_lkg_get_timings(trhip_lkg* stage, trhip_lkg_timings* out);   /* waits for the last frame */
+#define TRHIP_LKG_VIEW_INDICES 0      /* uint8 [out_h][out_w][4]: the view of r, g, b; 0 (record_view_indices only) */
+int trhip_lkg_download(trhip_lkg* stage, int which, void* host, size_t bytes);   /* synchronises the device */
+
 #ifdef __cplusplus
 }
 #endif

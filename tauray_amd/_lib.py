@@ -186,6 +186,20 @@ TAA_HISTORY, TAA_DECISIONS = 0, 1
 TAA_DECISION_OFFSET_MASK, TAA_DECISION_OUTSIDE, TAA_DECISION_NO_SURFACE = 0x0F, 0x10, 0x20
 
 
+class LkgOptionsC(C.Structure):
+    """trhip_lkg_options."""
+    _fields_ = [("viewport_count", C.c_uint32), ("pitch", C.c_float), ("tilt", C.c_float), ("center", C.c_float), ("invert", C.c_int32),
+                ("record_view_indices", C.c_int32)]
+
+
+class LkgTimingsC(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("frames", C.c_uint32), ("name", C.c_char * 64)]
+
+
+# trhip_lkg_download
+LKG_VIEW_INDICES = 0
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -290,6 +304,11 @@ SYMBOLS = {
     "trhip_taa_reset_history": (_i, [_vp]),
     "trhip_taa_get_timings": (_i, [_vp, C.POINTER(TaaTimingsC)]),
     "trhip_taa_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_lkg_create": (_i, [_vp, C.POINTER(LkgOptionsC), _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "trhip_lkg_destroy": (None, [_vp]),
+    "trhip_lkg_run": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "trhip_lkg_get_timings": (_i, [_vp, C.POINTER(LkgTimingsC)]),
+    "trhip_lkg_download": (_i, [_vp, _i, _vp, C.c_size_t]),
 }
 
 _LIB = None

@@ -194,6 +194,8 @@ class SceneAnimator:
         instances["model_prev"] = desc.instances["model"]
         point_lights, directional_lights = desc.point_lights.copy(), desc.directional_lights.copy()
 
+        rig = getattr(desc, "camera_rig", None)
+
         def visit(n, parent):
             node = desc.nodes[n]
             glob = parent @ node.local()
@@ -202,7 +204,12 @@ class SceneAnimator:
                 instances["model"][i] = S.to_glm(glob)
                 instances["model_normal"][i] = S.to_glm(np.linalg.inv(glob).T)
             for ci in node.cameras:
-                desc.cameras[ci].transform = glob
+                if rig is None:
+                    desc.cameras[ci].transform = glob
+                elif ci == 0:       # a Looking Glass rig hangs under the first camera's frame and replaces every camera of the file
+                    desc.camera_rig_frame = glob
+                    for cam, local in zip(desc.cameras, rig):
+                        cam.transform = glob @ local
             for kind, index, make in node.lights:       # point lights first, then spotlights, in one array (src/scene_stage.cc:1287-1317)
                 if kind == "directional":
                     directional_lights[index] = make(glob)

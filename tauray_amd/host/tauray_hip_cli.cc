@@ -11,6 +11,9 @@
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
 //              [--renderer=path-tracer|direct] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
+//              [--display=headless|looking-glass --lkg-params=viewports,midplane,depth,relative_dist
+//               --lkg-calibration=display_index,pitch,slope,center,fringe,viewCone,invView,verticalAngle,DPI,screenW,screenH,flipImageX,flipImageY,flipSubp]
+//              (a Looking Glass output: --width / --height are the size of one view, one composed screenW x screenH file per frame)
 //              [--camera-grid=w,h,x,y --camera-recentering-distance=5 --camera-grid-roll=0]   (light-field grid, one file per view)
 //
 // One process per GPU (include/tauray_hip_comm.hh): start N copies with --process-count=N --process-rank=0..N-1 --device=<HIP index>
@@ -47,11 +50,54 @@ static const char* const usage_text =
     "  --taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]   temporal antialiasing behind the tonemap stage: the cameras step through a\n"
     "                         jitter sequence of N sub-pixel offsets, every frame is blended into a history with weight 1 / N (edge\n"
     "                         dilation on, anti-shimmer off by default; one device; works with --animation, --headless, --denoiser=bmfr)\n"
+    "  --display=headless|looking-glass   looking-glass: the cameras become the rig of a Looking Glass display under the scene's first camera and\n"
+    "                         the views are interleaved, sub-pixel by sub-pixel, into the one image the lenticular panel shows: --width / --height\n"
+    "                         are the size of one view, --headless=PREFIX writes one composed screenW x screenH file per frame (one device; works\n"
+    "                         with --spatial-reprojection, --temporal-reprojection, --denoiser=bmfr, --taa and --animation)\n"
+    "  --lkg-params=viewports,midplane,depth,relative_dist   the rig (48,2,2,2); positional or name=value\n"
+    "  --lkg-calibration=display_index,pitch,slope,center,fringe,viewCone,invView,verticalAngle,DPI,screenW,screenH,flipImageX,flipImageY,flipSubp\n"
+    "                         the panel, as its calibration file has it (required: no display service is read here); positional or name=value\n"
     "  --tonemap=filmic|linear|gamma-correction|reinhard|reinhard-luminance --exposure=E --gamma=G\n"
     "  --animation[=NAME] --framerate=F --accumulation --envmap=FILE --camera-grid=w,h,x,y -t --skip-nan-check\n"
     "  --fake-devices=N | --devices=0,1,... --distribution-strategy=scanline|shuffled-strips --frames-in-flight=N --frames-per-launch=N\n"
     "  --process-count=N --process-rank=R --device=D --comm-id=FILE [--comm-nonce=N] [--exchange=rccl|ipc] [--shard=views]\n"
     "  --dump-scene=out.trsc\n";
+
+// A struct option of the reference (TR_STRUCT_OPT, src/options.cc): comma-separated values, positional in the order of `names` or name=value
+static std::map<std::string, std::string> parse_struct_option(const std::string& option, const std::string& text, const std::vector<std::string>& names)
+{
+    std::map<std::string, std::string> out;
+    std::stringstream ss(text); std::string tok;
+    size_t position = 0;
+    while(std::getline(ss, tok, ','))
+    {
+        const size_t eq = tok.find('=');
+        std::string name;
+        if(eq == std::string::npos)
+        {
+            if(position >= names.size()) throw std::runtime_error(option + ": more than " + std::to_string(names.size()) + " values");
+            name = names[position++];
+        }
+        else
+        {
+            name = tok.substr(0, eq); tok = tok.substr(eq + 1);
+            if(std::find(names.begin(), names.end(), name) == names.end()) throw std::runtime_error(option + ": " + name + " is not one of its fields");
+        }
+        if(tok.empty()) throw std::runtime_error(option + ": " + name + " has no value");
+        out[name] = tok;
+    }
+    return out;
+}
+static double struct_number(const std::string& option, const std::map<std::string, std::string>& v, const std::string& name, double fallback)
+{
+    auto it = v.find(name);
+    if(it == v.end()) return fallback;
+    size_t used = 0;
+    double d = 0;
+    try { d = std::stod(it->second, &used); } catch(std::exception&) { used = 0; }
+    if(used != it->second.size()) throw std::runtime_error(option + ": " + name + "=" + it->second + " is not a number");
+    return d;
+}
 
 int main(int argc, char** argv)
 {
@@ -81,6 +127,10 @@ int main(int argc, char** argv)
         uint64_t comm_nonce = 0;
         std::string exchange = "rccl";
         std::vector<double> workloads;      // --device-workloads=a,b,...: rt_renderer::set_device_workloads before the first frame
+        std::string display = "headless";                                   // --display (src/options.hh:331-341)
+        uint32_t lkg_viewports = 48;                                        // --lkg-params (src/options.hh:375-385)
+        double lkg_midplane = 2.0, lkg_depth = 2.0, lkg_relative_dist = 2.0;
+        std::optional<looking_glass_calibration> lkg_calibration;           // --lkg-calibration (src/options.hh:386-405)
         rt_renderer::options opt;
         opt.distribution.strategy = DISTRIBUTION_SHUFFLED_STRIPS;      // CLI default (src/options.hh:43-49)
         headless::options hopt;
@@ -135,6 +185,38 @@ int main(int argc, char** argv)
                 }
                 if(first) throw std::runtime_error("--taa=N: the length of the jitter sequence is missing");
                 opt.taa = t;
+            }
+            else if(starts(a, "--display="))
+            {
+                display = val("--display=");
+                if(display == "window" || display == "openxr" || display == "frame-server" || display == "frame-client")
+                    throw std::runtime_error("--display=" + display + ": not built (--display=headless|looking-glass)");
+                if(display != "headless" && display != "looking-glass") throw std::runtime_error("--display is headless or looking-glass, not " + display);
+            }
+            else if(starts(a, "--lkg-params="))
+            {
+                const auto v = parse_struct_option("--lkg-params", val("--lkg-params="), {"viewports", "midplane", "depth", "relative_dist"});
+                const double n = struct_number("--lkg-params", v, "viewports", 48);
+                if(!(n >= 1) || n > 255 || n != std::floor(n)) throw std::runtime_error("--lkg-params: viewports must be a whole number in 1..255 (the composition stage's limit)");
+                lkg_viewports = (uint32_t)n;
+                lkg_midplane = struct_number("--lkg-params", v, "midplane", 2.0); lkg_depth = struct_number("--lkg-params", v, "depth", 2.0);
+                lkg_relative_dist = struct_number("--lkg-params", v, "relative_dist", 2.0);
+                if(!(lkg_midplane >= 0.001) || !(lkg_depth >= 0.001) || !(lkg_relative_dist >= 0.001)) throw std::runtime_error("--lkg-params: midplane, depth and relative_dist must be at least 0.001");
+            }
+            else if(starts(a, "--lkg-calibration="))
+            {   // the fields the reference ignores (display_index, fringe, verticalAngle, the flips) are parsed and ignored
+                const std::vector<std::string> names = {"display_index", "pitch", "slope", "center", "fringe", "viewCone", "invView", "verticalAngle", "DPI", "screenW", "screenH",
+                                                        "flipImageX", "flipImageY", "flipSubp"};
+                const auto v = parse_struct_option("--lkg-calibration", val("--lkg-calibration="), names);
+                for(const std::string& n: names) (void)struct_number("--lkg-calibration", v, n, 0.0);
+                looking_glass_calibration c;
+                auto num = [&](const char* n) { return struct_number("--lkg-calibration", v, n, 0.0); };
+                c.pitch = (float)num("pitch"); c.slope = (float)num("slope"); c.center = (float)num("center"); c.view_cone = (float)num("viewCone");
+                c.invert = num("invView") > 0.5; c.dpi = (float)num("DPI");
+                if(!(num("screenW") >= 1) || !(num("screenH") >= 1) || num("screenW") > 16384 || num("screenH") > 16384) throw std::runtime_error("--lkg-calibration: screenW and screenH must be in 1..16384");
+                c.screen_w = (uint32_t)num("screenW"); c.screen_h = (uint32_t)num("screenH");
+                c.check();
+                lkg_calibration = c;
             }
             else if(a == "--skip-nan-check") hopt.skip_nan_check = true;     // headless::options::skip_nan_check (src/headless.hh:74); with --filetype=none: no readback at all
             else if(a == "--accumulation") opt.accumulate = true;
@@ -258,6 +340,25 @@ int main(int argc, char** argv)
         scene_data scene = is_glb ? load_glb(scene_path, size.x, size.y) : load_scene_dump(scene_path);
         if(!envmap_path.empty()) set_envmap(scene, envmap_path);      // src/tauray.cc:198-201
         uint32_t viewports = 1;
+        const bool looking_glass = display == "looking-glass";
+        if(looking_glass)
+        {   // looking_glass::setup_cameras with the metadata of --lkg-calibration (src/looking_glass.cc:62-88, 216-242)
+            if(!lkg_calibration)
+                throw std::runtime_error("--display=looking-glass needs --lkg-calibration=...: no display service is read here (the reference asks the HoloPlay service "
+                                         "of the machine the display hangs on; give the panel's calibration file on the command line instead)");
+            if(grid_w * grid_h > 1) throw std::runtime_error("--display=looking-glass sets the cameras up itself: no --camera-grid");
+            if(!is_glb) throw std::runtime_error("--display=looking-glass hangs its rig on the first camera of a glTF scene");
+            if(devices.size() > 1 || process_count > 0 || shard_views)
+                throw std::runtime_error("--display=looking-glass with several devices or processes: the composition stage reads every view of the light field on one device, "
+                                         "the views would have to be gathered first, which is not built; use one device");
+            if(frames_per_launch > 1) throw std::runtime_error("--display=looking-glass: a composed frame is one frame, --frames-per-launch must be 1");
+            viewports = looking_glass_cameras(scene, lkg_viewports, lkg_midplane, lkg_depth, lkg_relative_dist, *lkg_calibration);
+            rt_renderer::options::looking_glass_options lo;
+            lo.stage.viewport_count = viewports; lo.stage.pitch = lkg_calibration->corrected_pitch(); lo.stage.tilt = lkg_calibration->tilt();
+            lo.stage.center = lkg_calibration->center; lo.stage.invert = lkg_calibration->invert;
+            lo.output_size = uvec2{lkg_calibration->screen_w, lkg_calibration->screen_h};
+            opt.looking_glass = lo;
+        }
         if(grid_w * grid_h > 1) viewports = generate_cameras(scene, grid_w, grid_h, grid_dx, grid_dy, grid_recentering, grid_roll);      // src/tauray.cc:680-727
         // play(scene, name, !replay, name == "") (src/tauray.cc:252-253); ticks in microseconds per update (:1052)
         scene_animator animator(scene);
@@ -335,6 +436,11 @@ int main(int argc, char** argv)
             set_camera_jitter(scene, gltf_detail::get_camera_jitter_sequence(opt.taa->sequence_length, size.x, size.y));      // src/tauray.cc:816
         }
         hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
+        if(looking_glass)
+        {   // one composed frame of the panel's size per frame instead of a file per view
+            if(opt.projection != 0) throw std::runtime_error("--display=looking-glass: the rig's cameras are perspective cameras");
+            hopt.size = opt.looking_glass->output_size; hopt.display_count = 1;
+        }
         if(shard_views)
         {   // view shards: viewport v belongs to rank v mod N; every rank renders, tonemaps and saves its own
             // views under their global indices, nothing is exchanged
@@ -398,7 +504,7 @@ int main(int argc, char** argv)
             if(workloads.size() != rr.per_device.size()) throw std::runtime_error("--device-workloads needs one ratio per device");
             rr.set_device_workloads(workloads);
         }
-        if((frames_in_flight > 1 || frames_per_launch > 1) && !animated && !opt.taa)
+        if((frames_in_flight > 1 || frames_per_launch > 1) && !animated && !opt.taa && !opt.looking_glass)
         {   // frame f renders while the frames before it are read back, compressed and written (the reference overlaps
             // its save workers with the next frames the same way, src/headless.cc:349-422); with --frames-per-launch=B a slot
             // holds B consecutive frames, frame-major in its display image
@@ -461,7 +567,7 @@ int main(int argc, char** argv)
                     std::cout << "\tDEVICE " << i << ":\n\t\t[path tracing (" << opt.active_viewport_count << " viewports)] " << pt[i] << " ms\n";
                 std::cout << "\tHOST: " << std::chrono::duration<double, std::milli>(t1 - t0).count() << " ms\n";
             }
-            out.save(*rr.per_device[0].dev, rr.display, (unsigned)f);
+            out.save(*rr.per_device[0].dev, opt.looking_glass ? rr.composed : rr.display, (unsigned)f);
         }
         return 0;
         };
@@ -473,6 +579,7 @@ int main(int argc, char** argv)
             static_cast<path_tracer_stage::options&>(dopt) = opt;
             dopt.tonemap = opt.tonemap; dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;
             dopt.spatial_reprojection = opt.spatial_reprojection; dopt.temporal_reprojection = opt.temporal_reprojection;
+            if(opt.looking_glass) { direct_renderer::options::looking_glass_options lo; lo.stage = opt.looking_glass->stage; lo.output_size = opt.looking_glass->output_size; dopt.looking_glass = lo; }
             direct_renderer rr(devices, scene, size, dopt);
             return run(rr);
         }

@@ -989,6 +989,59 @@ class TaaStage:
             pass
 
 
+class LookingGlassStage:
+    """looking_glass_composition_stage (src/looking_glass_composition_stage.{hh,cc}): interleaves the views of a light field, sub-pixel by
+    sub-pixel, into the one image a lenticular panel shows (trhip_lkg_*, include/trhip.h).  `view_size`: the size of one view; `out_size`: the
+    panel's.  `options`: viewport_count (1..255), pitch / tilt / center (the reference's corrected_pitch, tilt, center:
+    looking_glass.LookingGlassCalibration.stage_options), invert, record_view_indices.  The stage has no history."""
+
+    DEFAULTS = dict(viewport_count=48, pitch=0.0, tilt=0.0, center=0.0, invert=False, record_view_indices=False)
+
+    def __init__(self, ctx: Context, view_size, out_size, options: Optional[dict] = None):
+        unknown = set(options or {}) - set(self.DEFAULTS)
+        if unknown:
+            raise ValueError(f"LookingGlassStage: not an option of the stage: {sorted(unknown)}")
+        self.options = dict(self.DEFAULTS, **(options or {}))
+        self.ctx = ctx
+        self.view_size, self.out_size = (int(view_size[0]), int(view_size[1])), (int(out_size[0]), int(out_size[1]))
+        self.h = None
+        o = self.options
+        opt = _lib.LkgOptionsC(max(int(o["viewport_count"]), 0), float(o["pitch"]), float(o["tilt"]), float(o["center"]), int(bool(o["invert"])),
+                               int(bool(o["record_view_indices"])))
+        h = C.c_void_p()
+        check(_lib.lib().trhip_lkg_create(getattr(ctx, "h", None), C.byref(opt), max(self.view_size[0], 0), max(self.view_size[1], 0),
+                                          max(self.out_size[0], 0), max(self.out_size[1], 0), C.byref(h)))
+        self.h = h.value
+
+    def run(self, src, dst=None, dst_rgba8=None, stream=None):
+        """stage::run: `src` RGBA32F [views][h][w] in display space; `dst` RGBA32F [out_h][out_w] and / or `dst_rgba8` uint8 [out_h][out_w][4]."""
+        check(_lib.lib().trhip_lkg_run(self.h, None if src is None else _ptr(src), None if dst is None else _ptr(dst),
+                                       None if dst_rgba8 is None else _ptr(dst_rgba8), stream))
+
+    def timings(self) -> dict:
+        """The reference's timer: its name, device ms of the last frame, frames run."""
+        t = _lib.LkgTimingsC()
+        check(_lib.lib().trhip_lkg_get_timings(self.h, C.byref(t)))
+        return {"name": t.name.decode(), "total_ms": float(t.total_ms), "frames": int(t.frames)}
+
+    def view_indices(self) -> np.ndarray:
+        """uint8 [out_h][out_w][4]: the view the last frame took r, g and b from; 0 (record_view_indices only)."""
+        out = np.empty((self.out_size[1], self.out_size[0], 4), np.uint8)
+        check(_lib.lib().trhip_lkg_download(self.h, _lib.LKG_VIEW_INDICES, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().trhip_lkg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _FrameSlot:
     """What one frame in flight owns: its stage (path buffers, counters), its images and the stream it is ordered on."""
 
@@ -999,6 +1052,7 @@ class _FrameSlot:
         self.features = None     # denoiser: the gbuffer targets next to the colour target
         self.color = None
         self.display = None
+        self.composed = self.composed8 = None      # a Looking Glass output: the panel's image in fp32 and in 8 bits
         self.stream = None
         self.frame = 0           # frame counter of the slot's last frame
         self.fused_info = None
@@ -1025,7 +1079,7 @@ class RtRenderer:
                  rank=0, world_size=1, viewports=1, tonemap: Optional[dict] = None, accumulate=False, use_torch=None,
                  shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None,
                  denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY, spatial_reprojection=None, temporal_reprojection=0.0,
-                 taa=0, taa_edge_dilation=True, taa_anti_shimmer=False):
+                 taa=0, taa_edge_dilation=True, taa_anti_shimmer=False, looking_glass=None):
         """`shard`: what the ranks divide among themselves - "pixels" (the reference's distribution strategies, partial frames
         stitched on rank 0), "views" (viewport v on rank v mod N; nothing is exchanged before output) or "samples" (every
         rank renders samples_per_pixel / N samples of every pixel; one reduce to rank 0).  SURVEY.md section 8(e).
@@ -1052,9 +1106,26 @@ class RtRenderer:
         (scene::update), the path tracer renders screen_motion, pos and instance_id next to the colour target, and TaaStage (alpha =
         1 / N, gamma = the tonemap stage's; `taa_edge_dilation`, `taa_anti_shimmer`: the reference's defaults) runs after the tonemap
         stage, in frame order on the default stream like the denoiser's history chain; the fused tonemap is off.  Every frame is a
-        fresh frame.  With denoiser="bmfr" or without."""
+        fresh frame.  With denoiser="bmfr" or without.
+        `looking_glass`: None, or a looking_glass.LookingGlassOutput (the reference's --display=looking-glass with --lkg-calibration and
+        --lkg-params): the scene's cameras are replaced by the rig of looking_glass::setup_cameras under the scene's first camera, `size` is
+        the size of one view, and LookingGlassStage runs at the end of post_process, behind tonemap and TAA: download("composed") is the
+        panel's image in fp32, download("composed8") in the reference's 8 bits.  The caller's scene stays rigged after close() (scene.cameras
+        are the rig, scene.camera_rig its local transforms).  One device; the fused tonemap is off.  With
+        spatial_reprojection / temporal_reprojection, denoiser="bmfr", taa or an animated scene."""
         if shard not in ("pixels", "views", "samples"):
             raise ValueError("shard must be pixels, views or samples")
+        if looking_glass is not None:
+            if world_size > 1:
+                raise ValueError(f"looking_glass with a {shard} distribution of count {world_size} > 1: the composition stage reads every view of the light "
+                                 "field on one device, the views would have to be gathered first, which is not built; use one device")
+            if viewports not in (1, looking_glass.viewports):
+                raise ValueError(f"looking_glass: the rig has {looking_glass.viewports} views, not viewports={viewports}")
+            if frames_per_launch > 1:
+                raise ValueError("looking_glass: a composed frame is one frame: frames_per_launch must be 1")
+            if options.projection != 0:
+                raise ValueError("looking_glass: the rig's cameras are perspective cameras (options.projection must be 0)")
+            viewports = looking_glass.viewports
         if denoiser not in (None, "none", "bmfr"):
             raise ValueError(f"denoiser {denoiser!r}: only \"bmfr\" is built" + (" (svgf is not built)" if denoiser == "svgf" else ""))
         denoiser = None if denoiser == "none" else denoiser
@@ -1135,6 +1206,11 @@ class RtRenderer:
         self.viewports = viewports
         self.strategy = DISTRIBUTION_DUPLICATE if (world_size == 1 or self.shard != "pixels") else strategy   # src/tauray.cc:519-521
         self.accumulate = accumulate
+        self.looking_glass = looking_glass
+        if looking_glass is not None:       # looking_glass::setup_cameras, before the scene goes to the device
+            from .looking_glass import looking_glass_cameras
+            looking_glass_cameras(scene, looking_glass.viewports, looking_glass.midplane, looking_glass.depth, looking_glass.relative_dist,
+                                  looking_glass.calibration)
         self.scene_update = SceneStage(ctx, scene, as_strategy=as_strategy, dynamic=dynamic)
         if self.shard == "pixels":
             workloads = [1.0 / world_size] * world_size
@@ -1183,7 +1259,11 @@ class RtRenderer:
                                                                 anti_shimmer=taa_anti_shimmer, base_camera_index=base, projection=options.projection))
             self.taa_input = self._alloc_display(viewports)     # the tonemap stage's output; the stage writes the display image
             self._last_cameras = self.scene_update.camera_data.copy()      # the first frame's camera_pair.previous: the cameras before their first step
-        self.fused_tonemap = (world_size == 1 and denoiser is None and not reprojection and not taa and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
+        self.lkg = None
+        if looking_glass is not None and viewports > 0:
+            self.lkg = LookingGlassStage(ctx, self.size, looking_glass.calibration.size,
+                                         looking_glass.calibration.stage_options(self.output_viewports, looking_glass.record_view_indices))
+        self.fused_tonemap = (world_size == 1 and denoiser is None and not reprojection and not taa and self.lkg is None and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
                               and hasattr(_lib.lib(), "trhip_pt_set_fused_tonemap") and os.environ.get("TRHIP_FUSED_TONEMAP", "1") != "0")
         self.slots = []
         for k in range(frames_in_flight):
@@ -1265,6 +1345,10 @@ class RtRenderer:
 
     def set_scene(self, scene: SceneDesc):
         self.sync()
+        if self.looking_glass is not None:
+            from .looking_glass import looking_glass_cameras
+            lg = self.looking_glass
+            looking_glass_cameras(scene, lg.viewports, lg.midplane, lg.depth, lg.relative_dist, lg.calibration)
         self.scene_update.set_scene(scene)
         if self.bmfr is not None:
             self.bmfr.reset_history()
@@ -1537,10 +1621,23 @@ class RtRenderer:
         if self.taa is not None:
             self.taa.run(dict(src=self.taa_input, dst=slot.display, screen_motion=slot.features["screen_motion"], pos=slot.features["pos"],
                               instance_id=slot.features["instance_id"]), stream)
+        if self.lkg is not None:
+            if slot.composed is None:
+                ow, oh = self.lkg.out_size
+                slot.composed, slot.composed8 = self.ctx.alloc(ow * oh * 16), self.ctx.alloc(ow * oh * 4)
+            self.lkg.run(slot.display, slot.composed, slot.composed8, stream)
 
     def download(self, which="color") -> np.ndarray:
-        """The most recent frame's partial colour target or tonemapped display image."""
+        """The most recent frame's partial colour target or tonemapped display image; with a Looking Glass output also "composed" (the
+        panel's image, RGBA32F [h][w][4]) and "composed8" (uint8 [h][w][4])."""
         self.sync()
+        if which in ("composed", "composed8"):
+            if self.lkg is None or self.current.composed is None:
+                raise KeyError(f"{which}: the renderer has no Looking Glass output (looking_glass=...) or no frame was post-processed")
+            ow, oh = self.lkg.out_size
+            if which == "composed":
+                return self.current.composed.download((oh, ow, 4), np.float32)
+            return self.current.composed8.download((oh, ow, 4), np.uint8)
         buf = self.color if which == "color" else self.display
         if which == "color":
             tw, th = self.target_size
@@ -1558,7 +1655,7 @@ class RtRenderer:
         if self.taa is not None and self.scene_update.scene is not None:
             for cam in self.scene_update.scene.cameras:      # the caller's cameras get their jitter from this renderer: it goes with it
                 cam.set_jitter([])
-        for stage in (self.bmfr, self.temporal, self.spatial, self.taa):
+        for stage in (self.bmfr, self.temporal, self.spatial, self.taa, self.lkg):
             if stage is not None:
                 stage.close()
         for slot in self.slots:

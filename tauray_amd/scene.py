@@ -146,6 +146,7 @@ class Camera:
     equirect_fov: tuple = (360.0, 180.0)
     jitter_sequence: tuple = ()             # camera::set_jitter: sub-pixel offsets of the projection, one per frame (perspective only)
     jitter_index: int = 0
+    closed_form_inverse: bool = False       # looking_glass_cameras: proj_inverse in closed form, jittered or not (the bytes of the C++ host)
 
     def set_jitter(self, seq):
         """camera::set_jitter (src/camera.cc:480-484): the sequence step_jitter walks; an empty one turns jitter off."""
@@ -225,7 +226,7 @@ class Camera:
             return out
         proj = self.projection_matrix()
         out["view_proj"][0] = to_glm(proj @ view)
-        jittered = bool(self.jitter_sequence) and self.projection == PROJ_PERSPECTIVE
+        jittered = (bool(self.jitter_sequence) or self.closed_form_inverse) and self.projection == PROJ_PERSPECTIVE
         # a jittered projection is inverted in closed form, operation for operation as the C++ host does it: both hosts then pack the same bytes
         out["proj_inverse"][0] = to_glm(perspective_matrix_inverse(proj) if jittered else np.linalg.inv(proj))
         out["dof_params"][0] = self.focus if self.projection == PROJ_PERSPECTIVE else (0, 0, 0, 0)
@@ -381,6 +382,8 @@ class SceneDesc:
     roots: list = field(default_factory=list)                      # root nodes of the file's scenes
     animations: dict = field(default_factory=dict)                 # glTF node index -> {clip name: animation.Animation}
     spotlight_base: int = 0                                        # index of the first spotlight in point_lights (point lights come first)
+    camera_rig: Optional[list] = None                              # looking_glass_cameras: the views' transforms under the first camera's node
+    camera_rig_frame: Optional[np.ndarray] = None                  # ... and that node's global transform, the rig's reference frame
 
     def joint_transforms(self, sk: "SkinnedMesh", node_globals: Optional[dict] = None) -> np.ndarray:
         """model::update_joints (src/model.cc:107-118): joint node's global transform * inverse bind matrix, (n, 4, 4)."""
