@@ -697,35 +697,19 @@ public:
 };
 
 //==============================================================================
-// rt_renderer<Pipeline> (src/rt_renderer.hh:28-77): all devices in one process, like the reference.  Pipeline is
-// path_tracer_stage or direct_stage (the reference instantiates the template for those, src/rt_renderer.cc:410-412);
-// `rt_renderer` and `direct_renderer` below are the two instantiations (src/rt_renderer.hh:75-77).
-//
-// render() never blocks the host, like the reference's (src/rt_renderer.cc:84-133, src/stage.cc:35-76): every device has
-// one stream per frame slot; a device's path tracing and the peer copy of its partial frame go onto its slot stream, the
-// display device's slot stream waits for those streams (trhip_stream_wait_peer = the `dependencies` the reference hands
-// from stage to stage), then stitches every partial in one launch and tonemaps.  The next frame of a slot starts on a
-// non-display device only after the display device has stitched the slot's previous frame (the receive buffer is free
-// again) - a stream dependency as well.  Frame slots (MAX_FRAMES_IN_FLIGHT, src/context.hh:26) work with any number of
-// devices.
+// post_processing_renderer (src/post_processing_renderer.{hh,cc}): the one owner of the chain behind the path tracer.  make_plan is its
+// policy - which stages run and in which order, which G-buffer entries the path tracer has to write for them (set_gbuffer_spec), whether a
+// history binds the chain to frame order, whether the path tracer may still write the display image itself - as a pure function that needs
+// no device.  The object builds the stages of a plan and the images that belong to the chain rather than to a frame slot's path tracing
+// (the TAA input, the destination G-buffer, the full and the composed images), keeps the previous-camera record and runs the chain for a
+// slot on a stream.  The renderer in front of it asks four things: alloc_targets per slot, chain.frame_order, chain.fused_tonemap, run.
 //==============================================================================
-template<typename Pipeline>
-class basic_rt_renderer
+class post_processing_renderer
 {
 public:
-    struct options: path_tracer_stage::options
+    struct options
     {
         tonemap_stage::options tonemap;
-        scene_stage::options scene;         // acceleration-structure strategy and dynamic instances of every device's scene stage
-        bool accumulate = false;
-        // Frame slots: frame i renders, is gathered and tonemapped on the streams of slot i % N while its predecessors are
-        // still running; `display` and finish_frame() refer to the frame render() was last called for, frame_slots[k] to
-        // the others.
-        int max_frames_in_flight = 1;
-        // Frames per launch: B > 1 makes every render() call B consecutive frames (trhip_pt_set_frame_batch): every image holds
-        // B * active_viewport_count layers, frame-major, and `display` B tonemapped frames.  For frames that do not accumulate.
-        // Bigger launches: less of a frame is the tail of its kernels (the pipelined figure of bench.py uses two).
-        int frames_per_launch = 1;
         // --denoiser=bmfr (src/post_processing_renderer.cc:53-106): the path tracer also renders the gbuffer entries the stage reads, every
         // frame is a fresh frame (the sample counter keeps counting), the stage runs between stitch and tonemap - which is then a stage of
         // its own - and gets last frame's cameras as camera_pair.previous.  One device (or view shards): the feature targets of a pixel
@@ -752,6 +736,255 @@ public:
         struct looking_glass_options { looking_glass_composition_stage::options stage; uvec2 output_size{0, 0}; };
         std::optional<looking_glass_options> looking_glass;
     };
+    // what the policy depends on besides the chain's own options
+    struct facts
+    {
+        size_t device_count = 1;
+        size_t viewports = 1;               // active_viewport_count, before a viewport list compacts it
+        bool accumulate = false;
+        uint32_t frames_per_launch = 1;
+        int projection = 0;
+        bool path_tracer = true;            // the pipeline is path_tracer_stage
+    };
+    struct plan
+    {
+        std::vector<std::string> stages;    // in chain order, out of: bmfr, temporal, gbuffer+spatial, tonemap, taa, looking_glass
+        std::vector<std::string> targets;   // the G-buffer entries the path tracer writes besides colour
+        bool frame_order = false;           // a history (or the destination G-buffer the slots share) is one chain over all frame slots
+        bool fused_tonemap = false;         // nothing sits between the path tracer and the tonemap stage
+        size_t output_layers = 1;           // layers of `display`
+        size_t traced_viewports = 1;        // the viewports the path tracer renders (the length of a viewport list) ...
+        size_t traced_layers = 1;           // ... and the layers of its targets: that times the frames per launch
+        bool has(const char* stage) const { return std::find(stages.begin(), stages.end(), stage) != stages.end(); }
+    };
+
+    static plan make_plan(const options& opt, const facts& f)
+    {
+        const std::string count = std::to_string(f.device_count);
+        const uint32_t batch = f.frames_per_launch;
+        if(opt.bmfr)
+        {
+            if(f.device_count > 1)
+                throw std::runtime_error("rt_renderer: a denoiser with a pixel distribution of count " + count + " > 1 is not built: "
+                                         "the feature targets (diffuse, albedo, normal, pos, instance id, screen motion) would have to be gathered and stitched like colour");
+            if(f.accumulate || batch > 1) throw std::runtime_error("rt_renderer: a denoised frame is a fresh frame: no accumulation, one frame per launch");
+            if(!f.path_tracer) throw std::runtime_error("rt_renderer: the denoiser reads the path tracer's diffuse target");
+        }
+        const bool spatial_on = !opt.spatial_reprojection.empty();
+        if(!(opt.temporal_reprojection >= 0.0f) || !(opt.temporal_reprojection < 1.0f))
+            throw std::runtime_error("rt_renderer: the temporal reprojection ratio must be in [0, 1) (0 = off)");
+        const bool temporal_on = opt.temporal_reprojection > 0.0f;
+        if(spatial_on) check_viewport_list(opt.spatial_reprojection, f.viewports, "rt_renderer: spatial reprojection");
+        if(spatial_on || temporal_on)
+        {
+            const std::string which = spatial_on ? "spatial reprojection" : "temporal reprojection";
+            if(f.device_count > 1)
+                throw std::runtime_error("rt_renderer: " + which + " with a distribution of count " + count + " > 1: the stages read the "
+                                         "G-buffer of whole viewports on one device, gathering it from several is not built; use one device");
+            if(opt.bmfr) throw std::runtime_error("rt_renderer: " + which + " together with a denoiser: a chain of reprojection and a denoiser is not built");
+            if(batch > 1) throw std::runtime_error("rt_renderer: " + which + ": a reprojected frame is one frame, frames per launch must be 1");
+            if(temporal_on && f.accumulate) throw std::runtime_error("rt_renderer: temporal reprojection blends the previous frame into a fresh frame: no accumulation");
+        }
+        if(opt.taa)
+        {
+            if(opt.taa->sequence_length < 1) throw std::runtime_error("rt_renderer: taa: the length of the jitter sequence must be positive");
+            if(f.device_count > 1)
+                throw std::runtime_error("rt_renderer: taa with a pixel distribution of count " + count + " > 1: the stage reads screen motion, "
+                                         "pos and instance id of whole viewports on one device, gathering them from several is not built; use one device");
+            if(f.accumulate) throw std::runtime_error("rt_renderer: taa blends a fresh, jittered frame into its history: no accumulation");
+            if(batch > 1) throw std::runtime_error("rt_renderer: taa: an antialiased frame is one frame (the jitter steps between frames), frames per launch must be 1");
+            if(spatial_on || temporal_on) throw std::runtime_error("rt_renderer: taa together with spatial / temporal reprojection: a chain of reprojection and taa is not built");
+            if(f.projection == 2)
+                throw std::runtime_error("rt_renderer: taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
+                                         "which an equirectangular camera does not have");
+            if(!f.path_tracer) throw std::runtime_error("rt_renderer: taa reads the path tracer's screen_motion target");
+        }
+        if(opt.looking_glass)
+        {
+            if(f.device_count > 1)
+                throw std::runtime_error("rt_renderer: a Looking Glass output with a pixel distribution of count " + count + " > 1: the composition "
+                                         "stage reads every view of the light field on one device, the views would have to be gathered first, which is not built; use one device");
+            if(batch > 1) throw std::runtime_error("rt_renderer: a Looking Glass output: a composed frame is one frame, frames per launch must be 1");
+            if(f.projection != 0) throw std::runtime_error("rt_renderer: a Looking Glass output: the rig's cameras are perspective cameras");
+            if(opt.looking_glass->stage.viewport_count != f.viewports)
+                throw std::runtime_error("rt_renderer: a Looking Glass output of " + std::to_string(opt.looking_glass->stage.viewport_count) + " views over " +
+                                         std::to_string(f.viewports) + " viewports");
+        }
+        plan p;
+        if(opt.bmfr) p.stages.push_back("bmfr");
+        if(temporal_on) p.stages.push_back("temporal");
+        if(spatial_on) p.stages.push_back("gbuffer+spatial");
+        p.stages.push_back("tonemap");
+        if(opt.taa) p.stages.push_back("taa");
+        if(opt.looking_glass) p.stages.push_back("looking_glass");
+        if(opt.bmfr) p.targets = {"diffuse", "albedo", "normal", "pos", "screen_motion", "instance_id"};
+        else if(opt.taa) p.targets = {"screen_motion", "pos", "instance_id"};
+        else if(spatial_on || temporal_on) { p.targets = {"normal", "pos", "instance_id"}; if(temporal_on) p.targets.push_back("screen_motion"); }
+        p.frame_order = opt.bmfr || temporal_on || spatial_on || opt.taa;
+        p.fused_tonemap = f.path_tracer && f.device_count == 1 && p.stages.size() == 1;
+        p.output_layers = f.viewports * batch;
+        p.traced_viewports = spatial_on ? opt.spatial_reprojection.size() : f.viewports;
+        p.traced_layers = p.traced_viewports * batch;
+        return p;
+    }
+
+    // `dev`: the display device; `slots`: the frame slots; `cameras`: scene_data::cameras of the scene the devices hold
+    post_processing_renderer(device& dev, uvec2 size, const options& opt, const plan& chain, size_t slots, int projection, float min_ray_dist,
+                             const std::vector<uint8_t>& cameras)
+    : dev(&dev), size(size), chain(chain), images(slots), last_cameras(cameras), current_cameras(cameras)
+    {
+        const size_t layer_px = size_t(size.x) * size.y, display_bytes = layer_px * 16 * chain.output_layers;
+        const uint32_t layers = (uint32_t)chain.traced_layers;
+        tonemap = std::make_unique<tonemap_stage>(dev, opt.tonemap);
+        if(chain.has("looking_glass"))
+        {
+            const uvec2 os = opt.looking_glass->output_size;
+            lkg = std::make_unique<looking_glass_composition_stage>(dev, size, os, opt.looking_glass->stage);
+            for(slot_images& im: images) { im.composed = dev.alloc(size_t(os.x) * os.y * 16); im.composed8 = dev.alloc(size_t(os.x) * os.y * 4); }
+        }
+        if(chain.has("bmfr")) bmfr = std::make_unique<bmfr_stage>(dev, trhip_bmfr_features{}, size, layers, *opt.bmfr);
+        if(chain.has("temporal"))
+            temporal = std::make_unique<temporal_reprojection_stage>(dev, size, layers, temporal_reprojection_stage::options{opt.temporal_reprojection});
+        if(chain.has("gbuffer+spatial"))
+        {
+            for(slot_images& im: images) { im.full = dev.alloc(display_bytes); check(trhip_memset(dev.h, im.full, 0, display_bytes, nullptr)); }
+            spatial = std::make_unique<spatial_reprojection_stage>(dev, size, (uint32_t)chain.output_layers, opt.spatial_reprojection);
+            gbuffer = std::make_unique<gbuffer_stage>(dev, size, projection, min_ray_dist);
+            const size_t dpx = layer_px * spatial->destinations.size();
+            destination_targets.normal = dev.alloc(dpx * 8); destination_targets.pos = dev.alloc(dpx * 16); destination_targets.instance_id = dev.alloc(dpx * 4);
+        }
+        if(chain.has("taa"))
+        {
+            taa_input = dev.alloc(display_bytes);
+            taa_stage::options to;
+            to.blending_ratio = 1.0f / (float)opt.taa->sequence_length; to.gamma = opt.tonemap.gamma;
+            to.edge_dilation = opt.taa->edge_dilation; to.anti_shimmer = opt.taa->anti_shimmer; to.projection = projection;
+            taa = std::make_unique<taa_stage>(dev, size, layers, to);
+        }
+        dev.sync();
+    }
+    post_processing_renderer(const post_processing_renderer&) = delete;
+    ~post_processing_renderer()
+    {
+        bmfr.reset(); temporal.reset(); spatial.reset(); taa.reset(); lkg.reset();
+        for(void* p: {taa_input, destination_targets.normal, destination_targets.pos, destination_targets.instance_id}) if(p) dev->free(p);
+        for(slot_images& im: images) for(void* p: {im.full, im.composed, im.composed8}) if(p) dev->free(p);
+    }
+
+    // "allocate these targets per slot": the G-buffer entries of the plan next to a slot's colour target, and their release
+    void alloc_targets(trhip_pt_targets& t) const
+    {
+        const size_t px = size_t(size.x) * size.y * chain.traced_layers;
+        for(const std::string& name: chain.targets) t.*target(name).member = dev->alloc(px * target(name).bytes_per_pixel);
+    }
+    void free_targets(trhip_pt_targets& t) const
+    {
+        for(const std::string& name: chain.targets) { void*& p = t.*target(name).member; if(p) dev->free(p); p = nullptr; }
+    }
+
+    // The scene's cameras changed (`s.cameras`); a whole scene update may bring its own previous cameras.
+    void cameras_changed(const scene_data& s, bool whole_scene)
+    {
+        current_cameras = s.cameras;
+        if(whole_scene && !s.previous_cameras.empty()) uploaded_previous_cameras = s.previous_cameras;
+    }
+
+    // In front of a frame's path tracing: camera_pair.previous on the device = the cameras of the frame before this one.  `wait` is called
+    // before the record changes (frames in flight read the cameras they were enqueued with).
+    template<typename Wait>
+    void begin_frame(scene_stage& scene_update, Wait&& wait)
+    {
+        if(!(bmfr || temporal || taa)) return;
+        if(last_cameras != uploaded_previous_cameras)
+        {
+            wait();
+            scene_update.set_previous_cameras(last_cameras.data(), (uint32_t)(last_cameras.size() / 320));
+            uploaded_previous_cameras = last_cameras;
+        }
+        last_cameras = current_cameras;
+    }
+
+    // The chain on slot k's images (src/post_processing_renderer.cc:53-106): `t` the slot's targets with its colour, `display` its display
+    // image; `run_tonemap` false: the path tracer wrote the display image itself.
+    void run(size_t k, const trhip_pt_targets& t, void* display, bool run_tonemap, uint32_t frame_index, void* stream)
+    {
+        slot_images& im = images[k];
+        if(bmfr)
+        {
+            bmfr->features = trhip_bmfr_features{t.color, t.diffuse, t.albedo, t.normal, t.pos, t.screen_motion, t.instance_id};
+            bmfr->run(frame_index, stream);
+        }
+        const void* final_color = t.color;
+        if(temporal) temporal->run(trhip_reprojection_images{t.color, t.normal, t.pos, t.instance_id, t.screen_motion}, stream);
+        if(spatial)
+        {
+            gbuffer->run(spatial->destinations, destination_targets, stream);
+            spatial->run(trhip_reprojection_images{t.color, t.normal, t.pos, t.instance_id, nullptr},
+                         trhip_reprojection_images{nullptr, destination_targets.normal, destination_targets.pos, destination_targets.instance_id, nullptr}, im.full, stream);
+            final_color = im.full;
+        }
+        if(run_tonemap) tonemap->run(final_color, taa ? taa_input : display, size, (uint32_t)chain.output_layers, stream);
+        if(taa) taa->run(trhip_taa_images{taa_input, display, t.screen_motion, t.pos, t.instance_id}, stream);
+        if(lkg) lkg->run(display, im.composed, im.composed8, stream);
+    }
+
+    struct slot_images { void* full = nullptr; void* composed = nullptr; void* composed8 = nullptr; };   // spatial reprojection: the colour of every viewport in natural order; a Looking Glass output: the panel's image
+    device* dev;
+    uvec2 size;
+    plan chain;
+    std::vector<slot_images> images;                            // one per frame slot
+    std::unique_ptr<tonemap_stage> tonemap;
+    std::unique_ptr<bmfr_stage> bmfr;                           // options.bmfr
+    std::unique_ptr<temporal_reprojection_stage> temporal;      // options.temporal_reprojection
+    std::unique_ptr<spatial_reprojection_stage> spatial;        // options.spatial_reprojection
+    std::unique_ptr<gbuffer_stage> gbuffer;
+    std::unique_ptr<taa_stage> taa;                             // options.taa
+    std::unique_ptr<looking_glass_composition_stage> lkg;       // options.looking_glass
+    void* taa_input = nullptr;                                  // the tonemap stage's output when taa runs behind it (the stage writes `display`)
+    trhip_gbuffer_targets destination_targets = {};             // the G-buffer of the viewports that are reprojected, shared by the slots
+    std::vector<uint8_t> last_cameras, current_cameras, uploaded_previous_cameras;   // camera_data of the last frame rendered / of the scene as it is / camera_pair.previous on the device
+
+private:
+    struct target_info { const char* name; void* trhip_pt_targets::* member; size_t bytes_per_pixel; };
+    static const target_info& target(const std::string& name)
+    {
+        static const target_info table[] = {{"diffuse", &trhip_pt_targets::diffuse, 16}, {"albedo", &trhip_pt_targets::albedo, 16}, {"normal", &trhip_pt_targets::normal, 8},
+                                            {"pos", &trhip_pt_targets::pos, 16}, {"screen_motion", &trhip_pt_targets::screen_motion, 8}, {"instance_id", &trhip_pt_targets::instance_id, 4}};
+        for(const target_info& t: table) if(name == t.name) return t;
+        throw std::runtime_error("post_processing_renderer: no G-buffer entry " + name);
+    }
+};
+
+//==============================================================================
+// rt_renderer<Pipeline> (src/rt_renderer.hh:28-77): all devices in one process, like the reference.  Pipeline is
+// path_tracer_stage or direct_stage (the reference instantiates the template for those, src/rt_renderer.cc:410-412);
+// `rt_renderer` and `direct_renderer` below are the two instantiations (src/rt_renderer.hh:75-77).
+//
+// render() never blocks the host, like the reference's (src/rt_renderer.cc:84-133, src/stage.cc:35-76): every device has
+// one stream per frame slot; a device's path tracing and the peer copy of its partial frame go onto its slot stream, the
+// display device's slot stream waits for those streams (trhip_stream_wait_peer = the `dependencies` the reference hands
+// from stage to stage), then stitches every partial in one launch and tonemaps.  The next frame of a slot starts on a
+// non-display device only after the display device has stitched the slot's previous frame (the receive buffer is free
+// again) - a stream dependency as well.  Frame slots (MAX_FRAMES_IN_FLIGHT, src/context.hh:26) work with any number of
+// devices.
+//==============================================================================
+template<typename Pipeline>
+class basic_rt_renderer
+{
+public:
+    struct options: path_tracer_stage::options, post_processing_renderer::options     // the chain's options keep their spelling: opt.bmfr, opt.taa, ...
+    {
+        scene_stage::options scene;         // acceleration-structure strategy and dynamic instances of every device's scene stage
+        bool accumulate = false;
+        // Frame slots: frame i renders, is gathered and tonemapped on the streams of slot i % N while its predecessors are
+        // still running; `display` and finish_frame() refer to the frame render() was last called for, frame_slots[k] to
+        // the others.
+        int max_frames_in_flight = 1;
+        // Frames per launch: B > 1 makes every render() call B consecutive frames (trhip_pt_set_frame_batch): every image holds
+        // B * active_viewport_count layers, frame-major, and `display` B tonemapped frames.  For frames that do not accumulate.
+        // Bigger launches: less of a frame is the tail of its kernels (the pipelined figure of bench.py uses two).
+        int frames_per_launch = 1;
+    };
 
     // `devices`: HIP device index per logical device (repeat an index for --fake-devices); device 0 displays.
     basic_rt_renderer(const std::vector<int>& devices, const scene_data& scene, uvec2 size, options opt)
@@ -765,60 +998,16 @@ public:
         batch = (uint32_t)std::max(this->opt.frames_per_launch, 1);
         if(batch > 1 && this->opt.accumulate)
             throw std::runtime_error("rt_renderer: accumulating frames depend on each other, frames per launch must be 1");
-        if(this->opt.bmfr)
-        {
-            if(devices.size() > 1)
-                throw std::runtime_error("rt_renderer: a denoiser with a pixel distribution of count " + std::to_string(devices.size()) + " > 1 is not built: "
-                                         "the feature targets (diffuse, albedo, normal, pos, instance id, screen motion) would have to be gathered and stitched like colour");
-            if(this->opt.accumulate || batch > 1) throw std::runtime_error("rt_renderer: a denoised frame is a fresh frame: no accumulation, one frame per launch");
-            if(!std::is_same<Pipeline, path_tracer_stage>::value) throw std::runtime_error("rt_renderer: the denoiser reads the path tracer's diffuse target");
-        }
-        const bool spatial_on = !this->opt.spatial_reprojection.empty();
-        if(!(this->opt.temporal_reprojection >= 0.0f) || !(this->opt.temporal_reprojection < 1.0f))
-            throw std::runtime_error("rt_renderer: the temporal reprojection ratio must be in [0, 1) (0 = off)");
-        const bool temporal_on = this->opt.temporal_reprojection > 0.0f;
-        if(spatial_on) check_viewport_list(this->opt.spatial_reprojection, this->opt.active_viewport_count, "rt_renderer: spatial reprojection");
-        if(spatial_on || temporal_on)
-        {
-            const std::string which = spatial_on ? "spatial reprojection" : "temporal reprojection";
-            if(devices.size() > 1)
-                throw std::runtime_error("rt_renderer: " + which + " with a distribution of count " + std::to_string(devices.size()) + " > 1: the stages read the "
-                                         "G-buffer of whole viewports on one device, gathering it from several is not built; use one device");
-            if(this->opt.bmfr) throw std::runtime_error("rt_renderer: " + which + " together with a denoiser: a chain of reprojection and a denoiser is not built");
-            if(batch > 1) throw std::runtime_error("rt_renderer: " + which + ": a reprojected frame is one frame, frames per launch must be 1");
-            if(temporal_on && this->opt.accumulate) throw std::runtime_error("rt_renderer: temporal reprojection blends the previous frame into a fresh frame: no accumulation");
-        }
-        if(this->opt.taa)
-        {
-            if(this->opt.taa->sequence_length < 1) throw std::runtime_error("rt_renderer: taa: the length of the jitter sequence must be positive");
-            if(devices.size() > 1)
-                throw std::runtime_error("rt_renderer: taa with a pixel distribution of count " + std::to_string(devices.size()) + " > 1: the stage reads screen motion, "
-                                         "pos and instance id of whole viewports on one device, gathering them from several is not built; use one device");
-            if(this->opt.accumulate) throw std::runtime_error("rt_renderer: taa blends a fresh, jittered frame into its history: no accumulation");
-            if(batch > 1) throw std::runtime_error("rt_renderer: taa: an antialiased frame is one frame (the jitter steps between frames), frames per launch must be 1");
-            if(spatial_on || temporal_on) throw std::runtime_error("rt_renderer: taa together with spatial / temporal reprojection: a chain of reprojection and taa is not built");
-            if(this->opt.projection == 2)
-                throw std::runtime_error("rt_renderer: taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
-                                         "which an equirectangular camera does not have");
-            if(!std::is_same<Pipeline, path_tracer_stage>::value) throw std::runtime_error("rt_renderer: taa reads the path tracer's screen_motion target");
-        }
-        if(this->opt.looking_glass)
-        {
-            if(devices.size() > 1)
-                throw std::runtime_error("rt_renderer: a Looking Glass output with a pixel distribution of count " + std::to_string(devices.size()) + " > 1: the composition "
-                                         "stage reads every view of the light field on one device, the views would have to be gathered first, which is not built; use one device");
-            if(batch > 1) throw std::runtime_error("rt_renderer: a Looking Glass output: a composed frame is one frame, frames per launch must be 1");
-            if(this->opt.projection != 0) throw std::runtime_error("rt_renderer: a Looking Glass output: the rig's cameras are perspective cameras");
-            if(this->opt.looking_glass->stage.viewport_count != this->opt.active_viewport_count)
-                throw std::runtime_error("rt_renderer: a Looking Glass output of " + std::to_string(this->opt.looking_glass->stage.viewport_count) + " views over " +
-                                         std::to_string(this->opt.active_viewport_count) + " viewports");
-        }
+        post_processing_renderer::facts facts;
+        facts.device_count = devices.size(); facts.viewports = this->opt.active_viewport_count; facts.accumulate = this->opt.accumulate;
+        facts.frames_per_launch = batch; facts.projection = this->opt.projection; facts.path_tracer = std::is_same<Pipeline, path_tracer_stage>::value;
+        const post_processing_renderer::plan chain = post_processing_renderer::make_plan(this->opt, facts);
         per_device.resize(devices.size());
         std::vector<double> ratios(devices.size(), 1.0 / devices.size());
         double cumulative = 0;
-        output_layers = this->opt.active_viewport_count * batch;                                  // layers of `display`
-        if(spatial_on) this->opt.active_viewport_count = this->opt.spatial_reprojection.size();  // the path tracer's layers: the active viewports, compact
-        const size_t layers = this->opt.active_viewport_count * batch;
+        output_layers = chain.output_layers;                         // layers of `display`
+        this->opt.active_viewport_count = chain.traced_viewports;    // the path tracer's layers: all viewports, or the active ones of a viewport list, compact
+        const size_t layers = chain.traced_layers;
         display_bytes = size_t(size.x) * size.y * 16 * output_layers;
         for(size_t i = 0; i < devices.size(); ++i)
         {
@@ -844,7 +1033,7 @@ public:
                 sl.ray_tracer = std::make_unique<Pipeline>(*d.dev, *d.scene_update, sl.color, po);
                 if(n_slots > 1) { sl.ray_tracer->set_frame_slots(n_slots); }   // the frames in flight fill the chip between them
                 if(batch > 1) sl.ray_tracer->set_frame_batch(batch);
-                if(spatial_on)
+                if(!this->opt.spatial_reprojection.empty())
                 {   // the list as arithmetic runs, one stage per run (usually one): layer l shows viewport list[l], its camera and its RNG stream
                     uint32_t first = 0;
                     for(const viewport_run& r: viewport_runs(this->opt.spatial_reprojection))
@@ -868,115 +1057,32 @@ public:
         frame_slots.resize((size_t)n_slots);
         for(frame_slot& fs: frame_slots) fs.display = per_device[0].dev->alloc(display_bytes);
         display = frame_slots[0].display;
-        tonemap = std::make_unique<tonemap_stage>(*per_device[0].dev, this->opt.tonemap);
+        post = std::make_unique<post_processing_renderer>(*per_device[0].dev, size, this->opt, chain, frame_slots.size(), this->opt.projection, this->opt.min_ray_dist, scene.cameras);
+        tonemap = post->tonemap.get();
+        composed = post->images[0].composed; composed8 = post->images[0].composed8;
+        for(slot_data& sl: per_device[0].slots) { sl.targets.color = sl.color; post->alloc_targets(sl.targets); }
         // One device: nothing sits between the path tracer and the tonemap stage (no transfer, no stitch), and the stage writes the slot's
         // display image while it writes its colour target - the same bits without a second pass over the frame.  TRHIP_FUSED_TONEMAP=0: off.
         const char* fe = getenv("TRHIP_FUSED_TONEMAP");
-        fused_tonemap = std::is_same<Pipeline, path_tracer_stage>::value && per_device.size() == 1 && !(fe && atoi(fe) == 0) && !this->opt.bmfr && !spatial_on && !temporal_on && !this->opt.taa && !this->opt.looking_glass;
-        if(this->opt.looking_glass)
-        {
-            device& d0 = *per_device[0].dev;
-            const uvec2 os = this->opt.looking_glass->output_size;
-            lkg = std::make_unique<looking_glass_composition_stage>(d0, size, os, this->opt.looking_glass->stage);
-            for(frame_slot& fs: frame_slots) { fs.composed = d0.alloc(size_t(os.x) * os.y * 16); fs.composed8 = d0.alloc(size_t(os.x) * os.y * 4); }
-            composed = frame_slots[0].composed; composed8 = frame_slots[0].composed8;
-        }
-        if(this->opt.bmfr)
-        {
-            device& d0 = *per_device[0].dev;
-            const size_t px = size_t(size.x) * size.y * layers;
-            for(slot_data& sl: per_device[0].slots)
-            {
-                trhip_pt_targets& t = sl.targets;
-                t.color = sl.color;
-                t.diffuse = d0.alloc(px * 16); t.albedo = d0.alloc(px * 16); t.pos = d0.alloc(px * 16);
-                t.normal = d0.alloc(px * 8); t.screen_motion = d0.alloc(px * 8); t.instance_id = d0.alloc(px * 4);
-            }
-            const trhip_pt_targets& t0 = per_device[0].slots[0].targets;
-            bmfr = std::make_unique<bmfr_stage>(d0, trhip_bmfr_features{t0.color, t0.diffuse, t0.albedo, t0.normal, t0.pos, t0.screen_motion, t0.instance_id},
-                                                size, (uint32_t)layers, *this->opt.bmfr);
-            last_cameras = scene.cameras;
-            current_cameras = scene.cameras;
-        }
-        if(spatial_on || temporal_on)
-        {
-            device& d0 = *per_device[0].dev;
-            const size_t layer_px = size_t(size.x) * size.y, px = layer_px * layers;
-            for(slot_data& sl: per_device[0].slots)
-            {
-                trhip_pt_targets& t = sl.targets;
-                t.color = sl.color;
-                t.pos = d0.alloc(px * 16); t.normal = d0.alloc(px * 8); t.instance_id = d0.alloc(px * 4);
-                if(temporal_on) t.screen_motion = d0.alloc(px * 8);
-                if(spatial_on) { sl.full = d0.alloc(display_bytes); check(trhip_memset(d0.h, sl.full, 0, display_bytes, nullptr)); }
-            }
-            if(temporal_on)
-            {
-                temporal = std::make_unique<temporal_reprojection_stage>(d0, size, (uint32_t)layers, temporal_reprojection_stage::options{this->opt.temporal_reprojection});
-                last_cameras = scene.cameras;
-                current_cameras = scene.cameras;
-            }
-            if(spatial_on)
-            {
-                spatial = std::make_unique<spatial_reprojection_stage>(d0, size, (uint32_t)output_layers, this->opt.spatial_reprojection);
-                gbuffer = std::make_unique<gbuffer_stage>(d0, size, this->opt.projection, this->opt.min_ray_dist);
-                const size_t dpx = layer_px * spatial->destinations.size();
-                destination_targets.normal = d0.alloc(dpx * 8); destination_targets.pos = d0.alloc(dpx * 16); destination_targets.instance_id = d0.alloc(dpx * 4);
-            }
-            d0.sync();
-        }
-        if(this->opt.taa)
-        {
-            device& d0 = *per_device[0].dev;
-            const size_t px = size_t(size.x) * size.y * layers;
-            for(slot_data& sl: per_device[0].slots)
-            {
-                trhip_pt_targets& t = sl.targets;
-                t.color = sl.color;
-                if(!t.pos) t.pos = d0.alloc(px * 16);
-                if(!t.screen_motion) t.screen_motion = d0.alloc(px * 8);
-                if(!t.instance_id) t.instance_id = d0.alloc(px * 4);
-            }
-            taa_input = d0.alloc(display_bytes);
-            taa_stage::options to;
-            to.blending_ratio = 1.0f / (float)this->opt.taa->sequence_length; to.gamma = this->opt.tonemap.gamma;
-            to.edge_dilation = this->opt.taa->edge_dilation; to.anti_shimmer = this->opt.taa->anti_shimmer; to.projection = this->opt.projection;
-            taa = std::make_unique<taa_stage>(d0, size, (uint32_t)layers, to);
-            last_cameras = scene.cameras;
-            current_cameras = scene.cameras;
-            d0.sync();
-        }
+        fused_tonemap = chain.fused_tonemap && !(fe && atoi(fe) == 0);
         fused_info.assign(frame_slots.size(), trhip_tonemap_info{-1, 0.0f, 0.0f, 0});     // what each slot's stage was last told: render() keeps it current
     }
 
     ~basic_rt_renderer()
     {
         finish_all();
-        bmfr.reset();
-        temporal.reset();
-        spatial.reset();
-        taa.reset();
-        lkg.reset();
-        if(taa_input) per_device[0].dev->free(taa_input);
-        for(void* p: {destination_targets.normal, destination_targets.pos, destination_targets.instance_id}) if(p) per_device[0].dev->free(p);
+        for(slot_data& sl: per_device[0].slots) post->free_targets(sl.targets);
+        post.reset();
         for(size_t i = 0; i < per_device.size(); ++i)
             for(slot_data& sl: per_device[i].slots)
             {
                 sl.ray_tracer.reset();
                 sl.extra_tracers.clear();
-                if(sl.full) per_device[i].dev->free(sl.full);
-                for(void* p: {sl.targets.diffuse, sl.targets.albedo, sl.targets.pos, sl.targets.normal, sl.targets.screen_motion, sl.targets.instance_id})
-                    if(p) per_device[i].dev->free(p);
                 if(sl.gbuffer_copy) per_device[0].dev->free(sl.gbuffer_copy);
                 per_device[i].dev->free(sl.color);
                 per_device[i].dev->destroy_stream(sl.stream);
             }
-        for(frame_slot& fs: frame_slots)
-        {
-            per_device[0].dev->free(fs.display);
-            if(fs.composed) per_device[0].dev->free(fs.composed);
-            if(fs.composed8) per_device[0].dev->free(fs.composed8);
-        }
+        for(frame_slot& fs: frame_slots) per_device[0].dev->free(fs.display);
     }
 
     void reset_accumulation(bool reset_sample_counter = false)
@@ -1007,8 +1113,7 @@ public:
     {
         finish_all();
         for(auto& d: per_device) d.scene_update->apply(s, rebuild);
-        current_cameras = s.cameras;
-        uploaded_previous_cameras = s.previous_cameras.empty() ? uploaded_previous_cameras : s.previous_cameras;
+        post->cameras_changed(s, true);
     }
 
     // Only the cameras changed (the jitter of a still scene stepped): scene_data::cameras go to every device.
@@ -1016,7 +1121,7 @@ public:
     {
         finish_all();
         for(auto& d: per_device) d.scene_update->update_cameras(s.cameras.data(), (uint32_t)(s.cameras.size() / 320));
-        current_cameras = s.cameras;
+        post->cameras_changed(s, false);
     }
 
     // rt_renderer::render (src/rt_renderer.cc:84-133): ray tracers -> transfers -> stitch -> tonemap.  Enqueues only.
@@ -1025,7 +1130,6 @@ public:
         const size_t k = (frame_index / batch) % frame_slots.size();
         current_slot = (int)k;
         const uint32_t layers = (uint32_t)opt.active_viewport_count * batch;
-        const bool reprojection = temporal || spatial;
         device& display_device = *per_device[0].dev;
         void* const display_stream = per_device[0].slots[k].stream;
         if(fused_tonemap)
@@ -1051,16 +1155,7 @@ public:
             }
             if(i != 0)   // the slot's previous frame has been stitched on the display device: its receive buffer is free
                 check(trhip_stream_wait_peer(d.dev->h, sl.stream, display_device.h, display_stream));
-            if(bmfr || temporal || taa)
-            {   // camera_pair.previous = the cameras of the frame before this one
-                if(last_cameras != uploaded_previous_cameras)
-                {   // frames in flight read the cameras they were enqueued with: they finish before the record changes
-                    if(frame_slots.size() > 1) finish_all();
-                    d.scene_update->set_previous_cameras(last_cameras.data(), (uint32_t)(last_cameras.size() / 320));
-                    uploaded_previous_cameras = last_cameras;
-                }
-                last_cameras = current_cameras;
-            }
+            post->begin_frame(*d.scene_update, [&] { if(frame_slots.size() > 1) finish_all(); });
             const uvec2 ts = get_distribution_target_size(d.dist);
             if(!sl.runs.empty())
             {   // a viewport list: every run of it into its layers of the compact targets
@@ -1073,7 +1168,7 @@ public:
                     check(trhip_pt_render_targets(r.stage->pt, &t, ts.x, ts.y, r.count, sl.stream));
                 }
             }
-            else if(bmfr || reprojection || taa) check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
+            else if(!post->chain.targets.empty()) check(trhip_pt_render_targets(sl.ray_tracer->pt, &sl.targets, ts.x, ts.y, layers, sl.stream));
             else sl.ray_tracer->run(sl.stream);
             if(i != 0) check(trhip_copy_peer(display_device.h, sl.gbuffer_copy, d.dev->h, sl.color, d.target_bytes(layers), sl.stream));
         }
@@ -1095,42 +1190,12 @@ public:
         }
         display = frame_slots[k].display;
         void* post_stream = display_stream;
-        if((bmfr || reprojection || taa) && frame_slots.size() > 1)
-        {   // the denoiser's / temporal stage's history is one chain over the frames of all slots: it runs in frame order on the display device's
-            // default stream (and so does the spatial stage, whose destination G-buffer the slots share)
+        if(post->chain.frame_order && frame_slots.size() > 1)
+        {   // a history is one chain over the frames of all slots: the chain runs in frame order on the display device's default stream
             check(trhip_stream_wait(display_device.h, nullptr, display_stream)); post_stream = nullptr;
         }
-        if(bmfr)
-        {
-            const trhip_pt_targets& t = per_device[0].slots[k].targets;
-            bmfr->features = trhip_bmfr_features{t.color, t.diffuse, t.albedo, t.normal, t.pos, t.screen_motion, t.instance_id};
-            bmfr->run(frame_index, post_stream);
-        }
-        const void* final_color = per_device[0].slots[k].color;
-        if(reprojection)
-        {
-            const slot_data& sl = per_device[0].slots[k];
-            const trhip_pt_targets& t = sl.targets;
-            if(temporal) temporal->run(trhip_reprojection_images{t.color, t.normal, t.pos, t.instance_id, t.screen_motion}, post_stream);
-            if(spatial)
-            {
-                gbuffer->run(spatial->destinations, destination_targets, post_stream);
-                spatial->run(trhip_reprojection_images{t.color, t.normal, t.pos, t.instance_id, nullptr},
-                             trhip_reprojection_images{nullptr, destination_targets.normal, destination_targets.pos, destination_targets.instance_id, nullptr}, sl.full, post_stream);
-                final_color = sl.full;
-            }
-        }
-        if(!fused_tonemap) tonemap->run(final_color, taa ? taa_input : display, size, (uint32_t)output_layers, post_stream);
-        if(taa)
-        {
-            const trhip_pt_targets& t = per_device[0].slots[k].targets;
-            taa->run(trhip_taa_images{taa_input, display, t.screen_motion, t.pos, t.instance_id}, post_stream);
-        }
-        if(lkg)
-        {
-            composed = frame_slots[k].composed; composed8 = frame_slots[k].composed8;
-            lkg->run(display, composed, composed8, post_stream);
-        }
+        post->run(k, per_device[0].slots[k].targets, display, !fused_tonemap, frame_index, post_stream);
+        composed = post->images[k].composed; composed8 = post->images[k].composed8;
         if(post_stream != display_stream) check(trhip_stream_wait(display_device.h, display_stream, nullptr));
         frame_index += batch;
         accumulated_frames++;
@@ -1178,7 +1243,6 @@ public:
         struct run { Pipeline* stage; uint32_t first, count; };
         std::vector<run> runs;          // a viewport list: one stage per arithmetic run of it (ray_tracer is the first), its first layer and layer count
         std::vector<std::unique_ptr<Pipeline>> extra_tracers;   // ... the stages of the runs after the first
-        void* full = nullptr;           // spatial reprojection: the colour of every viewport in natural order (`color` holds the sources)
     };
     using run_data = typename slot_data::run;
     struct per_device_data
@@ -1191,7 +1255,7 @@ public:
         size_t target_bytes(size_t layers) const { const uvec2 ts = get_distribution_target_size(dist); return size_t(ts.x) * ts.y * 16 * layers; }
     };
     std::vector<per_device_data> per_device;
-    struct frame_slot { void* display = nullptr; void* composed = nullptr; void* composed8 = nullptr; };   // tonemapped RGBA32F on the display device; a Looking Glass output: the panel's image
+    struct frame_slot { void* display = nullptr; };   // tonemapped RGBA32F on the display device
     std::vector<frame_slot> frame_slots;   // options.max_frames_in_flight of them (at least one)
     int current_slot = -1;
     uint32_t batch = 1;                    // options.frames_per_launch
@@ -1200,19 +1264,11 @@ public:
     options opt;
     void* display = nullptr;          // frame_slots[current_slot].display
     size_t display_bytes = 0;
-    std::unique_ptr<tonemap_stage> tonemap;
-    std::unique_ptr<bmfr_stage> bmfr;      // options.bmfr
-    std::unique_ptr<temporal_reprojection_stage> temporal;      // options.temporal_reprojection
-    std::unique_ptr<spatial_reprojection_stage> spatial;        // options.spatial_reprojection
-    std::unique_ptr<gbuffer_stage> gbuffer;
-    std::unique_ptr<taa_stage> taa;                             // options.taa
-    std::unique_ptr<looking_glass_composition_stage> lkg;       // options.looking_glass
-    void* composed = nullptr;                                   // frame_slots[current_slot].composed: RGBA32F [output_size.y][output_size.x]
+    std::unique_ptr<post_processing_renderer> post;             // the chain behind the path tracer, on the display device
+    tonemap_stage* tonemap = nullptr;                           // post->tonemap
+    void* composed = nullptr;                                   // a Looking Glass output, the current slot's: RGBA32F [output_size.y][output_size.x]
     void* composed8 = nullptr;                                  // ... and the same frame as uint8 [..][..][4]
-    void* taa_input = nullptr;                                  // the tonemap stage's output when taa runs behind it (the stage writes `display`)
-    trhip_gbuffer_targets destination_targets = {};             // the G-buffer of the viewports that are reprojected, shared by the slots
-    size_t output_layers = 1;                                    // layers of `display` (every viewport; the path tracer renders opt.active_viewport_count)
-    std::vector<uint8_t> last_cameras, current_cameras, uploaded_previous_cameras;   // denoiser: camera_data of the last frame rendered / of the scene as it is / camera_pair.previous on the device
+    size_t output_layers = 1;                                   // layers of `display` (every viewport; the path tracer renders opt.active_viewport_count)
     bool fused_tonemap = false;
     std::vector<trhip_tonemap_info> fused_info;
     unsigned accumulated_frames = 0;

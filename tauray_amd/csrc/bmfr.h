@@ -12,12 +12,7 @@
 
 #include "common.h"
 
-struct trhip_device;
-
 namespace tr {
-
-int set_error(const std::string& msg);                 // api.hip
-int device_index(const trhip_device* dev);             // api.hip: the HIP device of a handle, -1 for null
 
 constexpr int BMFR_BLOCK_EDGE = 32;
 constexpr int BMFR_BLOCK_PIXELS = BMFR_BLOCK_EDGE * BMFR_BLOCK_EDGE;

@@ -6,13 +6,12 @@
 #include <string>
 
 #include "bmfr.h"
+#include "stage_host.h"
 #include "taps.h"
 #include "rng.h"
 
 namespace tr {
 namespace {
-
-#define BMFR_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 struct BmfrParams {
     int w, h, layers, bw, bh, channels, nc;
@@ -361,14 +360,12 @@ void launch_fit(int channels, uint blocks, const float* rows, float* weights, fl
 
 using namespace tr;
 
-struct trhip_bmfr {
-    int hip_device = 0;
+struct trhip_bmfr : StageHost<5> {      // an event before the frame and one behind each of the four passes
     int settings = 0, channels = 3;
     float noise = 1e-2f;
     uint32_t w = 0, h = 0, layers = 0, bw = 0, bh = 0;
     int cur = 0;                     // the histories a frame reads; it writes cur ^ 1
     bool have_history = false;
-    uint32_t frames = 0;
     f4* noisy[2][2] = {};
     f4* filt[2][2] = {};
     f2* normal[2] = {};
@@ -376,27 +373,9 @@ struct trhip_bmfr {
     f4* weighted[2] = {};
     float *rows = nullptr, *weights = nullptr, *minmax = nullptr;
     uint8_t* accept = nullptr;
-    hipEvent_t ev[5] = {};
     size_t pixels() const { return (size_t)w * h * layers; }
     size_t blocks() const { return (size_t)bw * bh * layers; }
 };
-
-#define BMFR_DEVCHK(idx) do { hipError_t e_ = hipSetDevice(idx); if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)
-
-static void bmfr_release(trhip_bmfr* b) {
-    for (int i = 0; i < 2; ++i) {
-        for (int j = 0; j < 2; ++j) { if (b->noisy[i][j]) (void)hipFree(b->noisy[i][j]); if (b->filt[i][j]) (void)hipFree(b->filt[i][j]); }
-        if (b->normal[i]) (void)hipFree(b->normal[i]);
-        if (b->pos[i]) (void)hipFree(b->pos[i]);
-        if (b->weighted[i]) (void)hipFree(b->weighted[i]);
-    }
-    if (b->rows) (void)hipFree(b->rows);
-    if (b->weights) (void)hipFree(b->weights);
-    if (b->minmax) (void)hipFree(b->minmax);
-    if (b->accept) (void)hipFree(b->accept);
-    for (hipEvent_t e : b->ev) if (e) (void)hipEventDestroy(e);
-    delete b;
-}
 
 extern "C" {
 
@@ -410,7 +389,7 @@ int trhip_bmfr_create(trhip_device* dev, const trhip_bmfr_options* opt, uint32_t
     if (width == 0 || height == 0 || layers == 0) return set_error("trhip_bmfr_create: zero width, height or layer count");
     if (width > 16384 || height > 16384 || layers > 4096) return set_error("trhip_bmfr_create: image too large");
     if (!dev) return set_error("trhip_bmfr_create: null trhip_device (no HIP device: there is no CPU fallback)");
-    BMFR_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     trhip_bmfr* b = new trhip_bmfr;
     b->hip_device = device_index(dev);
     b->settings = opt->settings;
@@ -419,8 +398,7 @@ int trhip_bmfr_create(trhip_device* dev, const trhip_bmfr_options* opt, uint32_t
     b->w = width; b->h = height; b->layers = layers;
     b->bw = (width + 31) / 32 + 1; b->bh = (height + 31) / 32 + 1;
     const size_t px = b->pixels(), nb = b->blocks();
-    hipError_t e = hipSuccess;
-    auto alloc = [&](auto*& p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc((void**)&p, bytes); if (e == hipSuccess) e = hipMemset(p, 0, bytes); } };
+    auto alloc = [&](auto*& p, size_t bytes) { b->alloc_zeroed(p, bytes); };
     for (int i = 0; i < 2; ++i) {
         alloc(b->noisy[i][0], px * sizeof(f4)); alloc(b->noisy[i][1], px * sizeof(f4));
         alloc(b->filt[i][0], px * sizeof(f4));
@@ -433,19 +411,10 @@ int trhip_bmfr_create(trhip_device* dev, const trhip_bmfr_options* opt, uint32_t
     alloc(b->weights, nb * b->channels * BMFR_FEATURES * sizeof(float));
     alloc(b->minmax, nb * 12 * sizeof(float));
     alloc(b->accept, px);
-    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipEventCreate(&b->ev[i]);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { bmfr_release(b); return set_error(std::string("trhip_bmfr_create: ") + hipGetErrorString(e)); }
-    *out = b;
-    return 0;
+    return stage_finish_create("trhip_bmfr_create", b, out);
 }
 
-void trhip_bmfr_destroy(trhip_bmfr* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->hip_device);
-    (void)hipDeviceSynchronize();
-    bmfr_release(b);
-}
+void trhip_bmfr_destroy(trhip_bmfr* b) { stage_destroy(b); }
 
 int trhip_bmfr_reset_history(trhip_bmfr* b) {
     if (!b) return set_error("trhip_bmfr_reset_history: null stage");
@@ -458,7 +427,7 @@ int trhip_bmfr_run(trhip_bmfr* b, const trhip_bmfr_features* f, uint32_t frame_c
     if (!f) return set_error("trhip_bmfr_run: null features");
     if (!f->color || !f->diffuse || !f->albedo || !f->normal || !f->pos || !f->screen_motion)
         return set_error("trhip_bmfr_run: color, diffuse, albedo, normal, pos and screen_motion are required (only instance_id may be null)");
-    BMFR_DEVCHK(b->hip_device);
+    DEVCHK(b->hip_device);
     hipStream_t st = (hipStream_t)stream;
     BmfrParams P{};
     P.w = (int)b->w; P.h = (int)b->h; P.layers = (int)b->layers; P.bw = (int)b->bw; P.bh = (int)b->bh;
@@ -480,16 +449,16 @@ int trhip_bmfr_run(trhip_bmfr* b, const trhip_bmfr_features* f, uint32_t frame_c
     P.rows = b->rows; P.weights = b->weights; P.minmax = b->minmax; P.accept = b->accept;
 
     const uint pixel_groups = (uint)((b->pixels() + 255) / 256);
-    BMFR_HIPCHK(hipEventRecord(b->ev[0], st));
+    HIPCHK(hipEventRecord(b->ev[0], st));
     hipLaunchKernelGGL(k_bmfr_preprocess, dim3(b->bw, b->bh * 4, b->layers), dim3(256), 0, st, P);
-    BMFR_HIPCHK(hipEventRecord(b->ev[1], st));
+    HIPCHK(hipEventRecord(b->ev[1], st));
     launch_fit<false>(b->channels, (uint)b->blocks(), b->rows, b->weights, b->minmax, P.bw, P.bh, frame_counter, b->noise, st);
-    BMFR_HIPCHK(hipEventRecord(b->ev[2], st));
+    HIPCHK(hipEventRecord(b->ev[2], st));
     hipLaunchKernelGGL(k_bmfr_weighted_sum, dim3(pixel_groups), dim3(256), 0, st, P);
-    BMFR_HIPCHK(hipEventRecord(b->ev[3], st));
+    HIPCHK(hipEventRecord(b->ev[3], st));
     hipLaunchKernelGGL(k_bmfr_accumulate_output, dim3(pixel_groups), dim3(256), 0, st, P);
-    BMFR_HIPCHK(hipEventRecord(b->ev[4], st));
-    BMFR_HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(b->ev[4], st));
+    HIPCHK(hipGetLastError());
     b->cur = nx;
     b->have_history = true;
     b->frames += 1;
@@ -497,15 +466,10 @@ int trhip_bmfr_run(trhip_bmfr* b, const trhip_bmfr_features* f, uint32_t frame_c
 }
 
 int trhip_bmfr_get_timings(trhip_bmfr* b, trhip_bmfr_timings* out) {
-    if (!b || !out) return set_error("trhip_bmfr_get_timings: null argument");
-    memset(out, 0, sizeof(*out));
-    out->frames = b->frames;
+    if (int r = stage_total_ms("trhip_bmfr_get_timings", b, out)) return r;
     if (b->frames == 0) return 0;
-    BMFR_DEVCHK(b->hip_device);
-    BMFR_HIPCHK(hipEventSynchronize(b->ev[4]));
     float* dst[4] = {&out->preprocess_ms, &out->fit_ms, &out->weighted_sum_ms, &out->accumulate_output_ms};
-    for (int i = 0; i < 4; ++i) BMFR_HIPCHK(hipEventElapsedTime(dst[i], b->ev[i], b->ev[i + 1]));
-    BMFR_HIPCHK(hipEventElapsedTime(&out->total_ms, b->ev[0], b->ev[4]));
+    for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(dst[i], b->ev[i], b->ev[i + 1]));
     return 0;
 }
 
@@ -514,9 +478,9 @@ int trhip_bmfr_fit_blocks(trhip_device* dev, uint32_t blocks, uint32_t channels,
     if (channels != 3 && channels != 6) return set_error("trhip_bmfr_fit_blocks: channels must be 3 or 6");
     if (blocks == 0) return 0;
     if (!matrix_dev || !weights_dev) return set_error("trhip_bmfr_fit_blocks: null matrix or weights");
-    BMFR_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     launch_fit<true>((int)channels, blocks, matrix_dev, weights_dev, nullptr, 1, 1, 0, 0.0f, (hipStream_t)stream);
-    BMFR_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -529,29 +493,25 @@ int trhip_bmfr_download(trhip_bmfr* b, int which, void* host, size_t bytes) {
         memcpy(host, table, sizeof(table));
         return 0;
     }
-    const size_t px = b->pixels(), nb = b->blocks();
-    const void* src = nullptr;
-    size_t size = 0;
-    const int c = b->cur;      // what the last frame wrote
-    switch (which) {
-        case TRHIP_BMFR_NOISY_DIFFUSE: src = b->noisy[c][0]; size = px * sizeof(f4); break;
-        case TRHIP_BMFR_NOISY_SPECULAR: src = b->noisy[c][1]; size = px * sizeof(f4); break;
-        case TRHIP_BMFR_FILTERED_DIFFUSE: src = b->filt[c][0]; size = px * sizeof(f4); break;
-        case TRHIP_BMFR_FILTERED_SPECULAR: src = b->filt[c][1]; size = px * sizeof(f4); break;
-        case TRHIP_BMFR_FEATURE_ROWS: src = b->rows; size = nb * (BMFR_FEATURES + b->channels) * BMFR_BLOCK_PIXELS * sizeof(float); break;
-        case TRHIP_BMFR_WEIGHTS: src = b->weights; size = nb * b->channels * BMFR_FEATURES * sizeof(float); break;
-        case TRHIP_BMFR_MIN_MAX: src = b->minmax; size = nb * 12 * sizeof(float); break;
-        case TRHIP_BMFR_ACCEPT_BITS: src = b->accept; size = px; break;
-        case TRHIP_BMFR_PREVIOUS_NORMAL: src = b->normal[c]; size = px * sizeof(f2); break;
-        case TRHIP_BMFR_PREVIOUS_POS: src = b->pos[c]; size = px * sizeof(f4); break;
-        default: return set_error("trhip_bmfr_download: unknown buffer");
-    }
-    if (!src) return set_error("trhip_bmfr_download: the stage has no such buffer (the filtered specular history exists under DIFFUSE_SPECULAR)");
-    if (bytes != size) return set_error("trhip_bmfr_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
-    BMFR_DEVCHK(b->hip_device);
-    BMFR_HIPCHK(hipDeviceSynchronize());
-    BMFR_HIPCHK(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
-    return 0;
+    return stage_download("trhip_bmfr_download", b, host, bytes, [&](const void*& src, size_t& size) {
+        const size_t px = b->pixels(), nb = b->blocks();
+        const int c = b->cur;      // what the last frame wrote
+        switch (which) {
+            case TRHIP_BMFR_NOISY_DIFFUSE: src = b->noisy[c][0]; size = px * sizeof(f4); break;
+            case TRHIP_BMFR_NOISY_SPECULAR: src = b->noisy[c][1]; size = px * sizeof(f4); break;
+            case TRHIP_BMFR_FILTERED_DIFFUSE: src = b->filt[c][0]; size = px * sizeof(f4); break;
+            case TRHIP_BMFR_FILTERED_SPECULAR: src = b->filt[c][1]; size = px * sizeof(f4); break;
+            case TRHIP_BMFR_FEATURE_ROWS: src = b->rows; size = nb * (BMFR_FEATURES + b->channels) * BMFR_BLOCK_PIXELS * sizeof(float); break;
+            case TRHIP_BMFR_WEIGHTS: src = b->weights; size = nb * b->channels * BMFR_FEATURES * sizeof(float); break;
+            case TRHIP_BMFR_MIN_MAX: src = b->minmax; size = nb * 12 * sizeof(float); break;
+            case TRHIP_BMFR_ACCEPT_BITS: src = b->accept; size = px; break;
+            case TRHIP_BMFR_PREVIOUS_NORMAL: src = b->normal[c]; size = px * sizeof(f2); break;
+            case TRHIP_BMFR_PREVIOUS_POS: src = b->pos[c]; size = px * sizeof(f4); break;
+            default: return set_error("trhip_bmfr_download: unknown buffer");
+        }
+        if (!src) return set_error("trhip_bmfr_download: the stage has no such buffer (the filtered specular history exists under DIFFUSE_SPECULAR)");
+        return 0;
+    });
 }
 
 }  // extern "C"

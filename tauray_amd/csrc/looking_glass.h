@@ -25,12 +25,7 @@
 
 #include "common.h"
 
-struct trhip_device;
-
 namespace tr {
-
-int set_error(const std::string& msg);                 // api.hip
-int device_index(const trhip_device* dev);             // api.hip
 
 constexpr int LKG_WAVE = 64;                     // a wave is 64 consecutive x of one output row ...
 constexpr int LKG_ROWS = 4;                      // ... and a workgroup four such rows

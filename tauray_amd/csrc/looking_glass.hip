@@ -8,12 +8,10 @@
 #include <string>
 
 #include "looking_glass.h"
+#include "stage_host.h"
 
 namespace tr {
 namespace {
-
-#define LKG_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-#define LKG_DEVCHK(idx) do { hipError_t e_ = hipSetDevice(idx); if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)
 
 struct LkgParams {
     int W, H;              // output
@@ -81,23 +79,14 @@ __global__ __launch_bounds__(LKG_WAVE * LKG_ROWS) void k_looking_glass(LkgParams
 
 using namespace tr;
 
-struct trhip_lkg {
+struct trhip_lkg : StageHost<> {
     trhip_device* dev = nullptr;
-    int hip_device = 0;
     uint32_t view_w = 0, view_h = 0, out_w = 0, out_h = 0;
     trhip_lkg_options opt = {};
     f4 cal = {};
     uint* indices = nullptr;
-    hipEvent_t ev[2] = {};
-    uint32_t frames = 0;
     size_t pixels() const { return (size_t)out_w * out_h; }
 };
-
-static void lkg_release(trhip_lkg* t) {
-    if (t->indices) (void)hipFree(t->indices);
-    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    delete t;
-}
 
 extern "C" {
 
@@ -111,37 +100,24 @@ int trhip_lkg_create(trhip_device* dev, const trhip_lkg_options* opt, uint32_t v
         return set_error("trhip_lkg_create: viewport_count " + std::to_string(opt->viewport_count) + " is not in 1..255 (a recorded view index is one byte)");
     if (!std::isfinite(opt->pitch) || !std::isfinite(opt->tilt) || !std::isfinite(opt->center)) return set_error("trhip_lkg_create: pitch, tilt and center must be finite");
     if (!dev) return set_error("trhip_lkg_create: null trhip_device (no HIP device: there is no CPU fallback)");
-    LKG_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     trhip_lkg* t = new trhip_lkg;
     t->dev = dev; t->hip_device = device_index(dev);
     t->view_w = view_w; t->view_h = view_h; t->out_w = out_w; t->out_h = out_h; t->opt = *opt;
     // looking_glass_composition_stage.cc:61-68, in float and in exactly this form
     t->cal = F4(opt->pitch, opt->tilt * opt->pitch, opt->pitch / (3.0f * (float)out_w), -opt->center);
     if (opt->invert) t->cal = F4(-t->cal.x, -t->cal.y, -t->cal.z, -t->cal.w);
-    hipError_t e = hipSuccess;
-    if (opt->record_view_indices) {
-        e = hipMalloc((void**)&t->indices, t->pixels() * 4);
-        if (e == hipSuccess) e = hipMemset(t->indices, 0, t->pixels() * 4);
-    }
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&t->ev[i]);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { lkg_release(t); return set_error(std::string("trhip_lkg_create: ") + hipGetErrorString(e)); }
-    *out = t;
-    return 0;
+    if (opt->record_view_indices) t->alloc_zeroed(t->indices, t->pixels() * 4);
+    return stage_finish_create("trhip_lkg_create", t, out);
 }
 
-void trhip_lkg_destroy(trhip_lkg* t) {
-    if (!t) return;
-    (void)hipSetDevice(t->hip_device);
-    (void)hipDeviceSynchronize();
-    lkg_release(t);
-}
+void trhip_lkg_destroy(trhip_lkg* t) { stage_destroy(t); }
 
 int trhip_lkg_run(trhip_lkg* t, const void* src, void* dst, void* dst_rgba8, void* stream) {
     if (!t) return set_error("trhip_lkg_run: null stage");
     if (!src) return set_error("trhip_lkg_run: null src");
     if (!dst && !dst_rgba8) return set_error("trhip_lkg_run: dst and dst_rgba8 are both null: the frame would go nowhere");
-    LKG_DEVCHK(t->hip_device);
+    DEVCHK(t->hip_device);
     LkgParams P{};
     P.W = (int)t->out_w; P.H = (int)t->out_h; P.w = (int)t->view_w; P.h = (int)t->view_h;
     P.views = (int)t->opt.viewport_count;
@@ -149,37 +125,28 @@ int trhip_lkg_run(trhip_lkg* t, const void* src, void* dst, void* dst_rgba8, voi
     P.src = (const float*)src; P.dst = (f4*)dst; P.dst8 = (uint*)dst_rgba8; P.indices = t->indices;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((t->out_w + LKG_WAVE - 1) / LKG_WAVE, (t->out_h + LKG_ROWS - 1) / LKG_ROWS), block(LKG_WAVE, LKG_ROWS);
-    LKG_HIPCHK(hipEventRecord(t->ev[0], st));
+    HIPCHK(hipEventRecord(t->ev[0], st));
     if (t->indices) hipLaunchKernelGGL((k_looking_glass<true>), grid, block, 0, st, P);
     else hipLaunchKernelGGL((k_looking_glass<false>), grid, block, 0, st, P);
-    LKG_HIPCHK(hipEventRecord(t->ev[1], st));
-    LKG_HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(t->ev[1], st));
+    HIPCHK(hipGetLastError());
     t->frames += 1;
     return 0;
 }
 
 int trhip_lkg_get_timings(trhip_lkg* t, trhip_lkg_timings* out) {
-    if (!t || !out) return set_error("trhip_lkg_get_timings: null argument");
-    memset(out, 0, sizeof(*out));
-    snprintf(out->name, sizeof(out->name), "looking glass composition");
-    out->frames = t->frames;
-    if (t->frames == 0) return 0;
-    LKG_DEVCHK(t->hip_device);
-    LKG_HIPCHK(hipEventSynchronize(t->ev[1]));
-    LKG_HIPCHK(hipEventElapsedTime(&out->total_ms, t->ev[0], t->ev[1]));
-    return 0;
+    const int r = stage_total_ms("trhip_lkg_get_timings", t, out);
+    if (t && out) snprintf(out->name, sizeof(out->name), "looking glass composition");
+    return r;
 }
 
 int trhip_lkg_download(trhip_lkg* t, int which, void* host, size_t bytes) {
-    if (!t || !host) return set_error("trhip_lkg_download: null argument");
-    if (which != TRHIP_LKG_VIEW_INDICES) return set_error("trhip_lkg_download: unknown buffer");
-    if (!t->indices) return set_error("trhip_lkg_download: the stage was created without record_view_indices");
-    const size_t size = t->pixels() * 4;
-    if (bytes != size) return set_error("trhip_lkg_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
-    LKG_DEVCHK(t->hip_device);
-    LKG_HIPCHK(hipDeviceSynchronize());
-    LKG_HIPCHK(hipMemcpy(host, t->indices, size, hipMemcpyDeviceToHost));
-    return 0;
+    return stage_download("trhip_lkg_download", t, host, bytes, [&](const void*& src, size_t& size) {
+        if (which != TRHIP_LKG_VIEW_INDICES) return set_error("trhip_lkg_download: unknown buffer");
+        if (!t->indices) return set_error("trhip_lkg_download: the stage was created without record_view_indices");
+        src = t->indices; size = t->pixels() * 4;
+        return 0;
+    });
 }
 
 }  // extern "C"

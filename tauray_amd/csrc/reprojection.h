@@ -17,10 +17,6 @@ struct trhip_device;
 
 namespace tr {
 
-struct DeviceScene;
-int set_error(const std::string& msg);                 // api.hip
-int device_index(const trhip_device* dev);             // api.hip: the HIP device of a handle, -1 for null
-DeviceScene* device_scene(trhip_device* dev);          // api.hip: the scene of a handle
 uint* device_overflow_flag(trhip_device* dev);         // api.hip: the traversal-stack overflow flag of a handle
 
 constexpr int REPROJ_NONE = 0;           // nothing accepted: default_value (spatial) / colour unchanged (temporal)

@@ -10,15 +10,13 @@
 #include <vector>
 
 #include "reprojection.h"
+#include "stage_host.h"
 #include "taps.h"
 #include "pt.h"
 #include "trace.h"
 
 namespace tr {
 namespace {
-
-#define RP_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-#define RP_DEVCHK(idx) do { hipError_t e_ = hipSetDevice(idx); if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)
 
 constexpr int KB = TR_BLOCK;
 constexpr int GBUFFER_CHUNK = 64;      // viewports of one k_gbuffer launch (the list travels in the kernel arguments)
@@ -252,21 +250,17 @@ int check_size(const char* who, uint32_t w, uint32_t h, uint32_t layers) {
 
 using namespace tr;
 
-struct trhip_spatial_reprojection {
+struct trhip_spatial_reprojection : StageHost<> {
     trhip_device* dev = nullptr;
-    int hip_device = 0;
     uint32_t w = 0, h = 0, total = 0, sources = 0;
     f4 default_value = {0, 0, 0, 0};
     int* source_viewport = nullptr;      // device
     int* layer_of = nullptr;             // device
     ReprojRecord* record = nullptr;
-    hipEvent_t ev[2] = {};
-    uint32_t frames = 0;
     size_t record_count() const { return (size_t)(total - sources) * w * h; }
 };
 
-struct trhip_temporal_reprojection {
-    int hip_device = 0;
+struct trhip_temporal_reprojection : StageHost<> {
     uint32_t w = 0, h = 0, layers = 0;
     float ratio = 0;
     int cur = 0;                         // the history a frame reads; it writes cur ^ 1
@@ -275,29 +269,8 @@ struct trhip_temporal_reprojection {
     f2* normal[2] = {};
     f4* pos[2] = {};
     ReprojRecord* record = nullptr;
-    hipEvent_t ev[2] = {};
-    uint32_t frames = 0;
     size_t pixels() const { return (size_t)w * h * layers; }
 };
-
-static void spatial_release(trhip_spatial_reprojection* s) {
-    if (s->source_viewport) (void)hipFree(s->source_viewport);
-    if (s->layer_of) (void)hipFree(s->layer_of);
-    if (s->record) (void)hipFree(s->record);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
-    delete s;
-}
-
-static void temporal_release(trhip_temporal_reprojection* t) {
-    for (int i = 0; i < 2; ++i) {
-        if (t->color[i]) (void)hipFree(t->color[i]);
-        if (t->normal[i]) (void)hipFree(t->normal[i]);
-        if (t->pos[i]) (void)hipFree(t->pos[i]);
-    }
-    if (t->record) (void)hipFree(t->record);
-    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    delete t;
-}
 
 extern "C" {
 
@@ -308,7 +281,7 @@ int trhip_gbuffer_render(trhip_device* dev, int projection, const uint32_t* view
     if (count == 0) return 0;
     if (!viewports) return set_error("trhip_gbuffer_render: null viewport list");
     if (check_size("trhip_gbuffer_render", width, height, count)) return 1;
-    RP_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     DeviceScene* scene = device_scene(dev);
     if (!scene->accel_built) return set_error("trhip_gbuffer_render: call trhip_scene_build_accel first");
     for (uint32_t i = 0; i < count; ++i)
@@ -326,7 +299,7 @@ int trhip_gbuffer_render(trhip_device* dev, int projection, const uint32_t* view
         hipLaunchKernelGGL(scene->two_level ? k_gbuffer<true> : k_gbuffer<false>, tile_grid(width, height, n), dim3(KB), 0, (hipStream_t)stream, scene->view(), L,
                            projection, list, min_ray_dist, normal, pos, ids, device_overflow_flag(dev));
     }
-    RP_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -349,30 +322,20 @@ int trhip_spatial_reprojection_create(trhip_device* dev, uint32_t width, uint32_
     int d = 0;
     for (uint32_t v = 0; v < total_viewports; ++v) if (layer_of[v] < 0) layer_of[v] = -(d++ + 1);
     if (!dev) return set_error("trhip_spatial_reprojection_create: null trhip_device (no HIP device: there is no CPU fallback)");
-    RP_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     trhip_spatial_reprojection* s = new trhip_spatial_reprojection;
     s->dev = dev; s->hip_device = device_index(dev);
     s->w = width; s->h = height; s->total = total_viewports; s->sources = source_count;
     s->default_value = F4(default_value[0], default_value[1], default_value[2], default_value[3]);
-    hipError_t e = hipMalloc((void**)&s->source_viewport, src.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(s->source_viewport, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->layer_of, layer_of.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(s->layer_of, layer_of.data(), layer_of.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->record, s->record_count() * sizeof(ReprojRecord));
-    if (e == hipSuccess) e = hipMemset(s->record, 0, s->record_count() * sizeof(ReprojRecord));
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&s->ev[i]);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { spatial_release(s); return set_error(std::string("trhip_spatial_reprojection_create: ") + hipGetErrorString(e)); }
-    *out = s;
-    return 0;
+    s->alloc_zeroed(s->source_viewport, src.size() * sizeof(int));
+    if (s->err == hipSuccess) s->err = hipMemcpy(s->source_viewport, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice);
+    s->alloc_zeroed(s->layer_of, layer_of.size() * sizeof(int));
+    if (s->err == hipSuccess) s->err = hipMemcpy(s->layer_of, layer_of.data(), layer_of.size() * sizeof(int), hipMemcpyHostToDevice);
+    s->alloc_zeroed(s->record, s->record_count() * sizeof(ReprojRecord));
+    return stage_finish_create("trhip_spatial_reprojection_create", s, out);
 }
 
-void trhip_spatial_reprojection_destroy(trhip_spatial_reprojection* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->hip_device);
-    (void)hipDeviceSynchronize();
-    spatial_release(s);
-}
+void trhip_spatial_reprojection_destroy(trhip_spatial_reprojection* s) { stage_destroy(s); }
 
 int trhip_spatial_reprojection_run(trhip_spatial_reprojection* s, const trhip_reprojection_images* sources, const trhip_reprojection_images* destinations,
                                    void* color_out, void* stream) {
@@ -382,7 +345,7 @@ int trhip_spatial_reprojection_run(trhip_spatial_reprojection* s, const trhip_re
         return set_error("trhip_spatial_reprojection_run: the sources need color, normal, pos and instance_id");
     if (!destinations->normal || !destinations->pos || !destinations->instance_id)
         return set_error("trhip_spatial_reprojection_run: the destinations need normal, pos and instance_id");
-    RP_DEVCHK(s->hip_device);
+    DEVCHK(s->hip_device);
     DeviceScene* scene = device_scene(s->dev);
     if (scene->camera_count < s->total || !scene->cameras)
         return set_error("trhip_spatial_reprojection_run: the scene has " + std::to_string(scene->camera_count) + " cameras, the stage " + std::to_string(s->total) + " viewports");
@@ -393,34 +356,24 @@ int trhip_spatial_reprojection_run(trhip_spatial_reprojection* s, const trhip_re
     P.dst_normal = (const f2*)destinations->normal; P.dst_pos = (const f4*)destinations->pos; P.dst_id = (const int*)destinations->instance_id;
     P.out = (f4*)color_out; P.default_value = s->default_value; P.record = s->record;
     hipStream_t st = (hipStream_t)stream;
-    RP_HIPCHK(hipEventRecord(s->ev[0], st));
+    HIPCHK(hipEventRecord(s->ev[0], st));
     hipLaunchKernelGGL(k_spatial_reprojection, tile_grid(s->w, s->h, s->total), dim3(KB), 0, st, P);
-    RP_HIPCHK(hipEventRecord(s->ev[1], st));
-    RP_HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[1], st));
+    HIPCHK(hipGetLastError());
     s->frames += 1;
     return 0;
 }
 
 int trhip_spatial_reprojection_get_timings(trhip_spatial_reprojection* s, trhip_reprojection_timings* out) {
-    if (!s || !out) return set_error("trhip_spatial_reprojection_get_timings: null argument");
-    memset(out, 0, sizeof(*out));
-    out->frames = s->frames;
-    if (s->frames == 0) return 0;
-    RP_DEVCHK(s->hip_device);
-    RP_HIPCHK(hipEventSynchronize(s->ev[1]));
-    RP_HIPCHK(hipEventElapsedTime(&out->total_ms, s->ev[0], s->ev[1]));
-    return 0;
+    return stage_total_ms("trhip_spatial_reprojection_get_timings", s, out);
 }
 
 int trhip_spatial_reprojection_download(trhip_spatial_reprojection* s, int which, void* host, size_t bytes) {
-    if (!s || !host) return set_error("trhip_spatial_reprojection_download: null argument");
-    if (which != TRHIP_REPROJECTION_DECISIONS) return set_error("trhip_spatial_reprojection_download: unknown buffer");
-    const size_t size = s->record_count() * sizeof(ReprojRecord);
-    if (bytes != size) return set_error("trhip_spatial_reprojection_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
-    RP_DEVCHK(s->hip_device);
-    RP_HIPCHK(hipDeviceSynchronize());
-    RP_HIPCHK(hipMemcpy(host, s->record, size, hipMemcpyDeviceToHost));
-    return 0;
+    return stage_download("trhip_spatial_reprojection_download", s, host, bytes, [&](const void*& src, size_t& size) {
+        if (which != TRHIP_REPROJECTION_DECISIONS) return set_error("trhip_spatial_reprojection_download: unknown buffer");
+        src = s->record; size = s->record_count() * sizeof(ReprojRecord);
+        return 0;
+    });
 }
 
 int trhip_temporal_reprojection_create(trhip_device* dev, uint32_t width, uint32_t height, uint32_t layers, float ratio, trhip_temporal_reprojection** out) {
@@ -429,28 +382,17 @@ int trhip_temporal_reprojection_create(trhip_device* dev, uint32_t width, uint32
     if (check_size("trhip_temporal_reprojection_create", width, height, layers)) return 1;
     if (!(ratio > 0.0f) || !(ratio < 1.0f)) return set_error("trhip_temporal_reprojection_create: ratio must be in (0, 1)");
     if (!dev) return set_error("trhip_temporal_reprojection_create: null trhip_device (no HIP device: there is no CPU fallback)");
-    RP_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     trhip_temporal_reprojection* t = new trhip_temporal_reprojection;
     t->hip_device = device_index(dev);
     t->w = width; t->h = height; t->layers = layers; t->ratio = ratio;
     const size_t px = t->pixels();
-    hipError_t e = hipSuccess;
-    auto alloc = [&](auto*& p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc((void**)&p, bytes); if (e == hipSuccess) e = hipMemset(p, 0, bytes); } };
-    for (int i = 0; i < 2; ++i) { alloc(t->color[i], px * sizeof(f4)); alloc(t->normal[i], px * sizeof(f2)); alloc(t->pos[i], px * sizeof(f4)); }
-    alloc(t->record, px * sizeof(ReprojRecord));
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&t->ev[i]);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { temporal_release(t); return set_error(std::string("trhip_temporal_reprojection_create: ") + hipGetErrorString(e)); }
-    *out = t;
-    return 0;
+    for (int i = 0; i < 2; ++i) { t->alloc_zeroed(t->color[i], px * sizeof(f4)); t->alloc_zeroed(t->normal[i], px * sizeof(f2)); t->alloc_zeroed(t->pos[i], px * sizeof(f4)); }
+    t->alloc_zeroed(t->record, px * sizeof(ReprojRecord));
+    return stage_finish_create("trhip_temporal_reprojection_create", t, out);
 }
 
-void trhip_temporal_reprojection_destroy(trhip_temporal_reprojection* t) {
-    if (!t) return;
-    (void)hipSetDevice(t->hip_device);
-    (void)hipDeviceSynchronize();
-    temporal_release(t);
-}
+void trhip_temporal_reprojection_destroy(trhip_temporal_reprojection* t) { stage_destroy(t); }
 
 int trhip_temporal_reprojection_reset_history(trhip_temporal_reprojection* t) {
     if (!t) return set_error("trhip_temporal_reprojection_reset_history: null stage");
@@ -463,7 +405,7 @@ int trhip_temporal_reprojection_run(trhip_temporal_reprojection* t, const trhip_
     if (!images) return set_error("trhip_temporal_reprojection_run: null images");
     if (!images->color || !images->normal || !images->pos || !images->screen_motion)
         return set_error("trhip_temporal_reprojection_run: color, normal, pos and screen_motion are required (only instance_id may be null)");
-    RP_DEVCHK(t->hip_device);
+    DEVCHK(t->hip_device);
     TemporalParams P{};
     P.w = (int)t->w; P.h = (int)t->h; P.layers = (int)t->layers; P.have_history = t->have_history ? 1 : 0; P.ratio = t->ratio;
     P.color = (f4*)images->color; P.normal = (const f2*)images->normal; P.pos = (const f4*)images->pos; P.motion = (const f2*)images->screen_motion;
@@ -473,10 +415,10 @@ int trhip_temporal_reprojection_run(trhip_temporal_reprojection* t, const trhip_
     P.color_cur = t->color[nx]; P.normal_cur = t->normal[nx]; P.pos_cur = t->pos[nx];
     P.record = t->record;
     hipStream_t st = (hipStream_t)stream;
-    RP_HIPCHK(hipEventRecord(t->ev[0], st));
+    HIPCHK(hipEventRecord(t->ev[0], st));
     hipLaunchKernelGGL(k_temporal_reprojection, tile_grid(t->w, t->h, t->layers), dim3(KB), 0, st, P);
-    RP_HIPCHK(hipEventRecord(t->ev[1], st));
-    RP_HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(t->ev[1], st));
+    HIPCHK(hipGetLastError());
     t->cur = nx;
     t->have_history = true;
     t->frames += 1;
@@ -484,34 +426,22 @@ int trhip_temporal_reprojection_run(trhip_temporal_reprojection* t, const trhip_
 }
 
 int trhip_temporal_reprojection_get_timings(trhip_temporal_reprojection* t, trhip_reprojection_timings* out) {
-    if (!t || !out) return set_error("trhip_temporal_reprojection_get_timings: null argument");
-    memset(out, 0, sizeof(*out));
-    out->frames = t->frames;
-    if (t->frames == 0) return 0;
-    RP_DEVCHK(t->hip_device);
-    RP_HIPCHK(hipEventSynchronize(t->ev[1]));
-    RP_HIPCHK(hipEventElapsedTime(&out->total_ms, t->ev[0], t->ev[1]));
-    return 0;
+    return stage_total_ms("trhip_temporal_reprojection_get_timings", t, out);
 }
 
 int trhip_temporal_reprojection_download(trhip_temporal_reprojection* t, int which, void* host, size_t bytes) {
-    if (!t || !host) return set_error("trhip_temporal_reprojection_download: null argument");
-    const size_t px = t->pixels();
-    const void* src = nullptr;
-    size_t size = 0;
-    const int c = t->cur;      // what the last frame wrote
-    switch (which) {
-        case TRHIP_REPROJECTION_DECISIONS: src = t->record; size = px * sizeof(ReprojRecord); break;
-        case TRHIP_REPROJECTION_PREVIOUS_COLOR: src = t->color[c]; size = px * sizeof(f4); break;
-        case TRHIP_REPROJECTION_PREVIOUS_NORMAL: src = t->normal[c]; size = px * sizeof(f2); break;
-        case TRHIP_REPROJECTION_PREVIOUS_POS: src = t->pos[c]; size = px * sizeof(f4); break;
-        default: return set_error("trhip_temporal_reprojection_download: unknown buffer");
-    }
-    if (bytes != size) return set_error("trhip_temporal_reprojection_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
-    RP_DEVCHK(t->hip_device);
-    RP_HIPCHK(hipDeviceSynchronize());
-    RP_HIPCHK(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
-    return 0;
+    return stage_download("trhip_temporal_reprojection_download", t, host, bytes, [&](const void*& src, size_t& size) {
+        const size_t px = t->pixels();
+        const int c = t->cur;      // what the last frame wrote
+        switch (which) {
+            case TRHIP_REPROJECTION_DECISIONS: src = t->record; size = px * sizeof(ReprojRecord); break;
+            case TRHIP_REPROJECTION_PREVIOUS_COLOR: src = t->color[c]; size = px * sizeof(f4); break;
+            case TRHIP_REPROJECTION_PREVIOUS_NORMAL: src = t->normal[c]; size = px * sizeof(f2); break;
+            case TRHIP_REPROJECTION_PREVIOUS_POS: src = t->pos[c]; size = px * sizeof(f4); break;
+            default: return set_error("trhip_temporal_reprojection_download: unknown buffer");
+        }
+        return 0;
+    });
 }
 
 }  // extern "C"

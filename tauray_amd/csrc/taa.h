@@ -41,14 +41,7 @@
 
 #include "common.h"
 
-struct trhip_device;
-
 namespace tr {
-
-struct DeviceScene;
-int set_error(const std::string& msg);                 // api.hip
-int device_index(const trhip_device* dev);             // api.hip
-DeviceScene* device_scene(trhip_device* dev);          // api.hip
 
 constexpr int TAA_TILE = 16;                     // a workgroup is a 16 x 16 tile of one layer ...
 constexpr int TAA_HALO = TAA_TILE + 2;           // ... and stages the 18 x 18 pixels its windows touch

@@ -9,12 +9,10 @@
 
 #include "taa.h"
 #include "build.h"
+#include "stage_host.h"
 
 namespace tr {
 namespace {
-
-#define TAA_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-#define TAA_DEVCHK(idx) do { hipError_t e_ = hipSetDevice(idx); if (e_ != hipSuccess) return set_error(std::string("hipSetDevice: ") + hipGetErrorString(e_)); } while (0)
 
 constexpr int KB = TAA_TILE * TAA_TILE;
 
@@ -191,26 +189,16 @@ __global__ __launch_bounds__(KB) void k_taa(TaaParams P) {
 
 using namespace tr;
 
-struct trhip_taa {
+struct trhip_taa : StageHost<> {
     trhip_device* dev = nullptr;
-    int hip_device = 0;
     uint32_t w = 0, h = 0, layers = 0;
     trhip_taa_options opt = {};
     int cur = 0;                         // the history a frame reads; it writes cur ^ 1
     bool have_history = false;
     f4* history[2] = {};
     uint8_t* decisions = nullptr;
-    hipEvent_t ev[2] = {};
-    uint32_t frames = 0;
     size_t pixels() const { return (size_t)w * h * layers; }
 };
-
-static void taa_release(trhip_taa* t) {
-    for (f4* p : t->history) if (p) (void)hipFree(p);
-    if (t->decisions) (void)hipFree(t->decisions);
-    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    delete t;
-}
 
 extern "C" {
 
@@ -227,28 +215,17 @@ int trhip_taa_create(trhip_device* dev, const trhip_taa_options* opt, uint32_t w
                          "which an equirectangular camera does not have (shader/taa.comp has no projected-direction function for it)");
     if (opt->projection != 0 && opt->projection != 1) return set_error("trhip_taa_create: unknown projection " + std::to_string(opt->projection));
     if (!dev) return set_error("trhip_taa_create: null trhip_device (no HIP device: there is no CPU fallback)");
-    TAA_DEVCHK(device_index(dev));
+    DEVCHK(device_index(dev));
     trhip_taa* t = new trhip_taa;
     t->dev = dev; t->hip_device = device_index(dev);
     t->w = width; t->h = height; t->layers = layers; t->opt = *opt;
     const size_t px = t->pixels();
-    hipError_t e = hipSuccess;
-    auto alloc = [&](auto*& p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc((void**)&p, bytes); if (e == hipSuccess) e = hipMemset(p, 0, bytes); } };
-    for (int i = 0; i < 2; ++i) alloc(t->history[i], px * sizeof(f4));
-    alloc(t->decisions, px);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&t->ev[i]);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { taa_release(t); return set_error(std::string("trhip_taa_create: ") + hipGetErrorString(e)); }
-    *out = t;
-    return 0;
+    for (int i = 0; i < 2; ++i) t->alloc_zeroed(t->history[i], px * sizeof(f4));
+    t->alloc_zeroed(t->decisions, px);
+    return stage_finish_create("trhip_taa_create", t, out);
 }
 
-void trhip_taa_destroy(trhip_taa* t) {
-    if (!t) return;
-    (void)hipSetDevice(t->hip_device);
-    (void)hipDeviceSynchronize();
-    taa_release(t);
-}
+void trhip_taa_destroy(trhip_taa* t) { stage_destroy(t); }
 
 int trhip_taa_reset_history(trhip_taa* t) {
     if (!t) return set_error("trhip_taa_reset_history: null stage");
@@ -265,7 +242,7 @@ int trhip_taa_run(trhip_taa* t, const trhip_taa_images* images, void* stream) {
     const char* s = (const char*)images->src;
     const char* d = (const char*)images->dst;
     if (d != s && d < s + bytes && s < d + bytes) return set_error("trhip_taa_run: dst overlaps src without being src");
-    TAA_DEVCHK(t->hip_device);
+    DEVCHK(t->hip_device);
     DeviceScene* scene = device_scene(t->dev);
     if (!scene->cameras || (uint64_t)t->opt.base_camera_index + t->layers > scene->camera_count)
         return set_error("trhip_taa_run: the scene has " + std::to_string(scene->camera_count) + " cameras, the stage reads " + std::to_string(t->layers) +
@@ -284,14 +261,14 @@ int trhip_taa_run(trhip_taa* t, const trhip_taa_images* images, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((t->w + TAA_TILE - 1) / TAA_TILE, (t->h + TAA_TILE - 1) / TAA_TILE, t->layers);
     const bool edge = t->opt.edge_dilation != 0, shimmer = t->opt.anti_shimmer != 0;
-    TAA_HIPCHK(hipEventRecord(t->ev[0], st));
+    HIPCHK(hipEventRecord(t->ev[0], st));
     if (edge && shimmer) hipLaunchKernelGGL((k_taa<true, true>), grid, dim3(KB), 0, st, P);
     else if (edge) hipLaunchKernelGGL((k_taa<true, false>), grid, dim3(KB), 0, st, P);
     else if (shimmer) hipLaunchKernelGGL((k_taa<false, true>), grid, dim3(KB), 0, st, P);
     else hipLaunchKernelGGL((k_taa<false, false>), grid, dim3(KB), 0, st, P);
-    if (aliased) TAA_HIPCHK(hipMemcpyAsync(images->dst, t->history[nx], bytes, hipMemcpyDeviceToDevice, st));
-    TAA_HIPCHK(hipEventRecord(t->ev[1], st));
-    TAA_HIPCHK(hipGetLastError());
+    if (aliased) HIPCHK(hipMemcpyAsync(images->dst, t->history[nx], bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipEventRecord(t->ev[1], st));
+    HIPCHK(hipGetLastError());
     t->cur = nx;
     t->have_history = true;
     t->frames += 1;
@@ -299,31 +276,20 @@ int trhip_taa_run(trhip_taa* t, const trhip_taa_images* images, void* stream) {
 }
 
 int trhip_taa_get_timings(trhip_taa* t, trhip_taa_timings* out) {
-    if (!t || !out) return set_error("trhip_taa_get_timings: null argument");
-    memset(out, 0, sizeof(*out));
-    snprintf(out->name, sizeof(out->name), "temporal antialiasing (%u viewports)", t->layers);
-    out->frames = t->frames;
-    if (t->frames == 0) return 0;
-    TAA_DEVCHK(t->hip_device);
-    TAA_HIPCHK(hipEventSynchronize(t->ev[1]));
-    TAA_HIPCHK(hipEventElapsedTime(&out->total_ms, t->ev[0], t->ev[1]));
-    return 0;
+    const int r = stage_total_ms("trhip_taa_get_timings", t, out);
+    if (t && out) snprintf(out->name, sizeof(out->name), "temporal antialiasing (%u viewports)", t->layers);
+    return r;
 }
 
 int trhip_taa_download(trhip_taa* t, int which, void* host, size_t bytes) {
-    if (!t || !host) return set_error("trhip_taa_download: null argument");
-    const void* src = nullptr;
-    size_t size = 0;
-    switch (which) {
-        case TRHIP_TAA_HISTORY: src = t->history[t->cur]; size = t->pixels() * sizeof(f4); break;
-        case TRHIP_TAA_DECISIONS: src = t->decisions; size = t->pixels(); break;
-        default: return set_error("trhip_taa_download: unknown buffer");
-    }
-    if (bytes != size) return set_error("trhip_taa_download: " + std::to_string(bytes) + " bytes asked, the buffer has " + std::to_string(size));
-    TAA_DEVCHK(t->hip_device);
-    TAA_HIPCHK(hipDeviceSynchronize());
-    TAA_HIPCHK(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
-    return 0;
+    return stage_download("trhip_taa_download", t, host, bytes, [&](const void*& src, size_t& size) {
+        switch (which) {
+            case TRHIP_TAA_HISTORY: src = t->history[t->cur]; size = t->pixels() * sizeof(f4); break;
+            case TRHIP_TAA_DECISIONS: src = t->decisions; size = t->pixels(); break;
+            default: return set_error("trhip_taa_download: unknown buffer");
+        }
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -577,9 +577,8 @@ int main(int argc, char** argv)
             if(opt.taa) throw std::runtime_error("--taa reads the path tracer's screen_motion target: --renderer=path-tracer");
             direct_renderer::options dopt;
             static_cast<path_tracer_stage::options&>(dopt) = opt;
-            dopt.tonemap = opt.tonemap; dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;
-            dopt.spatial_reprojection = opt.spatial_reprojection; dopt.temporal_reprojection = opt.temporal_reprojection;
-            if(opt.looking_glass) { direct_renderer::options::looking_glass_options lo; lo.stage = opt.looking_glass->stage; lo.output_size = opt.looking_glass->output_size; dopt.looking_glass = lo; }
+            static_cast<post_processing_renderer::options&>(dopt) = opt;
+            dopt.scene = opt.scene; dopt.accumulate = opt.accumulate; dopt.max_frames_in_flight = opt.max_frames_in_flight; dopt.frames_per_launch = opt.frames_per_launch;
             direct_renderer rr(devices, scene, size, dopt);
             return run(rr);
         }

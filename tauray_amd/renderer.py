@@ -662,11 +662,63 @@ class TonemapStage:
         check(_lib.lib().trhip_tonemap(self.ctx.h, _ptr(src), _ptr(dst), width, height, layers, C.byref(self.info), stream))
 
 
-class BmfrStage:
+def _device_images(struct, images: dict, allowed, who, noun):
+    """A ctypes struct of device pointers filled from a dict; `noun` is the stage's own word for an entry of it."""
+    unknown = set(images) - set(allowed)
+    if unknown:
+        raise ValueError(f"{who}: not {noun}: {sorted(unknown)}")
+    f = struct()
+    for name, buf in images.items():
+        setattr(f, name, None if buf is None else _ptr(buf))
+    return f
+
+
+class _PostStage:
+    """What the post-processing stages share: the handle of a trhip_<PREFIX>_* object, its end, its timer and its downloads."""
+
+    PREFIX = TIMINGS = h = None
+
+    def _fn(self, name):
+        return getattr(_lib.lib(), f"trhip_{self.PREFIX}_{name}")
+
+    def _create(self, *args):
+        h = C.c_void_p()
+        check(self._fn("create")(*args, C.byref(h)))
+        self.h = h.value
+
+    def _images(self, struct, images: dict, allowed, noun="an image the stage reads"):
+        return _device_images(struct, images, allowed, type(self).__name__, noun)
+
+    def timings(self) -> dict:
+        """The stage's timer as the C struct names it: device ms of the last frame, the frames run, the reference's timer name if it has one."""
+        t = self.TIMINGS()
+        check(self._fn("get_timings")(self.h, C.byref(t)))
+        values = ((n, getattr(t, n)) for n, _ in t._fields_)
+        return {n: v.decode() if isinstance(v, bytes) else v for n, v in values}
+
+    def _download(self, code, shape, dtype=np.float32) -> np.ndarray:
+        out = np.empty(shape, dtype=dtype)
+        check(self._fn("download")(self.h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BmfrStage(_PostStage):
     """bmfr_stage(device&, gbuffer_target& current_features, gbuffer_target& prev_features, const options&) (src/bmfr_stage.{hh,cc}):
     the BMFR denoiser between the path tracer and the tonemap stage.  The stage keeps last frame's normal / pos and its histories
     itself (trhip_bmfr_*, include/trhip.h); `settings`: _lib.BMFR_DIFFUSE_ONLY (--denoiser=bmfr) or BMFR_DIFFUSE_SPECULAR."""
 
+    PREFIX, TIMINGS = "bmfr", _lib.BmfrTimingsC
     FEATURES = ("color", "diffuse", "albedo", "normal", "pos", "screen_motion", "instance_id")
     # trhip_bmfr_download: name -> (code, numpy dtype, shape(stage))
     BUFFERS = {
@@ -688,48 +740,21 @@ class BmfrStage:
         self.channels = 3 if self.settings == _lib.BMFR_DIFFUSE_ONLY else 6
         self.block_grid = ((self.size[0] + 31) // 32 + 1, (self.size[1] + 31) // 32 + 1)
         self.blocks = self.block_grid[0] * self.block_grid[1] * self.layers
-        self.h = None
         opt = _lib.BmfrOptionsC(self.settings, float(noise_amount))
-        h = C.c_void_p()
-        check(_lib.lib().trhip_bmfr_create(getattr(ctx, "h", None), C.byref(opt), self.size[0], self.size[1], self.layers, C.byref(h)))
-        self.h = h.value
+        self._create(getattr(ctx, "h", None), C.byref(opt), self.size[0], self.size[1], self.layers)
 
     def run(self, targets: dict, frame_counter: int, stream=None):
         """stage::run: denoises targets["color"] in place from the other gbuffer entries (device images of the stage's size)."""
-        unknown = set(targets) - set(self.FEATURES)
-        if unknown:
-            raise ValueError(f"BmfrStage: not a feature the stage reads: {sorted(unknown)}")
-        f = _lib.BmfrFeaturesC()
-        for name, buf in targets.items():
-            setattr(f, name, None if buf is None else _ptr(buf))
+        f = self._images(_lib.BmfrFeaturesC, targets, self.FEATURES, "a feature the stage reads")
         check(_lib.lib().trhip_bmfr_run(self.h, C.byref(f), int(frame_counter) & 0xFFFFFFFF, stream))
 
     def reset_history(self):
         check(_lib.lib().trhip_bmfr_reset_history(self.h))
 
-    def timings(self) -> dict:
-        """Device ms of the last frame's four kernels under the reference's timer names, their sum, and the frames run."""
-        t = _lib.BmfrTimingsC()
-        check(_lib.lib().trhip_bmfr_get_timings(self.h, C.byref(t)))
-        return {n: (int if n == "frames" else float)(getattr(t, n)) for n, _ in _lib.BmfrTimingsC._fields_}
-
     def download(self, name: str) -> np.ndarray:
         """A buffer of the stage as the last frame left it (trhip_bmfr_download; test hook)."""
         code, dtype, shape = self.BUFFERS[name]
-        out = np.empty(shape(self), dtype=dtype)
-        check(_lib.lib().trhip_bmfr_download(self.h, code, out.ctypes.data, out.nbytes))
-        return out
-
-    def close(self):
-        if self.h:
-            _lib.lib().trhip_bmfr_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._download(code, shape(self), dtype)
 
 
 def fit_blocks(ctx: Context, matrices: np.ndarray) -> np.ndarray:
@@ -802,37 +827,17 @@ class GbufferStage:
         return {n: self.ctx.alloc(max(layers, 1) * w * h * PathTracerStage.TARGETS[n][0] * 4).zero() for n in self.TARGETS}
 
     def run(self, viewports, targets: dict, stream=None):
-        unknown = set(targets) - set(self.TARGETS)
-        if unknown:
-            raise ValueError(f"GbufferStage: not a target the pass writes: {sorted(unknown)}")
-        t = _lib.GbufferTargetsC()
-        for name, buf in targets.items():
-            setattr(t, name, None if buf is None else _ptr(buf))
+        t = _device_images(_lib.GbufferTargetsC, targets, self.TARGETS, "GbufferStage", "a target the pass writes")
         v = (C.c_uint32 * max(len(viewports), 1))(*[int(x) for x in viewports])
         check(_lib.lib().trhip_gbuffer_render(self.ctx.h, self.projection, v, len(viewports), self.min_ray_dist, C.byref(t), self.size[0], self.size[1], stream))
 
 
-def _reprojection_images(images: dict, allowed, who):
-    unknown = set(images) - set(allowed)
-    if unknown:
-        raise ValueError(f"{who}: not an image the stage reads: {sorted(unknown)}")
-    f = _lib.ReprojectionImagesC()
-    for name, buf in images.items():
-        setattr(f, name, None if buf is None else _ptr(buf))
-    return f
-
-
-def _reprojection_timings(fn, h) -> dict:
-    t = _lib.ReprojectionTimingsC()
-    check(fn(h, C.byref(t)))
-    return {"total_ms": float(t.total_ms), "frames": int(t.frames)}
-
-
-class SpatialReprojectionStage:
+class SpatialReprojectionStage(_PostStage):
     """spatial_reprojection_stage (src/spatial_reprojection_stage.{hh,cc}): fills the viewports that were not path traced from the ones
     that were, through the G-buffer (trhip_spatial_reprojection_*, include/trhip.h).  `source_viewports`: the path-traced viewports, in the
     order of the source images' layers; the output holds every viewport in natural order."""
 
+    PREFIX, TIMINGS = "spatial_reprojection", _lib.ReprojectionTimingsC
     SOURCES = ("color", "normal", "pos", "instance_id")
     DESTINATIONS = ("normal", "pos", "instance_id")
 
@@ -840,96 +845,58 @@ class SpatialReprojectionStage:
         self.ctx, self.size, self.total = ctx, (int(size[0]), int(size[1])), int(total_viewports)
         self.sources = [int(v) for v in source_viewports]
         self.destinations = [v for v in range(self.total) if v not in set(self.sources)]
-        self.h = None
         src = (C.c_uint32 * max(len(self.sources), 1))(*[v & 0xFFFFFFFF for v in self.sources])
         dv = (C.c_float * 4)(*default_value)
-        h = C.c_void_p()
-        check(_lib.lib().trhip_spatial_reprojection_create(getattr(ctx, "h", None), self.size[0], self.size[1], max(self.total, 0), src, len(self.sources), dv, C.byref(h)))
-        self.h = h.value
+        self._create(getattr(ctx, "h", None), self.size[0], self.size[1], max(self.total, 0), src, len(self.sources), dv)
 
     def run(self, sources: dict, destinations: dict, color_out, stream=None):
-        s = _reprojection_images(sources, self.SOURCES, "SpatialReprojectionStage")
-        d = _reprojection_images(destinations, self.DESTINATIONS, "SpatialReprojectionStage")
+        s = self._images(_lib.ReprojectionImagesC, sources, self.SOURCES)
+        d = self._images(_lib.ReprojectionImagesC, destinations, self.DESTINATIONS)
         check(_lib.lib().trhip_spatial_reprojection_run(self.h, C.byref(s), C.byref(d), _ptr(color_out), stream))
-
-    def timings(self) -> dict:
-        return _reprojection_timings(_lib.lib().trhip_spatial_reprojection_get_timings, self.h)
 
     def decisions(self) -> np.ndarray:
         """The decision record of the last frame, [destinations][h][w] (fields kind, slot, bits, ox, oy; test hook)."""
-        out = np.empty((len(self.destinations), self.size[1], self.size[0]), dtype=np.dtype(_lib.REPROJECTION_RECORD))
-        check(_lib.lib().trhip_spatial_reprojection_download(self.h, _lib.REPROJECTION_DECISIONS, out.ctypes.data, out.nbytes))
-        return out
-
-    def close(self):
-        if self.h:
-            _lib.lib().trhip_spatial_reprojection_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._download(_lib.REPROJECTION_DECISIONS, (len(self.destinations), self.size[1], self.size[0]), np.dtype(_lib.REPROJECTION_RECORD))
 
 
-class TemporalReprojectionStage:
+class TemporalReprojectionStage(_PostStage):
     """temporal_reprojection_stage (src/temporal_reprojection_stage.{hh,cc}): blends last frame's colour, found through screen_motion, into
     the path-traced layers: color = mix(color, reprojected, ratio) (trhip_temporal_reprojection_*, include/trhip.h).  The stage keeps last
     frame's colour, normal and pos itself."""
 
+    PREFIX, TIMINGS = "temporal_reprojection", _lib.ReprojectionTimingsC
     IMAGES = ("color", "normal", "pos", "screen_motion", "instance_id")
     BUFFERS = {"previous_color": (_lib.REPROJECTION_PREVIOUS_COLOR, 4), "previous_normal": (_lib.REPROJECTION_PREVIOUS_NORMAL, 2),
                "previous_pos": (_lib.REPROJECTION_PREVIOUS_POS, 4)}
 
     def __init__(self, ctx: Context, size, layers=1, ratio=0.75):
         self.ctx, self.size, self.layers, self.ratio = ctx, (int(size[0]), int(size[1])), int(layers), float(ratio)
-        self.h = None
-        h = C.c_void_p()
-        check(_lib.lib().trhip_temporal_reprojection_create(getattr(ctx, "h", None), self.size[0], self.size[1], max(self.layers, 0), self.ratio, C.byref(h)))
-        self.h = h.value
+        self._create(getattr(ctx, "h", None), self.size[0], self.size[1], max(self.layers, 0), self.ratio)
 
     def run(self, images: dict, stream=None):
         """stage::run: blends into images["color"] in place."""
-        f = _reprojection_images(images, self.IMAGES, "TemporalReprojectionStage")
+        f = self._images(_lib.ReprojectionImagesC, images, self.IMAGES)
         check(_lib.lib().trhip_temporal_reprojection_run(self.h, C.byref(f), stream))
 
     def reset_history(self):
         check(_lib.lib().trhip_temporal_reprojection_reset_history(self.h))
 
-    def timings(self) -> dict:
-        return _reprojection_timings(_lib.lib().trhip_temporal_reprojection_get_timings, self.h)
-
     def decisions(self) -> np.ndarray:
-        out = np.empty((self.layers, self.size[1], self.size[0]), dtype=np.dtype(_lib.REPROJECTION_RECORD))
-        check(_lib.lib().trhip_temporal_reprojection_download(self.h, _lib.REPROJECTION_DECISIONS, out.ctypes.data, out.nbytes))
-        return out
+        return self._download(_lib.REPROJECTION_DECISIONS, (self.layers, self.size[1], self.size[0]), np.dtype(_lib.REPROJECTION_RECORD))
 
     def download(self, name: str) -> np.ndarray:
         """The history the last frame left (test hook)."""
         code, ch = self.BUFFERS[name]
-        out = np.empty((self.layers, self.size[1], self.size[0], ch), np.float32)
-        check(_lib.lib().trhip_temporal_reprojection_download(self.h, code, out.ctypes.data, out.nbytes))
-        return out
-
-    def close(self):
-        if self.h:
-            _lib.lib().trhip_temporal_reprojection_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._download(code, (self.layers, self.size[1], self.size[0], ch))
 
 
-class TaaStage:
+class TaaStage(_PostStage):
     """taa_stage (src/taa_stage.{hh,cc}): temporal antialiasing behind the tonemap stage (trhip_taa_*, include/trhip.h).  The stage keeps
     its two history images itself and reads the scene's cameras and previous cameras (with their jitter in pan.zw) on the device.
     `options`: alpha (weight of the new frame, 1 / sequence length), gamma (the tonemap stage's), edge_dilation, anti_shimmer,
     base_camera_index, projection."""
 
+    PREFIX, TIMINGS = "taa", _lib.TaaTimingsC
     IMAGES = ("src", "dst", "screen_motion", "pos", "instance_id")
     DEFAULTS = dict(alpha=0.125, gamma=2.2, edge_dilation=True, anti_shimmer=False, base_camera_index=0, projection=0)
 
@@ -939,62 +906,35 @@ class TaaStage:
             raise ValueError(f"TaaStage: not an option of the stage: {sorted(unknown)}")
         self.options = dict(self.DEFAULTS, **(options or {}))
         self.ctx, self.size, self.layers = ctx, (int(size[0]), int(size[1])), int(layers)
-        self.h = None
         o = self.options
         opt = _lib.TaaOptionsC(float(o["alpha"]), float(o["gamma"]), int(bool(o["edge_dilation"])), int(bool(o["anti_shimmer"])),
                                int(o["base_camera_index"]), int(o["projection"]))
-        h = C.c_void_p()
-        check(_lib.lib().trhip_taa_create(getattr(ctx, "h", None), C.byref(opt), max(self.size[0], 0), max(self.size[1], 0), max(self.layers, 0), C.byref(h)))
-        self.h = h.value
+        self._create(getattr(ctx, "h", None), C.byref(opt), max(self.size[0], 0), max(self.size[1], 0), max(self.layers, 0))
 
     def run(self, images: dict, stream=None):
         """stage::run: images["dst"] = this frame's images["src"] blended into the stage's history (dst may be src)."""
-        unknown = set(images) - set(self.IMAGES)
-        if unknown:
-            raise ValueError(f"TaaStage: not an image the stage reads: {sorted(unknown)}")
-        f = _lib.TaaImagesC()
-        for name, buf in images.items():
-            setattr(f, name, None if buf is None else _ptr(buf))
+        f = self._images(_lib.TaaImagesC, images, self.IMAGES)
         check(_lib.lib().trhip_taa_run(self.h, C.byref(f), stream))
 
     def reset_history(self):
         check(_lib.lib().trhip_taa_reset_history(self.h))
 
-    def timings(self) -> dict:
-        """The reference's timer: its name, device ms of the last frame, frames run."""
-        t = _lib.TaaTimingsC()
-        check(_lib.lib().trhip_taa_get_timings(self.h, C.byref(t)))
-        return {"name": t.name.decode(), "total_ms": float(t.total_ms), "frames": int(t.frames)}
-
     def download(self, name: str) -> np.ndarray:
         """"history": RGBA32F, what the next frame will read; "decisions": the decision byte per pixel (test hooks)."""
         if name == "history":
-            code, out = _lib.TAA_HISTORY, np.empty((self.layers, self.size[1], self.size[0], 4), np.float32)
-        elif name == "decisions":
-            code, out = _lib.TAA_DECISIONS, np.empty((self.layers, self.size[1], self.size[0]), np.uint8)
-        else:
-            raise KeyError(name)
-        check(_lib.lib().trhip_taa_download(self.h, code, out.ctypes.data, out.nbytes))
-        return out
-
-    def close(self):
-        if self.h:
-            _lib.lib().trhip_taa_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            return self._download(_lib.TAA_HISTORY, (self.layers, self.size[1], self.size[0], 4))
+        if name == "decisions":
+            return self._download(_lib.TAA_DECISIONS, (self.layers, self.size[1], self.size[0]), np.uint8)
+        raise KeyError(name)
 
 
-class LookingGlassStage:
+class LookingGlassStage(_PostStage):
     """looking_glass_composition_stage (src/looking_glass_composition_stage.{hh,cc}): interleaves the views of a light field, sub-pixel by
     sub-pixel, into the one image a lenticular panel shows (trhip_lkg_*, include/trhip.h).  `view_size`: the size of one view; `out_size`: the
     panel's.  `options`: viewport_count (1..255), pitch / tilt / center (the reference's corrected_pitch, tilt, center:
     looking_glass.LookingGlassCalibration.stage_options), invert, record_view_indices.  The stage has no history."""
 
+    PREFIX, TIMINGS = "lkg", _lib.LkgTimingsC
     DEFAULTS = dict(viewport_count=48, pitch=0.0, tilt=0.0, center=0.0, invert=False, record_view_indices=False)
 
     def __init__(self, ctx: Context, view_size, out_size, options: Optional[dict] = None):
@@ -1004,42 +944,253 @@ class LookingGlassStage:
         self.options = dict(self.DEFAULTS, **(options or {}))
         self.ctx = ctx
         self.view_size, self.out_size = (int(view_size[0]), int(view_size[1])), (int(out_size[0]), int(out_size[1]))
-        self.h = None
         o = self.options
         opt = _lib.LkgOptionsC(max(int(o["viewport_count"]), 0), float(o["pitch"]), float(o["tilt"]), float(o["center"]), int(bool(o["invert"])),
                                int(bool(o["record_view_indices"])))
-        h = C.c_void_p()
-        check(_lib.lib().trhip_lkg_create(getattr(ctx, "h", None), C.byref(opt), max(self.view_size[0], 0), max(self.view_size[1], 0),
-                                          max(self.out_size[0], 0), max(self.out_size[1], 0), C.byref(h)))
-        self.h = h.value
+        self._create(getattr(ctx, "h", None), C.byref(opt), max(self.view_size[0], 0), max(self.view_size[1], 0), max(self.out_size[0], 0), max(self.out_size[1], 0))
 
     def run(self, src, dst=None, dst_rgba8=None, stream=None):
         """stage::run: `src` RGBA32F [views][h][w] in display space; `dst` RGBA32F [out_h][out_w] and / or `dst_rgba8` uint8 [out_h][out_w][4]."""
         check(_lib.lib().trhip_lkg_run(self.h, None if src is None else _ptr(src), None if dst is None else _ptr(dst),
                                        None if dst_rgba8 is None else _ptr(dst_rgba8), stream))
 
-    def timings(self) -> dict:
-        """The reference's timer: its name, device ms of the last frame, frames run."""
-        t = _lib.LkgTimingsC()
-        check(_lib.lib().trhip_lkg_get_timings(self.h, C.byref(t)))
-        return {"name": t.name.decode(), "total_ms": float(t.total_ms), "frames": int(t.frames)}
-
     def view_indices(self) -> np.ndarray:
         """uint8 [out_h][out_w][4]: the view the last frame took r, g and b from; 0 (record_view_indices only)."""
-        out = np.empty((self.out_size[1], self.out_size[0], 4), np.uint8)
-        check(_lib.lib().trhip_lkg_download(self.h, _lib.LKG_VIEW_INDICES, out.ctypes.data, out.nbytes))
-        return out
+        return self._download(_lib.LKG_VIEW_INDICES, (self.out_size[1], self.out_size[0], 4), np.uint8)
+
+
+@dataclass(frozen=True)
+class PostProcessingPlan:
+    """What plan_post_processing decides about the chain behind the path tracer; needs no device."""
+    stages: tuple           # the chain in order, out of POST_STAGES
+    targets: tuple          # set_gbuffer_spec: the G-buffer entries the path tracer writes besides colour
+    frame_order: bool       # a stage's history (or the G-buffer the slots share) is one chain over all frame slots: the chain runs in frame order on the default stream
+    fused_tonemap: bool     # nothing sits between the path tracer and the tonemap stage: the path tracer may write the display image itself
+    output_layers: int      # layers of the display image
+    viewports: int          # the viewports of the scene (a Looking Glass rig brings its own count)
+    viewport_list: Optional[tuple]      # a sparse light field: the viewports that are path traced, as compact layers in this order
+    denoiser: Optional[str]
+    temporal_ratio: float
+    taa_length: int
+
+
+POST_STAGES = ("bmfr", "temporal", "gbuffer+spatial", "tonemap", "taa", "looking_glass")
+
+
+def plan_post_processing(*, denoiser=None, spatial_reprojection=None, temporal_reprojection=0.0, taa=0, looking_glass=None, device_count=1,
+                         shard="pixels", viewports=1, viewports_per_device=None, accumulate=False, frames_per_launch=1, projection=0,
+                         path_tracer=True) -> PostProcessingPlan:
+    """The policy of the post-processing chain (the reference's post_processing_renderer, src/post_processing_renderer.cc:53-106) as one pure
+    function of the chain's options and the facts of the renderer they depend on: which stages run and in which order, what the path tracer
+    has to write for them, whether the chain is bound to frame order and whether the tonemap may still be fused - or a ValueError that says
+    which combination is not built.  `viewports_per_device`: the viewports of this device's share (a view shard), default all."""
+    world_size = device_count
+    if looking_glass is not None:
+        if world_size > 1:
+            raise ValueError(f"looking_glass with a {shard} distribution of count {world_size} > 1: the composition stage reads every view of the light "
+                             "field on one device, the views would have to be gathered first, which is not built; use one device")
+        if viewports not in (1, looking_glass.viewports):
+            raise ValueError(f"looking_glass: the rig has {looking_glass.viewports} views, not viewports={viewports}")
+        if frames_per_launch > 1:
+            raise ValueError("looking_glass: a composed frame is one frame: frames_per_launch must be 1")
+        if projection != 0:
+            raise ValueError("looking_glass: the rig's cameras are perspective cameras (options.projection must be 0)")
+        viewports = viewports_per_device = looking_glass.viewports
+    if denoiser not in (None, "none", "bmfr"):
+        raise ValueError(f"denoiser {denoiser!r}: only \"bmfr\" is built" + (" (svgf is not built)" if denoiser == "svgf" else ""))
+    denoiser = None if denoiser == "none" else denoiser
+    if denoiser is not None:
+        if world_size > 1 and shard != "views":
+            raise ValueError(f"denoiser with a {shard} distribution of count {world_size} > 1: the feature targets (diffuse, albedo, normal, pos, "
+                             "instance id, screen motion) would have to be gathered and stitched like colour, which is not built; "
+                             "use one device or shard=\"views\"")
+        if accumulate or frames_per_launch > 1:
+            raise ValueError("a denoised frame is a fresh frame: accumulate must be False and frames_per_launch 1")
+        if not path_tracer:
+            raise ValueError("the denoiser reads the path tracer's demodulated diffuse target: stage_cls must be PathTracerStage")
+    temporal_reprojection = float(temporal_reprojection or 0.0)
+    if not (0.0 <= temporal_reprojection < 1.0):
+        raise ValueError(f"temporal_reprojection {temporal_reprojection!r}: the ratio must be in [0, 1) (0 = off)")
+    if spatial_reprojection is not None:
+        spatial_reprojection = check_viewport_list(spatial_reprojection, viewports)
+    spatial, temporal = spatial_reprojection is not None, temporal_reprojection > 0.0
+    if spatial or temporal:
+        which = "spatial_reprojection" if spatial else "temporal_reprojection"
+        if world_size > 1:
+            raise ValueError(f"{which} with a {shard} distribution of count {world_size} > 1: the stages read the G-buffer of whole viewports on one "
+                             "device, gathering it from several is not built; use one device")
+        if denoiser is not None:
+            raise ValueError(f"{which} together with denoiser={denoiser!r}: a chain of reprojection and a denoiser is not built")
+        if frames_per_launch > 1:
+            raise ValueError(f"{which}: a reprojected frame is one frame: frames_per_launch must be 1")
+        if temporal and accumulate:
+            raise ValueError("temporal_reprojection blends the previous frame into a fresh frame: accumulate must be False")
+    taa = int(taa or 0)
+    if taa < 0:
+        raise ValueError(f"taa {taa!r}: the length of the jitter sequence must be positive (0 = off)")
+    per_device = viewports if viewports_per_device is None else viewports_per_device
+    if taa:
+        if world_size > 1 and shard != "views":
+            raise ValueError(f"taa with a {shard} distribution of count {world_size} > 1: the stage reads screen motion, pos and instance id of whole "
+                             "viewports on one device, gathering them from several is not built; use one device or shard=\"views\"")
+        if world_size > 1 and shard == "views" and per_device > 1:
+            raise ValueError("taa with shard=\"views\": more than one viewport per device is not built (the stage reads consecutive cameras)")
+        if accumulate:
+            raise ValueError("taa blends a fresh, jittered frame into its history: accumulate must be False")
+        if frames_per_launch > 1:
+            raise ValueError("taa: an antialiased frame is one frame (the jitter steps between frames): frames_per_launch must be 1")
+        if spatial or temporal:
+            raise ValueError("taa together with spatial_reprojection / temporal_reprojection: a chain of reprojection and taa is not built")
+        if projection == 2:
+            raise ValueError("taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
+                             "which an equirectangular camera does not have")
+        if not path_tracer:
+            raise ValueError("taa reads the path tracer's screen_motion target: stage_cls must be PathTracerStage")
+    on = dict(zip(POST_STAGES, (denoiser == "bmfr", temporal, spatial, True, bool(taa), looking_glass is not None)))
+    if on["bmfr"]:
+        targets = tuple(n for n in BmfrStage.FEATURES if n != "color")
+    elif taa:
+        targets = ("screen_motion", "pos", "instance_id")
+    elif spatial or temporal:
+        targets = ("normal", "pos", "instance_id") + (("screen_motion",) if temporal else ())
+    else:
+        targets = ()
+    return PostProcessingPlan(stages=tuple(n for n in POST_STAGES if on[n]), targets=targets,
+                              frame_order=on["bmfr"] or temporal or spatial or bool(taa),
+                              fused_tonemap=world_size == 1 and path_tracer and not any(on[n] for n in POST_STAGES if n != "tonemap"),
+                              output_layers=viewports if spatial else per_device * frames_per_launch, viewports=viewports,
+                              viewport_list=tuple(spatial_reprojection) if spatial else None, denoiser=denoiser,
+                              temporal_ratio=temporal_reprojection, taa_length=taa)
+
+
+class PostProcessingRenderer:
+    """post_processing_renderer (src/post_processing_renderer.{hh,cc}): the owner of the chain behind the path tracer.  It builds the stages of
+    a PostProcessingPlan and the images that belong to the chain rather than to a frame slot's path tracing (the TAA input, the destination
+    G-buffer, the composed images), keeps the previous-camera record and the jitter step, and runs the chain for a slot on a stream.  The
+    renderer in front of it asks four things: alloc_targets (per slot), frame_order, plan.fused_tonemap, run.  The owner holds no reference to
+    that renderer: both are released by reference count, in the order their owner drops them.
+
+    `layers`: the layers the path tracer renders on this device (0: an empty view shard, no stage is built)."""
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, plan: PostProcessingPlan, size, layers, options: PtOptionsC, torch=None,
+                 tonemap: Optional[dict] = None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY, taa_edge_dilation=True, taa_anti_shimmer=False,
+                 looking_glass=None, base_camera=0):
+        self.ctx, self.ss, self.plan, self.size, self.layers, self.torch = ctx, scene_stage, plan, (int(size[0]), int(size[1])), layers, torch
+        self.tonemap = TonemapStage(ctx, **(tonemap or {}))
+        self.bmfr = self.temporal = self.spatial = self.gbuffer = self.destination_targets = self.taa = self.taa_input = self.lkg = None
+        self._last_cameras = None        # the cameras the last frame was rendered with (a history chain's camera_pair.previous)
+        if layers <= 0:
+            return
+        if "bmfr" in plan.stages:
+            self.bmfr = BmfrStage(ctx, self.size, layers, denoiser_settings)
+        if "temporal" in plan.stages:
+            self.temporal = TemporalReprojectionStage(ctx, self.size, layers, plan.temporal_ratio)
+        if "gbuffer+spatial" in plan.stages:
+            self.spatial = SpatialReprojectionStage(ctx, self.size, plan.viewports, plan.viewport_list)
+            self.gbuffer = GbufferStage(ctx, scene_stage, self.size, options.projection, options.min_ray_dist)
+            self.destination_targets = self.gbuffer.alloc_targets(len(self.spatial.destinations))
+        if "taa" in plan.stages:
+            self._jitter(scene_stage.scene)
+            # a view shard's stage reads its first camera (`base_camera`); TaaStage strides by one
+            self.taa = TaaStage(ctx, self.size, layers, dict(alpha=1.0 / plan.taa_length, gamma=self.tonemap.info.gamma, edge_dilation=taa_edge_dilation,
+                                                             anti_shimmer=taa_anti_shimmer, base_camera_index=base_camera, projection=options.projection))
+            self.taa_input = self.alloc_display(layers)      # the tonemap stage's output; the stage writes the display image
+        if "looking_glass" in plan.stages:
+            self.lkg = LookingGlassStage(ctx, self.size, looking_glass.calibration.size,
+                                         looking_glass.calibration.stage_options(plan.output_layers, looking_glass.record_view_indices))
+
+    def _jitter(self, scene):
+        """Every camera of the scene gets the TAA jitter sequence; the first frame's camera_pair.previous: the cameras before their first step."""
+        from .scene import get_camera_jitter_sequence
+        seq = get_camera_jitter_sequence(self.plan.taa_length, self.size)
+        for cam in scene.cameras:
+            cam.set_jitter(seq)
+        self.ss.update_cameras(scene.cameras)
+        self._last_cameras = self.ss.camera_data.copy()
+
+    @property
+    def frame_order(self) -> bool:
+        return self.plan.frame_order and self.layers > 0
+
+    def alloc_display(self, layers):
+        """A display-space image of `layers` layers (a torch tensor when the renderer exchanges frames through torch, `torch` = the module)."""
+        w, h = self.size
+        if self.torch is not None:
+            return self.torch.empty((layers, h, w, 4), dtype=self.torch.float32, device=f"cuda:{self.ctx.hip_device}")
+        return self.ctx.alloc(layers * w * h * 16)
+
+    def alloc_targets(self, tw, th):
+        """The G-buffer entries of one frame slot next to its colour target (None: the path tracer writes colour only)."""
+        if not self.plan.targets or self.layers <= 0:
+            return None
+        return {n: self.ctx.alloc(self.layers * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero() for n in self.plan.targets}
+
+    def set_scene(self, scene):
+        """A new scene is on the device: the histories start over."""
+        for stage in (self.bmfr, self.temporal):
+            if stage is not None:
+                stage.reset_history()
+                self._last_cameras = None
+        if self.taa is not None:
+            self._jitter(scene)
+            self.taa.reset_history()
+
+    def begin_frame(self, wait=None):
+        """In front of a frame's path tracing: the jitter steps, and the device's previous cameras become the cameras of the frame before this
+        one.  `wait`: called before the device's cameras change while frames are in flight (they read the cameras they were enqueued with)."""
+        if self.taa is not None:
+            # scene::update (src/scene.cc:228): every camera steps its jitter before it is packed
+            if wait is not None:
+                wait()
+            cams = self.ss.scene.cameras
+            for cam in cams:
+                cam.step_jitter()
+            self.ss.update_cameras(cams)
+        if self.bmfr is not None or self.temporal is not None or self.taa is not None:
+            cameras = self.ss.camera_data
+            prev = cameras if self._last_cameras is None else self._last_cameras
+            on_device = self.ss.previous_camera_data
+            if on_device is None or prev.tobytes() != on_device.tobytes():
+                if wait is not None:
+                    wait()
+                self.ss.set_previous_camera_data(prev)
+            self._last_cameras = cameras.copy()
+
+    def run(self, slot, stream=None, tonemap=True):
+        """The chain on one frame slot's images (src/post_processing_renderer.cc:53-106), in the order of POST_STAGES."""
+        w, h = self.size
+        if self.layers <= 0:
+            return
+        if self.bmfr is not None:
+            self.bmfr.run(dict(slot.features, color=slot.color), slot.frame, stream)
+        if self.temporal is not None:
+            self.temporal.run(dict(slot.features, color=slot.color), stream)
+        if self.spatial is not None:
+            self.gbuffer.run(self.spatial.destinations, self.destination_targets, stream)
+            self.spatial.run({n: (slot.color if n == "color" else slot.features[n]) for n in SpatialReprojectionStage.SOURCES},
+                             self.destination_targets, slot.full, stream)
+        if not tonemap:
+            return
+        if slot.display is None:
+            slot.display = self.alloc_display(self.plan.output_layers)
+        self.tonemap.run(slot.full if self.spatial is not None else slot.color, slot.display if self.taa is None else self.taa_input, w, h,
+                         self.plan.output_layers, stream)
+        if self.taa is not None:
+            self.taa.run(dict(src=self.taa_input, dst=slot.display, screen_motion=slot.features["screen_motion"], pos=slot.features["pos"],
+                              instance_id=slot.features["instance_id"]), stream)
+        if self.lkg is not None:
+            if slot.composed is None:
+                ow, oh = self.lkg.out_size
+                slot.composed, slot.composed8 = self.ctx.alloc(ow * oh * 16), self.ctx.alloc(ow * oh * 4)
+            self.lkg.run(slot.display, slot.composed, slot.composed8, stream)
 
     def close(self):
-        if self.h:
-            _lib.lib().trhip_lkg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if self.taa is not None and self.ss.scene is not None:
+            for cam in self.ss.scene.cameras:      # the caller's cameras get their jitter from this renderer: it goes with it
+                cam.set_jitter([])
+        for stage in (self.bmfr, self.temporal, self.spatial, self.taa, self.lkg):
+            if stage is not None:
+                stage.close()
 
 
 class _FrameSlot:
@@ -1115,65 +1266,12 @@ class RtRenderer:
         spatial_reprojection / temporal_reprojection, denoiser="bmfr", taa or an animated scene."""
         if shard not in ("pixels", "views", "samples"):
             raise ValueError("shard must be pixels, views or samples")
-        if looking_glass is not None:
-            if world_size > 1:
-                raise ValueError(f"looking_glass with a {shard} distribution of count {world_size} > 1: the composition stage reads every view of the light "
-                                 "field on one device, the views would have to be gathered first, which is not built; use one device")
-            if viewports not in (1, looking_glass.viewports):
-                raise ValueError(f"looking_glass: the rig has {looking_glass.viewports} views, not viewports={viewports}")
-            if frames_per_launch > 1:
-                raise ValueError("looking_glass: a composed frame is one frame: frames_per_launch must be 1")
-            if options.projection != 0:
-                raise ValueError("looking_glass: the rig's cameras are perspective cameras (options.projection must be 0)")
-            viewports = looking_glass.viewports
-        if denoiser not in (None, "none", "bmfr"):
-            raise ValueError(f"denoiser {denoiser!r}: only \"bmfr\" is built" + (" (svgf is not built)" if denoiser == "svgf" else ""))
-        denoiser = None if denoiser == "none" else denoiser
-        if denoiser is not None:
-            if world_size > 1 and shard != "views":
-                raise ValueError(f"denoiser with a {shard} distribution of count {world_size} > 1: the feature targets (diffuse, albedo, normal, pos, "
-                                 "instance id, screen motion) would have to be gathered and stitched like colour, which is not built; "
-                                 "use one device or shard=\"views\"")
-            if accumulate or frames_per_launch > 1:
-                raise ValueError("a denoised frame is a fresh frame: accumulate must be False and frames_per_launch 1")
-            if stage_cls is not None and stage_cls is not PathTracerStage:
-                raise ValueError("the denoiser reads the path tracer's demodulated diffuse target: stage_cls must be PathTracerStage")
-        temporal_reprojection = float(temporal_reprojection or 0.0)
-        if not (0.0 <= temporal_reprojection < 1.0):
-            raise ValueError(f"temporal_reprojection {temporal_reprojection!r}: the ratio must be in [0, 1) (0 = off)")
-        if spatial_reprojection is not None:
-            spatial_reprojection = check_viewport_list(spatial_reprojection, viewports)
-        if spatial_reprojection is not None or temporal_reprojection > 0.0:
-            which = "spatial_reprojection" if spatial_reprojection is not None else "temporal_reprojection"
-            if world_size > 1:
-                raise ValueError(f"{which} with a {shard} distribution of count {world_size} > 1: the stages read the G-buffer of whole viewports on one "
-                                 "device, gathering it from several is not built; use one device")
-            if denoiser is not None:
-                raise ValueError(f"{which} together with denoiser={denoiser!r}: a chain of reprojection and a denoiser is not built")
-            if frames_per_launch > 1:
-                raise ValueError(f"{which}: a reprojected frame is one frame: frames_per_launch must be 1")
-            if temporal_reprojection > 0.0 and accumulate:
-                raise ValueError("temporal_reprojection blends the previous frame into a fresh frame: accumulate must be False")
-        taa = int(taa or 0)
-        if taa < 0:
-            raise ValueError(f"taa {taa!r}: the length of the jitter sequence must be positive (0 = off)")
-        if taa:
-            if world_size > 1 and shard != "views":
-                raise ValueError(f"taa with a {shard} distribution of count {world_size} > 1: the stage reads screen motion, pos and instance id of whole "
-                                 "viewports on one device, gathering them from several is not built; use one device or shard=\"views\"")
-            if world_size > 1 and shard == "views" and max(viewports - rank + world_size - 1, 0) // world_size > 1:
-                raise ValueError("taa with shard=\"views\": more than one viewport per device is not built (the stage reads consecutive cameras)")
-            if accumulate:
-                raise ValueError("taa blends a fresh, jittered frame into its history: accumulate must be False")
-            if frames_per_launch > 1:
-                raise ValueError("taa: an antialiased frame is one frame (the jitter steps between frames): frames_per_launch must be 1")
-            if spatial_reprojection is not None or temporal_reprojection > 0.0:
-                raise ValueError("taa together with spatial_reprojection / temporal_reprojection: a chain of reprojection and taa is not built")
-            if options.projection == 2:
-                raise ValueError("taa with equirectangular cameras: the stage projects a miss's ray direction with the previous camera's view_proj, "
-                                 "which an equirectangular camera does not have")
-            if stage_cls is not None and stage_cls is not PathTracerStage:
-                raise ValueError("taa reads the path tracer's screen_motion target: stage_cls must be PathTracerStage")
+        path_tracer = stage_cls is None or stage_cls is PathTracerStage
+        mine = max(viewports - rank + world_size - 1, 0) // world_size if (world_size > 1 and shard == "views") else viewports
+        plan = plan_post_processing(denoiser=denoiser, spatial_reprojection=spatial_reprojection, temporal_reprojection=temporal_reprojection, taa=taa,
+                                    looking_glass=looking_glass, device_count=world_size, shard=shard, viewports=viewports, viewports_per_device=mine,
+                                    accumulate=accumulate, frames_per_launch=frames_per_launch, projection=getattr(options, "projection", 0), path_tracer=path_tracer)
+        self.plan, viewports = plan, plan.viewports
         if frames_in_flight < 1:
             raise ValueError("frames_in_flight must be >= 1")
         if frames_in_flight > 1 and accumulate:
@@ -1197,9 +1295,8 @@ class RtRenderer:
         if self.shard == "views":
             from .transfer import shard_viewports
             viewports = len(shard_viewports(viewports, rank, world_size))
-        self.spatial_sources = spatial_reprojection
-        if spatial_reprojection is not None:
-            viewports = len(spatial_reprojection)           # the path tracer's layers: the active viewports, compact, in list order
+        if plan.viewport_list is not None:
+            viewports = len(plan.viewport_list)             # the path tracer's layers: the active viewports, compact, in list order
         self.frames_per_launch = frames_per_launch
         self.frame_viewports = viewports                    # layers of one frame
         viewports = viewports * frames_per_launch           # layers of one launch: every buffer, transfer, stitch and tonemap below
@@ -1231,48 +1328,22 @@ class RtRenderer:
             import torch
             self._torch = torch
         self.frames_in_flight = frames_in_flight
-        self.tonemap = TonemapStage(ctx, **(tonemap or {}))
+        self.output_viewports = plan.output_layers      # layers of color / display
+        self.post = PostProcessingRenderer(ctx, self.scene_update, plan, self.size, viewports, options, self._torch, tonemap, denoiser_settings,
+                                           taa_edge_dilation, taa_anti_shimmer, looking_glass, base_camera=rank if self.shard == "views" else 0)
+        self.tonemap = self.post.tonemap
         # rt_renderer on one device has nothing between path_tracer_stage and tonemap_stage: the stage writes the display image itself
         # (trhip_pt_set_fused_tonemap: the same bits without the second pass over the frame); TRHIP_FUSED_TONEMAP=0 keeps the stage
-        self.denoiser = denoiser
-        self.bmfr = BmfrStage(ctx, self.size, viewports, denoiser_settings) if (denoiser == "bmfr" and viewports > 0) else None
-        self._last_cameras = None        # denoiser: the cameras the last frame was rendered with
-        self.output_viewports = self.total_viewports if spatial_reprojection is not None else viewports      # layers of color / display
-        self.temporal = (TemporalReprojectionStage(ctx, self.size, viewports, temporal_reprojection)
-                         if (temporal_reprojection > 0.0 and viewports > 0) else None)
-        self.spatial = self.gbuffer = self.destination_targets = None
-        if spatial_reprojection is not None:
-            self.spatial = SpatialReprojectionStage(ctx, self.size, self.total_viewports, spatial_reprojection)
-            self.gbuffer = GbufferStage(ctx, self.scene_update, self.size, options.projection, options.min_ray_dist)
-            self.destination_targets = self.gbuffer.alloc_targets(len(self.spatial.destinations))
-        reprojection = self.spatial is not None or self.temporal is not None
-        self.taa = self.taa_input = None
-        self.taa_length = taa
-        if taa and viewports > 0:
-            from .scene import get_camera_jitter_sequence
-            seq = get_camera_jitter_sequence(taa, self.size)
-            for cam in scene.cameras:
-                cam.set_jitter(seq)
-            self.scene_update.update_cameras(scene.cameras)
-            base = rank if self.shard == "views" else 0       # a view shard's stage reads its first camera; TaaStage strides by one
-            self.taa = TaaStage(ctx, self.size, viewports, dict(alpha=1.0 / taa, gamma=self.tonemap.info.gamma, edge_dilation=taa_edge_dilation,
-                                                                anti_shimmer=taa_anti_shimmer, base_camera_index=base, projection=options.projection))
-            self.taa_input = self._alloc_display(viewports)     # the tonemap stage's output; the stage writes the display image
-            self._last_cameras = self.scene_update.camera_data.copy()      # the first frame's camera_pair.previous: the cameras before their first step
-        self.lkg = None
-        if looking_glass is not None and viewports > 0:
-            self.lkg = LookingGlassStage(ctx, self.size, looking_glass.calibration.size,
-                                         looking_glass.calibration.stage_options(self.output_viewports, looking_glass.record_view_indices))
-        self.fused_tonemap = (world_size == 1 and denoiser is None and not reprojection and not taa and self.lkg is None and (stage_cls is None or stage_cls is PathTracerStage) and viewports > 0
-                              and hasattr(_lib.lib(), "trhip_pt_set_fused_tonemap") and os.environ.get("TRHIP_FUSED_TONEMAP", "1") != "0")
+        self.fused_tonemap = (plan.fused_tonemap and viewports > 0 and hasattr(_lib.lib(), "trhip_pt_set_fused_tonemap")
+                              and os.environ.get("TRHIP_FUSED_TONEMAP", "1") != "0")
         self.slots = []
         for k in range(frames_in_flight):
             slot = _FrameSlot()
             slot.pt = (stage_cls or PathTracerStage)(ctx, self.scene_update, options, self.dist)   # rt_renderer<Pipeline>: path_tracer_stage or direct_stage
-            if spatial_reprojection is not None:
+            if plan.viewport_list is not None:
                 # the list as arithmetic runs, one stage per run (usually one): layer l shows viewport list[l], its camera and its RNG stream
                 slot.runs, first = [], 0
-                for base, stride, count in viewport_runs(spatial_reprojection):
+                for base, stride, count in viewport_runs(plan.viewport_list):
                     stage = slot.pt if not slot.runs else (stage_cls or PathTracerStage)(ctx, self.scene_update, options, self.dist)
                     stage.set_shard(viewport_base=base, viewport_stride=stride)
                     slot.runs.append((stage, first, count))
@@ -1287,14 +1358,8 @@ class RtRenderer:
                 slot.pt.set_frame_slots(frames_in_flight)    # the frames in flight fill the chip between them: the stage picks one lane (two with two slots)
                 slot.stream = ctx.create_stream()
             slot.color = self._alloc_color(viewports, tw, th)
-            if self.bmfr is not None:
-                slot.features = {n: ctx.alloc(viewports * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero()
-                                 for n in BmfrStage.FEATURES if n != "color"}
-            elif reprojection or self.taa is not None:
-                names = ("screen_motion", "pos", "instance_id") if self.taa is not None else \
-                        ("normal", "pos", "instance_id") + (("screen_motion",) if self.temporal is not None else ())
-                slot.features = {n: ctx.alloc(max(viewports, 1) * tw * th * PathTracerStage.TARGETS[n][0] * 4).zero() for n in names}
-            if self.spatial is not None:
+            slot.features = self.post.alloc_targets(tw, th)
+            if plan.viewport_list is not None:
                 slot.full = self._alloc_color(self.output_viewports, tw, th)
             if self.fused_tonemap:
                 slot.display = self._alloc_display(viewports)
@@ -1307,6 +1372,14 @@ class RtRenderer:
         self.accumulated_frames = 0
         self.frame_index = 0
 
+    def __getattr__(self, name):
+        """What the owner of the chain holds - its stages and the chain's images - reads on the renderer under the same name, as it did
+        when the renderer held them itself (r.taa is r.post.taa)."""
+        post = self.__dict__.get("post")
+        if post is not None and not name.startswith("_") and name in vars(post):
+            return getattr(post, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
     # the stage / images of the most recent frame (the only ones there are with frames_in_flight = 1)
     @property
     def ray_tracer(self) -> PathTracerStage:
@@ -1314,7 +1387,7 @@ class RtRenderer:
 
     @property
     def color(self):
-        return self.current.full if self.spatial is not None else self.current.color
+        return self.current.full if self.plan.viewport_list is not None else self.current.color
 
     def _stages(self, slot):
         """The path tracer stages of a slot: one, or one per arithmetic run of the viewport list."""
@@ -1330,10 +1403,7 @@ class RtRenderer:
         return self.ctx.alloc(max(viewports * tw * th, 1) * 16).zero()
 
     def _alloc_display(self, viewports):
-        w, h = self.size
-        if self.use_torch:
-            return self._torch.empty((viewports, h, w, 4), dtype=self._torch.float32, device=f"cuda:{self.ctx.hip_device}")
-        return self.ctx.alloc(viewports * w * h * 16)
+        return self.post.alloc_display(viewports)
 
     def _device_dists(self, ratios) -> List[DistributionParams]:
         out, cumulative = [], 0.0
@@ -1350,20 +1420,7 @@ class RtRenderer:
             lg = self.looking_glass
             looking_glass_cameras(scene, lg.viewports, lg.midplane, lg.depth, lg.relative_dist, lg.calibration)
         self.scene_update.set_scene(scene)
-        if self.bmfr is not None:
-            self.bmfr.reset_history()
-            self._last_cameras = None
-        if self.temporal is not None:
-            self.temporal.reset_history()
-            self._last_cameras = None
-        if self.taa is not None:
-            from .scene import get_camera_jitter_sequence
-            seq = get_camera_jitter_sequence(self.taa_length, self.size)
-            for cam in scene.cameras:
-                cam.set_jitter(seq)
-            self.scene_update.update_cameras(scene.cameras)
-            self.taa.reset_history()
-            self._last_cameras = self.scene_update.camera_data.copy()
+        self.post.set_scene(scene)
 
     def program(self) -> dict:
         """The shading program of this rank's stage (PathTracerStage.program)."""
@@ -1506,23 +1563,7 @@ class RtRenderer:
         slot.frame = self.frame_index
         self.frame_index += self.frames_per_launch
         if self.viewports > 0:      # a view shard can be empty (more devices than views)
-            if self.taa is not None:
-                # scene::update (src/scene.cc:228): every camera steps its jitter before it is packed
-                if self.frames_in_flight > 1:
-                    self.sync()
-                cams = self.scene_update.scene.cameras
-                for cam in cams:
-                    cam.step_jitter()
-                self.scene_update.update_cameras(cams)
-            if self.bmfr is not None or self.temporal is not None or self.taa is not None:
-                cameras = self.scene_update.camera_data
-                prev = cameras if self._last_cameras is None else self._last_cameras
-                on_device = self.scene_update.previous_camera_data
-                if on_device is None or prev.tobytes() != on_device.tobytes():
-                    if self.frames_in_flight > 1:      # frames in flight read the cameras they were enqueued with
-                        self.sync()
-                    self.scene_update.set_previous_camera_data(prev)
-                self._last_cameras = cameras.copy()
+            self.post.begin_frame(self.sync if self.frames_in_flight > 1 else None)
             st = stream if stream is not None else slot.stream
             if slot.runs is not None:
                 tw, th = self.target_size
@@ -1556,9 +1597,8 @@ class RtRenderer:
         self.render_partial(tonemap=tonemap)
         slot = self.current
         if self.world_size == 1:
-            if self.bmfr is not None or self.temporal is not None or self.spatial is not None or self.taa is not None:
-                # the denoiser's / temporal stage's history is one chain over the frames of all slots: it runs on the default stream, in frame
-                # order (and so does the spatial stage, whose destination G-buffer the slots share)
+            if self.post.frame_order:
+                # a history is one chain over the frames of all slots: the chain runs on the default stream, in frame order
                 if slot.stream is not None:
                     self.ctx.stream_wait(None, slot.stream)
                 self.post_process(None, tonemap=tonemap)
@@ -1579,7 +1619,7 @@ class RtRenderer:
             self.ctx.stream_wait(None, slot.stream)
         if self.shard == "views":
             # every rank finishes its own views (tonemap is per pixel); `gather_views` ships them to the writer on rank 0
-            if (tonemap or self.bmfr is not None) and self.viewports > 0:
+            if (tonemap or self.plan.stages[0] != "tonemap") and self.viewports > 0:      # stages in front of the tonemap run without it
                 self.post_process(tonemap=tonemap)
             if gather_views:
                 from .transfer import gather_views_to_display
@@ -1599,42 +1639,17 @@ class RtRenderer:
         self.accumulated_frames += 1
 
     def post_process(self, stream=None, tonemap=True):
-        """The post-processing chain of the last frame (src/post_processing_renderer.cc:53-106): denoiser, then tonemap."""
-        w, h = self.size
-        if self.viewports == 0:
-            return
-        slot = self.current
-        if self.bmfr is not None:
-            self.bmfr.run(dict(slot.features, color=slot.color), slot.frame, stream)
-        if self.temporal is not None:
-            self.temporal.run(dict(slot.features, color=slot.color), stream)
-        if self.spatial is not None:
-            self.gbuffer.run(self.spatial.destinations, self.destination_targets, stream)
-            self.spatial.run({n: (slot.color if n == "color" else slot.features[n]) for n in SpatialReprojectionStage.SOURCES},
-                             self.destination_targets, slot.full, stream)
-        if not tonemap:
-            return
-        if slot.display is None:
-            slot.display = self._alloc_display(self.output_viewports)
-        self.tonemap.run(slot.full if self.spatial is not None else slot.color, slot.display if self.taa is None else self.taa_input, w, h,
-                         self.output_viewports, stream)
-        if self.taa is not None:
-            self.taa.run(dict(src=self.taa_input, dst=slot.display, screen_motion=slot.features["screen_motion"], pos=slot.features["pos"],
-                              instance_id=slot.features["instance_id"]), stream)
-        if self.lkg is not None:
-            if slot.composed is None:
-                ow, oh = self.lkg.out_size
-                slot.composed, slot.composed8 = self.ctx.alloc(ow * oh * 16), self.ctx.alloc(ow * oh * 4)
-            self.lkg.run(slot.display, slot.composed, slot.composed8, stream)
+        """The post-processing chain of the last frame (PostProcessingRenderer.run)."""
+        self.post.run(self.current, stream, tonemap)
 
     def download(self, which="color") -> np.ndarray:
         """The most recent frame's partial colour target or tonemapped display image; with a Looking Glass output also "composed" (the
         panel's image, RGBA32F [h][w][4]) and "composed8" (uint8 [h][w][4])."""
         self.sync()
         if which in ("composed", "composed8"):
-            if self.lkg is None or self.current.composed is None:
+            if self.post.lkg is None or self.current.composed is None:
                 raise KeyError(f"{which}: the renderer has no Looking Glass output (looking_glass=...) or no frame was post-processed")
-            ow, oh = self.lkg.out_size
+            ow, oh = self.post.lkg.out_size
             if which == "composed":
                 return self.current.composed.download((oh, ow, 4), np.float32)
             return self.current.composed8.download((oh, ow, 4), np.uint8)
@@ -1652,12 +1667,7 @@ class RtRenderer:
         if not self.slots:
             return
         self.sync()
-        if self.taa is not None and self.scene_update.scene is not None:
-            for cam in self.scene_update.scene.cameras:      # the caller's cameras get their jitter from this renderer: it goes with it
-                cam.set_jitter([])
-        for stage in (self.bmfr, self.temporal, self.spatial, self.taa, self.lkg):
-            if stage is not None:
-                stage.close()
+        self.post.close()
         for slot in self.slots:
             for pt in self._stages(slot):
                 pt.close()

@@ -646,7 +646,7 @@ def test_renderer_with_denoiser_equals_the_stages_driven_by_hand(R, ctx):
     scene = _glb("test.glb", size)
     opt = R.options_for_scene(scene, max_bounces=3)
     r = R.RtRenderer(ctx, scene, opt, size, denoiser="bmfr")
-    assert not r.fused_tonemap and r.bmfr is not None
+    assert not r.fused_tonemap and r.post.bmfr is not None
     frames = []
     for _ in range(4):
         r.render()

@@ -468,7 +468,7 @@ def test_renderer_composes_what_the_stage_composes_and_the_cli_writes_the_same_f
     r = R.RtRenderer(ctx, scene, R.options_for_scene(scene, max_bounces=3), (W, H), spatial_reprojection=sources, looking_glass=LookingGlassOutput(cal, *rig))
     r.render()
     display, composed, composed8 = r.download("display"), r.download("composed"), r.download("composed8")
-    t = r.lkg.timings()
+    t = r.post.lkg.timings()
     r.close()
     assert display.shape == (rig[0], H, W, 4) and composed.shape == (screen[1], screen[0], 4) and t["frames"] == 1
     by_hand = _run_stage(R, ctx, display, screen, _opts(cal, rig[0]))
@@ -490,6 +490,18 @@ def test_renderer_composes_what_the_stage_composes_and_the_cli_writes_the_same_f
     img = np.asarray(exr.load_exr_rgba(prefix + "x.exr"))
     assert img.shape[:2] == (screen[1], screen[0])
     assert np.array_equal(np.isfinite(img[..., :3]), finite) and np.array_equal(img[..., :3][finite], composed[..., :3][finite])
+    # frame slots: two frames one at a time and two in flight compose the same panels bit for bit
+    panels = {}
+    for slots in (1, 2):
+        scene = _glb("test.glb", (W, H))
+        r = R.RtRenderer(ctx, scene, R.options_for_scene(scene, max_bounces=3), (W, H), spatial_reprojection=sources, looking_glass=LookingGlassOutput(cal, *rig),
+                         frames_in_flight=slots)
+        panels[slots] = []
+        for f in range(2):
+            r.render()
+            panels[slots].append(r.download("composed").tobytes())
+        r.close()
+    assert panels[1] == panels[2] and panels[1][0] == composed.tobytes() and panels[1][0] != panels[1][1]
 
 
 @pytest.mark.gpu

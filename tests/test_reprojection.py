@@ -512,12 +512,12 @@ def _sparse_frame(R, ctx, scene, size, total, sources, **kw):
     slot = r.current
     src = dict(color=slot.color.download((S, h, w, 4)), normal=slot.features["normal"].download((S, h, w, 2)),
                pos=slot.features["pos"].download((S, h, w, 4)), instance_id=slot.features["instance_id"].download((S, h, w), np.int32))
-    dst = dict(normal=r.destination_targets["normal"].download((D, h, w, 2)), pos=r.destination_targets["pos"].download((D, h, w, 4)),
-               instance_id=r.destination_targets["instance_id"].download((D, h, w), np.int32))
+    dst = dict(normal=r.post.destination_targets["normal"].download((D, h, w, 2)), pos=r.post.destination_targets["pos"].download((D, h, w, 4)),
+               instance_id=r.post.destination_targets["instance_id"].download((D, h, w), np.int32))
     out = r.download("color")
-    dec = r.spatial.decisions()
+    dec = r.post.spatial.decisions()
     vp = r.scene_update.camera_data.view(np.float32).reshape(total, 80)[:, 32:48].reshape(total, 4, 4)
-    timings = r.spatial.timings()
+    timings = r.post.spatial.timings()
     r.close()
     return vp, src, dst, out, dec, timings
 
@@ -791,7 +791,7 @@ def test_renderer_with_both_options_equals_the_stages_driven_by_hand(R, ctx):
     scene = _grid_scene(_glb("test.glb", size), 3, 3, 0.05)
     opt = R.options_for_scene(scene, max_bounces=3)
     r = R.RtRenderer(ctx, scene, opt, size, viewports=total, spatial_reprojection=sources, temporal_reprojection=ratio)
-    assert not r.fused_tonemap and r.spatial is not None and r.temporal is not None
+    assert not r.fused_tonemap and r.post.spatial is not None and r.post.temporal is not None
     frames = []
     for _ in range(3):
         r.render()
@@ -902,8 +902,8 @@ def test_full_size_sparse_frame_is_cheaper_than_the_full_frame(R, ctx):
     full.close()
     sparse = R.RtRenderer(ctx, scene, opt, (W, H), viewports=V, use_torch=False, spatial_reprojection=sources)
     sparse_ms = frame_ms(sparse)
-    stages = {"path_tracing_ms": sparse.timings()["path_tracing_ms"], "spatial_ms": sparse.spatial.timings()["total_ms"]}
-    dec = sparse.spatial.decisions()
+    stages = {"path_tracing_ms": sparse.timings()["path_tracing_ms"], "spatial_ms": sparse.post.spatial.timings()["total_ms"]}
+    dec = sparse.post.spatial.decisions()
     filled = float((dec["kind"] != M.NONE).mean())
     out = sparse.download("color")
     sparse.close()

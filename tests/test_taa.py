@@ -762,7 +762,7 @@ def test_it_antialiases(R, ctx):
         img = r.download("display")[0]
         if taa:
             ids = r.current.features["instance_id"].download((h, w), np.int32)
-            assert r.taa.timings()["frames"] == 17
+            assert r.post.taa.timings()["frames"] == 17
         r.close()
         figures[taa] = img
     edge = np.zeros((h, w), bool)
@@ -792,14 +792,22 @@ def test_renderer_and_cli_produce_the_same_frames(R, ctx, tmp_path):
         subprocess.check_call([exe, glb, f"--width={W}", f"--height={H}", "--max-ray-depth=3", "--filetype=raw", "--taa=8", f"--frames={frames}", f"--headless={prefix}"] + extra)
         scene = _glb("test.glb", (W, H))
         r = R.RtRenderer(ctx, scene, R.options_for_scene(scene, max_bounces=3), (W, H), taa=8, **kw)
-        plain = None
+        plain, one_slot = None, []
         for f in range(frames):
             r.render()
             ref = r.download("display")[0]
+            one_slot.append(ref)
             got = np.fromfile(f"{prefix}{f}.raw", dtype=np.float32).reshape(H, W, 4)
             differing = float((np.abs(got - ref).max(-1) > 1e-3).mean())
             assert differing < 2e-3 and abs(float(got.mean()) - float(ref.mean())) < 1e-4, f"{extra} frame {f}: {differing:.4%} of the pixels differ"
             if f == 0:
                 plain = ref
         assert float((np.abs(plain - ref).max(-1) > 1e-3).mean()) > 0.01, "the history does nothing"
+        r.close()
+        # two frames in flight: the stage's history is one chain in frame order, the same frames bit for bit
+        scene = _glb("test.glb", (W, H))
+        r = R.RtRenderer(ctx, scene, R.options_for_scene(scene, max_bounces=3), (W, H), taa=8, frames_in_flight=2, **kw)
+        for f in range(frames):
+            r.render()
+            assert r.download("display")[0].tobytes() == one_slot[f].tobytes(), f"{extra} frame {f} differs with two frames in flight"
         r.close()

@@ -77,15 +77,15 @@ def main():
         pt_full.append(full.timings()["path_tracing_ms"])
         t_sparse.append(frame(sparse))
         pt_sparse.append(sparse.timings()["path_tracing_ms"])
-        spatial_ms.append(sparse.spatial.timings()["total_ms"])
+        spatial_ms.append(sparse.post.spatial.timings()["total_ms"])
     gb = []
     for _ in range(args.rounds):
         ctx.sync()
         t0 = time.perf_counter()
-        sparse.gbuffer.run(sparse.spatial.destinations, sparse.destination_targets)
+        sparse.post.gbuffer.run(sparse.post.spatial.destinations, sparse.post.destination_targets)
         ctx.sync()
         gb.append((time.perf_counter() - t0) * 1e3)
-    dec = sparse.spatial.decisions()
+    dec = sparse.post.spatial.decisions()
     filled = float((dec["kind"] != 0).mean())
     sparse_frame = sparse.download("color")
     ss = sparse.scene_update
