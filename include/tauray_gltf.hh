@@ -800,6 +800,7 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
     std::vector<gltf_camera> cameras;
     double light_angle = 0, light_radius = 0;
     std::map<int, mat4d> node_globals;
+    std::vector<sh_grid> sh_grids;
     struct pending_skin { uint32_t instance; int skin; const std::vector<trhip_skin>* skins; };
     std::vector<pending_skin> skinned_pending;
 
@@ -849,6 +850,32 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
         }
         const mat4d glob = mul(parent, local);
         node_globals[node_index] = glob;
+
+        if(tr) if(const json* probe = tr->find("light_probe"))
+        {
+            const json* type = probe->find("type");
+            if(type && type->str == "GRID")
+            {   // an irradiance volume (src/gltf.cc:462-481); its scale must not be negative
+                mat4d pg = glob;
+                if(rec.has_trs)
+                {
+                    const double abs_scale[3] = {std::fabs(rec.scale[0]), std::fabs(rec.scale[1]), std::fabs(rec.scale[2])};
+                    pg = mul(parent, trs_matrix(rec.translation, rec.rotation, abs_scale));
+                }
+                sh_grid g;
+                const char* keys[3] = {"resolution_x", "resolution_y", "resolution_z"};
+                for(int k = 0; k < 3; ++k)
+                {
+                    const double r = probe->number(keys[k], 0.0);
+                    if(!(r >= 1.0)) throw std::runtime_error("glTF: TR_data.light_probe needs resolution_x, resolution_y and resolution_z >= 1");
+                    g.resolution[k] = (uint32_t)r;
+                }
+                g.radius = (float)probe->number("radius", 0.0);
+                for(int c = 0; c < 4; ++c) for(int r = 0; r < 4; ++r) g.transform[c * 4 + r] = (float)pg.m[r][c];
+                for(int c = 0; c < 3; ++c) g.scaling[c] = (float)std::sqrt(pg.m[0][c] * pg.m[0][c] + pg.m[1][c] * pg.m[1][c] + pg.m[2][c] * pg.m[2][c]);
+                sh_grids.push_back(g);
+            }
+        }
 
         if(node.has("mesh"))
         {
@@ -1083,6 +1110,7 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
         s.skinned.push_back(std::move(out));
     }
     s.animation = anim;
+    s.sh_grids = sh_grids;
     return s;
 }
 

@@ -178,6 +178,18 @@ public:
 //==============================================================================
 struct gltf_animation;      // node tree + animation clips of a loaded glTF file (include/tauray_gltf.hh)
 
+// sh_grid + its transformable (src/sh_grid.{hh,cc}; TR_data.light_probe of type GRID, src/gltf.cc:462-481): a grid of light probes in the box
+// the transform maps [-1, 1]^3 onto.
+struct sh_grid
+{
+    uint32_t resolution[3] = {1, 1, 1};
+    float radius = 0.0f;
+    float transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};      // get_global_transform(), column-major
+    float scaling[3] = {1, 1, 1};                                               // get_scaling(), made absolute
+    int order = 2;                                                              // sh_grid::set_order (--sh-order)
+    static int get_coef_count(int order) { return (order + 1) * (order + 1); }
+};
+
 struct scene_data
 {
     std::vector<uint8_t> instances, spans, vertices, indices, point_lights, directional_lights, texture_infos, texels,
@@ -195,6 +207,7 @@ struct scene_data
     // What tr::scene_animator needs to play the file's animation clips (tauray_gltf.hh); null for scenes without a node tree.
     std::shared_ptr<gltf_animation> animation;
     std::vector<uint8_t> previous_cameras;       // camera_pair.previous of the current frame (empty = the cameras themselves)
+    std::vector<sh_grid> sh_grids;               // the file's light-probe grids, in node order (not part of the .trsc dump)
 
     uint32_t instance_count() const { return (uint32_t)(instances.size() / 288); }
     uint32_t camera_count() const { return (uint32_t)(cameras.size() / 320); }
@@ -670,6 +683,98 @@ public:
     uvec2 view_size, output_size;
     options opt;
     trhip_lkg* h = nullptr;
+};
+
+// grid_data_buffer of render number `history_length` (>= 1) of a grid at `frame_counter`, as sh_path_tracer_stage::update packs it
+// (src/sh_path_tracer_stage.cc:115-137): transform, normal_transform, cell_scale, the rotations of the direction lattice, mix_ratio.  Needs no device.
+inline trhip_sh_grid_data sh_grid_parameters(const sh_grid& g, uint32_t samples_per_probe, uint32_t frame_counter, uint32_t history_length, float temporal_ratio)
+{
+    trhip_sh_grid_data out;
+    check(trhip_sh_pack_grid_data(g.transform, g.scaling, g.resolution, samples_per_probe, frame_counter, history_length, temporal_ratio, &out));
+    return out;
+}
+
+// sh_path_tracer_stage followed by sh_compact_stage (src/sh_path_tracer_stage.{hh,cc}, src/sh_compact_stage.cc; trhip_sh_*): bakes one sh_grid
+// as spherical-harmonics coefficients on the path tracer's kernels.  The stage owns both volumes: RGBA32F [rz][ry * C][rx] and its RGBA16F copy.
+class sh_path_tracer_stage
+{
+public:
+    struct options      // the reference's defaults (src/sh_path_tracer_stage.hh:14-31, rt_stage::options)
+    {
+        int max_ray_depth = 8;
+        float min_ray_dist = 1e-4f;
+        int rng_seed = 0;
+        sampler_type local_sampler = sampler_type::UNIFORM_RANDOM;      // the only one the stage accepts
+        int samples_per_probe = 1;
+        film_filter film = film_filter::BLACKMAN_HARRIS;
+        multiple_importance_sampling_mode mis_mode = multiple_importance_sampling_mode::MIS_POWER_HEURISTIC;
+        float film_radius = 1.0f;
+        float russian_roulette_delta = 0;
+        float temporal_ratio = 0.02f;
+        float indirect_clamping = 100.0f;
+        float regularization_gamma = 1.0f;
+        light_sampling_weights sampling_weights;
+        bounce_sampling_mode bounce_mode = bounce_sampling_mode::MATERIAL;
+        tri_light_sampling_mode tri_light_mode = tri_light_sampling_mode::SOLID_ANGLE;
+        int sh_order = 2;
+    };
+    sh_path_tracer_stage(device& dev, const sh_grid& grid, const options& opt): dev(&dev), grid(grid), opt(opt)
+    {
+        trhip_pt_options o = {};
+        o.max_bounces = opt.max_ray_depth; o.min_ray_dist = opt.min_ray_dist; o.rng_seed = (uint32_t)opt.rng_seed; o.sampler = (int)opt.local_sampler;
+        o.samples_per_pixel = 1; o.samples_per_pass = 1;
+        o.film = (int)opt.film; o.film_radius = opt.film_radius; o.mis_mode = (int)opt.mis_mode; o.russian_roulette_delta = opt.russian_roulette_delta;
+        o.indirect_clamping = opt.indirect_clamping; o.regularization_gamma = opt.regularization_gamma;
+        o.nee_point = opt.sampling_weights.point_lights; o.nee_directional = opt.sampling_weights.directional_lights;
+        o.nee_envmap = opt.sampling_weights.envmap; o.nee_triangles = opt.sampling_weights.emissive_triangles;
+        o.bounce_mode = (int)opt.bounce_mode; o.tri_light_mode = (int)opt.tri_light_mode;
+        trhip_sh_options so = {};
+        so.order = opt.sh_order; so.samples_per_probe = (uint32_t)std::max(opt.samples_per_probe, 0); so.temporal_ratio = opt.temporal_ratio;
+        for(int i = 0; i < 3; ++i) so.resolution[i] = grid.resolution[i];
+        check(trhip_sh_create(dev.h, &o, &so, &h));
+        check(trhip_sh_set_transform(h, grid.transform, grid.scaling));
+    }
+    sh_path_tracer_stage(const sh_path_tracer_stage&) = delete;
+    ~sh_path_tracer_stage() { trhip_sh_destroy(h); }
+    void set_frame_counter(uint32_t frame_counter) { check(trhip_sh_set_frame_counter(h, frame_counter)); }
+    void reset_history() { check(trhip_sh_reset_history(h)); }
+    void run(void* stream = nullptr) { check(trhip_sh_render(h, stream)); }
+    trhip_sh_timings get_timings() { trhip_sh_timings t; check(trhip_sh_get_timings(h, &t)); return t; }
+    trhip_counters get_counters() { trhip_counters c; check(trhip_sh_get_counters(h, &c)); return c; }
+    uint32_t coef_count() const { return (uint32_t)sh_grid::get_coef_count(opt.sh_order); }
+    // The float volume unfolded to an image of width rx and height ry * C * rz (its rows in memory order)
+    uvec2 unfolded_size() const { return uvec2{grid.resolution[0], grid.resolution[1] * coef_count() * grid.resolution[2]}; }
+    std::vector<float> download()
+    {
+        const uvec2 sz = unfolded_size();
+        std::vector<float> out(size_t(sz.x) * sz.y * 4);
+        check(trhip_sh_download(h, TRHIP_SH_GRID, out.data(), out.size() * sizeof(float)));
+        return out;
+    }
+
+    device* dev;
+    sh_grid grid;
+    options opt;
+    trhip_sh* h = nullptr;
+};
+
+// sh_renderer (src/sh_renderer.{hh,cc}): one sh_path_tracer_stage per sh_grid of the scene, each with the grid's order.
+class sh_renderer
+{
+public:
+    using options = sh_path_tracer_stage::options;
+    sh_renderer(device& dev, const std::vector<sh_grid>& grids, const options& opt)
+    {
+        if(grids.empty()) throw std::runtime_error("sh_renderer: the scene has no light-probe grid (TR_data.light_probe of type GRID)");
+        for(const sh_grid& g: grids)
+        {
+            options o = opt;
+            o.sh_order = g.order;
+            stages.emplace_back(new sh_path_tracer_stage(dev, g, o));
+        }
+    }
+    void render(void* stream = nullptr) { for(auto& s: stages) s->run(stream); }
+    std::vector<std::unique_ptr<sh_path_tracer_stage>> stages;
 };
 
 class load_balancer

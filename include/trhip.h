@@ -715,6 +715,91 @@ int trhip_lkg_get_timings(trhip_lkg* stage, trhip_lkg_timings* out);   /* waits 
 #define TRHIP_LKG_VIEW_INDICES 0      /* uint8 [out_h][out_w][4]: the view of r, g, b; 0 (record_view_indices only) */
 int trhip_lkg_download(trhip_lkg* stage, int which, void* host, size_t bytes);   /* synchronises the device */
 
+/* ---- sh_path_tracer_stage + sh_compact_stage (src/sh_path_tracer_stage.{hh,cc}, shader/sh_path_tracer.rgen, src/sh_grid.{hh,cc},
+ * shader/sh_compact.comp): bakes a grid of light probes as spherical-harmonics coefficients - the server half of the reference's DDISH-GI.
+ * csrc/sh_probes.hip; the order of operations is pinned in csrc/sh_probes.h.  For probe (x, y, z) of a grid of resolution R and sample s of
+ * N = samples_per_probe:
+ *   1. ls = init_local_sampler(uvec4(x, y, z, s)) with sample_counter = frame_counter * N and the rng_seed rule of src/rt_stage.cc:81-82
+ *   2. probe-space offset: 0 (point film), generate_spatial_sample(ls) * 2 - 1 (box), sample_blackman_harris_ball(generate_spatial_sample(ls))
+ *   3. local_pos = ((vec3(p) + offset * film_radius + 0.5) / vec3(R)) * 2 - 1; global_pos = (transform * vec4(local_pos, 1)).xyz
+ *   4. local_dir = even_sample_sphere(s, N, (rotation_x, rotation_y)); global_dir = normalize(normal_transform * local_dir), with
+ *      rotation_x = pcg(frame_counter * N) / float(0xFFFFFFFF), rotation_y the same of frame_counter * N + 1 and
+ *      normal_transform = mat4(get_matrix_orientation(transform))
+ *   5. evaluate_ray with HIDE_LIGHTS and INDIRECT_CLAMP_FIRST_BOUNCE (shader/path_tracer.glsl:422-427, 465-467): the bounce loop of the path
+ *      tracer stage on its general kernels; value = modulate_color(first_hit_material, diffuse.rgb, reflection.rgb), no emission term
+ *   6. dist = clamp(distance(first_hit_vertex.pos, global_pos) * length(local_dir * cell_scale), 0, sqrt(3)), cell_scale = 0.5 * vec3(R) / scaling
+ *   7. coefficient l of the probe = sum over s of vec4(value, dist) * (4 pi / N) * sh_basis(local_dir)[l]
+ *   8. out = mix(previous, new, mix_ratio), mix_ratio = max(1 / history_length, temporal_ratio); history_length counts renders since
+ *      creation or trhip_sh_reset_history; with mix_ratio >= 1 the previous value is not read
+ *   9. one RGBA32F volume [rz][ry * C][rx], C = (order + 1)^2, coefficient l of probe (x, y, z) at (x, y + l * ry, z), and its RGBA16F copy
+ *      in the same layout (what sh_grid::create_texture holds after sh_compact)
+ * Deviations from the reference: (1) the stage keeps a frame counter of its own for the sampler and the rotation
+ * (trhip_sh_set_frame_counter; it advances by one per render) where the reference reads the context's; (2) only sampler = 0
+ * (uniform-random, the command line's default) is accepted: the Sobol samplers take their index from a pixel launch; (3) the N samples of
+ * a probe are summed in one fixed tree (csrc/sh_probes.h) where the reference splits them into invocations and z-slices for Vulkan's 3D
+ * image limit: the same sum in another order.
+ * Of `path` the stage reads max_bounces, min_ray_dist, rng_seed, sampler, film, film_radius, mis_mode, russian_roulette_delta,
+ * indirect_clamping, regularization_gamma, nee_point, nee_directional, nee_envmap, nee_triangles, bounce_mode and tri_light_mode; the sample
+ * counts, projection, depth of field, hide_lights, white albedo, transparent background and pre-transformed vertices do not apply. */
+typedef struct trhip_sh trhip_sh;
+typedef struct trhip_sh_options {     /* sh_path_tracer_stage::options (src/sh_path_tracer_stage.hh) + sh_grid (src/sh_grid.hh) */
+    int32_t order;                    /* 0..4; C = (order + 1)^2 coefficients per probe */
+    uint32_t resolution[3];           /* sh_grid::get_resolution, each 1..1024 */
+    uint32_t samples_per_probe;       /* N >= 1; a probe's samples fit one batch (at most 1920 * 1080) */
+    float temporal_ratio;             /* in [0, 1] */
+} trhip_sh_options;
+typedef struct trhip_sh_grid_data {   /* grid_data_buffer of src/sh_path_tracer_stage.cc:10-19 as the next render would pack it (test hook) */
+    float transform[16], normal_transform[16];   /* column-major */
+    uint32_t grid_size[3];
+    float mix_ratio;
+    float cell_scale[3];
+    float rotation_x, rotation_y;
+} trhip_sh_grid_data;
+typedef struct trhip_sh_timings {     /* the reference's timer, device ms of the last render (every batch, the projection included) */
+    float total_ms;
+    uint32_t frames;                  /* renders since the stage was created */
+    char name[64];                    /* "SH path tracing" */
+    /* Per-kernel device time, only collected while detailed timing is on (trhip_sh_set_profiling: one lane, an event pair around every
+     * launch): the bounce loop's kernels cumulative since trhip_sh_reset_counters (as trhip_timings), k_sh_project of the last render. */
+    float raygen_ms, trace_closest_ms, trace_shadow_ms, shade_ms, project_ms;
+} trhip_sh_timings;
+/* sh_path_tracer_stage ctor.  Refuses a zero resolution, an order outside 0..4, samples_per_probe < 1, a temporal_ratio outside [0, 1],
+ * sampler != 0 and a null device (there is no CPU fallback). */
+int trhip_sh_create(trhip_device* dev, const trhip_pt_options* path, const trhip_sh_options* opt, trhip_sh** out);
+void trhip_sh_destroy(trhip_sh* stage);
+/* The grid's transformable: get_global_transform() (column-major; maps [-1, 1]^3 onto the grid's box) and get_scaling()
+ * (src/sh_path_tracer_stage.cc:119-132).  Identity and (1, 1, 1) until set.  Refuses a transform that is not finite. */
+int trhip_sh_set_transform(trhip_sh* stage, const float transform[16], const float scaling[3]);
+int trhip_sh_set_frame_counter(trhip_sh* stage, uint32_t frame_counter);   /* context::get_frame_counter of the next render */
+int trhip_sh_reset_history(trhip_sh* stage);                               /* history_length = 0: the next render replaces the grid */
+int trhip_sh_set_lanes(trhip_sh* stage, int lanes);                        /* trhip_pt_set_lanes of the stage's bounce loop */
+/* A grid is rendered in batches of whole probes; 0 (the default) = as many as fit 1920 * 1080 paths, the frame the lane schedule was tuned
+ * on.  The grids do not depend on it (tests). */
+int trhip_sh_set_batch_probes(trhip_sh* stage, uint32_t probes);
+int trhip_sh_set_shading_arithmetic(trhip_sh* stage, int ieee);            /* trhip_pt_set_shading_arithmetic of the bounce loop */
+/* TEST AND TOOL HOOKS - the four entries below replace nothing of the reference and are not what an adapter binds; they are exported
+ * like trhip_taa_download and trhip_bmfr_fit_blocks, for the tests and tools/sh_probe_bake_probe.py.
+ * grid_data_buffer as sh_path_tracer_stage::update packs it (src/sh_path_tracer_stage.cc:115-137): of the stage's next render, or - host
+ * only, no device - of render number history_length (>= 1) at frame_counter of a grid with these parameters.  Both hosts call the second
+ * one for their sh_grid_parameters, so a comparison of the hosts checks their argument marshalling; the values are checked against
+ * tests/sh_probes_model.py, which is written from the rule and shares no code with the library. */
+int trhip_sh_get_grid_data(trhip_sh* stage, trhip_sh_grid_data* out);
+int trhip_sh_pack_grid_data(const float transform[16], const float scaling[3], const uint32_t resolution[3], uint32_t samples_per_probe,
+                            uint32_t frame_counter, uint32_t history_length, float temporal_ratio, trhip_sh_grid_data* out);
+/* sh_path_tracer_stage::update + record_command_buffer and sh_compact_stage: one render of the whole grid, asynchronous on `stream`.  Renders
+ * of one stage form one history: run them in order on one stream (or on streams ordered with trhip_stream_wait).  Refuses a device
+ * without a scene or without an acceleration structure. */
+int trhip_sh_render(trhip_sh* stage, void* stream);
+/* The device images, for a consumer (sample_sh_grid reads the RGBA16F one): valid for the life of the stage. */
+int trhip_sh_get_grids(trhip_sh* stage, void** grid_dev, void** grid_half_dev);
+#define TRHIP_SH_GRID 0               /* RGBA32F [rz][ry * C][rx] */
+#define TRHIP_SH_GRID_HALF 1          /* RGBA16F, the same layout */
+int trhip_sh_download(trhip_sh* stage, int which, void* host, size_t bytes);   /* synchronises the device */
+int trhip_sh_get_counters(trhip_sh* stage, trhip_counters* out);   /* rays traced, cumulative (trhip_pt_get_counters of the bounce loop); synchronises the stream */
+int trhip_sh_get_timings(trhip_sh* stage, trhip_sh_timings* out);  /* waits for the last render */
+int trhip_sh_set_profiling(trhip_sh* stage, int count_work, int detailed_timing);   /* tool hook: trhip_pt_set_profiling of the bounce loop */
+int trhip_sh_reset_counters(trhip_sh* stage);                      /* tool hook: trhip_pt_reset_counters of the bounce loop; synchronises the stream */
+
 #ifdef __cplusplus
 }
 #endif

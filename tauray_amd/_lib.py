@@ -200,6 +200,26 @@ class LkgTimingsC(C.Structure):
 LKG_VIEW_INDICES = 0
 
 
+class ShOptionsC(C.Structure):
+    """trhip_sh_options."""
+    _fields_ = [("order", C.c_int32), ("resolution", C.c_uint32 * 3), ("samples_per_probe", C.c_uint32), ("temporal_ratio", C.c_float)]
+
+
+class ShGridDataC(C.Structure):
+    """trhip_sh_grid_data: grid_data_buffer as the next render would pack it."""
+    _fields_ = [("transform", C.c_float * 16), ("normal_transform", C.c_float * 16), ("grid_size", C.c_uint32 * 3), ("mix_ratio", C.c_float),
+                ("cell_scale", C.c_float * 3), ("rotation_x", C.c_float), ("rotation_y", C.c_float)]
+
+
+class ShTimingsC(C.Structure):
+    _fields_ = ([("total_ms", C.c_float), ("frames", C.c_uint32), ("name", C.c_char * 64)] +
+                [(n, C.c_float) for n in ("raygen_ms", "trace_closest_ms", "trace_shadow_ms", "shade_ms", "project_ms")])
+
+
+# trhip_sh_download
+SH_GRID, SH_GRID_HALF = 0, 1
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -309,6 +329,23 @@ SYMBOLS = {
     "trhip_lkg_run": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "trhip_lkg_get_timings": (_i, [_vp, C.POINTER(LkgTimingsC)]),
     "trhip_lkg_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_sh_create": (_i, [_vp, C.POINTER(PtOptionsC), C.POINTER(ShOptionsC), C.POINTER(_vp)]),
+    "trhip_sh_destroy": (None, [_vp]),
+    "trhip_sh_set_transform": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
+    "trhip_sh_set_frame_counter": (_i, [_vp, _u32]),
+    "trhip_sh_reset_history": (_i, [_vp]),
+    "trhip_sh_set_lanes": (_i, [_vp, _i]),
+    "trhip_sh_set_batch_probes": (_i, [_vp, _u32]),
+    "trhip_sh_set_shading_arithmetic": (_i, [_vp, _i]),
+    "trhip_sh_get_grid_data": (_i, [_vp, C.POINTER(ShGridDataC)]),
+    "trhip_sh_pack_grid_data": (_i, [C.POINTER(_f), C.POINTER(_f), C.POINTER(_u32), _u32, _u32, _u32, _f, C.POINTER(ShGridDataC)]),
+    "trhip_sh_render": (_i, [_vp, _vp]),
+    "trhip_sh_get_grids": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "trhip_sh_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_sh_get_counters": (_i, [_vp, C.POINTER(CountersC)]),
+    "trhip_sh_get_timings": (_i, [_vp, C.POINTER(ShTimingsC)]),
+    "trhip_sh_set_profiling": (_i, [_vp, _i, _i]),
+    "trhip_sh_reset_counters": (_i, [_vp]),
 }
 
 _LIB = None

@@ -2,6 +2,7 @@
 // rt_camera_stage / path_tracer_stage: options, distribution params, frame and sample counters).
 #pragma once
 #include "build.h"
+#include "sh_probes.h"
 
 namespace tr {
 
@@ -16,6 +17,8 @@ void stream_pool_release(hipStream_t s);
 // idle and not capturing is probed, anything else is -1 for now.
 int stream_pool_class(hipStream_t s, int* cls, bool blocking = false);
 int stream_pool_pipe_classes(int* classes_out, int* streams_out);      // distinct classes this process reaches on the current device
+
+struct PathBuffers;
 
 class PtStage {
 public:
@@ -50,6 +53,11 @@ public:
     int specialize = -1;             // trhip_pt_set_specialization: 1 = a shading program compiled for this stage's option set (hipRTC / kernel cache), 0 = the general kernels, -1 = TRHIP_SPECIALIZE decides (default on)
     int terminal_query = -1;         // trhip_pt_set_terminal_query: TRHIP_TERMINAL_QUERY_AUTO / _OFF, -1 = TRHIP_TERMINAL_QUERY decides (default auto)
     bool direct = false;             // direct_stage instead of path_tracer_stage (trhip_direct_create)
+    // sh_path_tracer_stage instead (trhip_sh_create): render() traces the batch `probes` names - k_sh_raygen instead of k_raygen, the bounce
+    // loop with hidden lights and the first-bounce clamp on the general kernels, no resolve (sh_probes.hip projects the path state)
+    bool probe_mode = false;
+    const ShProbeBatch* probes = nullptr;
+    const PathBuffers* path_buffers() const;
     hipStream_t last_stream = nullptr;
 
     // which kernels shade this stage (render() and get_program() decide it the same way)

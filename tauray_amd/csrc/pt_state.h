@@ -39,6 +39,7 @@ struct PathBuffers {
     uint* bounce;
     int* qspill;      // deep stack entries of the quad-cooperative tail of the closest-hit waves (trace_quad.h): 16 * TR_QSPILL words per wave of a launch
     uint* counters;   // per lane: statistics (CNT_*): overflow flag, ray / node / triangle / alpha / surface counts, debug slots
+    float* first_dist; // probe stage only (null otherwise): length(first_hit_vertex.pos - origin), written by bounce 0 (sh_path_tracer.rgen:90-93)
 };
 
 // Every counter of PathBuffers::bounce sits in its own 256 bytes: k_shade appends to the shadow queue and to the next
@@ -72,6 +73,7 @@ struct PtParams {
     trhip_pt_targets T;           // device images; null = target not requested
     f4* tm_display;               // trhip_pt_set_fused_tonemap: the last pass's k_resolve also writes tonemap(colour) here (null = off)
     int tm_op; float tm_exposure, tm_gamma; int tm_grid;
+    int clamp_first_bounce;       // INDIRECT_CLAMP_FIRST_BOUNCE (path_tracer.glsl:422-427, 465-467): the probe stage's 1; 0 for every camera stage
 };
 
 

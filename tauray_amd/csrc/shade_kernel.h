@@ -204,6 +204,7 @@ struct SpecCli {
         P.opt.russian_roulette_delta = 0.0f; P.opt.indirect_clamping = 0.0f; P.opt.regularization_gamma = 0.0f;
         P.opt.depth_of_field = 0; P.opt.hide_lights = 0; P.opt.use_white_albedo_on_first_bounce = 0; P.opt.transparent_background = 0;
         P.opt.pre_transformed_vertices = 0;
+        P.clamp_first_bounce = 0;
     }
 };
 #ifdef TR_SPEC_SAMPLER
@@ -224,6 +225,7 @@ struct SpecMacros {
         if (!TR_SPEC_NEE_TRI) P.prob_tri = 0.0f;
         if (!TR_SPEC_NEE_DIR) P.prob_dir = 0.0f;
         if (!TR_SPEC_NEE_ENV) P.prob_env = 0.0f;
+        P.clamp_first_bounce = 0;
     }
 };
 #endif
@@ -315,6 +317,7 @@ TR_DEV void shade_path(const SceneView& sv, const PtParams& P, const PathBuffers
             } else mat.emission += F3(c);
         }
         if (!surface) { STL(STL_NOSURFACE); }
+        if (bounce == 0 && pb.first_dist) pb.first_dist[id] = length(v.pos - pos);      // the probe stage's distance channel (null for a camera stage)
         const bool terminal = LAST || !surface || bounce == P.opt.max_bounces - 1;
 
         // ---- emission with MIS (path_tracer.glsl:413-435)
@@ -322,7 +325,7 @@ TR_DEV void shade_path(const SceneView& sv, const PtParams& P, const PathBuffers
         float mis_weight = 1.0f;
         if (bsdf_pdf != 0) { attenuation = attenuation / bsdf_pdf; mis_weight = bsdf_pdf / mis_pdf; }
         light = attenuation * mis_weight * (mat.emission + light);
-        if (bounce != 0) light *= clamp_contribution_mul(P, light);
+        if (bounce != 0 || P.clamp_first_bounce) light *= clamp_contribution_mul(P, light);
 
         // add_demodulated_color(primary_lobes, light, diffuse, reflection) (path_tracer.glsl:435, material.glsl:66-73)
         if (bounce == 0 || light.x != 0.0f || light.y != 0.0f || light.z != 0.0f) {
@@ -375,6 +378,7 @@ TR_DEV void shade_path(const SceneView& sv, const PtParams& P, const PathBuffers
                 } else {
                     // primary_lobes = lobes (path_tracer.glsl:466)
                     pl = F2(lobes.diffuse + lobes.transmission, lobes.dielectric_reflection + lobes.metallic_reflection);
+                    if (P.clamp_first_bounce && P.opt.indirect_clamping > 0.0f) clamp_lum = rgb_to_luminance(radiance);
                 }
                 if (cast) {
                     // contrib *= shadow_ray(...) happens in k_trace_shadow, including the clamp on the occluded value

@@ -328,6 +328,7 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
     light_meta = {"angle": 0.0, "radius": 0.0}
     node_globals, skinned_pending = {}, []
     nodes, roots = {}, []
+    sh_grids = []
 
     visited = set()
 
@@ -356,6 +357,19 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
         nodes[node_index] = rec      # what SceneAnimator needs to move the node later (tauray_amd/animation.py)
         glob = parent @ local
         node_globals[node_index] = glob
+
+        probe = tr.get("light_probe") if tr else None
+        if probe and probe.get("type") == "GRID":      # an irradiance volume (src/gltf.cc:462-481); its scale must not be negative
+            if "matrix" in node:
+                probe_glob = glob
+            else:
+                probe_glob = parent @ S.trs_matrix(node.get("translation", (0, 0, 0)), node.get("rotation", (0, 0, 0, 1)),
+                                                   np.abs(np.array(node.get("scale", (1, 1, 1)), dtype=np.float64)))
+            res = tuple(int(probe.get(k, 0)) for k in ("resolution_x", "resolution_y", "resolution_z"))
+            if min(res) < 1:
+                raise ValueError("glTF: TR_data.light_probe needs resolution_x, resolution_y and resolution_z >= 1")
+            sh_grids.append(S.ShGrid(resolution=res, radius=float(probe.get("radius", 0.0)), transform=probe_glob,
+                                     scaling=tuple(float(np.linalg.norm(probe_glob[:3, c])) for c in range(3))))
 
         if "mesh" in node:
             sto = 0.0
@@ -461,6 +475,7 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
     desc.node_globals = node_globals
     desc.nodes, desc.roots, desc.animations = nodes, roots, animations
     desc.spotlight_base = len(point_lights)
+    desc.sh_grids = sh_grids
     for inst, skin_index, skin in skinned_pending:
         sk = j["skins"][skin_index]
         joints = list(sk["joints"])

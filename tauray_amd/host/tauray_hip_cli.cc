@@ -9,7 +9,7 @@
 //              [--filetype=exr|raw|none] [--format=rgb16|rgb32|rgba16|rgba32] [--tonemap=filmic|linear|gamma-correction|
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
-//              [--renderer=path-tracer|direct] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
+//              [--renderer=path-tracer|direct|sh-probes [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
 //              [--display=headless|looking-glass --lkg-params=viewports,midplane,depth,relative_dist
 //               --lkg-calibration=display_index,pitch,slope,center,fringe,viewCone,invView,verticalAngle,DPI,screenW,screenH,flipImageX,flipImageY,flipSubp]
@@ -41,6 +41,10 @@ static bool starts(const std::string& s, const std::string& p) { return s.compar
 static const char* const usage_text =
     "usage: tauray_hip scene.glb|scene.gltf|scene.trsc [options]\n"
     "  --width=W --height=H --headless=PREFIX --frames=N --warmup-frames=N --filetype=exr|raw|none --format=rgb16|rgb32|rgba16|rgba32\n"
+    "  --renderer=sh-probes --samples-per-probe=N --sh-order=0..4 --dshgi-temporal-ratio=r   bakes the scene's light-probe grids (TR_data.light_probe)\n"
+    "                         as spherical harmonics; --headless=PREFIX writes PREFIX_grid<k> per grid and frame: the RGBA32F volume unfolded to\n"
+    "                         width rx and height ry * (order + 1)^2 * rz, as rgba32 unless --format says otherwise (alpha is the projected\n"
+    "                         distance; rgb16 / rgb32 drop it) (one device; no denoiser, --taa or reprojection)\n"
     "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
     "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
     "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
@@ -112,10 +116,13 @@ int main(int argc, char** argv)
         uvec2 size{1280, 720};
         int frames = 1, warmup = 0, fake_devices = 1, frames_in_flight = 1, frames_per_launch = 1;
         std::string renderer = "path-tracer";
+        int samples_per_probe = 512, sh_order = 2;                          // --samples-per-probe, --sh-order, --dshgi-temporal-ratio (src/options.hh:254-284)
+        float dshgi_temporal_ratio = 0.01f;
         std::vector<int> devices;
         bool timing = false;
         std::string dump_scene;
         std::string envmap_path;
+        bool format_given = false;                                          // --format: sh-probes defaults to rgba32 (the alpha channel is the distance)
         bool frames_given = false, animation_flag = false;      // --animation[=name] --framerate=F (src/options.hh:110-129)
         std::string animation_name;
         double framerate = 60.0;
@@ -237,7 +244,22 @@ int main(int argc, char** argv)
             else if(starts(a, "--renderer="))
             {
                 renderer = val("--renderer=");
-                if(renderer != "path-tracer" && renderer != "direct") throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct)");
+                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes") throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes)");
+            }
+            else if(starts(a, "--samples-per-probe="))
+            {   // src/options.hh:254-257
+                samples_per_probe = std::stoi(val("--samples-per-probe="));
+                if(samples_per_probe < 1) throw std::runtime_error("--samples-per-probe=N: at least one sample per probe, not " + val("--samples-per-probe="));
+            }
+            else if(starts(a, "--sh-order="))
+            {   // src/options.hh:282-284
+                sh_order = std::stoi(val("--sh-order="));
+                if(sh_order < 0 || sh_order > 4) throw std::runtime_error("--sh-order=O: the order is 0 ... 4, not " + val("--sh-order="));
+            }
+            else if(starts(a, "--dshgi-temporal-ratio="))
+            {   // src/options.hh:258-260
+                dshgi_temporal_ratio = std::stof(val("--dshgi-temporal-ratio="));
+                if(!(dshgi_temporal_ratio >= 0.0f) || !(dshgi_temporal_ratio <= 1.0f)) throw std::runtime_error("--dshgi-temporal-ratio=r: the ratio is in [0, 1]");
             }
             else if(starts(a, "--dump-scene=")) dump_scene = val("--dump-scene=");
             else if(starts(a, "--as-strategy="))     // scene_stage::options::group_strategy (src/options.hh:519-532); see trhip.h
@@ -312,6 +334,7 @@ int main(int argc, char** argv)
             else if(starts(a, "--format="))
             {
                 std::string v = val("--format=");
+                format_given = true;
                 hopt.output_format = v == "rgb32" ? headless::RGB32 : v == "rgba16" ? headless::RGBA16 : v == "rgba32" ? headless::RGBA32 : headless::RGB16;
             }
             else if(starts(a, "--tonemap="))
@@ -408,6 +431,50 @@ int main(int argc, char** argv)
         opt.samples_per_pass = std::min(opt.samples_per_pass, opt.samples_per_pixel);
         opt.active_viewport_count = viewports;
 
+        if(renderer == "sh-probes")
+        {   // sh_renderer (src/tauray.cc:423-433, src/sh_renderer.cc): bakes the scene's probe grids, one sh_path_tracer_stage per grid
+            if(opt.bmfr || opt.taa || !opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)
+                throw std::runtime_error("--renderer=sh-probes bakes probe grids: a denoiser, --taa and reprojection do not apply");
+            if(devices.size() > 1 || process_count > 0 || shard_views)
+                throw std::runtime_error("--renderer=sh-probes runs on one device: the probes of a grid share one history on one device, baking across several is not built");
+            if(looking_glass || grid_w * grid_h > 1) throw std::runtime_error("--renderer=sh-probes renders no camera: no --display=looking-glass, no --camera-grid");
+            if(opt.local_sampler != sampler_type::UNIFORM_RANDOM)
+                throw std::runtime_error("--renderer=sh-probes: --sampler must be uniform-random (the Sobol samplers take their index from a pixel launch)");
+            if(scene.sh_grids.empty())
+                throw std::runtime_error("--renderer=sh-probes: " + scene_path + " has no light-probe grid (a node with TR_data.light_probe of type GRID)");
+            for(sh_grid& g: scene.sh_grids) g.order = sh_order;      // src/tauray.cc:151
+            sh_renderer::options so;
+            so.max_ray_depth = opt.max_ray_depth; so.min_ray_dist = opt.min_ray_dist; so.rng_seed = opt.rng_seed; so.local_sampler = opt.local_sampler;
+            so.samples_per_probe = samples_per_probe; so.film = opt.film; so.film_radius = opt.film_radius; so.mis_mode = opt.mis_mode;
+            so.russian_roulette_delta = opt.russian_roulette_delta; so.temporal_ratio = dshgi_temporal_ratio; so.indirect_clamping = opt.indirect_clamping;
+            so.regularization_gamma = opt.regularization_gamma; so.sampling_weights = opt.sampling_weights;
+            so.bounce_mode = opt.bounce_mode; so.tri_light_mode = opt.tri_light_mode;
+            device dev(devices[0]);
+            scene_stage ss(dev, opt.scene);
+            ss.set_scene(scene);
+            sh_renderer sr(dev, scene.sh_grids, so);
+            for(int f = -warmup; f < frames; ++f)
+            {
+                sr.render();
+                dev.sync();
+                if(f < 0) continue;
+                if(timing)
+                {
+                    std::cout << "FRAME " << f << ":\n\tDEVICE 0:\n";
+                    for(auto& st: sr.stages) { const trhip_sh_timings t = st->get_timings(); std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n"; }
+                }
+                for(size_t k = 0; k < sr.stages.size(); ++k)
+                {   // the RGBA32F volume unfolded to width rx, height ry * C * rz
+                    headless::options go = hopt;
+                    go.size = sr.stages[k]->unfolded_size(); go.output_prefix = prefix + "_grid" + std::to_string(k); go.display_count = 1;
+                    if(!format_given) go.output_format = headless::RGBA32;      // coefficients, not colours: full precision, and alpha holds the distance
+                    headless gout(go);
+                    const std::vector<float> img = sr.stages[k]->download();
+                    gout.write_image(gout.get_filename(0, (unsigned)f), img.data());
+                }
+            }
+            return 0;
+        }
         opt.max_frames_in_flight = frames_in_flight;
         opt.frames_per_launch = frames_per_launch;
         if(!opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)

@@ -10,6 +10,8 @@ TrhipError where the reference throws std::runtime_error):
 * ``FeatureStage``       - feature_stage (src/feature_stage.{hh,cc})
 * ``StitchStage``        - stitch_stage (src/stitch_stage.{hh,cc})
 * ``TonemapStage``       - tonemap_stage (src/tonemap_stage.{hh,cc})
+* ``ShPathTracerStage`` / ``ShRenderer`` - sh_path_tracer_stage + sh_compact_stage, sh_renderer (src/sh_path_tracer_stage.{hh,cc},
+                           src/sh_renderer.{hh,cc}): the probe grids of a scene baked as spherical harmonics
 * ``RtRenderer``         - rt_renderer<path_tracer_stage> (src/rt_renderer.{hh,cc}); one process per GPU,
                            partial frames gathered with torch.distributed (RCCL) instead of host-bounce copies
 """
@@ -27,7 +29,7 @@ from ._lib import (AccelInfoC, AccelLayoutC, CountersC, DistributionC, LightAcce
                    TonemapInfoC, TrhipError, check)
 from .distribution import (DISTRIBUTION_DUPLICATE, DISTRIBUTION_SCANLINE, DISTRIBUTION_SHUFFLED_STRIPS, DistributionParams,
                            get_device_distribution_params, get_distribution_target_size)
-from .scene import SceneDesc, build_alias_table
+from .scene import SceneDesc, ShGrid, build_alias_table
 
 # film_filter, multiple_importance_sampling_mode, bounce_sampling_mode, tri_light_sampling_mode (src/rt_common.hh)
 FILM_POINT, FILM_BOX, FILM_BLACKMAN_HARRIS = 0, 1, 2
@@ -957,6 +959,145 @@ class LookingGlassStage(_PostStage):
     def view_indices(self) -> np.ndarray:
         """uint8 [out_h][out_w][4]: the view the last frame took r, g and b from; 0 (record_view_indices only)."""
         return self._download(_lib.LKG_VIEW_INDICES, (self.out_size[1], self.out_size[0], 4), np.uint8)
+
+
+def sh_coef_count(order: int) -> int:
+    """sh_grid::get_coef_count (src/sh_grid.cc)."""
+    return (int(order) + 1) ** 2
+
+
+def sh_options(**kw) -> dict:
+    """sh_path_tracer_stage::options at the reference's defaults (src/sh_path_tracer_stage.hh:14-31; rt_stage::options for the rest)."""
+    o = dict(max_bounces=8, min_ray_dist=1e-4, rng_seed=0, sampler=SAMPLER_UNIFORM_RANDOM, samples_per_probe=1, film=FILM_BLACKMAN_HARRIS,
+             film_radius=1.0, mis_mode=MIS_POWER_HEURISTIC, russian_roulette_delta=0.0, temporal_ratio=0.02, indirect_clamping=100.0,
+             regularization_gamma=1.0, nee_point=1.0, nee_directional=1.0, nee_envmap=1.0, nee_triangles=1.0, bounce_mode=BOUNCE_MATERIAL,
+             tri_light_mode=TRI_LIGHT_SOLID_ANGLE, sh_order=2)
+    unknown = set(kw) - set(o)
+    if unknown:
+        raise AttributeError(f"not an option of the SH path tracer stage: {sorted(unknown)}")
+    o.update(kw)
+    return o
+
+
+def _sh_grid_data_dict(g) -> dict:
+    return dict(transform=np.array(g.transform, dtype=np.float32).reshape(4, 4).T, normal_transform=np.array(g.normal_transform, dtype=np.float32).reshape(4, 4).T,
+                grid_size=tuple(g.grid_size), mix_ratio=float(g.mix_ratio), cell_scale=np.array(g.cell_scale, dtype=np.float32),
+                rotation_x=float(g.rotation_x), rotation_y=float(g.rotation_y))
+
+
+def sh_grid_parameters(grid: ShGrid, samples_per_probe: int, frame_counter: int, history_length: int, temporal_ratio: float) -> dict:
+    """grid_data_buffer of render number `history_length` of `grid` at `frame_counter` (src/sh_path_tracer_stage.cc:115-137): transform and
+    normal_transform as mathematical 4x4, cell_scale, the rotations of the direction lattice, mix_ratio.  Needs no device."""
+    t = np.ascontiguousarray(np.asarray(grid.transform, dtype=np.float64).T, dtype=np.float32).reshape(16)
+    sc = np.asarray(grid.scaling, dtype=np.float32).reshape(3)
+    res = (C.c_uint32 * 3)(*[int(r) for r in grid.resolution])
+    g = _lib.ShGridDataC()
+    check(_lib.lib().trhip_sh_pack_grid_data(t.ctypes.data_as(C.POINTER(C.c_float)), sc.ctypes.data_as(C.POINTER(C.c_float)), res, int(samples_per_probe),
+                                             int(frame_counter) & 0xFFFFFFFF, int(history_length), float(temporal_ratio), C.byref(g)))
+    return _sh_grid_data_dict(g)
+
+
+class ShPathTracerStage(_PostStage):
+    """sh_path_tracer_stage(device&, scene_stage&, texture& output_grid, layout, const options&) followed by sh_compact_stage
+    (src/sh_path_tracer_stage.{hh,cc}, src/sh_compact_stage.cc): bakes one sh_grid (trhip_sh_*, include/trhip.h).  `grid`: a scene.ShGrid;
+    `options`: sh_options().  The stage owns both volumes: RGBA32F [rz][ry * C][rx] and its RGBA16F copy."""
+
+    PREFIX, TIMINGS = "sh", _lib.ShTimingsC
+
+    def __init__(self, ctx: Context, scene_stage: Optional[SceneStage], grid: ShGrid, options: Optional[dict] = None):
+        self.options = sh_options(**(options or {}))
+        self.ctx, self.scene_stage, self.grid = ctx, scene_stage, grid
+        o = self.options
+        self.order, self.samples = int(o["sh_order"]), int(o["samples_per_probe"])
+        self.resolution = tuple(int(r) for r in grid.resolution)
+        path = make_options(**{k: o[k] for k in ("max_bounces", "min_ray_dist", "rng_seed", "sampler", "film", "film_radius", "mis_mode",
+                                                 "russian_roulette_delta", "indirect_clamping", "regularization_gamma", "nee_point",
+                                                 "nee_directional", "nee_envmap", "nee_triangles", "bounce_mode", "tri_light_mode")})
+        opt = _lib.ShOptionsC(self.order, (C.c_uint32 * 3)(*[max(r, 0) for r in self.resolution]), max(self.samples, 0), float(o["temporal_ratio"]))
+        self._create(getattr(ctx, "h", None), C.byref(path), C.byref(opt))
+        self.set_transform(grid.transform, grid.scaling)
+
+    def set_transform(self, transform, scaling):
+        """The grid's transformable: `transform` a mathematical 4x4 (get_global_transform), `scaling` its get_scaling()."""
+        t = np.ascontiguousarray(np.asarray(transform, dtype=np.float64).T, dtype=np.float32).reshape(16)      # column-major, as glm
+        sc = np.asarray(scaling, dtype=np.float32).reshape(3)
+        check(_lib.lib().trhip_sh_set_transform(self.h, t.ctypes.data_as(C.POINTER(C.c_float)), sc.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def set_frame_counter(self, frame_counter: int):
+        check(_lib.lib().trhip_sh_set_frame_counter(self.h, frame_counter))
+
+    def reset_history(self):
+        check(_lib.lib().trhip_sh_reset_history(self.h))
+
+    def set_lanes(self, lanes: int):
+        check(_lib.lib().trhip_sh_set_lanes(self.h, lanes))
+
+    def set_batch_probes(self, probes: int):
+        check(_lib.lib().trhip_sh_set_batch_probes(self.h, probes))
+
+    def set_shading_arithmetic(self, ieee: bool):
+        check(_lib.lib().trhip_sh_set_shading_arithmetic(self.h, 1 if ieee else 0))
+
+    def grid_data(self) -> dict:
+        """grid_data_buffer as the next run would pack it: transform and normal_transform as mathematical 4x4, cell_scale, the rotations,
+        mix_ratio."""
+        g = _lib.ShGridDataC()
+        check(_lib.lib().trhip_sh_get_grid_data(self.h, C.byref(g)))
+        return _sh_grid_data_dict(g)
+
+    def run(self, stream=None):
+        """stage::run: one render of the whole grid, blended into the stage's history."""
+        check(_lib.lib().trhip_sh_render(self.h, stream))
+
+    @property
+    def shape(self):
+        rx, ry, rz = self.resolution
+        return (rz, ry * sh_coef_count(self.order), rx, 4)
+
+    def download(self, name: str = "grid") -> np.ndarray:
+        """"grid": RGBA32F [rz][ry * C][rx][4]; "half": the RGBA16F copy."""
+        if name == "grid":
+            return self._download(_lib.SH_GRID, self.shape)
+        if name == "half":
+            return self._download(_lib.SH_GRID_HALF, self.shape, np.float16)
+        raise KeyError(name)
+
+    def device_grids(self):
+        """The device addresses of the two volumes, for a consumer."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(_lib.lib().trhip_sh_get_grids(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def counters(self) -> dict:
+        c = CountersC()
+        check(_lib.lib().trhip_sh_get_counters(self.h, C.byref(c)))
+        return {n: getattr(c, n) for n, _ in c._fields_}
+
+    def set_profiling(self, count_work=False, detailed_timing=False):
+        check(_lib.lib().trhip_sh_set_profiling(self.h, int(count_work), int(detailed_timing)))
+
+    def reset_counters(self):
+        check(_lib.lib().trhip_sh_reset_counters(self.h))
+
+
+class ShRenderer:
+    """sh_renderer (src/sh_renderer.{hh,cc}): one ShPathTracerStage per sh_grid of the scene."""
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, grids, options: Optional[dict] = None):
+        if not grids:
+            raise ValueError("ShRenderer: the scene has no light-probe grid (TR_data.light_probe of type GRID)")
+        self.stages = [ShPathTracerStage(ctx, scene_stage, g, options) for g in grids]
+
+    def render(self, stream=None):
+        for st in self.stages:
+            st.run(stream)
+
+    def download(self, name: str = "grid"):
+        return [st.download(name) for st in self.stages]
+
+    def close(self):
+        for st in self.stages:
+            st.close()
 
 
 @dataclass(frozen=True)

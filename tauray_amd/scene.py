@@ -362,6 +362,16 @@ class SkinnedMesh:
 
 
 @dataclass
+class ShGrid:
+    """sh_grid + its transformable (src/sh_grid.hh; TR_data.light_probe of type GRID, src/gltf.cc:462-481): a grid of light probes in the
+    box the node's global transform maps [-1, 1]^3 onto."""
+    resolution: tuple                          # (rx, ry, rz)
+    radius: float = 0.0
+    transform: np.ndarray = field(default_factory=lambda: np.eye(4))   # mathematical 4x4: get_global_transform()
+    scaling: tuple = (1.0, 1.0, 1.0)           # get_scaling(), made absolute
+
+
+@dataclass
 class SceneDesc:
     """Everything `trhip_scene_upload` takes: the flattened scene of
     scene_stage::update (src/scene_stage.cc:1026-1496)."""
@@ -384,6 +394,7 @@ class SceneDesc:
     spotlight_base: int = 0                                        # index of the first spotlight in point_lights (point lights come first)
     camera_rig: Optional[list] = None                              # looking_glass_cameras: the views' transforms under the first camera's node
     camera_rig_frame: Optional[np.ndarray] = None                  # ... and that node's global transform, the rig's reference frame
+    sh_grids: List["ShGrid"] = field(default_factory=list)         # TR_data.light_probe nodes of type GRID, in node order
 
     def joint_transforms(self, sk: "SkinnedMesh", node_globals: Optional[dict] = None) -> np.ndarray:
         """model::update_joints (src/model.cc:107-118): joint node's global transform * inverse bind matrix, (n, 4, 4)."""
