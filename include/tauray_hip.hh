@@ -777,6 +777,169 @@ public:
     std::vector<std::unique_ptr<sh_path_tracer_stage>> stages;
 };
 
+// get_sh_grid, then get_largest_sh_grid (src/scene.cc:163-211) for `position`: the index into `grids`, -1 without any.  Needs no device.
+inline int dshgi_pick_grid(const std::vector<sh_grid>& grids, const float position[3])
+{
+    std::vector<float> transforms, scalings, radii;
+    std::vector<uint32_t> resolutions;
+    for(const sh_grid& g: grids)
+    {
+        transforms.insert(transforms.end(), g.transform, g.transform + 16);
+        scalings.insert(scalings.end(), g.scaling, g.scaling + 3);
+        resolutions.insert(resolutions.end(), g.resolution, g.resolution + 3);
+        radii.push_back(g.radius);
+    }
+    int32_t index = -1;
+    check(trhip_dshgi_pick_grid(transforms.data(), scalings.data(), resolutions.data(), radii.data(), (uint32_t)grids.size(), position, &index));
+    return index;
+}
+
+// sh_grid_index of every instance (src/scene_stage.cc:1075-1083): the grid picked for model[3], the instance's origin.
+inline std::vector<int32_t> dshgi_instance_grids(const std::vector<sh_grid>& grids, const scene_data& scene)
+{
+    std::vector<int32_t> out(scene.instance_count());
+    for(uint32_t i = 0; i < scene.instance_count(); ++i)
+    {
+        float p[3];
+        std::memcpy(p, scene.instances.data() + 288 * size_t(i) + 16 + 48, sizeof(p));      // model[3].xyz
+        out[i] = dshgi_pick_grid(grids, p);
+    }
+    return out;
+}
+
+// The indirect light of dshgi_renderer (shader/forward.frag; trhip_dshgi_*): first hit, SH grid lookup, brdf_indirect, added to the direct
+// stage's colour.  `size`, `layers`: the images of a frame.
+class dshgi_stage
+{
+public:
+    struct options
+    {
+        int sh_order = 2;
+        bool use_probe_visibility = false;      // --use-probe-visibility; off = SH_INTERPOLATION_TRILINEAR
+        bool record_surface = false;
+        int projection = 0;
+        float min_ray_dist = 1e-4f;
+    };
+    dshgi_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), size(size), layers(layers), opt(opt)
+    {
+        trhip_dshgi_options o = {};
+        o.order = opt.sh_order; o.use_probe_visibility = opt.use_probe_visibility; o.record_surface = opt.record_surface;
+        check(trhip_dshgi_create(dev.h, &o, size.x, size.y, layers, &h));
+    }
+    dshgi_stage(const dshgi_stage&) = delete;
+    ~dshgi_stage() { trhip_dshgi_destroy(h); }
+    // `images`: the RGBA16F volume of each grid on the device (trhip_sh_get_grids' second image)
+    void set_grids(const std::vector<sh_grid>& grids, const std::vector<const void*>& images)
+    {
+        std::vector<trhip_dshgi_grid> g(grids.size());
+        for(size_t i = 0; i < grids.size(); ++i)
+        {
+            g[i].grid_half_dev = images[i];
+            std::memcpy(g[i].resolution, grids[i].resolution, sizeof(g[i].resolution));
+            std::memcpy(g[i].transform, grids[i].transform, sizeof(g[i].transform));
+            std::memcpy(g[i].scaling, grids[i].scaling, sizeof(g[i].scaling));
+        }
+        check(trhip_dshgi_set_grids(h, g.data(), (uint32_t)g.size()));
+    }
+    void set_instance_grids(const std::vector<int32_t>& v) { check(trhip_dshgi_set_instance_grids(h, v.data(), (uint32_t)v.size())); }
+    void set_brdf_integration(const void* table_dev, uint32_t w, uint32_t h_) { check(trhip_dshgi_set_brdf_integration(h, table_dev, w, h_)); }
+    // out = direct + indirect for the listed viewports; a null `direct` writes the indirect term alone, `out` may be `direct`
+    void run(const std::vector<uint32_t>& viewports, const void* direct, void* out, void* stream = nullptr)
+    {
+        check(trhip_dshgi_render(h, opt.projection, viewports.data(), (uint32_t)viewports.size(), opt.min_ray_dist, direct, out, stream));
+    }
+    trhip_dshgi_timings get_timings() { trhip_dshgi_timings t; check(trhip_dshgi_get_timings(h, &t)); return t; }
+
+    device* dev;
+    uvec2 size;
+    uint32_t layers;
+    options opt;
+    trhip_dshgi* h = nullptr;
+};
+
+// dshgi_renderer (src/dshgi_renderer.{hh,cc}): per frame the scene's probe grids are baked (sh_renderer), the direct stage renders every
+// viewport, the indirect light of the grids is added (dshgi_stage), the frame is tonemapped - all on one stream.  The first bake has
+// history 1, so the grids are complete before they are read.  The reference rasterises and uses shadow maps; here the first hit is a ray
+// and direct light is the direct stage.  Direct light is what the reference's raster pass lights with - point and
+// directional lights: the direct stage samples neither the emissive triangles nor the environment map (it still shows them where a pixel
+// sees them), because the probes see both and the indirect term carries their light.
+class dshgi_renderer
+{
+public:
+    struct options
+    {
+        path_tracer_stage::options direct;      // the direct stage; its distribution is set here
+        sh_renderer::options sh;                // the bake
+        bool use_probe_visibility = false;
+        std::vector<float> brdf_integration;    // RG32F [h][w]; empty = the generated 256 x 256 table of 1024 samples
+        uint32_t brdf_integration_width = 0, brdf_integration_height = 0;
+        tonemap_stage::options tonemap;
+    };
+    dshgi_renderer(device& dev, scene_stage& ss, const scene_data& scene, uvec2 size, const options& opt_)
+    : dev(&dev), size(size), grids(scene.sh_grids), viewports(std::max(scene.camera_count(), 1u)), opt(opt_), sh(dev, scene.sh_grids, opt_.sh)
+    {
+        const size_t bytes = size_t(size.x) * size.y * 16 * viewports;
+        color = dev.alloc(bytes); display = dev.alloc(bytes);
+        check(trhip_memset(dev.h, color, 0, bytes, nullptr));
+        check(trhip_memset(dev.h, display, 0, bytes, nullptr));
+        opt.direct.distribution = distribution_params{size, DISTRIBUTION_DUPLICATE, 0, 1, true};
+        opt.direct.active_viewport_count = viewports;
+        opt.direct.sampling_weights.emissive_triangles = 0; opt.direct.sampling_weights.envmap = 0;
+        direct.reset(new direct_stage(dev, ss, color, opt.direct));
+        dshgi_stage::options io;
+        io.sh_order = grids[0].order; io.use_probe_visibility = opt.use_probe_visibility; io.projection = opt.direct.projection; io.min_ray_dist = opt.direct.min_ray_dist;
+        indirect.reset(new dshgi_stage(dev, size, viewports, io));
+        std::vector<const void*> images;
+        for(auto& st: sh.stages) { void* half = nullptr; check(trhip_sh_get_grids(st->h, nullptr, &half)); images.push_back(half); }
+        indirect->set_grids(grids, images);
+        uint32_t tw = 256, th = 256;
+        if(!opt.brdf_integration.empty()) { tw = opt.brdf_integration_width; th = opt.brdf_integration_height; }
+        void* table = dev.alloc(size_t(tw) * th * 8);
+        if(opt.brdf_integration.empty()) check(trhip_brdf_integration_generate(dev.h, tw, 1024, table, nullptr));
+        else
+        {
+            if(opt.brdf_integration.size() != size_t(tw) * th * 2) throw std::runtime_error("dshgi_renderer: the BRDF-integration table is not width * height * 2 floats");
+            check(trhip_upload(dev.h, table, opt.brdf_integration.data(), size_t(tw) * th * 8, nullptr));
+        }
+        dev.sync();
+        indirect->set_brdf_integration(table, tw, th);
+        dev.free(table);
+        tonemap.reset(new tonemap_stage(dev, opt.tonemap));
+        for(uint32_t v = 0; v < viewports; ++v) viewport_list.push_back(v);
+        set_scene(scene);
+    }
+    dshgi_renderer(const dshgi_renderer&) = delete;
+    ~dshgi_renderer() { direct.reset(); indirect.reset(); dev->free(color); dev->free(display); }
+    // the instances have moved (the scene stage holds them already): every instance picks its grid again
+    void set_scene(const scene_data& scene)
+    {
+        instance_grids = dshgi_instance_grids(grids, scene);
+        indirect->set_instance_grids(instance_grids);
+    }
+    void render(void* stream = nullptr)
+    {
+        sh.render(stream);
+        direct->reset_accumulated_samples();
+        direct->run(stream);
+        indirect->run(viewport_list, color, color, stream);
+        tonemap->run(color, display, size, viewports, stream);
+    }
+
+    device* dev;
+    uvec2 size;
+    std::vector<sh_grid> grids;
+    uint32_t viewports;
+    options opt;
+    sh_renderer sh;
+    std::unique_ptr<direct_stage> direct;
+    std::unique_ptr<dshgi_stage> indirect;
+    std::unique_ptr<tonemap_stage> tonemap;
+    std::vector<uint32_t> viewport_list;
+    std::vector<int32_t> instance_grids;
+    void* color = nullptr;
+    void* display = nullptr;
+};
+
 class load_balancer
 {
 public:

@@ -790,7 +790,7 @@ int trhip_sh_pack_grid_data(const float transform[16], const float scaling[3], c
  * of one stage form one history: run them in order on one stream (or on streams ordered with trhip_stream_wait).  Refuses a device
  * without a scene or without an acceleration structure. */
 int trhip_sh_render(trhip_sh* stage, void* stream);
-/* The device images, for a consumer (sample_sh_grid reads the RGBA16F one): valid for the life of the stage. */
+/* The device images, for a consumer (trhip_dshgi_set_grids takes the RGBA16F one: sample_sh_grid reads it): valid for the life of the stage. */
 int trhip_sh_get_grids(trhip_sh* stage, void** grid_dev, void** grid_half_dev);
 #define TRHIP_SH_GRID 0               /* RGBA32F [rz][ry * C][rx] */
 #define TRHIP_SH_GRID_HALF 1          /* RGBA16F, the same layout */
@@ -799,6 +799,88 @@ int trhip_sh_get_counters(trhip_sh* stage, trhip_counters* out);   /* rays trace
 int trhip_sh_get_timings(trhip_sh* stage, trhip_sh_timings* out);  /* waits for the last render */
 int trhip_sh_set_profiling(trhip_sh* stage, int count_work, int detailed_timing);   /* tool hook: trhip_pt_set_profiling of the bounce loop */
 int trhip_sh_reset_counters(trhip_sh* stage);                      /* tool hook: trhip_pt_reset_counters of the bounce loop; synchronises the stream */
+
+/* ---- dshgi_renderer's indirect light (src/dshgi_renderer.{hh,cc}, shader/forward.frag:100-159, shader/spherical_harmonics.glsl:80-312,
+ * src/scene_stage.cc:1119-1131, src/scene.cc:163-211, src/sh_grid.cc:116-144, shader/ggx.glsl:69-72): the consumer half of the reference's
+ * DDISH-GI - direct light plus indirect light looked up in the baked SH grids, no bounce rays per pixel.  csrc/dshgi.hip; the order of
+ * operations is pinned in csrc/dshgi.h.  Per pixel of each viewport one ray goes through the pixel centre, as trhip_gbuffer_render traces
+ * it.  On a hit:
+ *   1. shade_surface gives v (pos, smooth_normal, mapped_normal) and mat; view = normalize(v.pos - camera origin)
+ *   2. grid g = instance_grids[hit.instance_id] (trhip_dshgi_pick_grid below); per grid pos_from_world = affineInverse(transform),
+ *      normal_from_world = mat4(inverse(get_matrix_orientation(transform))), grid_clamp = 0.5 / R
+ *   3. sample_pos = pos_from_world * v.pos; sample_normal (of smooth_normal), sh_normal (of mapped_normal) and
+ *      sh_ref = reflect(view, mapped_normal) go through normal_from_world and are normalized
+ *   4. sample_sh_grid, chosen per stage by use_probe_visibility (the reference's --use-probe-visibility; off = trilinear):
+ *      trilinear   p = clamp(sample_pos * 0.5 + 0.5, grid_clamp, 1 - grid_clamp); c = p * R - 0.5; lo = floor(c), hi = min(lo + 1, R - 1), the
+ *                  weights are the fractions in fp32; eight RGBA16F texels per coefficient at (x, y + l * ry, z), one fixed chain of sums
+ *      visibility  spherical_harmonics.glsl:245-308: interp_pos, the eight weight[k], normal_factor,
+ *                  visibility = calc_sh_value(lc, -normalize(sample_dir * inv_grid_size)).w,
+ *                  visibility_factor = clamp(visibility - sample_dist + 0.4, 0, 1), renormalised by sum_weight (0 when the sum is 0).
+ *                  clamp(x, lo, hi) is fmin(fmax(x, lo), hi): a shading point exactly on a probe has sample_dir = 0 / 0 there, both
+ *                  factors become 0 and that corner has weight 0 (GLSL leaves clamp(NaN) undefined)
+ *   5. incoming_diffuse = max(sum coef[l].rgb * cosine_lobe(sh_normal)[l], 0), band factors 1, 2/3, 1/4, 0, -1/24;
+ *      incoming_reflection = max(sum coef[l].rgb * ggx_lobe(sh_ref, sqrt(mat.roughness))[l], 0), the fitted zh curves of lines 126-151
+ *   6. brdf_indirect: cos_v = max(dot(mapped_normal, -view), 0); fresnel = fresnel_schlick_attenuated(cos_v, f0, roughness);
+ *      kd = (1 - fresnel)(1 - metallic)(1 - transmittance); bi = the bilinear, clamp-to-edge fetch of the BRDF-integration table at
+ *      (cos_v, sqrt(roughness)); diffuse = kd * incoming_diffuse; reflection = incoming_reflection * mix(fresnel * bi.x + bi.y, 1, metallic)
+ *   7. indirect = modulate_color(mat, diffuse, reflection), no emission term; a miss or an instance without a grid (index -1) gives 0
+ *   8. colour.rgb = direct.rgb + indirect, one fp32 add per channel; alpha is the direct stage's (modulate_color is linear, so this
+ *      equals the reference's single call)
+ * Deviations from the reference: (1) the reference rasterises the first hit and lights it with shadow maps; here the
+ * first hit is a ray and direct light is the direct stage (trhip_direct_create); (2) Vulkan's sampler filters the trilinear branch with
+ * 8-bit fixed-point weights, these are fp32; (3) the reference gives an instance without a grid an ambient colour, here it gets 0;
+ * (4) the BRDF-integration table is generated (below) unless one is uploaded. */
+typedef struct trhip_dshgi trhip_dshgi;
+typedef struct trhip_dshgi_options {
+    int32_t order;                    /* 0..4, the order the grids were baked at */
+    int32_t use_probe_visibility;     /* 0 = SH_INTERPOLATION_TRILINEAR */
+    int32_t record_surface;           /* keep TRHIP_DSHGI_SURFACE (test hook) */
+} trhip_dshgi_options;
+typedef struct trhip_dshgi_grid {     /* sh_grid + its transformable + its texture */
+    const void* grid_half_dev;        /* RGBA16F [rz][ry * C][rx], trhip_sh_get_grids' second image or any upload of that layout */
+    uint32_t resolution[3];           /* each 1..1024 */
+    float transform[16];              /* get_global_transform(), column-major */
+    float scaling[3];                 /* get_global_scaling() */
+} trhip_dshgi_grid;
+typedef struct trhip_dshgi_surface {  /* TRHIP_DSHGI_SURFACE: what the kernel shaded a pixel with; instance_id -1 = a miss (the rest 0) */
+    float pos[3], smooth_normal[3], mapped_normal[3], view[3], albedo[4];
+    float metallic, roughness, f0, transmittance;
+    int32_t grid, instance_id;
+} trhip_dshgi_surface;
+typedef struct trhip_dshgi_timings {  /* device ms of the last render */
+    float total_ms;
+    uint32_t frames;
+    char name[64];                    /* "dshgi indirect" */
+} trhip_dshgi_timings;
+/* Refuses a null device (there is no CPU fallback), an order outside 0..4 and a zero width, height or layer count. */
+int trhip_dshgi_create(trhip_device* dev, const trhip_dshgi_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_dshgi** out);
+void trhip_dshgi_destroy(trhip_dshgi* stage);
+/* The scene's grids; the library derives pos_from_world, normal_from_world and grid_clamp.  The images stay the caller's.  Synchronous. */
+int trhip_dshgi_set_grids(trhip_dshgi* stage, const trhip_dshgi_grid* grids, uint32_t count);
+/* sh_grid_index of every instance of the scene, -1 = none.  Refuses an index outside the grids set.  Synchronous. */
+int trhip_dshgi_set_instance_grids(trhip_dshgi* stage, const int32_t* instance_grids, uint32_t count);
+/* The BRDF-integration table, RG32F [h][w] on the device: texel (i, j) holds scale and bias at cos_v = (i + 0.5) / w and
+ * sqrt(roughness) = (j + 0.5) / h.  The stage keeps a copy.  Synchronous. */
+int trhip_dshgi_set_brdf_integration(trhip_dshgi* stage, const void* table_dev, uint32_t w, uint32_t h);
+/* One frame of `count` viewports (at most the stage's layers), one launch per 64, asynchronous on `stream`: out_color_dev RGBA32F
+ * [count][h][w] = direct_color_dev + indirect.  `out` may alias `direct`; a null `direct` writes the indirect term alone (alpha 0).
+ * Refuses: no grids set, an instance count different from the scene's, no table, a device without a scene or acceleration structure. */
+int trhip_dshgi_render(trhip_dshgi* stage, int projection, const uint32_t* viewports, uint32_t count, float min_ray_dist,
+                       const void* direct_color_dev, void* out_color_dev, void* stream);
+int trhip_dshgi_get_timings(trhip_dshgi* stage, trhip_dshgi_timings* out);   /* waits for the last render */
+#define TRHIP_DSHGI_INDIRECT 0        /* RGBA32F [layers][h][w]: the indirect term of the last render, alpha 0 */
+#define TRHIP_DSHGI_SURFACE 1         /* trhip_dshgi_surface [layers][h][w] (record_surface only) */
+int trhip_dshgi_download(trhip_dshgi* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
+/* get_sh_grid and get_largest_sh_grid (src/scene.cc:163-211) for `position` (the hosts pass model[3] of an instance): inside several grids
+ * the densest wins (`>` on density), otherwise the nearest within its guard distance (`<=` on sh_grid::point_distance with the grid's
+ * radius, later grids win ties), otherwise the grid of largest volume; -1 when there is none.  transforms 16, scalings 3, resolutions 3
+ * values and one radius per grid.  Host only, no device: both hosts call it, the model of tests/dshgi_model.py checks it. */
+int trhip_dshgi_pick_grid(const float* transforms, const float* scalings, const uint32_t* resolutions, const float* radii, uint32_t count,
+                          const float position[3], int32_t* index);
+/* The table the reference loads from data/brdf_integration.exr, evaluated on the device: size x size cells of `samples` Hammersley samples
+ * of the split sum with this library's GGX terms (csrc/dshgi.h), cell (i, j) at cos_v = (i + 0.5) / size, alpha = ((j + 0.5) / size)^2.
+ * out_dev_rg32f: size * size * 8 bytes.  Asynchronous on `stream`.  The hosts generate 256 x 256 with 1024 samples. */
+int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t samples, void* out_dev_rg32f, void* stream);
 
 #ifdef __cplusplus
 }

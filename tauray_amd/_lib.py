@@ -220,6 +220,26 @@ class ShTimingsC(C.Structure):
 SH_GRID, SH_GRID_HALF = 0, 1
 
 
+class DshgiOptionsC(C.Structure):
+    """trhip_dshgi_options."""
+    _fields_ = [("order", C.c_int32), ("use_probe_visibility", C.c_int32), ("record_surface", C.c_int32)]
+
+
+class DshgiGridC(C.Structure):
+    """trhip_dshgi_grid."""
+    _fields_ = [("grid_half_dev", C.c_void_p), ("resolution", C.c_uint32 * 3), ("transform", C.c_float * 16), ("scaling", C.c_float * 3)]
+
+
+class DshgiTimingsC(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("frames", C.c_uint32), ("name", C.c_char * 64)]
+
+
+# trhip_dshgi_download; DSHGI_SURFACE is trhip_dshgi_surface per pixel
+DSHGI_INDIRECT, DSHGI_SURFACE = 0, 1
+DSHGI_SURFACE_DTYPE = [("pos", "<f4", 3), ("smooth_normal", "<f4", 3), ("mapped_normal", "<f4", 3), ("view", "<f4", 3), ("albedo", "<f4", 4),
+                       ("metallic", "<f4"), ("roughness", "<f4"), ("f0", "<f4"), ("transmittance", "<f4"), ("grid", "<i4"), ("instance_id", "<i4")]
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -346,6 +366,16 @@ SYMBOLS = {
     "trhip_sh_get_timings": (_i, [_vp, C.POINTER(ShTimingsC)]),
     "trhip_sh_set_profiling": (_i, [_vp, _i, _i]),
     "trhip_sh_reset_counters": (_i, [_vp]),
+    "trhip_dshgi_create": (_i, [_vp, C.POINTER(DshgiOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),
+    "trhip_dshgi_destroy": (None, [_vp]),
+    "trhip_dshgi_set_grids": (_i, [_vp, C.POINTER(DshgiGridC), _u32]),
+    "trhip_dshgi_set_instance_grids": (_i, [_vp, C.POINTER(C.c_int32), _u32]),
+    "trhip_dshgi_set_brdf_integration": (_i, [_vp, _vp, _u32, _u32]),
+    "trhip_dshgi_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _f, _vp, _vp, _vp]),
+    "trhip_dshgi_get_timings": (_i, [_vp, C.POINTER(DshgiTimingsC)]),
+    "trhip_dshgi_download": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "trhip_dshgi_pick_grid": (_i, [C.POINTER(_f), C.POINTER(_f), C.POINTER(_u32), C.POINTER(_f), _u32, C.POINTER(_f), C.POINTER(C.c_int32)]),
+    "trhip_brdf_integration_generate": (_i, [_vp, _u32, _u32, _vp, _vp]),
 }
 
 _LIB = None

@@ -83,6 +83,42 @@ TR_HD uint sh_id_of_path(const ShProbeBatch& b, uint q, uint s) {
 #endif
 }
 
+// The orientation of a transform as the reference's host computes it (get_matrix_orientation, src/math.cc:44-52): glm::quat_cast of the
+// columns normalized, (x, y, z, w); and glm::mat3_cast of a quaternion.  In float like the reference's host.  Host only.
+inline f4 orientation_quat(const m4& t) {
+    float m[3][3];      // m[column][row]
+    for (int c = 0; c < 3; ++c) {
+        const f4 v = t.c[c];
+        const float len = sqrtf(((v.x * v.x + v.y * v.y) + v.z * v.z) + v.w * v.w);      // glm::normalize of the vec4 column
+        m[c][0] = v.x / len; m[c][1] = v.y / len; m[c][2] = v.z / len;
+    }
+    const float fx = m[0][0] - m[1][1] - m[2][2], fy = m[1][1] - m[0][0] - m[2][2], fz = m[2][2] - m[0][0] - m[1][1], fw = m[0][0] + m[1][1] + m[2][2];
+    int big = 0;
+    float fbig = fw;
+    if (fx > fbig) { fbig = fx; big = 1; }
+    if (fy > fbig) { fbig = fy; big = 2; }
+    if (fz > fbig) { fbig = fz; big = 3; }
+    const float bv = sqrtf(fbig + 1.0f) * 0.5f, mult = 0.25f / bv;
+    float qw, qx, qy, qz;
+    switch (big) {
+        case 0: qw = bv; qx = (m[1][2] - m[2][1]) * mult; qy = (m[2][0] - m[0][2]) * mult; qz = (m[0][1] - m[1][0]) * mult; break;
+        case 1: qw = (m[1][2] - m[2][1]) * mult; qx = bv; qy = (m[0][1] + m[1][0]) * mult; qz = (m[2][0] + m[0][2]) * mult; break;
+        case 2: qw = (m[2][0] - m[0][2]) * mult; qx = (m[0][1] + m[1][0]) * mult; qy = bv; qz = (m[1][2] + m[2][1]) * mult; break;
+        default: qw = (m[0][1] - m[1][0]) * mult; qx = (m[2][0] + m[0][2]) * mult; qy = (m[1][2] + m[2][1]) * mult; qz = bv; break;
+    }
+    return F4(qx, qy, qz, qw);
+}
+inline m3 mat3_of_quat(f4 q) {
+    const float qx = q.x, qy = q.y, qz = q.z, qw = q.w;
+    const float qxx = qx * qx, qyy = qy * qy, qzz = qz * qz, qxz = qx * qz, qxy = qx * qy, qyz = qy * qz, qwx = qw * qx, qwy = qw * qy, qwz = qw * qz;
+    m3 r;
+    r.c[0] = F3(1.0f - 2.0f * (qyy + qzz), 2.0f * (qxy + qwz), 2.0f * (qxz - qwy));
+    r.c[1] = F3(2.0f * (qxy - qwz), 1.0f - 2.0f * (qxx + qzz), 2.0f * (qyz + qwx));
+    r.c[2] = F3(2.0f * (qxz + qwy), 2.0f * (qyz - qwx), 1.0f - 2.0f * (qxx + qyy));
+    return r;
+}
+inline m3 matrix_orientation(const m4& t) { return mat3_of_quat(orientation_quat(t)); }
+
 TR_HD float sh_sin(float x) { return (float)sin((double)x); }
 TR_HD float sh_cos(float x) { return (float)cos((double)x); }
 TR_HD float sh_pow(float x, float y) { return (float)pow((double)x, (double)y); }

@@ -126,37 +126,6 @@ __global__ __launch_bounds__(SH_BLOCK) void k_sh_project(PathBuffers pb, ShProje
 }
 static_assert(SH_BLOCK == 256, "k_sh_project combines four waves of 64");
 
-// glm::mat3_cast(glm::quat_cast(m)) for the orientation of a transform (get_matrix_orientation, src/math.cc:44-52): the columns normalized,
-// through a quaternion and back, in float like the reference's host
-m3 matrix_orientation(const m4& t) {
-    float m[3][3];      // m[column][row]
-    for (int c = 0; c < 3; ++c) {
-        const f4 v = t.c[c];
-        const float len = sqrtf(((v.x * v.x + v.y * v.y) + v.z * v.z) + v.w * v.w);      // glm::normalize of the vec4 column
-        m[c][0] = v.x / len; m[c][1] = v.y / len; m[c][2] = v.z / len;
-    }
-    const float fx = m[0][0] - m[1][1] - m[2][2], fy = m[1][1] - m[0][0] - m[2][2], fz = m[2][2] - m[0][0] - m[1][1], fw = m[0][0] + m[1][1] + m[2][2];
-    int big = 0;
-    float fbig = fw;
-    if (fx > fbig) { fbig = fx; big = 1; }
-    if (fy > fbig) { fbig = fy; big = 2; }
-    if (fz > fbig) { fbig = fz; big = 3; }
-    const float bv = sqrtf(fbig + 1.0f) * 0.5f, mult = 0.25f / bv;
-    float qw, qx, qy, qz;
-    switch (big) {
-        case 0: qw = bv; qx = (m[1][2] - m[2][1]) * mult; qy = (m[2][0] - m[0][2]) * mult; qz = (m[0][1] - m[1][0]) * mult; break;
-        case 1: qw = (m[1][2] - m[2][1]) * mult; qx = bv; qy = (m[0][1] + m[1][0]) * mult; qz = (m[2][0] + m[0][2]) * mult; break;
-        case 2: qw = (m[2][0] - m[0][2]) * mult; qx = (m[0][1] + m[1][0]) * mult; qy = bv; qz = (m[1][2] + m[2][1]) * mult; break;
-        default: qw = (m[0][1] - m[1][0]) * mult; qx = (m[2][0] + m[0][2]) * mult; qy = (m[1][2] + m[2][1]) * mult; qz = bv; break;
-    }
-    const float qxx = qx * qx, qyy = qy * qy, qzz = qz * qz, qxz = qx * qz, qxy = qx * qy, qyz = qy * qz, qwx = qw * qx, qwy = qw * qy, qwz = qw * qz;
-    m3 r;
-    r.c[0] = F3(1.0f - 2.0f * (qyy + qzz), 2.0f * (qxy + qwz), 2.0f * (qxz - qwy));
-    r.c[1] = F3(2.0f * (qxy - qwz), 1.0f - 2.0f * (qxx + qzz), 2.0f * (qyz + qwx));
-    r.c[2] = F3(2.0f * (qxz + qwy), 2.0f * (qyz - qwx), 1.0f - 2.0f * (qxx + qyy));
-    return r;
-}
-
 }  // namespace
 
 void launch_sh_raygen(uint blocks, hipStream_t stream, const PtParams& P, const PathBuffers& pb, const ShProbeBatch& batch) {

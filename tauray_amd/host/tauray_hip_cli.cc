@@ -9,7 +9,8 @@
 //              [--filetype=exr|raw|none] [--format=rgb16|rgb32|rgba16|rgba32] [--tonemap=filmic|linear|gamma-correction|
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
-//              [--renderer=path-tracer|direct|sh-probes [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
+//              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
+//               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
 //              [--display=headless|looking-glass --lkg-params=viewports,midplane,depth,relative_dist
 //               --lkg-calibration=display_index,pitch,slope,center,fringe,viewCone,invView,verticalAngle,DPI,screenW,screenH,flipImageX,flipImageY,flipSubp]
@@ -45,6 +46,12 @@ static const char* const usage_text =
     "                         as spherical harmonics; --headless=PREFIX writes PREFIX_grid<k> per grid and frame: the RGBA32F volume unfolded to\n"
     "                         width rx and height ry * (order + 1)^2 * rz, as rgba32 unless --format says otherwise (alpha is the projected\n"
     "                         distance; rgb16 / rgb32 drop it) (one device; no denoiser, --taa or reprojection)\n"
+    "  --renderer=dshgi [--use-probe-visibility] [--brdf-integration=FILE.exr] --samples-per-probe=N --sh-order=0..4 --dshgi-temporal-ratio=r\n"
+    "                         direct light plus indirect light looked up in the scene's light-probe grids, which are baked every frame as\n"
+    "                         --renderer=sh-probes bakes them; no bounce rays per pixel.  --use-probe-visibility weighs the probes by their\n"
+    "                         stored distances instead of filtering trilinearly; the BRDF-integration table is generated unless a file is named\n"
+    "                         (one device; works with --animation, --headless, --camera-grid, --tonemap, --samples-per-pixel and --envmap; no\n"
+    "                         denoiser, --taa, reprojection or --display=looking-glass)\n"
     "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
     "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
     "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
@@ -118,6 +125,8 @@ int main(int argc, char** argv)
         std::string renderer = "path-tracer";
         int samples_per_probe = 512, sh_order = 2;                          // --samples-per-probe, --sh-order, --dshgi-temporal-ratio (src/options.hh:254-284)
         float dshgi_temporal_ratio = 0.01f;
+        bool use_probe_visibility = false;                                  // --use-probe-visibility, --brdf-integration (src/options.hh, data/brdf_integration.exr)
+        std::string brdf_integration_path;
         std::vector<int> devices;
         bool timing = false;
         std::string dump_scene;
@@ -244,8 +253,11 @@ int main(int argc, char** argv)
             else if(starts(a, "--renderer="))
             {
                 renderer = val("--renderer=");
-                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes") throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes)");
+                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes" && renderer != "dshgi")
+                    throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes, dshgi)");
             }
+            else if(a == "--use-probe-visibility") use_probe_visibility = true;
+            else if(starts(a, "--brdf-integration=")) brdf_integration_path = val("--brdf-integration=");
             else if(starts(a, "--samples-per-probe="))
             {   // src/options.hh:254-257
                 samples_per_probe = std::stoi(val("--samples-per-probe="));
@@ -356,6 +368,7 @@ int main(int argc, char** argv)
             else scene_path = a;
         }
         if(scene_path.empty()) throw std::runtime_error(usage_text);
+        if(renderer == "dshgi" && display == "looking-glass") throw std::runtime_error("--renderer=dshgi: no --display=looking-glass (the composition of a light field from it is not built)");
         if(devices.empty()) devices.assign((size_t)std::max(fake_devices, 1), 0);
 
         const bool is_glb = (scene_path.size() > 4 && scene_path.compare(scene_path.size() - 4, 4, ".glb") == 0) ||
@@ -472,6 +485,66 @@ int main(int argc, char** argv)
                     const std::vector<float> img = sr.stages[k]->download();
                     gout.write_image(gout.get_filename(0, (unsigned)f), img.data());
                 }
+            }
+            return 0;
+        }
+        if(renderer == "dshgi")
+        {   // dshgi_renderer (src/tauray.cc:355-421, src/dshgi_renderer.cc): the grids are baked, the direct stage renders, the indirect light of the grids is added
+            if(opt.bmfr || opt.taa || !opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)
+                throw std::runtime_error("--renderer=dshgi: a denoiser, --taa and reprojection do not apply");
+            if(devices.size() > 1 || process_count > 0 || shard_views)
+                throw std::runtime_error("--renderer=dshgi runs on one device: the grids' histories and the frame live on one device");
+            if(opt.local_sampler != sampler_type::UNIFORM_RANDOM)
+                throw std::runtime_error("--renderer=dshgi: --sampler must be uniform-random (the bake's Sobol samplers would take their index from a pixel launch)");
+            if(scene.sh_grids.empty())
+                throw std::runtime_error("--renderer=dshgi: " + scene_path + " has no light-probe grid (a node with TR_data.light_probe of type GRID)");
+            for(sh_grid& g: scene.sh_grids) g.order = sh_order;      // src/tauray.cc:151
+            dshgi_renderer::options go;
+            go.direct = opt;
+            go.sh.max_ray_depth = opt.max_ray_depth; go.sh.min_ray_dist = opt.min_ray_dist; go.sh.rng_seed = opt.rng_seed; go.sh.local_sampler = opt.local_sampler;
+            go.sh.samples_per_probe = samples_per_probe; go.sh.film = opt.film; go.sh.film_radius = opt.film_radius; go.sh.mis_mode = opt.mis_mode;
+            go.sh.russian_roulette_delta = opt.russian_roulette_delta; go.sh.temporal_ratio = dshgi_temporal_ratio; go.sh.indirect_clamping = opt.indirect_clamping;
+            go.sh.regularization_gamma = opt.regularization_gamma; go.sh.sampling_weights = opt.sampling_weights;
+            go.sh.bounce_mode = opt.bounce_mode; go.sh.tri_light_mode = opt.tri_light_mode;
+            go.use_probe_visibility = use_probe_visibility;
+            go.tonemap = opt.tonemap;
+            if(!brdf_integration_path.empty())
+            {   // texture(brdf_integration, uv).xy: the file's R and G, row 0 first
+                int channels = 0;
+                const std::vector<float> f = exr::load_exr(brdf_integration_path, go.brdf_integration_width, go.brdf_integration_height, channels);
+                if(channels < 2) throw std::runtime_error("--brdf-integration=" + brdf_integration_path + ": a BRDF-integration table has the channels R (scale) and G (bias)");
+                go.brdf_integration.resize(size_t(go.brdf_integration_width) * go.brdf_integration_height * 2);
+                for(size_t i = 0; i < go.brdf_integration.size() / 2; ++i) { go.brdf_integration[2 * i] = f[i * (size_t)channels]; go.brdf_integration[2 * i + 1] = f[i * (size_t)channels + 1]; }
+            }
+            hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
+            headless out(hopt);
+            device dev(devices[0]);
+            scene_stage ss(dev, opt.scene);
+            ss.set_scene(scene);
+            dshgi_renderer gr(dev, ss, scene, size, go);
+            for(int f = -warmup; f < frames; ++f)
+            {
+                if(animated && f >= 0)
+                {   // update(s, dt, true) before the frame, the first one by dt = 0 (src/tauray.cc:1064-1092); the instances pick their grids again
+                    if(!frames_given && !animator.is_playing()) break;
+                    animator.update(f == 0 ? 0 : update_dt);
+                    if(!frames_given && !animator.is_playing()) break;
+                    dev.sync();
+                    ss.apply(scene, f % 3 == 2);
+                    gr.set_scene(scene);
+                }
+                gr.render();
+                dev.sync();
+                if(f < 0) continue;
+                if(timing)
+                {
+                    std::cout << "FRAME " << f << ":\n\tDEVICE 0:\n";
+                    for(auto& st: gr.sh.stages) { const trhip_sh_timings t = st->get_timings(); std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n"; }
+                    std::cout << "\t\t[direct (" << viewports << " viewports)] " << gr.direct->get_duration_ms() << " ms\n";
+                    const trhip_dshgi_timings t = gr.indirect->get_timings();
+                    std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n";
+                }
+                out.save(dev, gr.display, (unsigned)f);
             }
             return 0;
         }

@@ -12,6 +12,8 @@ TrhipError where the reference throws std::runtime_error):
 * ``TonemapStage``       - tonemap_stage (src/tonemap_stage.{hh,cc})
 * ``ShPathTracerStage`` / ``ShRenderer`` - sh_path_tracer_stage + sh_compact_stage, sh_renderer (src/sh_path_tracer_stage.{hh,cc},
                            src/sh_renderer.{hh,cc}): the probe grids of a scene baked as spherical harmonics
+* ``DshgiStage`` / ``DshgiRenderer`` - dshgi_renderer (src/dshgi_renderer.{hh,cc}, shader/forward.frag): direct light plus the indirect
+                           light looked up in the baked grids
 * ``RtRenderer``         - rt_renderer<path_tracer_stage> (src/rt_renderer.{hh,cc}); one process per GPU,
                            partial frames gathered with torch.distributed (RCCL) instead of host-bounce copies
 """
@@ -1098,6 +1100,159 @@ class ShRenderer:
     def close(self):
         for st in self.stages:
             st.close()
+
+
+def dshgi_pick_grid(grids, position) -> int:
+    """get_sh_grid, then get_largest_sh_grid (src/scene.cc:163-211) for `position`: the index into `grids` (scene.ShGrid), -1 without any.
+    Needs no device (trhip_dshgi_pick_grid)."""
+    n = len(grids)
+    if n == 0:
+        return -1
+    t = np.ascontiguousarray([np.asarray(g.transform, dtype=np.float64).T for g in grids], dtype=np.float32).reshape(n * 16)
+    sc = np.ascontiguousarray([g.scaling for g in grids], dtype=np.float32).reshape(n * 3)
+    res = np.ascontiguousarray([g.resolution for g in grids], dtype=np.uint32).reshape(n * 3)
+    rad = np.ascontiguousarray([g.radius for g in grids], dtype=np.float32)
+    pos = np.ascontiguousarray(position, dtype=np.float32).reshape(3)
+    fp, index = C.POINTER(C.c_float), C.c_int32(-1)
+    check(_lib.lib().trhip_dshgi_pick_grid(t.ctypes.data_as(fp), sc.ctypes.data_as(fp), res.ctypes.data_as(C.POINTER(C.c_uint32)), rad.ctypes.data_as(fp), n,
+                                           pos.ctypes.data_as(fp), C.byref(index)))
+    return index.value
+
+
+def dshgi_instance_grids(grids, instances: np.ndarray) -> np.ndarray:
+    """sh_grid_index of every instance (src/scene_stage.cc:1075-1083): the grid picked for model[3], the instance's origin."""
+    return np.array([dshgi_pick_grid(grids, inst["model"][3][:3]) for inst in instances], dtype=np.int32)
+
+
+def brdf_integration_table(ctx: "Context", size=256, samples=1024, stream=None) -> "DeviceBuffer":
+    """The BRDF-integration table generated on the device (trhip_brdf_integration_generate): RG32F [size][size]."""
+    buf = ctx.alloc(size * size * 8)
+    check(_lib.lib().trhip_brdf_integration_generate(ctx.h, size, samples, buf.data_ptr(), stream))
+    return buf
+
+
+def load_brdf_integration(path: str) -> np.ndarray:
+    """The table of an EXR file as texture() sees it (data/brdf_integration.exr: channels R and G, row 0 first): (h, w, 2) float32."""
+    from .exr import load_exr
+    img = load_exr(path)
+    if img.shape[2] < 2:
+        raise ValueError(f"{path}: {img.shape[2]} channel; a BRDF-integration table has R (scale) and G (bias)")
+    return np.ascontiguousarray(img[..., :2], dtype=np.float32)
+
+
+class DshgiStage(_PostStage):
+    """The indirect light of dshgi_renderer (src/dshgi_renderer.{hh,cc}, shader/forward.frag): first hit, SH grid lookup, brdf_indirect,
+    added to the direct stage's colour (trhip_dshgi_*, include/trhip.h).  `size`: (w, h); `layers`: the viewports of a frame."""
+
+    PREFIX, TIMINGS = "dshgi", _lib.DshgiTimingsC
+
+    def __init__(self, ctx: Context, scene_stage: Optional[SceneStage], size, layers=1, order=2, use_probe_visibility=False, record_surface=False,
+                 projection=0, min_ray_dist=1e-4):
+        self.ctx, self.scene_stage, self.size, self.layers = ctx, scene_stage, tuple(size), int(layers)
+        self.order, self.projection, self.min_ray_dist = int(order), int(projection), float(min_ray_dist)
+        opt = _lib.DshgiOptionsC(self.order, int(bool(use_probe_visibility)), int(bool(record_surface)))
+        self._create(getattr(ctx, "h", None), C.byref(opt), max(int(self.size[0]), 0), max(int(self.size[1]), 0), max(self.layers, 0))
+
+    def set_grids(self, grids, images):
+        """`grids`: scene.ShGrid; `images`: the RGBA16F volume of each on the device (ShPathTracerStage.device_grids()[1] or an upload)."""
+        n = len(grids)
+        arr = (_lib.DshgiGridC * max(n, 1))()
+        for g, img, a in zip(grids, images, arr):
+            a.grid_half_dev = _ptr(img)
+            a.resolution = (C.c_uint32 * 3)(*[int(r) for r in g.resolution])
+            a.transform = (C.c_float * 16)(*np.asarray(g.transform, dtype=np.float64).T.astype(np.float32).reshape(16).tolist())
+            a.scaling = (C.c_float * 3)(*[float(s) for s in g.scaling])
+        check(_lib.lib().trhip_dshgi_set_grids(self.h, arr, n))
+
+    def set_instance_grids(self, instance_grids):
+        a = np.ascontiguousarray(instance_grids, dtype=np.int32)
+        check(_lib.lib().trhip_dshgi_set_instance_grids(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size))
+
+    def set_brdf_integration(self, table, w, h):
+        """`table`: RG32F [h][w] on the device; the stage keeps a copy."""
+        check(_lib.lib().trhip_dshgi_set_brdf_integration(self.h, _ptr(table), w, h))
+
+    def run(self, viewports, direct, out, stream=None):
+        """One frame: out = direct + indirect for the listed viewports; `direct` None writes the indirect term alone, `out` may be `direct`."""
+        v = np.ascontiguousarray(viewports, dtype=np.uint32)
+        check(_lib.lib().trhip_dshgi_render(self.h, self.projection, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size, self.min_ray_dist,
+                                            None if direct is None else _ptr(direct), _ptr(out), stream))
+
+    def download(self, name: str = "indirect") -> np.ndarray:
+        """"indirect": RGBA32F [layers][h][w][4]; "surface": the record per pixel (record_surface), a structured array [layers][h][w]."""
+        shape = (self.layers, self.size[1], self.size[0])
+        if name == "indirect":
+            return self._download(_lib.DSHGI_INDIRECT, shape + (4,))
+        if name == "surface":
+            return self._download(_lib.DSHGI_SURFACE, shape, np.dtype(_lib.DSHGI_SURFACE_DTYPE))
+        raise KeyError(name)
+
+
+class DshgiRenderer:
+    """dshgi_renderer (src/dshgi_renderer.{hh,cc}): per frame the scene's probe grids are baked (ShRenderer), the direct stage renders every
+    viewport, the indirect light of the grids is added (DshgiStage), the frame is tonemapped - all on one stream.  The first bake has
+    history 1, so the grids are complete before they are read.  `options`: the direct stage's PtOptionsC; `sh`: sh_options() of the bake;
+    `brdf_integration`: None (the generated 256 x 256 table of 1024 samples), a file name or an (h, w, 2) array.
+    Direct light is what the reference's raster pass lights with - point and directional lights: the direct stage samples neither the
+    emissive triangles nor the environment map (their weights are set to 0; it still shows them where a pixel sees them), because the probes
+    see both and the indirect term carries their light."""
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: PtOptionsC, sh: Optional[dict] = None,
+                 use_probe_visibility=False, brdf_integration=None, tonemap: Optional[TonemapStage] = None, record_surface=False):
+        if not scene.sh_grids:
+            raise ValueError("DshgiRenderer: the scene has no light-probe grid (TR_data.light_probe of type GRID)")
+        self.ctx, self.ss, self.size = ctx, scene_stage, tuple(size)
+        self.grids = list(scene.sh_grids)
+        self.viewports = max(len(scene.cameras), 1)
+        self.sh = ShRenderer(ctx, scene_stage, self.grids, sh)
+        order = self.sh.stages[0].order
+        self.direct = DirectStage(ctx, scene_stage, copy_options(options, nee_triangles=0.0, nee_envmap=0.0),
+                                  DistributionParams(self.size, DISTRIBUTION_DUPLICATE, 0, 1, True))
+        self.indirect = DshgiStage(ctx, scene_stage, self.size, self.viewports, order, use_probe_visibility, record_surface, options.projection,
+                                   options.min_ray_dist)
+        self.indirect.set_grids(self.grids, [st.device_grids()[1] for st in self.sh.stages])
+        if brdf_integration is None:
+            w = h = 256
+            table = brdf_integration_table(ctx, w, 1024)
+            ctx.sync()
+        else:
+            host = load_brdf_integration(brdf_integration) if isinstance(brdf_integration, str) else np.ascontiguousarray(brdf_integration, dtype=np.float32)
+            h, w = host.shape[:2]
+            table = ctx.alloc(host.nbytes).upload(host)
+        self.indirect.set_brdf_integration(table, w, h)
+        table.free()
+        self.tonemap = tonemap or TonemapStage(ctx)
+        pixels = self.size[0] * self.size[1] * self.viewports
+        self.color, self.display = ctx.alloc(pixels * 16).zero(), ctx.alloc(pixels * 16).zero()
+        self.set_scene(scene)
+
+    def set_scene(self, scene: SceneDesc):
+        """The instances have moved (the scene stage holds them already): every instance picks its grid again."""
+        self.instance_grids = dshgi_instance_grids(self.grids, scene.instances)
+        self.indirect.set_instance_grids(self.instance_grids)
+
+    def render(self, stream=None, tonemap=True):
+        self.sh.render(stream)
+        self.direct.reset_accumulated_samples()
+        self.direct.run(self.color, self.viewports, stream)
+        self.indirect.run(np.arange(self.viewports), self.color, self.color, stream)
+        if tonemap:
+            self.tonemap.run(self.color, self.display, self.size[0], self.size[1], self.viewports, stream)
+
+    def timings(self) -> dict:
+        return {"bake": [st.timings() for st in self.sh.stages], "direct": self.direct.timings(), "indirect": self.indirect.timings()}
+
+    def download(self, which="color") -> np.ndarray:
+        self.ctx.sync()
+        buf = self.color if which == "color" else self.display
+        return buf.download((self.viewports, self.size[1], self.size[0], 4))
+
+    def close(self):
+        self.sh.close()
+        self.direct.close()
+        self.indirect.close()
+        for b in (self.color, self.display):
+            b.free()
 
 
 @dataclass(frozen=True)
