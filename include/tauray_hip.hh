@@ -22,8 +22,10 @@
 #include <fstream>
 #include <functional>
 #include <limits>
+#include <map>
 #include <memory>
 #include <optional>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -45,6 +47,42 @@ inline void check(int rc)
 }
 
 struct uvec2 { uint32_t x = 0, y = 0; };
+
+// A struct option of the reference (TR_STRUCT_OPT, src/options.cc): comma-separated values, positional in the order of `names` or name=value
+inline std::map<std::string, std::string> parse_struct_option(const std::string& option, const std::string& text, const std::vector<std::string>& names)
+{
+    std::map<std::string, std::string> out;
+    std::stringstream ss(text); std::string tok;
+    size_t position = 0;
+    while(std::getline(ss, tok, ','))
+    {
+        const size_t eq = tok.find('=');
+        std::string name;
+        if(eq == std::string::npos)
+        {
+            if(position >= names.size()) throw std::runtime_error(option + ": more than " + std::to_string(names.size()) + " values");
+            name = names[position++];
+        }
+        else
+        {
+            name = tok.substr(0, eq); tok = tok.substr(eq + 1);
+            if(std::find(names.begin(), names.end(), name) == names.end()) throw std::runtime_error(option + ": " + name + " is not one of its fields");
+        }
+        if(tok.empty()) throw std::runtime_error(option + ": " + name + " has no value");
+        out[name] = tok;
+    }
+    return out;
+}
+inline double struct_number(const std::string& option, const std::map<std::string, std::string>& v, const std::string& name, double fallback)
+{
+    auto it = v.find(name);
+    if(it == v.end()) return fallback;
+    size_t used = 0;
+    double d = 0;
+    try { d = std::stod(it->second, &used); } catch(std::exception&) { used = 0; }
+    if(used != it->second.size()) throw std::runtime_error(option + ": " + name + "=" + it->second + " is not a number");
+    return d;
+}
 
 //==============================================================================
 // distribution_strategy.hh
@@ -936,6 +974,124 @@ public:
     std::unique_ptr<tonemap_stage> tonemap;
     std::vector<uint32_t> viewport_list;
     std::vector<int32_t> instance_grids;
+    void* color = nullptr;
+    void* display = nullptr;
+};
+
+// ReSTIR DI (trhip_restir_di_*; written after shader/restir_di.glsl and its two ray generation shaders): per frame the canonical kernel
+// (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).  `size`, `layers`: the images
+// of a frame.  The decisions where the shaders are stale or undefined are listed in trhip.h and DESIGN.md section 21.
+class restir_di_stage
+{
+public:
+    struct options
+    {
+        uint32_t candidates = 4;          // --restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse
+        uint32_t spatial_samples = 2;
+        float search_radius = 32.0f;
+        float max_confidence = 16.0f;
+        bool temporal_reuse = true;
+        float min_ray_dist = 1e-4f;
+        uint32_t rng_seed = 0;
+        bool record = false;
+        int projection = 0;
+        // what trhip_restir_di_create refuses, said without a device
+        void check() const
+        {
+            if(candidates < 1 || candidates > 32) throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " is outside 1..32");
+            if(spatial_samples > 4) throw std::runtime_error("restir-di: spatial_samples " + std::to_string(spatial_samples) + " is outside 0..4");
+            if(!(search_radius > 0.0f) || !(search_radius <= 1024.0f)) throw std::runtime_error("restir-di: search_radius must be in (0, 1024]");
+            if(!(max_confidence >= 1.0f) || !std::isfinite(max_confidence)) throw std::runtime_error("restir-di: max_confidence must be finite and at least 1");
+            if(!(min_ray_dist > 0.0f) || !std::isfinite(min_ray_dist)) throw std::runtime_error("restir-di: min_ray_dist must be finite and positive");
+        }
+        // --restir=...: positional or name=value; a field left out keeps its value
+        void parse(const std::string& text)
+        {
+            const char* const o = "--restir";
+            const auto v = parse_struct_option(o, text, {"candidates", "spatial_samples", "search_radius", "max_confidence", "temporal_reuse"});
+            auto whole = [&](const char* name, uint32_t& field, double lo, double hi)
+            {
+                const double n = struct_number(o, v, name, (double)field);
+                if(!(n >= lo) || !(n <= hi) || n != std::floor(n))
+                    throw std::runtime_error(std::string(o) + ": " + name + " must be a whole number in " + std::to_string((int)lo) + ".." + std::to_string((int)hi));
+                field = (uint32_t)n;
+            };
+            whole("candidates", candidates, 1, 32);
+            whole("spatial_samples", spatial_samples, 0, 4);
+            search_radius = (float)struct_number(o, v, "search_radius", search_radius);
+            max_confidence = (float)struct_number(o, v, "max_confidence", max_confidence);
+            auto it = v.find("temporal_reuse");
+            if(it != v.end())
+            {
+                const std::string& t = it->second;
+                if(t == "on" || t == "true" || t == "1") temporal_reuse = true;
+                else if(t == "off" || t == "false" || t == "0") temporal_reuse = false;
+                else throw std::runtime_error(std::string(o) + ": temporal_reuse=" + t + " is neither on nor off");
+            }
+            check();
+        }
+    };
+    restir_di_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), size(size), layers(layers), opt(opt)
+    {
+        opt.check();
+        trhip_restir_di_options o = {};
+        o.candidates = opt.candidates; o.spatial_samples = opt.spatial_samples; o.search_radius = opt.search_radius; o.max_confidence = opt.max_confidence;
+        o.temporal_reuse = opt.temporal_reuse; o.min_ray_dist = opt.min_ray_dist; o.rng_seed = opt.rng_seed; o.record = opt.record;
+        check(trhip_restir_di_create(dev.h, &o, size.x, size.y, layers, &h));
+    }
+    restir_di_stage(const restir_di_stage&) = delete;
+    ~restir_di_stage() { trhip_restir_di_destroy(h); }
+    // one frame of the listed viewports into `out` (RGBA32F [viewports][h][w])
+    void run(const std::vector<uint32_t>& viewports, void* out, void* stream = nullptr)
+    {
+        check(trhip_restir_di_render(h, opt.projection, viewports.data(), (uint32_t)viewports.size(), out, stream));
+    }
+    void reset() { check(trhip_restir_di_reset(h)); }
+    trhip_restir_di_timings get_timings() { trhip_restir_di_timings t; check(trhip_restir_di_get_timings(h, &t)); return t; }
+
+    device* dev;
+    uvec2 size;
+    uint32_t layers;
+    options opt;
+    trhip_restir_di* h = nullptr;
+};
+
+// --renderer=restir-di: the ReSTIR DI stage renders every viewport, the frame is tonemapped - on one stream.
+class restir_di_renderer
+{
+public:
+    struct options
+    {
+        restir_di_stage::options restir;
+        tonemap_stage::options tonemap;
+    };
+    restir_di_renderer(device& dev, const scene_data& scene, uvec2 size, const options& opt_)
+    : dev(&dev), size(size), viewports(std::max(scene.camera_count(), 1u)), opt(opt_)
+    {
+        opt.restir.check();
+        const size_t bytes = size_t(size.x) * size.y * 16 * viewports;
+        color = dev.alloc(bytes); display = dev.alloc(bytes);
+        check(trhip_memset(dev.h, color, 0, bytes, nullptr));
+        check(trhip_memset(dev.h, display, 0, bytes, nullptr));
+        stage.reset(new restir_di_stage(dev, size, viewports, opt.restir));
+        tonemap.reset(new tonemap_stage(dev, opt.tonemap));
+        for(uint32_t v = 0; v < viewports; ++v) viewport_list.push_back(v);
+    }
+    restir_di_renderer(const restir_di_renderer&) = delete;
+    ~restir_di_renderer() { stage.reset(); dev->free(color); dev->free(display); }
+    void render(void* stream = nullptr)
+    {
+        stage->run(viewport_list, color, stream);
+        tonemap->run(color, display, size, viewports, stream);
+    }
+
+    device* dev;
+    uvec2 size;
+    uint32_t viewports;
+    options opt;
+    std::unique_ptr<restir_di_stage> stage;
+    std::unique_ptr<tonemap_stage> tonemap;
+    std::vector<uint32_t> viewport_list;
     void* color = nullptr;
     void* display = nullptr;
 };

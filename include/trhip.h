@@ -882,6 +882,107 @@ int trhip_dshgi_pick_grid(const float* transforms, const float* scalings, const 
  * out_dev_rg32f: size * size * 8 bytes.  Asynchronous on `stream`.  The hosts generate 256 x 256 with 1024 samples. */
 int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t samples, void* out_dev_rg32f, void* stream);
 
+/* ---- ReSTIR DI: reservoir resampling of direct light, written after shader/restir_di.glsl, shader/restir_di_canonical_and_temporal.rgen
+ * and shader/restir_di_spatial.rgen, which the reference carries but no longer wires up (its --renderer=restir is ReSTIR PT and is not
+ * built here: this is `restir-di` everywhere).  csrc/restir_di.hip; the order of operations and of random draws is pinned in
+ * csrc/restir_di.h.  Per frame and chunk of 64 viewports two launches:
+ *   canonical  the first hit of the pixel centre's ray, its surface record, `candidates` light samples drawn as sample_canonical draws
+ *              them and resampled (RIS) with target = luminance(light_contribution * shadow ray); with temporal_reuse the history
+ *              reservoir of the stochastically reprojected pixel is merged by confidence unless temporal_edge_detection rejects it
+ *   spatial    up to spatial_samples neighbours within search_radius, merged with pairwise MIS and the reconnection Jacobian, one shadow
+ *              ray per re-evaluation; the chosen sample is shaded: colour = contribution * uc_weight + emission, alpha 1
+ * Decisions where the shaders are stale, undefined or depart from this library:
+ *   1. BSDF: the ggx_bsdf_pdf lobes through modulate_bsdf, as the direct stage's light sample gets them, shading_view.z clamped to 1e-5
+ *      (restir_di.glsl:234-244 calls a ggx_brdf signature that no longer exists).
+ *   2. The first hit is a traced ray, not a raster G-buffer; view = normalize(pos - ray origin).
+ *   3. light_data and the previous frame's normal and position are fp32 (the previous surface record), not rg16 / rg16_snorm images.
+ *   4. A directional light with dir_cutoff >= 1 has light_pdf = dir_prob / light_count (the shader's -1 marker, restir_di.glsl:319, gives a
+ *      negative resampling weight).
+ *   5. The two kernels draw from disjoint random streams (sampler coordinate w = 2 * frame and 2 * frame + 1, plus rng_seed as
+ *      init_local_sampler adds it); the shaders seed both passes alike.  The order of draws within a kernel is the shaders'.
+ *   6. Only the default visibility path: a shadow ray inside every target function (no SHARED_VISIBILITY / SAMPLE_VISIBILITY).
+ *   7. An empty neighbour slot is skipped (restir_di_spatial.rgen:145-149 reads out of bounds and adds 0).
+ *   8. The first frame after create or reset has no history; history light indices refer to the current frame's light arrays, an index
+ *      past the end counts as the null sample.
+ *   9. One pass per frame; no accumulation over frames.
+ *  10. Sphere lights are lit as points (color / max(dist^2, 1e-7)); shadow rays do not see lights.
+ *  11. A draw that takes no light class (no lights, or u.w past the sum of the probabilities by rounding) is the null sample with pdf 1
+ *      (restir_di.glsl:265-353 has no such branch and leaves its outputs undefined).
+ *  12. A NaN resampling weight is 0 in every merge (the shader says so for candidates only, restir_di_canonical_and_temporal.rgen:98-100).
+ *  13. A neighbour candidate without a surface is passed over like one off screen (restir_di_spatial.rgen:111-116 compares NaN positions);
+ *      round() of an offset is floor(x + 0.5) (GLSL leaves the tie to the implementation).
+ *  14. A contribution without a positive component casts no shadow ray and has visibility 0 (the product is 0 either way).
+ *  15. Triangle lights are sampled by solid angle; the light class weights are all 1.
+ *  16. sin, cos, pow and atan2 of the resampling code (light sampling, light_contribution, the neighbour offsets) are the double function of
+ *      the float argument rounded once, not the device library's sinf / cosf / powf / atan2f: GLSL leaves their accuracy open, and this is
+ *      the one rounding a host model can repeat bit for bit - in all but the rarest case, a double result so near a float rounding boundary
+ *      that two libraries' doubles fall on either side of it.  The first hit is shaded as every other stage shades it. */
+typedef struct trhip_restir_di trhip_restir_di;
+typedef struct trhip_restir_di_options {
+    uint32_t candidates;              /* 1..32 light samples per pixel (RIS_SAMPLE_COUNT) */
+    uint32_t spatial_samples;         /* 0..4 (SPATIAL_SAMPLE_COUNT) */
+    float search_radius;              /* pixels, > 0, at most 1024 */
+    float max_confidence;             /* >= 1, the clamp of the temporal merge */
+    int32_t temporal_reuse;           /* 0 / 1 */
+    float min_ray_dist;               /* > 0 */
+    uint32_t rng_seed;                /* raw; pcg() applied if non-zero, as the path tracer's */
+    int32_t record;                   /* keep the decision records (test hook) */
+} trhip_restir_di_options;
+typedef struct trhip_restir_di_surface {      /* the shader's `domain`; instance_id -1 = a miss (the rest 0) */
+    float pos[3]; int32_t instance_id;
+    float mapped_normal[3], metallic;
+    float flat_normal[3], roughness;
+    float view[3], transmittance;
+    float albedo[4];
+    float emission[3], f0;
+    float ior_in, ior_out, pad[2];
+} trhip_restir_di_surface;
+typedef struct trhip_restir_di_reservoir {    /* light = light_type << 30 | light_index; the null sample is type 0, index (1u << 30) - 1 */
+    float uc_weight, target_function; uint32_t light; float confidence;
+    float light_data[2]; uint32_t pad[2];
+} trhip_restir_di_reservoir;
+typedef struct trhip_restir_di_candidate {    /* per candidate; contribution is unshadowed; selected: update_reservoir took it */
+    uint32_t light; float light_data[2], pdf;
+    float contribution[3], visibility;
+    float weight, draw; uint32_t selected, pad;
+} trhip_restir_di_candidate;
+typedef struct trhip_restir_di_temporal {     /* per pixel; target, weight, draw are 0 without reuse */
+    int32_t px, py; uint32_t reuse; float prev_confidence;
+    float target, weight, draw; uint32_t selected;
+} trhip_restir_di_temporal;
+typedef struct trhip_restir_di_spatial {      /* per neighbour slot; px -1 = empty; _n: the neighbour's sample here, _c: the canonical sample there */
+    int32_t px, py; uint32_t good, selected;
+    float target_n, visibility_n, jacobian_n, m;
+    float wi, draw, target_c, visibility_c;
+    float jacobian_c, mis_canonical, pad[2];
+} trhip_restir_di_spatial;
+typedef struct trhip_restir_di_final {        /* per pixel: the chosen sample's unshadowed contribution and its shadow ray, the canonical merge */
+    float contribution[3], visibility;
+    float canonical_m, wi, draw; uint32_t selected;
+} trhip_restir_di_final;
+typedef struct trhip_restir_di_timings {      /* device ms of the last render */
+    float canonical_ms, spatial_ms, total_ms;
+    uint32_t frames;
+    char canonical_name[64], spatial_name[64];    /* "restir di canonical", "restir di spatial" */
+} trhip_restir_di_timings;
+/* Refuses a null device (there is no CPU fallback), zero or oversized dimensions and every option outside its range. */
+int trhip_restir_di_create(trhip_device* dev, const trhip_restir_di_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_restir_di** out);
+void trhip_restir_di_destroy(trhip_restir_di* stage);
+int trhip_restir_di_reset(trhip_restir_di* stage);        /* forgets the history and restarts the frame counter */
+/* One frame of `count` viewports (at most the stage's layers), two launches per 64, asynchronous on `stream`: out_color_dev RGBA32F
+ * [count][h][w].  Refuses a device without a scene or acceleration structure and a viewport out of range.  History is kept per layer, the
+ * position in the list: with temporal_reuse, a list that differs from the last frame's is refused until trhip_restir_di_reset. */
+int trhip_restir_di_render(trhip_restir_di* stage, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream);
+int trhip_restir_di_get_timings(trhip_restir_di* stage, trhip_restir_di_timings* out);   /* waits for the last render */
+#define TRHIP_RESTIR_DI_SURFACE 0     /* trhip_restir_di_surface [layers][h][w] of the last frame */
+#define TRHIP_RESTIR_DI_CANONICAL 1   /* trhip_restir_di_reservoir [layers][h][w]: what the canonical kernel wrote */
+#define TRHIP_RESTIR_DI_HISTORY 2     /* trhip_restir_di_reservoir [layers][h][w]: what the spatial kernel wrote */
+#define TRHIP_RESTIR_DI_CANDIDATES 3  /* trhip_restir_di_candidate [layers][h][w][candidates] (record only, as the three below) */
+#define TRHIP_RESTIR_DI_TEMPORAL 4    /* trhip_restir_di_temporal [layers][h][w] */
+#define TRHIP_RESTIR_DI_SPATIAL 5     /* trhip_restir_di_spatial [layers][h][w][spatial_samples] */
+#define TRHIP_RESTIR_DI_FINAL 6       /* trhip_restir_di_final [layers][h][w] */
+int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,37 @@ DSHGI_SURFACE_DTYPE = [("pos", "<f4", 3), ("smooth_normal", "<f4", 3), ("mapped_
                        ("metallic", "<f4"), ("roughness", "<f4"), ("f0", "<f4"), ("transmittance", "<f4"), ("grid", "<i4"), ("instance_id", "<i4")]
 
 
+class RestirDiOptionsC(C.Structure):
+    """trhip_restir_di_options."""
+    _fields_ = [("candidates", C.c_uint32), ("spatial_samples", C.c_uint32), ("search_radius", C.c_float), ("max_confidence", C.c_float),
+                ("temporal_reuse", C.c_int32), ("min_ray_dist", C.c_float), ("rng_seed", C.c_uint32), ("record", C.c_int32)]
+
+
+class RestirDiTimingsC(C.Structure):
+    _fields_ = [("canonical_ms", C.c_float), ("spatial_ms", C.c_float), ("total_ms", C.c_float), ("frames", C.c_uint32),
+                ("canonical_name", C.c_char * 64), ("spatial_name", C.c_char * 64)]
+
+
+# trhip_restir_di_download and the records behind the codes (include/trhip.h)
+(RESTIR_DI_SURFACE, RESTIR_DI_CANONICAL, RESTIR_DI_HISTORY, RESTIR_DI_CANDIDATES, RESTIR_DI_TEMPORAL, RESTIR_DI_SPATIAL,
+ RESTIR_DI_FINAL) = range(7)
+RESTIR_DI_NULL_INDEX = (1 << 30) - 1
+RESTIR_DI_SURFACE_DTYPE = [("pos", "<f4", 3), ("instance_id", "<i4"), ("mapped_normal", "<f4", 3), ("metallic", "<f4"), ("flat_normal", "<f4", 3),
+                           ("roughness", "<f4"), ("view", "<f4", 3), ("transmittance", "<f4"), ("albedo", "<f4", 4), ("emission", "<f4", 3),
+                           ("f0", "<f4"), ("ior_in", "<f4"), ("ior_out", "<f4"), ("pad", "<f4", 2)]
+RESTIR_DI_RESERVOIR_DTYPE = [("uc_weight", "<f4"), ("target_function", "<f4"), ("light", "<u4"), ("confidence", "<f4"), ("light_data", "<f4", 2),
+                             ("pad", "<u4", 2)]
+RESTIR_DI_CANDIDATE_DTYPE = [("light", "<u4"), ("light_data", "<f4", 2), ("pdf", "<f4"), ("contribution", "<f4", 3), ("visibility", "<f4"),
+                             ("weight", "<f4"), ("draw", "<f4"), ("selected", "<u4"), ("pad", "<u4")]
+RESTIR_DI_TEMPORAL_DTYPE = [("px", "<i4"), ("py", "<i4"), ("reuse", "<u4"), ("prev_confidence", "<f4"), ("target", "<f4"), ("weight", "<f4"),
+                            ("draw", "<f4"), ("selected", "<u4")]
+RESTIR_DI_SPATIAL_DTYPE = [("px", "<i4"), ("py", "<i4"), ("good", "<u4"), ("selected", "<u4"), ("target_n", "<f4"), ("visibility_n", "<f4"),
+                           ("jacobian_n", "<f4"), ("m", "<f4"), ("wi", "<f4"), ("draw", "<f4"), ("target_c", "<f4"), ("visibility_c", "<f4"),
+                           ("jacobian_c", "<f4"), ("mis_canonical", "<f4"), ("pad", "<f4", 2)]
+RESTIR_DI_FINAL_DTYPE = [("contribution", "<f4", 3), ("visibility", "<f4"), ("canonical_m", "<f4"), ("wi", "<f4"), ("draw", "<f4"),
+                         ("selected", "<u4")]
+
+
 # every symbol include/trhip.h declares: (name, restype, argtypes)
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 SYMBOLS = {
@@ -376,6 +407,12 @@ SYMBOLS = {
     "trhip_dshgi_download": (_i, [_vp, _i, _vp, C.c_size_t]),
     "trhip_dshgi_pick_grid": (_i, [C.POINTER(_f), C.POINTER(_f), C.POINTER(_u32), C.POINTER(_f), _u32, C.POINTER(_f), C.POINTER(C.c_int32)]),
     "trhip_brdf_integration_generate": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "trhip_restir_di_create": (_i, [_vp, C.POINTER(RestirDiOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),
+    "trhip_restir_di_destroy": (None, [_vp]),
+    "trhip_restir_di_reset": (_i, [_vp]),
+    "trhip_restir_di_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _vp, _vp]),
+    "trhip_restir_di_get_timings": (_i, [_vp, C.POINTER(RestirDiTimingsC)]),
+    "trhip_restir_di_download": (_i, [_vp, _i, _vp, C.c_size_t]),
 }
 
 _LIB = None

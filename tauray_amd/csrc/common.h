@@ -101,6 +101,26 @@ TR_HD float tpow(float x, float y) { return powf(x, y); }
 TR_HD float tpow_ge0(float x, float y) { return powf(x, y); }
 #endif
 
+// The same functions as a type: the shading functions that call them take it as a template parameter, LibMath by default - the
+// translation unit's functions above, unchanged bits.  RoundedMath is the double function of the float argument, rounded once: the
+// correctly rounded fp32 result in all but the rarest case and the same number on any host, which sinf / cosf / powf / atan2f (each
+// library within an ulp or two of it, in its own way) are not.  A kernel whose arithmetic a host model repeats bit for bit asks for it
+// (restir_di.hip); it costs fp64 instructions, so nothing on the path tracer's path does.
+struct LibMath {
+    static TR_HD float sin(float x) { return tsin(x); }
+    static TR_HD float cos(float x) { return tcos(x); }
+    static TR_HD float pow(float x, float y) { return tpow(x, y); }
+    static TR_HD float pow_ge0(float x, float y) { return tpow_ge0(x, y); }
+    static TR_HD float atan2(float y, float x) { return atan2f(y, x); }
+};
+struct RoundedMath {
+    static TR_HD float sin(float x) { return (float)::sin((double)x); }
+    static TR_HD float cos(float x) { return (float)::cos((double)x); }
+    static TR_HD float pow(float x, float y) { return (float)::pow((double)x, (double)y); }
+    static TR_HD float pow_ge0(float x, float y) { return (float)::pow((double)x, (double)y); }
+    static TR_HD float atan2(float y, float x) { return (float)::atan2((double)y, (double)x); }
+};
+
 // column-major matrices, as glm / GLSL
 struct m3 { f3 c[3]; };
 struct m4 { f4 c[4]; };

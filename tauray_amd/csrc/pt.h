@@ -8,6 +8,19 @@ namespace tr {
 
 void get_ray_count(const trhip_distribution& d, uint& w, uint& h);
 
+// get_nee_sampling_probabilities (shader/rt.glsl:302-335): scene constants, evaluated once in fp32 on the host.  A class whose weight is
+// not positive or that the scene does not have gets 0.  The path tracer, the direct stage and ReSTIR DI (restir_di.hip) share it.
+inline void nee_probabilities(const DeviceScene& scene, float w_point, float w_tri, float w_dir, float w_env, float& prob_point, float& prob_tri,
+                              float& prob_dir, float& prob_env) {
+    float point = (w_point > 0 && scene.point_light_count > 0) ? w_point : 0.0f;
+    float tri = (w_tri > 0 && scene.tri_light_count > 0) ? w_tri : 0.0f;
+    float dir = (w_dir > 0 && scene.directional_light_count > 0) ? w_dir : 0.0f;
+    float env = (w_env > 0 && scene.environment_proj >= 0) ? w_env : 0.0f;
+    float sum = point + tri + dir + env;
+    float inv_sum = sum <= 0.0f ? 0.0f : (1.0f / sum + 1e-5f);
+    prob_point = point * inv_sum; prob_tri = tri * inv_sum; prob_dir = dir * inv_sum; prob_env = env * inv_sum;
+}
+
 // Streams of the current device, kept for the life of the process and classified by hardware pipe (stream_pool.hip): a new stream
 // for a taker whose launches must overlap those of `overlap_with` (streams of any origin, the null stream included).
 int stream_pool_acquire(hipStream_t* out, const hipStream_t* overlap_with = nullptr, int n_overlap = 0);

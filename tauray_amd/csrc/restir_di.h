@@ -1,0 +1,314 @@
+// ReSTIR DI - reservoir resampling of direct light (shader/restir_di.glsl, shader/restir_di_canonical_and_temporal.rgen,
+// shader/restir_di_spatial.rgen restated; the reference's own host no longer wires these up): constants, layouts, the order of operations
+// and the order of random draws of k_restir_di_canonical and k_restir_di_spatial (restir_di.hip) behind the entry points trhip_restir_di_*
+// (include/trhip.h).  tests/restir_di_model.py repeats this file in float32 and float64.
+//
+// Layouts (all fp32 / u32 / i32, [layers][h][w] records):
+//   surface record    RestirSurface, 112 bytes = seven aligned 16-byte words (the shader's `domain`, restir_di.glsl:39-46,86-99); a miss is
+//                     all zero but instance_id = -1.  Two of them: frame f writes half f & 1 and reads the other as the previous frame's.
+//   reservoir         RestirReservoir, 32 bytes = two aligned 16-byte words: uc_weight, target_function, light_type << 30 | light_index,
+//                     confidence, light_data.xy, two zero words (write_reservoir_buffer, restir_di.glsl:411-425).  The null sample is
+//                     type 0 with index (1u << 30) - 1.  `canonical` is written by the canonical kernel and read by the spatial one,
+//                     `history` is written by the spatial kernel and read by the next frame's canonical kernel.
+//   decision records  (options.record) RestirCandidateRecord [pixel][candidates], RestirTemporalRecord [pixel], RestirSpatialRecord
+//                     [pixel][spatial_samples], RestirFinalRecord [pixel]
+//
+// Random draws.  sampler = init_local_sampler((px, py, viewport, 0), 2 * frame + pass, pcg(rng_seed) or 0, uniform) (rng.h), pass = 0 in
+// the canonical kernel and 1 in the spatial one, frame = the stage's frame counter: two disjoint streams (the shaders seed both passes
+// alike).  A draw is pcg4d(sampler.rs); "unit" = float(word) * 2^-32 per component.  Order:
+//   canonical  [TEMPORAL: one draw, unit .xy: the reprojection]  per candidate: one draw (the four words: sample_canonical), one draw
+//              (unit .x: the selection)  [reuse: one draw, unit .x: the temporal merge]
+//   spatial    2 * SPATIAL draws (unit .xy: the offsets), per slot that holds a neighbour whose sample is not null one draw (unit .x),
+//              one draw (unit .x: the canonical merge)
+//
+// Order of operations (plain fp32, no contraction, correctly rounded divide and square root; dot(a, b) = a.x * b.x + a.y * b.y + a.z * b.z
+// left to right; the functions named are those of shading.h with RoundedMath (common.h) for their sin, cos, pow and atan2: the double
+// function of the float argument rounded once, so that the model has the kernels' bits; the first hit is shaded as every stage shades it):
+//   surface      v, mat = shade_surface of the first hit (k_gbuffer's front half);  view = normalize(v.pos - ray origin);
+//                flat_normal = v.hard_normal
+//   contribution light_contribution (restir_di.glsl:155-249) of sample (type, index, data) at a surface:
+//                point      to = pl.pos - pos; dir = normalize(to); dist2 = dot(to, to); normal = 0;
+//                           colour = (pl.color * get_spotlight_intensity(pl, dir)) / max(dist2, 1e-7f)
+//                triangle   A, B, C = tl.pos[k] - pos;  p = (data.x * A + data.y * B) + (1.0f - data.x - data.y) * C;  dir = normalize(p);
+//                           dist2 = dot(p, p);  normal = normalize(cross(tl.pos[2] - tl.pos[0], tl.pos[1] - tl.pos[0]));
+//                           colour = r9g9b9e5_to_rgb(emission_factor), 0 when |dot(dir, normal)| < 0.001f, times the emission texture at
+//                           (data.x * uv0 + data.y * uv1) + b.z * uv2 when there is one
+//                directional dir = sample_cone(data, -dl.dir, dl.dir_cutoff);  dist2 = inf;
+//                           colour = dl.dir_cutoff >= 1 ? dl.color : dl.color * (1.0f / (2.0f * pi * (1.0f - dl.dir_cutoff)))
+//                environment dir = uv_to_latlong_direction(data);  dist2 = inf;  colour = environment_factor.rgb * sample_envmap(data).rgb
+//                then: dot(dir, flat_normal) < 1e-6f gives 0;  tbn = create_tangent_space(mapped_normal);
+//                shading_view = view_to_tangent_space(view, tbn) (z clamped to 1e-5f);  shading_light = dir * tbn;
+//                lobes = 0; ggx_bsdf_pdf(shading_light, shading_view, mat, lobes); correct_lobes_for_normal_map(dir, flat_normal, lobes);
+//                value = modulate_bsdf(mat, lobes) * colour;  a NaN in data gives 0.  The null sample, or an index past the current
+//                frame's light count of its type, gives 0 with dir = 0, dist2 = 0 and no shadow ray.
+//   visibility   a contribution with a component > 0 casts trace_shadow4(pos, dir, min_ray_dist, sqrtf(dist2) - min_ray_dist); any other
+//                casts none and has visibility 0.  target = rgb_to_luminance(contribution * visibility)
+//   candidates   sample_canonical (restir_di.glsl:251-354) with u = unit(draw): classes in the order point, triangle, directional,
+//                environment by `(u.w -= prob) < 0` with the scene's NEE probabilities (nee_probabilities, pt.h; all four weights 1);
+//                point: index = clamp(int(u.x * n), 0, n - 1), pdf = (1.0f / n) * prob;  triangle: index from u.z,
+//                dir = sample_triangle_light(solid angle, u.xy, A, B, C, tri_pdf), len = ray_plane_intersection_dist(dir, A, B, C),
+//                tri_pdf = 1e9f when it is inf, <= 0, len <= min_ray_dist or dir has a NaN, data = get_barycentric_coords(dir * len, A, B, C).xy,
+//                pdf = (tri_pdf * (1.0f / n)) * prob;  directional: index from u.z, data = u.xy,
+//                pdf = ((cutoff >= 1 ? 1.0f : 1.0f / (2.0f * pi * (1.0f - cutoff))) / n) * prob;  environment: the alias table as
+//                sample_environment_map (shade_kernel.h) reads it, data = (pixel + off) / size, pdf = entry pdf * prob;  no class taken
+//                (no lights, or u.w past the sum by rounding): the null sample with pdf 1.
+//                weight = (1.0f / (float(candidates) + prev_confidence)) * target / pdf, NaN -> 0;  update_reservoir:
+//                weight_sum += weight; selected = u * weight_sum < weight (then the reservoir takes sample and target);  confidence += 1
+//                after the loop uc_weight = weight_sum > 0 ? weight_sum / target : 0
+//   reprojection m = get_camera_projection(previous camera, surface_prev_pos).xy;  m.y = 1.0f - m.y;  m = m * size - 0.5f;  im = int(m)
+//                (truncation);  off = m - float(im);  pixel = im + (off.x < u.x ? 0 : 1, off.y < u.y ? 0 : 1)   (restir_di.glsl:138-153)
+//   reuse        there is history, the pixel is on screen, and not (dot(prev.mapped_normal, mapped_normal) < 0.95f or
+//                length(pos - prev.pos) > 0.01f * length(origin - pos) / (|dot(view, mapped_normal)| + 0.001f))   (:375-388)
+//                prev_confidence = reuse ? history.confidence : 0
+//   temporal     target' = luminance(contribution of the history sample here), no shadow ray;
+//                weight = ((prev.confidence / (confidence + prev.confidence)) * target') * prev.uc_weight, NaN -> 0;  update_reservoir;
+//                confidence += prev.confidence;  uc_weight as above;  with TEMPORAL always confidence = min(confidence, max_confidence)
+//   neighbours   offset = floorf(search_radius * sample_blackman_harris_concentric_disk(u.xy) + 0.5f) per component;  candidates off screen
+//                or without a surface are passed over;  inv = 1.0f / (min(|2 proj_inverse[0][0]|, |2 proj_inverse[1][1]|) *
+//                |dot(view_inverse[2].xyz, view_inverse[3].xyz - pos)|);  good = clamp(1.0f - |dot(flat_normal, npos - pos)| * inv, 0, 1) >= 0.99f
+//                and dot(nflat, flat_normal) >= 0.75f;  good ones fill slots from the front while fewer than SPATIAL are held, bad ones from
+//                the back while good + bad < SPATIAL (restir_di_spatial.rgen:104-130)
+//   spatial      total = canonical.confidence + the held neighbours' confidences in slot order;  canonical_m = canonical.confidence / total;
+//                per held slot, in order: the neighbour's sample, if not null, is re-evaluated here with a shadow ray (target_n),
+//                j = type > 1 ? 1 : reconnection_jacobian(npos, x, normal, pos, x, normal) with x = pos + dir * sqrtf(dist2);
+//                m = mis_noncanonical(c.conf, n.conf, total, n.target_function, target_n, j);  wi = ((target_n * m) * n.uc_weight) * j, NaN -> 0;
+//                update_reservoir;  confidence += n.confidence;  then, if the canonical sample is not null, it is evaluated at the
+//                neighbour's surface with a shadow ray (target_c), jc the Jacobian the other way round, and
+//                canonical_m += mis_canonical(c.conf, n.conf, total, c.target_function, target_c, jc)
+//                wi = (canonical_m * c.target_function) * c.uc_weight, NaN -> 0;  update_reservoir;  confidence += c.confidence;
+//                uc_weight = weight_sum > 0 ? weight_sum / target : 0.  SPATIAL = 0: the canonical reservoir as it is.
+//   jacobian     q = prev_src - dst, r = cur_src - dst;  (|dot(n, r)| * (lq * lq * lq)) / (|dot(n, q)| * (lr * lr * lr)) with lq = length(q),
+//                lr = length(r);  1 for n = 0;  0 when inf or NaN   (restir_di.glsl:477-501)
+//   colour       contribution of the chosen sample here times its shadow ray's visibility;
+//                out = (contribution * uc_weight + emission, 1);  a pixel without a surface: the null reservoir and the direct stage's
+//                miss colour (k_direct: the visible directional lights in order, then the environment)
+#pragma once
+#include "common.h"
+#include "shading.h"
+
+namespace tr {
+
+constexpr uint RESTIR_NULL_INDEX = (1u << 30) - 1u;
+constexpr int RESTIR_MAX_CANDIDATES = 32, RESTIR_MAX_SPATIAL = 4;
+
+struct alignas(16) RestirSurface {       // trhip_restir_di_surface
+    f3 pos; int instance_id;
+    f3 mapped_normal; float metallic;
+    f3 flat_normal; float roughness;
+    f3 view; float transmittance;
+    f4 albedo;
+    f3 emission; float f0;
+    float ior_in, ior_out, pad0, pad1;
+};
+struct alignas(16) RestirReservoir {     // trhip_restir_di_reservoir
+    float uc_weight, target_function; uint light; float confidence;
+    f2 light_data; uint pad0, pad1;
+};
+struct RestirCandidateRecord {           // trhip_restir_di_candidate
+    uint light; f2 light_data; float pdf;
+    f3 contribution; float visibility;   // the unshadowed contribution
+    float weight, draw; uint selected, pad;
+};
+struct RestirTemporalRecord {            // trhip_restir_di_temporal
+    int px, py; uint reuse; float prev_confidence;
+    float target, weight, draw; uint selected;
+};
+struct RestirSpatialRecord {             // trhip_restir_di_spatial
+    int px, py; uint good, selected;     // px = -1: an empty slot
+    float target_n, visibility_n, jacobian_n, m;
+    float wi, draw, target_c, visibility_c;
+    float jacobian_c, mis_canonical, pad0, pad1;
+};
+struct RestirFinalRecord {               // trhip_restir_di_final
+    f3 contribution; float visibility;   // the unshadowed contribution of the chosen sample
+    float canonical_m, wi, draw; uint selected;
+};
+static_assert(sizeof(RestirSurface) == 112 && sizeof(RestirReservoir) == 32 && sizeof(RestirCandidateRecord) == 48, "layout");
+static_assert(sizeof(RestirTemporalRecord) == 32 && sizeof(RestirSpatialRecord) == 64 && sizeof(RestirFinalRecord) == 32, "layout");
+
+// Word i of a record: the buffers are device allocations and every record is 16-byte aligned - one global (not flat) 16-byte load or store
+TR_HD u4 restir_word(const void* p, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint v4u __attribute__((ext_vector_type(4)));
+    const v4u v = ((const v4u __attribute__((address_space(1)))*)p)[i];
+    return u4{v.x, v.y, v.z, v.w};
+#else
+    return ((const u4*)p)[i];
+#endif
+}
+TR_HD void restir_set_word(void* p, int i, u4 w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint v4u __attribute__((ext_vector_type(4)));
+    ((v4u __attribute__((address_space(1)))*)p)[i] = v4u{w.x, w.y, w.z, w.w};
+#else
+    ((u4*)p)[i] = w;
+#endif
+}
+
+struct RestirSample { uint type, index; f2 data; };
+TR_DEV bool restir_is_null(const RestirSample& s) { return s.type == 0u && s.index == RESTIR_NULL_INDEX; }
+TR_DEV RestirSample restir_null_sample() { return {0u, RESTIR_NULL_INDEX, F2(0.0f)}; }
+
+struct RestirState {                     // `reservoir` (restir_di.glsl:29-37) without its contribution
+    RestirSample ls;
+    float target_function, weight_sum, uc_weight, confidence;
+};
+TR_DEV RestirState restir_create() { return {restir_null_sample(), 0.0f, 0.0f, 0.0f, 0.0f}; }
+TR_DEV bool restir_update(RestirState& r, const RestirSample& ls, float weight, float u) {    // update_reservoir (restir_di.glsl:118-131)
+    r.weight_sum = r.weight_sum + weight;
+    if (u * r.weight_sum < weight) { r.ls = ls; return true; }
+    return false;
+}
+TR_DEV float restir_uc_weight(const RestirState& r) { return r.weight_sum > 0.0f ? r.weight_sum / r.target_function : 0.0f; }
+
+TR_DEV RestirReservoir restir_pack(const RestirState& r) {
+    return {r.uc_weight, r.target_function, r.ls.type << 30 | r.ls.index, r.confidence, r.ls.data, 0u, 0u};
+}
+TR_DEV void restir_store(RestirReservoir* dst, const RestirReservoir& r) {
+    restir_set_word(dst, 0, u4{__float_as_uint(r.uc_weight), __float_as_uint(r.target_function), r.light, __float_as_uint(r.confidence)});
+    restir_set_word(dst, 1, u4{__float_as_uint(r.light_data.x), __float_as_uint(r.light_data.y), 0u, 0u});
+}
+TR_DEV RestirState restir_load(const RestirReservoir* src) {                                   // read_reservoir_buffer (:427-454)
+    const u4 a = restir_word(src, 0), b = restir_word(src, 1);
+    RestirState r;
+    r.uc_weight = __uint_as_float(a.x); r.target_function = __uint_as_float(a.y);
+    r.ls.type = a.z >> 30; r.ls.index = a.z & 0x3FFFFFFFu;
+    r.confidence = __uint_as_float(a.w);
+    r.ls.data = F2(__uint_as_float(b.x), __uint_as_float(b.y));
+    r.weight_sum = 0.0f;
+    return r;
+}
+
+// The part of a surface record light_contribution reads (the shader's `domain`)
+struct RestirDomain {
+    f3 pos, mapped_normal, flat_normal, view;
+    SampledMaterial mat;
+};
+TR_DEV void restir_store_surface(RestirSurface* dst, const RestirDomain& d, int instance_id) {
+#define TR_U(x) __float_as_uint(x)
+    restir_set_word(dst, 0, u4{TR_U(d.pos.x), TR_U(d.pos.y), TR_U(d.pos.z), (uint)instance_id});
+    restir_set_word(dst, 1, u4{TR_U(d.mapped_normal.x), TR_U(d.mapped_normal.y), TR_U(d.mapped_normal.z), TR_U(d.mat.metallic)});
+    restir_set_word(dst, 2, u4{TR_U(d.flat_normal.x), TR_U(d.flat_normal.y), TR_U(d.flat_normal.z), TR_U(d.mat.roughness)});
+    restir_set_word(dst, 3, u4{TR_U(d.view.x), TR_U(d.view.y), TR_U(d.view.z), TR_U(d.mat.transmittance)});
+    restir_set_word(dst, 4, u4{TR_U(d.mat.albedo.x), TR_U(d.mat.albedo.y), TR_U(d.mat.albedo.z), TR_U(d.mat.albedo.w)});
+    restir_set_word(dst, 5, u4{TR_U(d.mat.emission.x), TR_U(d.mat.emission.y), TR_U(d.mat.emission.z), TR_U(d.mat.f0)});
+    restir_set_word(dst, 6, u4{TR_U(d.mat.ior_in), TR_U(d.mat.ior_out), 0u, 0u});
+#undef TR_U
+}
+// Position, instance id and flat normal alone: what the neighbour search reads (two words)
+TR_DEV void restir_load_surface_head(const RestirSurface* src, f3& pos, int& instance_id, f3& flat_normal) {
+    const u4 a = restir_word(src, 0), c = restir_word(src, 2);
+    pos = F3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)); instance_id = (int)a.w;
+    flat_normal = F3(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z));
+}
+TR_DEV int restir_load_surface(const RestirSurface* src, RestirDomain& d) {
+    const u4 a = restir_word(src, 0), b = restir_word(src, 1), c = restir_word(src, 2), e = restir_word(src, 3), f = restir_word(src, 4), g = restir_word(src, 5),
+             h = restir_word(src, 6);
+#define TR_F(x) __uint_as_float(x)
+    d.pos = F3(TR_F(a.x), TR_F(a.y), TR_F(a.z));
+    d.mapped_normal = F3(TR_F(b.x), TR_F(b.y), TR_F(b.z)); d.mat.metallic = TR_F(b.w);
+    d.flat_normal = F3(TR_F(c.x), TR_F(c.y), TR_F(c.z)); d.mat.roughness = TR_F(c.w);
+    d.view = F3(TR_F(e.x), TR_F(e.y), TR_F(e.z)); d.mat.transmittance = TR_F(e.w);
+    d.mat.albedo = F4(TR_F(f.x), TR_F(f.y), TR_F(f.z), TR_F(f.w));
+    d.mat.emission = F3(TR_F(g.x), TR_F(g.y), TR_F(g.z)); d.mat.f0 = TR_F(g.w);
+    d.mat.ior_in = TR_F(h.x); d.mat.ior_out = TR_F(h.y);
+#undef TR_F
+    return (int)a.w;
+}
+
+// A light's record as sample_explicit_light (shade_kernel.h) fetches it: the kind and the record are decided first, then one masked fetch
+// per kind into the same four registers; the branches behind it only compute.  An environment sample has no record (the candidate
+// sampler fetches its alias entry into r0 itself).  valid: not the null sample, and the index is inside the current frame's array.
+struct RestirLightRecord { u4 r0, r1, r2, r3; bool valid; };
+TR_DEV RestirLightRecord restir_fetch_light(const SceneView& sv, const RestirSample& s) {
+    RestirLightRecord L;
+    L.r0 = u4{0u, 0u, 0u, 0u}; L.r1 = L.r0; L.r2 = L.r0; L.r3 = L.r0;
+    const uint n_point = sv.point_light_count, n_tri = sv.tri_light_count, n_dir = sv.directional_light_count;
+    int kind = s.type == 0u ? (s.index < n_point ? 1 : 0) : s.type == 1u ? (s.index < n_tri ? 2 : 0) : s.type == 2u ? (s.index < n_dir ? 3 : 0)
+                                                                                                                   : (sv.environment_proj >= 0 ? 4 : 0);
+    asm volatile("" : "+v"(kind));       // as sample_explicit_light: keeps the fetches out of the tests above
+    if (kind == 1) { const u4* rec = reinterpret_cast<const u4*>(sv.point_lights + s.index); L.r0 = rec[0]; L.r1 = rec[1]; L.r2 = rec[2]; L.r3 = rec[3]; }
+    if (kind == 2) { const u4* rec = reinterpret_cast<const u4*>(sv.tri_lights + s.index); L.r0 = rec[0]; L.r1 = rec[1]; L.r2 = rec[2]; L.r3 = rec[3]; }
+    if (kind == 3) { const u4* rec = reinterpret_cast<const u4*>(sv.directional_lights + s.index); L.r0 = rec[0]; L.r1 = rec[1]; }
+    L.valid = kind != 0;
+    return L;
+}
+
+// light_contribution (restir_di.glsl:155-249), the BSDF as the direct stage's light sample gets it (k_direct, path_tracer.hip)
+TR_DEV f3 restir_contribution(const SceneView& sv, const RestirSample& s, const RestirLightRecord& L, const RestirDomain& dom, f3& dir, float& dist2, f3& normal) {
+#define TR_F(x) __uint_as_float(x)
+    dir = F3(0.0f); dist2 = 0.0f; normal = F3(0.0f);
+    if (!L.valid) return F3(0.0f);
+    f3 light_color = F3(0.0f);
+    if (s.type == 0u) {
+        PointLight pl;
+        pl.color = F3(TR_F(L.r0.x), TR_F(L.r0.y), TR_F(L.r0.z)); pl.dir = F3(TR_F(L.r0.w), TR_F(L.r1.x), TR_F(L.r1.y)); pl.pos = F3(TR_F(L.r1.z), TR_F(L.r1.w), TR_F(L.r2.x));
+        pl.radius = TR_F(L.r2.y); pl.dir_cutoff = TR_F(L.r2.z); pl.dir_falloff = TR_F(L.r2.w);
+        const f3 to_light = pl.pos - dom.pos;
+        dir = normalize(to_light);
+        dist2 = dot(to_light, to_light);
+        light_color = (pl.color * get_spotlight_intensity<RoundedMath>(pl, dir)) / fmax2(dist2, 1e-7f);
+    } else if (s.type == 1u) {
+        const f3 P0 = F3(TR_F(L.r0.x), TR_F(L.r0.y), TR_F(L.r0.z)), P1 = F3(TR_F(L.r0.w), TR_F(L.r1.x), TR_F(L.r1.y)), P2 = F3(TR_F(L.r1.z), TR_F(L.r1.w), TR_F(L.r2.x));
+        const f3 A = P0 - dom.pos, B = P1 - dom.pos, C = P2 - dom.pos;
+        const float bz = 1.0f - s.data.x - s.data.y;
+        const f3 p = (s.data.x * A + s.data.y * B) + bz * C;
+        dir = normalize(p);
+        dist2 = dot(p, p);
+        normal = normalize(cross(P2 - P0, P1 - P0));
+        f3 color = r9g9b9e5_to_rgb(L.r2.y);
+        if (fabsf(dot(dir, normal)) < 0.001f) color = F3(0.0f);
+        const int emission_tex_id = (int)L.r3.w;
+        if (emission_tex_id >= 0) {
+            const f2 uv = (s.data.x * unpack_half2x16(L.r3.x) + s.data.y * unpack_half2x16(L.r3.y)) + bz * unpack_half2x16(L.r3.z);
+            color = color * F3(sample_texture(sv, emission_tex_id, uv));
+        }
+        light_color = color;
+    } else if (s.type == 2u) {
+        const f3 dl_color = F3(TR_F(L.r0.x), TR_F(L.r0.y), TR_F(L.r0.z)), dl_dir = F3(TR_F(L.r1.x), TR_F(L.r1.y), TR_F(L.r1.z));
+        const float dir_cutoff = TR_F(L.r1.w);
+        dist2 = __builtin_huge_valf();
+        dir = sample_cone<RoundedMath>(s.data, -dl_dir, dir_cutoff);
+        light_color = dir_cutoff >= 1.0f ? dl_color : dl_color * (1.0f / (2.0f * TR_PI * (1.0f - dir_cutoff)));
+    } else {
+        dir = uv_to_latlong_direction<RoundedMath>(s.data);
+        dist2 = __builtin_huge_valf();
+        light_color = F3(sv.environment_factor) * F3(sample_envmap(sv, s.data));
+    }
+#undef TR_F
+    if (dot(dir, dom.flat_normal) < 1e-6f) return F3(0.0f);
+    const m3 tbn = create_tangent_space(dom.mapped_normal);
+    const f3 shading_view = view_to_tangent_space(dom.view, tbn);
+    const f3 shading_light = mulT(dir, tbn);
+    Lobes lobes = {0, 0, 0, 0};
+    ggx_bsdf_pdf<RoundedMath>(shading_light, shading_view, dom.mat, lobes);
+    if (dot(dom.flat_normal, dir) < 0) { lobes.diffuse = 0; lobes.dielectric_reflection = 0; lobes.metallic_reflection = 0; }     // correct_lobes_for_normal_map
+    else lobes.transmission = 0;
+    f3 value = modulate_bsdf(dom.mat, lobes) * light_color;
+    if (isnan(s.data.x) || isnan(s.data.y)) value = F3(0.0f);
+    return value;
+}
+TR_DEV bool restir_casts(f3 c) { return c.x > 0.0f || c.y > 0.0f || c.z > 0.0f; }
+
+// reconnection_jacobian, mis_canonical, mis_noncanonical (restir_di.glsl:477-533)
+TR_DEV float restir_jacobian(f3 prev_src, f3 cur_src, f3 dst, f3 n) {
+    const f3 qdelta = prev_src - dst, rdelta = cur_src - dst;
+    const float lq = length(qdelta), lr = length(rdelta);
+    const float theta_q = fabsf(dot(n, qdelta)), theta_r = fabsf(dot(n, rdelta));
+    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 1.0f;
+    float v = (theta_r * (lq * lq * lq)) / (theta_q * (lr * lr * lr));
+    if (isinf(v) || isnan(v)) v = 0.0f;
+    return v;
+}
+TR_DEV float restir_mis_canonical(float c_conf, float o_conf, float total, float c_target, float c_in_other, float jacobian) {
+    if (c_target == 0.0f) return 0.0f;
+    const float w = c_conf * c_target;
+    return ((o_conf / total) * w) / (w + ((total - c_conf) * c_in_other) * jacobian);
+}
+TR_DEV float restir_mis_noncanonical(float c_conf, float o_conf, float total, float o_target, float o_in_canonical, float jacobian) {
+    if (o_target == 0.0f) return 0.0f;
+    const float w = (total - c_conf) * o_target;
+    return ((o_conf / total) * w) / (w + (c_conf * o_in_canonical) * jacobian);
+}
+
+}  // namespace tr

@@ -50,20 +50,22 @@ TR_DEV f2 sample_concentric_disk(f2 u) {     // math.glsl:205-218
     f2 rt = (a.x > a.y) ? F2(uo.x, TR_PI / 4 * (uo.y / uo.x)) : F2(uo.y, TR_PI / 2 - TR_PI / 4 * (uo.x / uo.y));
     return rt.x * F2(tcos(rt.y), tsin(rt.y));
 }
+template <class M = LibMath>
 TR_DEV float sample_blackman_harris(float u) {   // math.glsl:220-228
     bool flip = u > 0.5f;
     u = flip ? 1 - u : u;
-    float vx = -0.33518669f * tpow(u, 0.5f), vy = -0.51620529f * tpow(u, 0.3333333333f);
-    float vz = 1.87406934f * tpow(u, 0.25f), vw = -0.66315464f * tpow(u, 0.2f);
+    float vx = -0.33518669f * M::pow(u, 0.5f), vy = -0.51620529f * M::pow(u, 0.3333333333f);
+    float vz = 1.87406934f * M::pow(u, 0.25f), vw = -0.66315464f * M::pow(u, 0.2f);
     float s = 0.29627329f * u + vx + vy + vz + vw;
     return flip ? 1 - s : s;
 }
+template <class M = LibMath>
 TR_DEV f2 sample_blackman_harris_concentric_disk(f2 u) {   // math.glsl:230-241
     f2 uo = 2.0f * u - 1.0f;
     f2 a = {fabsf(uo.x), fabsf(uo.y)};
     if (a.x < 0.0001f && a.y < 0.0001f) return F2(0);
     f2 rt = (a.x > a.y) ? F2(u.x, TR_PI / 4 * (uo.y / uo.x)) : F2(u.y, TR_PI / 2 - TR_PI / 4 * (uo.x / uo.y));
-    return (2.0f * sample_blackman_harris(rt.x) - 1.0f) * F2(tcos(rt.y), tsin(rt.y));
+    return (2.0f * sample_blackman_harris<M>(rt.x) - 1.0f) * F2(M::cos(rt.y), M::sin(rt.y));
 }
 TR_DEV f2 sample_regular_polygon(f2 u, float angle, uint sides) {   // math.glsl:281-292
     float side = floorf(u.x * sides);
@@ -94,11 +96,12 @@ TR_DEV f3 sample_hemisphere(f2 u) {          // math.glsl:317-327
     float phi = u.y * 2 * TR_PI;
     return F3(tcos(phi) * sin_theta, tsin(phi) * sin_theta, cos_theta);
 }
+template <class M = LibMath>
 TR_DEV f3 sample_cone(f2 u, f3 dir, float cos_theta_min) {   // math.glsl:342-358
     float cos_theta = mixf(1.0f, cos_theta_min, u.x);
     float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
     float phi = u.y * 2 * TR_PI;
-    f3 o = mul(create_tangent_space(dir), F3(tcos(phi) * sin_theta, tsin(phi) * sin_theta, cos_theta));
+    f3 o = mul(create_tangent_space(dir), F3(M::cos(phi) * sin_theta, M::sin(phi) * sin_theta, cos_theta));
     return dot(o, dir) <= cos_theta_min ? dir : o;
 }
 TR_DEV f3 sample_triangle_area(f2 u, f3 A, f3 B, f3 C) {     // math.glsl:360-371
@@ -115,6 +118,7 @@ TR_DEV float determinant_accurate(f3 nA, f3 nB, f3 nC) {     // math.glsl:373-38
     f3 c = nC - 2.0f * h * dot(h, nC);
     return fabsf(a.y * c.z - c.y * a.z);
 }
+template <class M = LibMath>
 TR_DEV f3 sample_spherical_triangle(f2 xi, f3 A, f3 B, f3 C, float& pdf) {   // math.glsl:385-419
     f3 nA = normalize(A), nB = normalize(B), nC = normalize(C);
     float dAB = dot(nA, nB), dBC = dot(nB, nC), dAC = dot(nA, nC);
@@ -126,18 +130,19 @@ TR_DEV f3 sample_spherical_triangle(f2 xi, f3 A, f3 B, f3 C, float& pdf) {   // 
     float G0 = fabsf(a.y * c.z - c.y * a.z);
     float G1 = dAC + dBC;
     float G2 = 1.0f + dAB;
-    float solid_angle = 2.0f * atan2f(G0, G1 + G2);
+    float solid_angle = 2.0f * M::atan2(G0, G1 + G2);
     pdf = 1.0f / solid_angle;
     float chosen_split = xi.x * solid_angle * 0.5f;
-    f3 r = (G0 * tcos(chosen_split) - G1 * tsin(chosen_split)) * nA + G2 * tsin(chosen_split) * nC;
+    f3 r = (G0 * M::cos(chosen_split) - G1 * M::sin(chosen_split)) * nA + G2 * M::sin(chosen_split) * nC;
     f3 Ch = 2.0f * dot(nA, r) * r / dot(r, r) - nA;
     float d = dot(Ch, nB);
     float z = 1 - xi.y + d * xi.y;
     float st = sqrtf((1.0f - z * z) / (1.0f - d * d));
     return (z - st * d) * nB + st * Ch;
 }
+template <class M = LibMath>
 TR_DEV float spherical_triangle_solid_angle(f3 nA, f3 nB, f3 nC) {   // math.glsl:422-429
-    return 2.0f * atan2f(determinant_accurate(nA, nB, nC), 1.0f + (dot(nA, nB) + (dot(nB, nC) + dot(nA, nC))));
+    return 2.0f * M::atan2(determinant_accurate(nA, nB, nC), 1.0f + (dot(nA, nB) + (dot(nB, nC) + dot(nA, nC))));
 }
 TR_DEV float triangle_area_pdf(f3 p, f3 a, f3 b, f3 c) {             // math.glsl:441-447
     f3 normal = cross(a - b, a - c);
@@ -195,16 +200,19 @@ TR_DEV int latlong_direction_to_pixel_id(f3 dir, int sx, int sy) {   // alias_ta
     int px = (int)(uv.x * sx + 0.5f), py = (int)(uv.y * sy + 0.5f);
     return px + py * sx;
 }
+template <class M = LibMath>
 TR_DEV f3 uv_to_latlong_direction(f2 uv) {     // alias_table.glsl:29-35
     uv = (uv - 0.5f) * TR_PI;
-    f3 dir = F3(tcos(2.0f * uv.x), -tsin(uv.y), tsin(2.0f * uv.x));
+    f3 dir = F3(M::cos(2.0f * uv.x), -M::sin(uv.y), M::sin(2.0f * uv.x));
     float s = sqrtf(1 - dir.y * dir.y);
     dir.x *= s; dir.z *= s;
     return dir;
 }
 
 // ------------------------------------------------------------------ ggx.glsl
-TR_DEV float ggx_fresnel_schlick(float cos_d, float f0) { return f0 + (1.0f - f0) * tpow(fmax2(1.0f - cos_d, 0.0f), 5.0f); }
+template <class M = LibMath>
+TR_DEV float ggx_fresnel_schlick(float cos_d, float f0) { return f0 + (1.0f - f0) * M::pow(fmax2(1.0f - cos_d, 0.0f), 5.0f); }
+template <class M = LibMath>
 TR_DEV float ggx_fresnel(float cos_d, const SampledMaterial& mat) {         // ggx.glsl:36-49
     if (mat.ior_in > mat.ior_out) {
         float inv_eta = mat.ior_in / mat.ior_out;
@@ -212,8 +220,9 @@ TR_DEV float ggx_fresnel(float cos_d, const SampledMaterial& mat) {         // g
         if (sin_theta2 >= 1.0f) return 1.0f;
         cos_d = sqrtf(1.0f - sin_theta2);
     } else if (mat.ior_in == mat.ior_out) return 0.0f;
-    return ggx_fresnel_schlick(cos_d, mat.f0);
+    return ggx_fresnel_schlick<M>(cos_d, mat.f0);
 }
+template <class M = LibMath>
 TR_DEV float fresnel_importance(float cos_d, const SampledMaterial& mat) {  // ggx.glsl:54-67
     if (mat.ior_in > mat.ior_out) {
         float inv_eta = mat.ior_in / mat.ior_out;
@@ -221,7 +230,7 @@ TR_DEV float fresnel_importance(float cos_d, const SampledMaterial& mat) {  // g
         if (sin_theta2 >= 1.0f) return 1.0f;
         cos_d = sqrtf(1.0f - sin_theta2);
     } else if (mat.ior_in == mat.ior_out) return 0.0f;
-    return mat.f0 + (fmax2(1.0f - mat.roughness, mat.f0) - mat.f0) * tpow_ge0(1.0f - cos_d, 5.0f);
+    return mat.f0 + (fmax2(1.0f - mat.roughness, mat.f0) - mat.f0) * M::pow_ge0(1.0f - cos_d, 5.0f);
 }
 TR_DEV float ggx_masking(float v_dot_n, float v_dot_h, float a) {           // ggx.glsl:82-87
     float a2 = a * a;
@@ -339,6 +348,7 @@ TR_DEV void ggx_bsdf_sample(f4 ur, f3 view_dir, const SampledMaterial& mat, f3& 
     }
 }
 // ggx_bsdf_pdf = ggx_bsdf_lobe_pdf(MATERIAL_LOBE_ALL) (ggx.glsl:403-510)
+template <class M = LibMath>
 TR_DEV float ggx_bsdf_pdf(f3 out_dir, f3 view_dir, const SampledMaterial& mat, Lobes& bsdf) {
     float cos_l = out_dir.z, cos_v = view_dir.z;
     f3 h;
@@ -347,12 +357,12 @@ TR_DEV float ggx_bsdf_pdf(f3 out_dir, f3 view_dir, const SampledMaterial& mat, L
     float cos_h = h.z;
     float cos_d = dot(view_dir, h);
     float cos_o = dot(out_dir, h);
-    float fresnel = ggx_fresnel(cos_d, mat);
+    float fresnel = ggx_fresnel<M>(cos_d, mat);
     float geometry = ggx_masking_shadowing_predivided(cos_v, cos_d, cos_l, cos_o, mat.roughness);
     const bool zero_roughness = mat.roughness < 0.001f;
     float distribution = zero_roughness ? 0 : ggx_distribution(cos_h, mat.roughness);
     float max_albedo = fmax2(mat.albedo.x, fmax2(mat.albedo.y, mat.albedo.z));
-    float specular_cutoff = mixf(1.0f, fresnel_importance(view_dir.z, mat), (1 - mat.metallic) * max_albedo);
+    float specular_cutoff = mixf(1.0f, fresnel_importance<M>(view_dir.z, mat), (1 - mat.metallic) * max_albedo);
     float diffuse_cutoff = 1.0f - mat.transmittance;
     float specular_probability = specular_cutoff;
     float diffuse_probability = (1.0f - specular_cutoff) * diffuse_cutoff;
@@ -414,10 +424,11 @@ TR_DEV f3 modulate_bsdf(const SampledMaterial& mat, const Lobes& b) {      // ma
 }
 
 // ------------------------------------------------------------------ light.glsl
+template <class M = LibMath>
 TR_DEV float get_spotlight_intensity(const PointLight& l, f3 dir) {        // light.glsl:45-58
     if (l.dir_falloff > 0) {
         float cutoff = dot(dir, -l.dir);
-        cutoff = cutoff > l.dir_cutoff ? 1.0f - tpow(fmax2(1.0f - cutoff, 0.0f) / (1.0f - l.dir_cutoff), l.dir_falloff) : 0.0f;
+        cutoff = cutoff > l.dir_cutoff ? 1.0f - M::pow(fmax2(1.0f - cutoff, 0.0f) / (1.0f - l.dir_cutoff), l.dir_falloff) : 0.0f;
         return cutoff;
     }
     return 1.0f;
@@ -451,11 +462,12 @@ TR_DEV float sample_triangle_light_pdf(int mode, f3 P, f3 A, f3 B, f3 C) { // li
     if (mode == 1) return 1.0f / solid_angle;
     return solid_angle > 1e-6f ? 1.0f / solid_angle : triangle_area_pdf(P, A, B, C);
 }
+template <class M = LibMath>
 TR_DEV f3 sample_triangle_light(int mode, f2 u, f3 A, f3 B, f3 C, float& pdf) {
-    if (mode == 1) return sample_spherical_triangle(u, A, B, C, pdf);
+    if (mode == 1) return sample_spherical_triangle<M>(u, A, B, C, pdf);
     if (mode == 2) {
-        float solid_angle = spherical_triangle_solid_angle(normalize(A), normalize(B), normalize(C));
-        if (solid_angle > 1e-6f) return sample_spherical_triangle(u, A, B, C, pdf);
+        float solid_angle = spherical_triangle_solid_angle<M>(normalize(A), normalize(B), normalize(C));
+        if (solid_angle > 1e-6f) return sample_spherical_triangle<M>(u, A, B, C, pdf);
     }
     f3 P = sample_triangle_area(u, A, B, C);
     pdf = triangle_area_pdf(P, A, B, C);

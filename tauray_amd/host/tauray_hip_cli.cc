@@ -9,6 +9,7 @@
 //              [--filetype=exr|raw|none] [--format=rgb16|rgb32|rgba16|rgba32] [--tonemap=filmic|linear|gamma-correction|
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
+//              [--renderer=restir-di [--restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse]]
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
@@ -52,6 +53,12 @@ static const char* const usage_text =
     "                         stored distances instead of filtering trilinearly; the BRDF-integration table is generated unless a file is named\n"
     "                         (one device; works with --animation, --headless, --camera-grid, --tonemap, --samples-per-pixel and --envmap; no\n"
     "                         denoiser, --taa, reprojection or --display=looking-glass)\n"
+    "  --renderer=restir-di [--restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse]   (4,2,32,16,on; positional or name=value)\n"
+    "                         ReSTIR DI: direct light by reservoir resampling - `candidates` (1..32) light samples per pixel, one kept; the previous\n"
+    "                         frame's reservoir is reused through screen motion and up to `spatial_samples` (0..4) neighbours within search_radius\n"
+    "                         pixels are merged; one pass per frame (one device; works with --animation, --headless, --camera-grid, --tonemap,\n"
+    "                         --envmap and -t; no denoiser, --taa, reprojection, --display=looking-glass or --samples-per-pixel above 1;\n"
+    "                         --renderer=restir, the reference's ReSTIR PT, is not built)\n"
     "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
     "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
     "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
@@ -74,42 +81,6 @@ static const char* const usage_text =
     "  --process-count=N --process-rank=R --device=D --comm-id=FILE [--comm-nonce=N] [--exchange=rccl|ipc] [--shard=views]\n"
     "  --dump-scene=out.trsc\n";
 
-// A struct option of the reference (TR_STRUCT_OPT, src/options.cc): comma-separated values, positional in the order of `names` or name=value
-static std::map<std::string, std::string> parse_struct_option(const std::string& option, const std::string& text, const std::vector<std::string>& names)
-{
-    std::map<std::string, std::string> out;
-    std::stringstream ss(text); std::string tok;
-    size_t position = 0;
-    while(std::getline(ss, tok, ','))
-    {
-        const size_t eq = tok.find('=');
-        std::string name;
-        if(eq == std::string::npos)
-        {
-            if(position >= names.size()) throw std::runtime_error(option + ": more than " + std::to_string(names.size()) + " values");
-            name = names[position++];
-        }
-        else
-        {
-            name = tok.substr(0, eq); tok = tok.substr(eq + 1);
-            if(std::find(names.begin(), names.end(), name) == names.end()) throw std::runtime_error(option + ": " + name + " is not one of its fields");
-        }
-        if(tok.empty()) throw std::runtime_error(option + ": " + name + " has no value");
-        out[name] = tok;
-    }
-    return out;
-}
-static double struct_number(const std::string& option, const std::map<std::string, std::string>& v, const std::string& name, double fallback)
-{
-    auto it = v.find(name);
-    if(it == v.end()) return fallback;
-    size_t used = 0;
-    double d = 0;
-    try { d = std::stod(it->second, &used); } catch(std::exception&) { used = 0; }
-    if(used != it->second.size()) throw std::runtime_error(option + ": " + name + "=" + it->second + " is not a number");
-    return d;
-}
-
 int main(int argc, char** argv)
 {
     // hardware queues of the HIP runtime (default 4): more than three frame slots only pay off with more; read when the
@@ -127,6 +98,8 @@ int main(int argc, char** argv)
         float dshgi_temporal_ratio = 0.01f;
         bool use_probe_visibility = false;                                  // --use-probe-visibility, --brdf-integration (src/options.hh, data/brdf_integration.exr)
         std::string brdf_integration_path;
+        restir_di_stage::options restir;                                    // --restir
+        bool restir_given = false;
         std::vector<int> devices;
         bool timing = false;
         std::string dump_scene;
@@ -253,9 +226,10 @@ int main(int argc, char** argv)
             else if(starts(a, "--renderer="))
             {
                 renderer = val("--renderer=");
-                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes" && renderer != "dshgi")
-                    throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes, dshgi)");
+                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes" && renderer != "dshgi" && renderer != "restir-di")
+                    throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes, dshgi, restir-di)");
             }
+            else if(starts(a, "--restir=")) { restir.parse(val("--restir=")); restir_given = true; }
             else if(a == "--use-probe-visibility") use_probe_visibility = true;
             else if(starts(a, "--brdf-integration=")) brdf_integration_path = val("--brdf-integration=");
             else if(starts(a, "--samples-per-probe="))
@@ -369,6 +343,18 @@ int main(int argc, char** argv)
         }
         if(scene_path.empty()) throw std::runtime_error(usage_text);
         if(renderer == "dshgi" && display == "looking-glass") throw std::runtime_error("--renderer=dshgi: no --display=looking-glass (the composition of a light field from it is not built)");
+        if(restir_given && renderer != "restir-di") throw std::runtime_error("--restir sets the options of --renderer=restir-di");
+        if(renderer == "restir-di")
+        {   // what the renderer does not do, said before a scene is read
+            if(opt.bmfr) throw std::runtime_error("--renderer=restir-di: no --denoiser (the resampling is the noise reduction; the denoiser's feature targets are not written)");
+            if(opt.taa) throw std::runtime_error("--renderer=restir-di: no --taa (the stage writes no screen_motion target and its cameras do not jitter)");
+            if(!opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)
+                throw std::runtime_error("--renderer=restir-di: no --spatial-reprojection or --temporal-reprojection (the stage writes no G-buffer targets)");
+            if(display == "looking-glass") throw std::runtime_error("--renderer=restir-di: no --display=looking-glass (the composition of a light field from it is not built)");
+            if(opt.samples_per_pixel > 1) throw std::runtime_error("--renderer=restir-di: one pass per frame, --samples-per-pixel must be 1 (raise the candidates of --restir instead)");
+            if(devices.size() > 1 || fake_devices > 1) throw std::runtime_error("--renderer=restir-di runs on one device: the reservoirs of neighbouring pixels and of the previous frame live on one device");
+            if(process_count > 0 || shard_views) throw std::runtime_error("--renderer=restir-di runs in one process: no --process-count or --shard");
+        }
         if(devices.empty()) devices.assign((size_t)std::max(fake_devices, 1), 0);
 
         const bool is_glb = (scene_path.size() > 4 && scene_path.compare(scene_path.size() - 4, 4, ".glb") == 0) ||
@@ -545,6 +531,42 @@ int main(int argc, char** argv)
                     std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n";
                 }
                 out.save(dev, gr.display, (unsigned)f);
+            }
+            return 0;
+        }
+        if(renderer == "restir-di")
+        {
+            restir_di_renderer::options ro;
+            ro.restir = restir;
+            ro.restir.min_ray_dist = opt.min_ray_dist; ro.restir.rng_seed = (uint32_t)opt.rng_seed; ro.restir.projection = opt.projection;
+            ro.tonemap = opt.tonemap;
+            ro.restir.check();
+            hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
+            headless out(hopt);
+            device dev(devices[0]);
+            scene_stage ss(dev, opt.scene);
+            ss.set_scene(scene);
+            restir_di_renderer rr(dev, scene, size, ro);
+            for(int f = -warmup; f < frames; ++f)
+            {
+                if(animated && f >= 0)
+                {   // update(s, dt, true) before the frame, the first one by dt = 0 (src/tauray.cc:1064-1092)
+                    if(!frames_given && !animator.is_playing()) break;
+                    animator.update(f == 0 ? 0 : update_dt);
+                    if(!frames_given && !animator.is_playing()) break;
+                    dev.sync();
+                    ss.apply(scene, f % 3 == 2);
+                }
+                rr.render();
+                dev.sync();
+                if(f < 0) continue;
+                if(timing)
+                {
+                    const trhip_restir_di_timings t = rr.stage->get_timings();
+                    std::cout << "FRAME " << f << ":\n\tDEVICE 0:\n";
+                    std::cout << "\t\t[" << t.canonical_name << "] " << t.canonical_ms << " ms\n\t\t[" << t.spatial_name << "] " << t.spatial_ms << " ms\n";
+                }
+                out.save(dev, rr.display, (unsigned)f);
             }
             return 0;
         }

@@ -1255,6 +1255,95 @@ class DshgiRenderer:
             b.free()
 
 
+def restir_di_options(**kw) -> dict:
+    """trhip_restir_di_options at the command line's defaults (--restir=4,2,32,16,on)."""
+    o = dict(candidates=4, spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0,
+             record=False)
+    unknown = set(kw) - set(o)
+    if unknown:
+        raise AttributeError(f"unknown ReSTIR DI option {sorted(unknown)}")
+    o.update(kw)
+    return o
+
+
+class RestirDiStage(_PostStage):
+    """ReSTIR DI (trhip_restir_di_*, include/trhip.h; written after shader/restir_di.glsl and its two ray generation shaders): per frame
+    the canonical kernel (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).
+    `size`: (w, h); `layers`: the viewports of a frame; `options`: restir_di_options()."""
+
+    PREFIX, TIMINGS = "restir_di", _lib.RestirDiTimingsC
+    _RECORDS = {"surface": (_lib.RESTIR_DI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_DI_CANONICAL, _lib.RESTIR_DI_RESERVOIR_DTYPE),
+                "history": (_lib.RESTIR_DI_HISTORY, _lib.RESTIR_DI_RESERVOIR_DTYPE), "candidates": (_lib.RESTIR_DI_CANDIDATES, _lib.RESTIR_DI_CANDIDATE_DTYPE),
+                "temporal": (_lib.RESTIR_DI_TEMPORAL, _lib.RESTIR_DI_TEMPORAL_DTYPE), "spatial": (_lib.RESTIR_DI_SPATIAL, _lib.RESTIR_DI_SPATIAL_DTYPE),
+                "final": (_lib.RESTIR_DI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE)}
+
+    def __init__(self, ctx: Optional[Context], scene_stage: Optional[SceneStage], size, layers=1, options: Optional[dict] = None, projection=0):
+        self.ctx, self.scene_stage, self.size, self.layers, self.projection = ctx, scene_stage, tuple(size), int(layers), int(projection)
+        o = self.options = restir_di_options(**(options or {}))
+        opt = _lib.RestirDiOptionsC(max(int(o["candidates"]), 0), max(int(o["spatial_samples"]), 0), float(o["search_radius"]), float(o["max_confidence"]),
+                                    int(o["temporal_reuse"]), float(o["min_ray_dist"]), int(o["rng_seed"]) & 0xFFFFFFFF, int(o["record"]))
+        if int(o["candidates"]) < 0 or int(o["spatial_samples"]) < 0:
+            raise TrhipError("RestirDiStage: candidates and spatial_samples are counts")
+        self._create(getattr(ctx, "h", None), C.byref(opt), max(int(self.size[0]), 0), max(int(self.size[1]), 0), max(self.layers, 0))
+
+    def run(self, viewports, out, stream=None):
+        """One frame: `out` RGBA32F [len(viewports)][h][w] = contribution * uc_weight + emission of the listed viewports.  History is kept
+        per position in the list: with temporal reuse the list stays the same from frame to frame until `reset`."""
+        v = np.ascontiguousarray(viewports, dtype=np.uint32)
+        check(_lib.lib().trhip_restir_di_render(self.h, self.projection, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size, _ptr(out), stream))
+
+    def reset(self):
+        """Forgets the history: the next frame is the first frame of a new stage."""
+        check(_lib.lib().trhip_restir_di_reset(self.h))
+
+    def download(self, name: str) -> np.ndarray:
+        """A structured array [layers][h][w] ("candidates", "spatial": one more axis) of "surface", "canonical", "history" and, with
+        record, "candidates", "temporal", "spatial", "final"."""
+        code, dtype = self._RECORDS[name]
+        shape = (self.layers, self.size[1], self.size[0])
+        if name == "candidates":
+            shape += (int(self.options["candidates"]),)
+        if name == "spatial":
+            shape += (int(self.options["spatial_samples"]),)
+        return self._download(code, shape, np.dtype(dtype))
+
+
+class RestirDiRenderer:
+    """--renderer=restir-di: the ReSTIR DI stage renders every viewport, the frame is tonemapped - on one stream."""
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: Optional[dict] = None, projection=None,
+                 tonemap: Optional[TonemapStage] = None):
+        self.ctx, self.ss, self.size = ctx, scene_stage, tuple(size)
+        self.viewports = max(len(scene.cameras), 1)
+        if projection is None:
+            projection = scene.cameras[0].projection if scene.cameras else 0
+        self.stage = RestirDiStage(ctx, scene_stage, self.size, self.viewports, options, projection)
+        self.tonemap = tonemap or TonemapStage(ctx)
+        pixels = self.size[0] * self.size[1] * self.viewports
+        self.color, self.display = ctx.alloc(pixels * 16).zero(), ctx.alloc(pixels * 16).zero()
+
+    def render(self, stream=None, tonemap=True):
+        self.stage.run(np.arange(self.viewports), self.color, stream)
+        if tonemap:
+            self.tonemap.run(self.color, self.display, self.size[0], self.size[1], self.viewports, stream)
+
+    def reset(self):
+        self.stage.reset()
+
+    def timings(self) -> dict:
+        return self.stage.timings()
+
+    def download(self, which="color") -> np.ndarray:
+        self.ctx.sync()
+        buf = self.color if which == "color" else self.display
+        return buf.download((self.viewports, self.size[1], self.size[0], 4))
+
+    def close(self):
+        self.stage.close()
+        for b in (self.color, self.display):
+            b.free()
+
+
 @dataclass(frozen=True)
 class PostProcessingPlan:
     """What plan_post_processing decides about the chain behind the path tracer; needs no device."""
