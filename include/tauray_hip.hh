@@ -895,13 +895,44 @@ public:
     trhip_dshgi* h = nullptr;
 };
 
+// What the single-device renderers of whole viewports share (dshgi_renderer, restir_di_renderer): the zeroed `color` and `display` images of
+// every viewport (one per camera), the tonemap stage, the list of all viewports and the tail of a frame that tonemaps it.  A derived
+// renderer's destructor releases the stages that write the images; the images go after them.
+class viewport_frame_renderer
+{
+public:
+    viewport_frame_renderer(device& dev, const scene_data& scene, uvec2 size, const tonemap_stage::options& tonemap_opt)
+    : dev(&dev), size(size), viewports(std::max(scene.camera_count(), 1u))
+    {
+        const size_t bytes = size_t(size.x) * size.y * 16 * viewports;
+        color = dev.alloc(bytes); display = dev.alloc(bytes);
+        check(trhip_memset(dev.h, color, 0, bytes, nullptr));
+        check(trhip_memset(dev.h, display, 0, bytes, nullptr));
+        tonemap.reset(new tonemap_stage(dev, tonemap_opt));
+        for(uint32_t v = 0; v < viewports; ++v) viewport_list.push_back(v);
+    }
+    viewport_frame_renderer(const viewport_frame_renderer&) = delete;
+    ~viewport_frame_renderer() { dev->free(color); dev->free(display); }
+
+    device* dev;
+    uvec2 size;
+    uint32_t viewports;
+    std::unique_ptr<tonemap_stage> tonemap;
+    std::vector<uint32_t> viewport_list;
+    void* color = nullptr;
+    void* display = nullptr;
+
+protected:
+    void finish_frame(void* stream) { tonemap->run(color, display, size, viewports, stream); }
+};
+
 // dshgi_renderer (src/dshgi_renderer.{hh,cc}): per frame the scene's probe grids are baked (sh_renderer), the direct stage renders every
 // viewport, the indirect light of the grids is added (dshgi_stage), the frame is tonemapped - all on one stream.  The first bake has
 // history 1, so the grids are complete before they are read.  The reference rasterises and uses shadow maps; here the first hit is a ray
 // and direct light is the direct stage.  Direct light is what the reference's raster pass lights with - point and
 // directional lights: the direct stage samples neither the emissive triangles nor the environment map (it still shows them where a pixel
 // sees them), because the probes see both and the indirect term carries their light.
-class dshgi_renderer
+class dshgi_renderer: public viewport_frame_renderer
 {
 public:
     struct options
@@ -914,12 +945,8 @@ public:
         tonemap_stage::options tonemap;
     };
     dshgi_renderer(device& dev, scene_stage& ss, const scene_data& scene, uvec2 size, const options& opt_)
-    : dev(&dev), size(size), grids(scene.sh_grids), viewports(std::max(scene.camera_count(), 1u)), opt(opt_), sh(dev, scene.sh_grids, opt_.sh)
+    : viewport_frame_renderer(dev, scene, size, opt_.tonemap), grids(scene.sh_grids), opt(opt_), sh(dev, scene.sh_grids, opt_.sh)
     {
-        const size_t bytes = size_t(size.x) * size.y * 16 * viewports;
-        color = dev.alloc(bytes); display = dev.alloc(bytes);
-        check(trhip_memset(dev.h, color, 0, bytes, nullptr));
-        check(trhip_memset(dev.h, display, 0, bytes, nullptr));
         opt.direct.distribution = distribution_params{size, DISTRIBUTION_DUPLICATE, 0, 1, true};
         opt.direct.active_viewport_count = viewports;
         opt.direct.sampling_weights.emissive_triangles = 0; opt.direct.sampling_weights.envmap = 0;
@@ -942,12 +969,9 @@ public:
         dev.sync();
         indirect->set_brdf_integration(table, tw, th);
         dev.free(table);
-        tonemap.reset(new tonemap_stage(dev, opt.tonemap));
-        for(uint32_t v = 0; v < viewports; ++v) viewport_list.push_back(v);
         set_scene(scene);
     }
-    dshgi_renderer(const dshgi_renderer&) = delete;
-    ~dshgi_renderer() { direct.reset(); indirect.reset(); dev->free(color); dev->free(display); }
+    ~dshgi_renderer() { direct.reset(); indirect.reset(); }
     // the instances have moved (the scene stage holds them already): every instance picks its grid again
     void set_scene(const scene_data& scene)
     {
@@ -960,22 +984,15 @@ public:
         direct->reset_accumulated_samples();
         direct->run(stream);
         indirect->run(viewport_list, color, color, stream);
-        tonemap->run(color, display, size, viewports, stream);
+        finish_frame(stream);
     }
 
-    device* dev;
-    uvec2 size;
     std::vector<sh_grid> grids;
-    uint32_t viewports;
     options opt;
     sh_renderer sh;
     std::unique_ptr<direct_stage> direct;
     std::unique_ptr<dshgi_stage> indirect;
-    std::unique_ptr<tonemap_stage> tonemap;
-    std::vector<uint32_t> viewport_list;
     std::vector<int32_t> instance_grids;
-    void* color = nullptr;
-    void* display = nullptr;
 };
 
 // ReSTIR DI (trhip_restir_di_*; written after shader/restir_di.glsl and its two ray generation shaders): per frame the canonical kernel
@@ -1057,7 +1074,7 @@ public:
 };
 
 // --renderer=restir-di: the ReSTIR DI stage renders every viewport, the frame is tonemapped - on one stream.
-class restir_di_renderer
+class restir_di_renderer: public viewport_frame_renderer
 {
 public:
     struct options
@@ -1066,34 +1083,22 @@ public:
         tonemap_stage::options tonemap;
     };
     restir_di_renderer(device& dev, const scene_data& scene, uvec2 size, const options& opt_)
-    : dev(&dev), size(size), viewports(std::max(scene.camera_count(), 1u)), opt(opt_)
+    : viewport_frame_renderer(dev, scene, size, checked(opt_).tonemap), opt(opt_)
     {
-        opt.restir.check();
-        const size_t bytes = size_t(size.x) * size.y * 16 * viewports;
-        color = dev.alloc(bytes); display = dev.alloc(bytes);
-        check(trhip_memset(dev.h, color, 0, bytes, nullptr));
-        check(trhip_memset(dev.h, display, 0, bytes, nullptr));
         stage.reset(new restir_di_stage(dev, size, viewports, opt.restir));
-        tonemap.reset(new tonemap_stage(dev, opt.tonemap));
-        for(uint32_t v = 0; v < viewports; ++v) viewport_list.push_back(v);
     }
-    restir_di_renderer(const restir_di_renderer&) = delete;
-    ~restir_di_renderer() { stage.reset(); dev->free(color); dev->free(display); }
+    ~restir_di_renderer() { stage.reset(); }
     void render(void* stream = nullptr)
     {
         stage->run(viewport_list, color, stream);
-        tonemap->run(color, display, size, viewports, stream);
+        finish_frame(stream);
     }
 
-    device* dev;
-    uvec2 size;
-    uint32_t viewports;
     options opt;
     std::unique_ptr<restir_di_stage> stage;
-    std::unique_ptr<tonemap_stage> tonemap;
-    std::vector<uint32_t> viewport_list;
-    void* color = nullptr;
-    void* display = nullptr;
+
+private:
+    static const options& checked(const options& o) { o.restir.check(); return o; }      // the options are refused before anything is allocated
 };
 
 class load_balancer

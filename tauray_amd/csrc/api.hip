@@ -1,5 +1,6 @@
 // C ABI of libtrhip.so (include/trhip.h) + the small kernels around the path tracer:
-// feature_stage, ray-level query hooks, stitch_stage and tonemap_stage.
+// feature_stage, ray-level query hooks, stitch_stage and tonemap_stage.  k_feature's first hit is first_hit.h's, which the kernels that take
+// a viewport list share.
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -8,6 +9,7 @@
 
 #include "pt.h"
 #include "trace.h"
+#include "first_hit.h"
 #include "trace_quad.h"
 #include "specialize.h"
 #include "tonemap.h"
@@ -38,19 +40,16 @@ __global__ __launch_bounds__(KB) void k_feature(SceneView sv, LaunchCtx L, int f
     int px, py, wx, wy;
     if (!get_pixel_pos(L, lx, ly, px, py) || !get_write_pixel_pos(L, lx, ly, wx, wy)) return;
     const CameraData cam = sv.cameras[viewport];
-    f3 origin, dir;
-    get_screen_camera_ray(L, px, py, cam, projection, false, F2(0), F2(0.5f), origin, dir);
-    f3 ray_origin = projection == 2 ? origin : F3(cam.origin);   // rt_feature.rgen:35 traces from cam.origin
+    f3 ray_origin, dir;
     HitRecord hit;
-    TraceStats st = {};
-    int overflow = 0;
-    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), 0u, s_stack + threadIdx.x, hit, st, overflow);
+    int overflow;
+    first_hit<TWO_LEVEL>(sv, L, cam, projection, px, py, min_ray_dist, s_stack + threadIdx.x, ray_origin, dir, hit, overflow);
     if (overflow) *overflow_flag = 1;
     f4 data = default_value;
     if (hit.instance_id >= 0) {
         SurfacePoint v;
         SampledMaterial mat;
-        shade_surface(sv, hit.instance_id, hit.primitive_id, hit.u, hit.v, dir, ray_origin, false, 0, false, v, mat);
+        first_hit_surface(sv, hit, dir, ray_origin, v, mat);
         switch (feature) {
             default:
             case 0: data = mat.albedo; break;

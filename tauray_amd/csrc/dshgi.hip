@@ -1,13 +1,13 @@
 // dshgi_renderer's indirect light for gfx950 - the consumer half of the reference's DDISH-GI (src/dshgi_renderer.{hh,cc}, shader/forward.frag,
 // shader/spherical_harmonics.glsl restated) behind the entry points trhip_dshgi_* and trhip_brdf_integration_generate of include/trhip.h.
-//   k_dshgi_indirect      per pixel of every viewport: the first hit as k_gbuffer (reprojection.hip) finds and shades it, the instance's SH
+//   k_dshgi_indirect      per pixel of every viewport: the first hit and its surface (first_hit.h), the instance's SH
 //                         grid sampled at the hit (trilinear or probe visibility), the cosine and GGX lobes, brdf_indirect, modulate_color;
 //                         the result is added to the direct stage's colour
 //   k_brdf_integration    the split-sum scale and bias table the reference loads from data/brdf_integration.exr
 // The reference rasterises the first hit and lights it with shadow maps; here the first hit is a ray and direct light is the direct stage's
 // (DESIGN.md section 20).  Constants, layouts and the order of operations: dshgi.h.  Both kernels are IEEE fp32, evaluated without
-// contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  Built with the flags of api.hip, so that the
-// front half computes what k_gbuffer and k_feature compute.
+// contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  The front half is first_hit.h's, the one
+// k_gbuffer and k_feature call.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "dshgi.h"
-#include "reprojection.h"
+#include "first_hit.h"
 #include "stage_host.h"
 #include "pt.h"
 #include "trace.h"
@@ -24,10 +24,6 @@ namespace tr {
 namespace {
 
 constexpr int KB = TR_BLOCK;
-constexpr int DSHGI_CHUNK = 64;        // viewports of one launch (the list travels in the kernel arguments), as k_gbuffer
-static_assert(REPROJ_TILE * REPROJ_TILE == KB, "a workgroup is one tile");
-
-struct DshgiViewports { uint v[DSHGI_CHUNK]; };
 
 struct DshgiParams {
     const DshgiGrid* grids;
@@ -40,26 +36,22 @@ struct DshgiParams {
     DshgiSurface* surface;             // null unless record_surface
 };
 
-// A workgroup is a 16 x 16 tile of layer blockIdx.z, a wave an 8 x 8 quarter of it: coherent primary rays, and the pixels of a wave fall
-// into a few grid cells, so its texel reads collapse onto a few lines.
+// tile_pixel's launch shape: coherent primary rays, and the pixels of a wave fall into a few grid cells, so its texel reads collapse onto
+// a few lines.
 template <bool TWO_LEVEL, int ORDER, bool VISIBILITY>
-__global__ __launch_bounds__(KB) void k_dshgi_indirect(SceneView sv, LaunchCtx L, int projection, DshgiViewports list, float min_ray_dist, DshgiParams P,
+__global__ __launch_bounds__(KB) void k_dshgi_indirect(SceneView sv, LaunchCtx L, int projection, ViewportList list, float min_ray_dist, DshgiParams P,
                                                        uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
     int* const s_stack = s_stack_rows + TR_STACK_ROW0;
-    const uint t = threadIdx.x, wave = t >> 6, k = t & 63u;
-    const int px = (int)(blockIdx.x * REPROJ_TILE + ((wave & 1u) << 3) + (k & 7u));
-    const int py = (int)(blockIdx.y * REPROJ_TILE + ((wave >> 1) << 3) + (k >> 3));
+    int px, py;
+    tile_pixel(px, py);
     if ((uint)px >= L.launch_w || (uint)py >= L.launch_h) return;
     const uint layer = blockIdx.z;
     const CameraData cam = sv.cameras[list.v[layer]];
-    f3 origin, dir;
-    get_screen_camera_ray(L, px, py, cam, projection, false, F2(0), F2(0.5f), origin, dir);
-    const f3 ray_origin = projection == 2 ? origin : F3(cam.origin);
+    f3 ray_origin, dir;
     HitRecord hit;
-    TraceStats st = {};
-    int overflow = 0;
-    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), 0u, s_stack + threadIdx.x, hit, st, overflow);
+    int overflow;
+    first_hit<TWO_LEVEL>(sv, L, cam, projection, px, py, min_ray_dist, s_stack + threadIdx.x, ray_origin, dir, hit, overflow);
     if (overflow) *overflow_flag = 1;
     DshgiSurface s = {};
     s.grid = -1; s.instance_id = -1;
@@ -67,7 +59,7 @@ __global__ __launch_bounds__(KB) void k_dshgi_indirect(SceneView sv, LaunchCtx L
     if (hit.instance_id >= 0) {
         SurfacePoint v;
         SampledMaterial mat;
-        shade_surface(sv, hit.instance_id, hit.primitive_id, hit.u, hit.v, dir, ray_origin, false, 0, false, v, mat);
+        first_hit_surface(sv, hit, dir, ray_origin, v, mat);
         s.pos = v.pos; s.smooth_normal = v.smooth_normal; s.mapped_normal = v.mapped_normal;
         s.view = dsh_normalize(v.pos - ray_origin);
         s.albedo = mat.albedo; s.metallic = mat.metallic; s.roughness = mat.roughness; s.f0 = mat.f0; s.transmittance = mat.transmittance;
@@ -153,14 +145,16 @@ float point_distance(const m4& pos_from_world, float radius, f3 p) {
     return -1.0f;
 }
 
-template <bool TWO_LEVEL, bool VISIBILITY, class... Args>
-void launch_dshgi(int order, dim3 grid, hipStream_t st, Args... args) {
+using DshgiKernel = void (*)(SceneView, LaunchCtx, int, ViewportList, float, DshgiParams, uint*);
+
+template <bool TWO_LEVEL, bool VISIBILITY>
+DshgiKernel dshgi_kernel(int order) {
     switch (order) {
-        case 0: hipLaunchKernelGGL((k_dshgi_indirect<TWO_LEVEL, 0, VISIBILITY>), grid, dim3(KB), 0, st, args...); break;
-        case 1: hipLaunchKernelGGL((k_dshgi_indirect<TWO_LEVEL, 1, VISIBILITY>), grid, dim3(KB), 0, st, args...); break;
-        case 2: hipLaunchKernelGGL((k_dshgi_indirect<TWO_LEVEL, 2, VISIBILITY>), grid, dim3(KB), 0, st, args...); break;
-        case 3: hipLaunchKernelGGL((k_dshgi_indirect<TWO_LEVEL, 3, VISIBILITY>), grid, dim3(KB), 0, st, args...); break;
-        default: hipLaunchKernelGGL((k_dshgi_indirect<TWO_LEVEL, 4, VISIBILITY>), grid, dim3(KB), 0, st, args...); break;
+        case 0: return k_dshgi_indirect<TWO_LEVEL, 0, VISIBILITY>;
+        case 1: return k_dshgi_indirect<TWO_LEVEL, 1, VISIBILITY>;
+        case 2: return k_dshgi_indirect<TWO_LEVEL, 2, VISIBILITY>;
+        case 3: return k_dshgi_indirect<TWO_LEVEL, 3, VISIBILITY>;
+        default: return k_dshgi_indirect<TWO_LEVEL, 4, VISIBILITY>;
     }
 }
 
@@ -341,11 +335,9 @@ int trhip_dshgi_render(trhip_dshgi* s, int projection, const uint32_t* viewports
                        void* out_color_dev, void* stream) {
     if (!s) return set_error("trhip_dshgi_render: null stage");
     if (!viewports || !out_color_dev) return set_error("trhip_dshgi_render: null argument");
-    if (count == 0 || count > s->layers) return set_error("trhip_dshgi_render: " + std::to_string(count) + " viewports, the stage has " + std::to_string(s->layers) + " layers");
     DEVCHK(s->hip_device);
     DeviceScene* scene = device_scene(s->dev);
-    if (scene->instance_count == 0) return set_error("trhip_dshgi_render: no scene (trhip_scene_upload)");
-    if (!scene->accel_built) return set_error("trhip_dshgi_render: no acceleration structure: call trhip_scene_build_accel first");
+    if (int r = check_scene_ready("trhip_dshgi_render", scene->instance_count, scene->accel_built)) return r;
     if (s->grid_count == 0) return set_error("trhip_dshgi_render: no grids set (trhip_dshgi_set_grids)");
     if (s->host_instance_grid.size() != scene->instance_count)
         return set_error("trhip_dshgi_render: " + std::to_string(s->host_instance_grid.size()) + " instance grids set (trhip_dshgi_set_instance_grids), the scene has " +
@@ -353,33 +345,23 @@ int trhip_dshgi_render(trhip_dshgi* s, int projection, const uint32_t* viewports
     for (int32_t g : s->host_instance_grid)
         if (g >= (int32_t)s->grid_count) return set_error("trhip_dshgi_render: grid index " + std::to_string(g) + " is out of range: " + std::to_string(s->grid_count) + " grids");
     if (!s->table) return set_error("trhip_dshgi_render: no BRDF-integration table (trhip_dshgi_set_brdf_integration)");
-    for (uint32_t i = 0; i < count; ++i)
-        if (viewports[i] >= scene->camera_count) return set_error("trhip_dshgi_render: viewport " + std::to_string(viewports[i]) + " out of range");
-    LaunchCtx L{};      // a duplicate distribution of the whole image, as trhip_gbuffer_render
-    L.size_x = s->w; L.size_y = s->h; L.strategy = 0; L.index = 0; L.count = 1; L.primary = 1; L.launch_w = s->w; L.launch_h = s->h;
+    if (int r = check_viewport_list("trhip_dshgi_render", viewports, count, s->layers, scene->camera_count)) return r;
+    const LaunchCtx L = whole_image_launch(s->w, s->h);
     const size_t layer_px = (size_t)s->w * s->h;
+    const bool visibility = s->opt.use_probe_visibility != 0;
+    const DshgiKernel kernel = scene->two_level ? (visibility ? dshgi_kernel<true, true>(s->opt.order) : dshgi_kernel<true, false>(s->opt.order))
+                                                : (visibility ? dshgi_kernel<false, true>(s->opt.order) : dshgi_kernel<false, false>(s->opt.order));
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipEventRecord(s->ev[0], st));
-    for (uint32_t first = 0; first < count; first += DSHGI_CHUNK) {
-        const uint32_t n = std::min<uint32_t>(DSHGI_CHUNK, count - first);
-        DshgiViewports list{};
-        for (uint32_t i = 0; i < n; ++i) list.v[i] = viewports[first + i];
+    for_each_viewport_chunk<ViewportList>(viewports, count, [&](uint32_t first, uint32_t n, const ViewportList& list) {
         DshgiParams P{};
         P.grids = s->grids; P.instance_grid = s->instance_grid; P.table = s->table; P.table_w = (int)s->table_w; P.table_h = (int)s->table_h;
         P.direct = direct_color_dev ? (const f4*)direct_color_dev + first * layer_px : nullptr;
         P.out = (f4*)out_color_dev + first * layer_px;
         P.indirect = s->indirect + first * layer_px;
         P.surface = s->surface ? s->surface + first * layer_px : nullptr;
-        const dim3 grid((s->w + REPROJ_TILE - 1) / REPROJ_TILE, (s->h + REPROJ_TILE - 1) / REPROJ_TILE, n);
-        uint* flag = device_overflow_flag(s->dev);
-        if (scene->two_level) {
-            if (s->opt.use_probe_visibility) launch_dshgi<true, true>(s->opt.order, grid, st, scene->view(), L, projection, list, min_ray_dist, P, flag);
-            else launch_dshgi<true, false>(s->opt.order, grid, st, scene->view(), L, projection, list, min_ray_dist, P, flag);
-        } else {
-            if (s->opt.use_probe_visibility) launch_dshgi<false, true>(s->opt.order, grid, st, scene->view(), L, projection, list, min_ray_dist, P, flag);
-            else launch_dshgi<false, false>(s->opt.order, grid, st, scene->view(), L, projection, list, min_ray_dist, P, flag);
-        }
-    }
+        hipLaunchKernelGGL(kernel, tile_grid(s->w, s->h, n), dim3(KB), 0, st, scene->view(), L, projection, list, min_ray_dist, P, device_overflow_flag(s->dev));
+    });
     HIPCHK(hipEventRecord(s->ev[1], st));
     HIPCHK(hipGetLastError());
     s->frames += 1;

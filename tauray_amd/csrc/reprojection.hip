@@ -3,13 +3,14 @@
 // temporal_reprojection_stage (src/temporal_reprojection_stage.{hh,cc}, shader/temporal_reprojection.comp restated:
 // k_temporal_reprojection), with the entry points trhip_gbuffer_render, trhip_spatial_reprojection_* and trhip_temporal_reprojection_*
 // of include/trhip.h.  Layouts: reprojection.h.  Everything is fp32 and evaluated without contraction in a fixed order, no atomics: two
-// runs of the same inputs give the same bits.  Built with the flags of api.hip, so that k_gbuffer computes what k_feature computes.
+// runs of the same inputs give the same bits.  k_gbuffer's first hit is first_hit.h's, the one k_feature (api.hip) calls.
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "reprojection.h"
+#include "first_hit.h"
 #include "stage_host.h"
 #include "taps.h"
 #include "pt.h"
@@ -19,22 +20,11 @@ namespace tr {
 namespace {
 
 constexpr int KB = TR_BLOCK;
-constexpr int GBUFFER_CHUNK = 64;      // viewports of one k_gbuffer launch (the list travels in the kernel arguments)
-static_assert(REPROJ_TILE * REPROJ_TILE == KB, "a workgroup is one tile");
-
-struct ViewportList { uint v[GBUFFER_CHUNK]; };
 
 TR_DEV f2 octahedral_pack(f3 n) {        // math.glsl:480-485, as write_first_hit_gbuffer (path_tracer.hip) evaluates it
     const f3 nn = n / (fabsf(n.x) + fabsf(n.y) + fabsf(n.z));
     return nn.z >= 0.0f ? F2(nn.x, nn.y)
                         : F2((1 - fabsf(nn.y)) * ((nn.x >= 0.0f ? 1.0f : 0.0f) * 2 - 1), (1 - fabsf(nn.x)) * ((nn.y >= 0.0f ? 1.0f : 0.0f) * 2 - 1));
-}
-
-// Pixel of a thread: a workgroup is a 16 x 16 tile of layer blockIdx.z, a wave an 8 x 8 quarter of it (coherent primary rays, shared tap lines).
-TR_DEV void tile_pixel(int& x, int& y) {
-    const uint t = threadIdx.x, wave = t >> 6, k = t & 63u;
-    x = (int)(blockIdx.x * REPROJ_TILE + ((wave & 1u) << 3) + (k & 7u));
-    y = (int)(blockIdx.y * REPROJ_TILE + ((wave >> 1) << 3) + (k >> 3));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -50,20 +40,17 @@ __global__ __launch_bounds__(KB) void k_gbuffer(SceneView sv, LaunchCtx L, int p
     if ((uint)px >= L.launch_w || (uint)py >= L.launch_h) return;
     const uint layer = blockIdx.z;
     const CameraData cam = sv.cameras[list.v[layer]];
-    f3 origin, dir;
-    get_screen_camera_ray(L, px, py, cam, projection, false, F2(0), F2(0.5f), origin, dir);
-    const f3 ray_origin = projection == 2 ? origin : F3(cam.origin);
+    f3 ray_origin, dir;
     HitRecord hit;
-    TraceStats st = {};
-    int overflow = 0;
-    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, min_ray_dist, __builtin_huge_valf(), 0u, s_stack + threadIdx.x, hit, st, overflow);
+    int overflow;
+    first_hit<TWO_LEVEL>(sv, L, cam, projection, px, py, min_ray_dist, s_stack + threadIdx.x, ray_origin, dir, hit, overflow);
     if (overflow) *overflow_flag = 1;
     f3 p = ray_origin, n = -dir;
     int id = -1;
     if (hit.instance_id >= 0) {
         SurfacePoint v;
         SampledMaterial mat;
-        shade_surface(sv, hit.instance_id, hit.primitive_id, hit.u, hit.v, dir, ray_origin, false, 0, false, v, mat);
+        first_hit_surface(sv, hit, dir, ray_origin, v, mat);
         p = v.pos; n = v.mapped_normal; id = hit.instance_id;
     }
     const size_t pix = ((size_t)layer * L.launch_h + (uint)py) * L.launch_w + (uint)px;
@@ -237,8 +224,6 @@ __global__ __launch_bounds__(KB) void k_temporal_reprojection(TemporalParams P) 
     P.record[pix] = rec;
 }
 
-dim3 tile_grid(uint w, uint h, uint layers) { return dim3((w + REPROJ_TILE - 1) / REPROJ_TILE, (h + REPROJ_TILE - 1) / REPROJ_TILE, layers); }
-
 int check_size(const char* who, uint32_t w, uint32_t h, uint32_t layers) {
     if (w == 0 || h == 0 || layers == 0) return set_error(std::string(who) + ": zero width, height or layer count");
     if (w > 16384 || h > 16384 || layers > 4096) return set_error(std::string(who) + ": image too large");      // the record's tap origin is int16
@@ -284,21 +269,16 @@ int trhip_gbuffer_render(trhip_device* dev, int projection, const uint32_t* view
     DEVCHK(device_index(dev));
     DeviceScene* scene = device_scene(dev);
     if (!scene->accel_built) return set_error("trhip_gbuffer_render: call trhip_scene_build_accel first");
-    for (uint32_t i = 0; i < count; ++i)
-        if (viewports[i] >= scene->camera_count) return set_error("trhip_gbuffer_render: viewport " + std::to_string(viewports[i]) + " out of range");
-    LaunchCtx L{};      // a duplicate distribution of the whole image: what trhip_feature_render launches for it
-    L.size_x = width; L.size_y = height; L.strategy = 0; L.index = 0; L.count = 1; L.primary = 1; L.launch_w = width; L.launch_h = height;
+    if (int r = check_viewport_list("trhip_gbuffer_render", viewports, count, 0, scene->camera_count)) return r;
+    const LaunchCtx L = whole_image_launch(width, height);
     const size_t layer_px = (size_t)width * height;
-    for (uint32_t first = 0; first < count; first += GBUFFER_CHUNK) {
-        const uint32_t n = std::min<uint32_t>(GBUFFER_CHUNK, count - first);
-        ViewportList list{};
-        for (uint32_t i = 0; i < n; ++i) list.v[i] = viewports[first + i];
+    for_each_viewport_chunk<ViewportList>(viewports, count, [&](uint32_t first, uint32_t n, const ViewportList& list) {
         f2* normal = targets->normal ? (f2*)targets->normal + first * layer_px : nullptr;
         f4* pos = targets->pos ? (f4*)targets->pos + first * layer_px : nullptr;
         int* ids = targets->instance_id ? (int*)targets->instance_id + first * layer_px : nullptr;
         hipLaunchKernelGGL(scene->two_level ? k_gbuffer<true> : k_gbuffer<false>, tile_grid(width, height, n), dim3(KB), 0, (hipStream_t)stream, scene->view(), L,
                            projection, list, min_ray_dist, normal, pos, ids, device_overflow_flag(dev));
-    }
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }

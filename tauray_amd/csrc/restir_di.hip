@@ -1,13 +1,13 @@
 // ReSTIR DI for gfx950 - reservoir resampling of direct light, written after the reference's shader/restir_di.glsl,
 // shader/restir_di_canonical_and_temporal.rgen and shader/restir_di_spatial.rgen, behind the entry points trhip_restir_di_* of include/trhip.h.
-//   k_restir_di_canonical  per pixel of every viewport: the first hit as k_gbuffer (reprojection.hip) finds and shades it, the surface
+//   k_restir_di_canonical  per pixel of every viewport: the first hit and its surface (first_hit.h), the surface
 //                          record, RIS over `candidates` light samples (a shadow ray in every target function), the temporal merge of
 //                          the reprojected pixel's history reservoir
 //   k_restir_di_spatial    per pixel: the neighbour search, the pairwise-MIS merge of the neighbours' canonical reservoirs (two shadow rays
 //                          a neighbour), the chosen sample's shading (one more), the history reservoir and the colour
 // Constants, layouts, the order of operations and the order of random draws: restir_di.h.  Both kernels are IEEE fp32, evaluated without
-// contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  Built with the flags of api.hip, so that the
-// front half computes what k_gbuffer and k_feature compute.
+// contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  The front half is first_hit.h's, the one
+// k_gbuffer and k_feature call.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "restir_di.h"
-#include "reprojection.h"
+#include "first_hit.h"
 #include "stage_host.h"
 #include "pt.h"
 #include "trace.h"
@@ -24,10 +24,6 @@ namespace tr {
 namespace {
 
 constexpr int KB = TR_BLOCK;
-constexpr int RESTIR_CHUNK = 64;       // viewports of one launch (the list travels in the kernel arguments), as k_gbuffer
-static_assert(REPROJ_TILE * REPROJ_TILE == KB, "a workgroup is one tile");
-
-struct RestirViewports { uint v[RESTIR_CHUNK]; };
 
 struct RestirParams {
     int candidates;
@@ -47,12 +43,6 @@ struct RestirParams {
 };
 
 #define TR_U(x) __float_as_uint(x)
-
-TR_DEV void tile_pixel(int& x, int& y) {
-    const uint t = threadIdx.x, wave = t >> 6, k = t & 63u;
-    x = (int)(blockIdx.x * REPROJ_TILE + ((wave & 1u) << 3) + (k & 7u));
-    y = (int)(blockIdx.y * REPROJ_TILE + ((wave >> 1) << 3) + (k >> 3));
-}
 
 // sample_canonical (restir_di.glsl:251-354): select, fetch, compute, as sample_explicit_light.  The record stays in L for the contribution.
 TR_DEV RestirSample sample_canonical(const SceneView& sv, const RestirParams& P, u4 rnd, f3 pos, RestirLightRecord& L, float& light_pdf) {
@@ -129,10 +119,10 @@ TR_DEV float shadow_of(const SceneView& sv, const RestirParams& P, f3 pos, f3 co
     return visibility;
 }
 
-// A workgroup is a 16 x 16 tile of layer blockIdx.z, a wave an 8 x 8 quarter of it (k_gbuffer's launch shape).
+// tile_pixel's launch shape (first_hit.h).
 // Two waves per SIMD: unbounded, the fp64 functions of RoundedMath took it to 256 VGPRs plus AGPR copies at one wave.
 template <bool TWO_LEVEL, bool TEMPORAL>
-__global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, LaunchCtx L, int projection, RestirViewports list, RestirParams P, uint* overflow_flag) {
+__global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, LaunchCtx L, int projection, ViewportList list, RestirParams P, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
     int* const s_stack = s_stack_rows + TR_STACK_ROW0;
     int px, py;
@@ -140,13 +130,10 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, Lau
     if ((uint)px >= L.launch_w || (uint)py >= L.launch_h) return;
     const uint layer = blockIdx.z, viewport = list.v[layer];
     const CameraData cam = sv.cameras[viewport];
-    f3 origin, dir;
-    get_screen_camera_ray(L, px, py, cam, projection, false, F2(0), F2(0.5f), origin, dir);
-    const f3 ray_origin = projection == 2 ? origin : F3(cam.origin);
+    f3 ray_origin, dir;
     HitRecord hit;
-    TraceStats st = {};
-    int overflow = 0;
-    trace_closest4<1, false, TWO_LEVEL>(sv, ray_origin, dir, P.min_ray_dist, __builtin_huge_valf(), 0u, s_stack + threadIdx.x, hit, st, overflow);
+    int overflow;
+    first_hit<TWO_LEVEL>(sv, L, cam, projection, px, py, P.min_ray_dist, s_stack + threadIdx.x, ray_origin, dir, hit, overflow);
     const size_t layer_px = (size_t)L.launch_w * L.launch_h;
     const size_t pix = layer * layer_px + (size_t)py * L.launch_w + (uint)px;
     RestirDomain dom = {};
@@ -154,7 +141,7 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, Lau
     RestirTemporalRecord trec = {-1, -1, 0u, 0.0f, 0.0f, 0.0f, 0.0f, 0u};
     if (hit.instance_id >= 0) {
         SurfacePoint v;
-        shade_surface(sv, hit.instance_id, hit.primitive_id, hit.u, hit.v, dir, ray_origin, false, 0, false, v, dom.mat);
+        first_hit_surface(sv, hit, dir, ray_origin, v, dom.mat);
         dom.pos = v.pos; dom.mapped_normal = v.mapped_normal; dom.flat_normal = v.hard_normal;
         dom.view = normalize(v.pos - ray_origin);
         LocalSampler ls = init_local_sampler(u4{(uint)px, (uint)py, viewport, 0u}, 2u * P.frame, P.rng_seed, SAMPLER_UNIFORM);
@@ -257,7 +244,7 @@ TR_DEV void get_slot(const int (&sx)[N], const int (&sy)[N], int k, int& x, int&
 }
 
 template <bool TWO_LEVEL, int SPATIAL>
-__global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, LaunchCtx L, int projection, RestirViewports list, RestirParams P, uint* overflow_flag) {
+__global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, LaunchCtx L, int projection, ViewportList list, RestirParams P, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
     int* const s_stack = s_stack_rows + TR_STACK_ROW0;
     int px, py;
@@ -423,14 +410,16 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, Launc
     }
 }
 
-template <bool TWO_LEVEL, class... Args>
-void launch_spatial(int spatial, dim3 grid, hipStream_t st, Args... args) {
+using RestirKernel = void (*)(SceneView, LaunchCtx, int, ViewportList, RestirParams, uint*);
+
+template <bool TWO_LEVEL>
+RestirKernel spatial_kernel(uint32_t spatial) {
     switch (spatial) {
-        case 0: hipLaunchKernelGGL((k_restir_di_spatial<TWO_LEVEL, 0>), grid, dim3(KB), 0, st, args...); break;
-        case 1: hipLaunchKernelGGL((k_restir_di_spatial<TWO_LEVEL, 1>), grid, dim3(KB), 0, st, args...); break;
-        case 2: hipLaunchKernelGGL((k_restir_di_spatial<TWO_LEVEL, 2>), grid, dim3(KB), 0, st, args...); break;
-        case 3: hipLaunchKernelGGL((k_restir_di_spatial<TWO_LEVEL, 3>), grid, dim3(KB), 0, st, args...); break;
-        default: hipLaunchKernelGGL((k_restir_di_spatial<TWO_LEVEL, 4>), grid, dim3(KB), 0, st, args...); break;
+        case 0: return k_restir_di_spatial<TWO_LEVEL, 0>;
+        case 1: return k_restir_di_spatial<TWO_LEVEL, 1>;
+        case 2: return k_restir_di_spatial<TWO_LEVEL, 2>;
+        case 3: return k_restir_di_spatial<TWO_LEVEL, 3>;
+        default: return k_restir_di_spatial<TWO_LEVEL, 4>;
     }
 }
 
@@ -506,18 +495,14 @@ int trhip_restir_di_reset(trhip_restir_di* s) {
 int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
     if (!s) return set_error("trhip_restir_di_render: null stage");
     if (!viewports || !out_color_dev) return set_error("trhip_restir_di_render: null argument");
-    if (count == 0 || count > s->layers) return set_error("trhip_restir_di_render: " + std::to_string(count) + " viewports, the stage has " + std::to_string(s->layers) + " layers");
     DEVCHK(s->hip_device);
     DeviceScene* scene = device_scene(s->dev);
-    if (scene->instance_count == 0) return set_error("trhip_restir_di_render: no scene (trhip_scene_upload)");
-    if (!scene->accel_built) return set_error("trhip_restir_di_render: no acceleration structure: call trhip_scene_build_accel first");
-    for (uint32_t i = 0; i < count; ++i)
-        if (viewports[i] >= scene->camera_count) return set_error("trhip_restir_di_render: viewport " + std::to_string(viewports[i]) + " out of range");
+    if (int r = check_scene_ready("trhip_restir_di_render", scene->instance_count, scene->accel_built)) return r;
+    if (int r = check_viewport_list("trhip_restir_di_render", viewports, count, s->layers, scene->camera_count)) return r;
     // History and the previous surface records are kept per layer, the position in the list: another list would merge another viewport's
     if (s->opt.temporal_reuse && s->frame > 0 && !std::equal(viewports, viewports + count, s->viewports.begin(), s->viewports.end()))
         return set_error("trhip_restir_di_render: the viewport list differs from the last frame's, whose history it would reuse: call trhip_restir_di_reset first");
-    LaunchCtx L{};      // a duplicate distribution of the whole image, as trhip_gbuffer_render
-    L.size_x = s->w; L.size_y = s->h; L.strategy = 0; L.index = 0; L.count = 1; L.primary = 1; L.launch_w = s->w; L.launch_h = s->h;
+    const LaunchCtx L = whole_image_launch(s->w, s->h);
     const size_t layer_px = (size_t)s->w * s->h;
     hipStream_t st = (hipStream_t)stream;
     RestirParams base{};
@@ -528,15 +513,15 @@ int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* v
     base.frame = s->frame;
     base.has_history = s->frame > 0;
     const bool temporal = s->opt.temporal_reuse != 0;
+    const RestirKernel kernels[2] = {
+        scene->two_level ? (temporal ? k_restir_di_canonical<true, true> : k_restir_di_canonical<true, false>)
+                         : (temporal ? k_restir_di_canonical<false, true> : k_restir_di_canonical<false, false>),
+        scene->two_level ? spatial_kernel<true>(s->opt.spatial_samples) : spatial_kernel<false>(s->opt.spatial_samples)};
     const int cur = (int)(s->frame & 1u);
-    uint* flag = device_overflow_flag(s->dev);
     // The canonical kernels of every chunk first, then the spatial ones: a chunk's spatial launch reads only its own layers
     HIPCHK(hipEventRecord(s->ev[0], st));
     for (int pass = 0; pass < 2; ++pass) {
-        for (uint32_t first = 0; first < count; first += RESTIR_CHUNK) {
-            const uint32_t n = std::min<uint32_t>(RESTIR_CHUNK, count - first);
-            RestirViewports list{};
-            for (uint32_t i = 0; i < n; ++i) list.v[i] = viewports[first + i];
+        for_each_viewport_chunk<ViewportList>(viewports, count, [&](uint32_t first, uint32_t n, const ViewportList& list) {
             RestirParams P = base;
             const size_t off = first * layer_px;
             P.surface = s->surface[cur] + off; P.prev_surface = s->surface[cur ^ 1] + off;
@@ -546,20 +531,8 @@ int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* v
             P.rec_temporal = s->rec_temporal ? s->rec_temporal + off : nullptr;
             P.rec_spatial = s->rec_spatial ? s->rec_spatial + off * s->opt.spatial_samples : nullptr;
             P.rec_final = s->rec_final ? s->rec_final + off : nullptr;
-            const dim3 grid((s->w + REPROJ_TILE - 1) / REPROJ_TILE, (s->h + REPROJ_TILE - 1) / REPROJ_TILE, n);
-            if (pass == 0) {
-                if (scene->two_level) {
-                    if (temporal) hipLaunchKernelGGL((k_restir_di_canonical<true, true>), grid, dim3(KB), 0, st, scene->view(), L, projection, list, P, flag);
-                    else hipLaunchKernelGGL((k_restir_di_canonical<true, false>), grid, dim3(KB), 0, st, scene->view(), L, projection, list, P, flag);
-                } else {
-                    if (temporal) hipLaunchKernelGGL((k_restir_di_canonical<false, true>), grid, dim3(KB), 0, st, scene->view(), L, projection, list, P, flag);
-                    else hipLaunchKernelGGL((k_restir_di_canonical<false, false>), grid, dim3(KB), 0, st, scene->view(), L, projection, list, P, flag);
-                }
-            } else {
-                if (scene->two_level) launch_spatial<true>((int)s->opt.spatial_samples, grid, st, scene->view(), L, projection, list, P, flag);
-                else launch_spatial<false>((int)s->opt.spatial_samples, grid, st, scene->view(), L, projection, list, P, flag);
-            }
-        }
+            hipLaunchKernelGGL(kernels[pass], tile_grid(s->w, s->h, n), dim3(KB), 0, st, scene->view(), L, projection, list, P, device_overflow_flag(s->dev));
+        });
         HIPCHK(hipEventRecord(s->ev[pass + 1], st));
     }
     HIPCHK(hipGetLastError());

@@ -295,8 +295,7 @@ int trhip_sh_render(trhip_sh* s, void* stream) {
     if (!s) return set_error("trhip_sh_render: null stage");
     DEVCHK(s->hip_device);
     DeviceScene* scene = device_scene(s->dev);
-    if (scene->instance_count == 0) return set_error("trhip_sh_render: no scene (trhip_scene_upload)");
-    if (!scene->accel_built) return set_error("trhip_sh_render: no acceleration structure: call trhip_scene_build_accel first");
+    if (int r = check_scene_ready("trhip_sh_render", scene->instance_count, scene->accel_built)) return r;
     hipStream_t st = (hipStream_t)stream;
     s->last_stream = st;
     const uint32_t n = s->opt.samples_per_probe;

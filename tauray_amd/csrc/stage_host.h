@@ -1,7 +1,8 @@
 // The host skeleton of the post-processing stage objects (bmfr.hip, reprojection.hip, taa.hip, looking_glass.hip): what every stage owns
 // (its HIP device, its events, its frame counter, its device allocations) and the tails every entry point shares (finishing create,
 // destroy, the total time, a size-checked download).  Host only: nothing here is seen by a kernel.  A stage struct derives from StageHost
-// and keeps its own fields; argument validation, parameter packing and kernel launches stay in the stage's file.
+// and keeps its own fields; argument validation, parameter packing and kernel launches stay in the stage's file.  The entry points that
+// render a list of viewports (gbuffer, dshgi, restir_di) share the checks and the chunk walk at the end of the file.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -99,6 +100,39 @@ int stage_download(const char* fn, Stage* s, void* host, size_t bytes, Find find
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(host, src, size, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The host side of a viewport frame: what the entry points that trace the first hit of every pixel of a list of viewports share
+// (trhip_gbuffer_render, trhip_dshgi_render, trhip_restir_di_render; the kernels' side is first_hit.h).  The checks take plain numbers.
+
+// `layers`: what the stage's images hold, 0 = no bound.  trhip_gbuffer_render refuses a null list in words of its own before it asks.
+inline int check_viewport_list(const char* fn, const uint32_t* viewports, uint32_t count, uint32_t layers, uint32_t camera_count) {
+    if (!viewports) return set_error(std::string(fn) + ": null argument");
+    if (layers && (count == 0 || count > layers))
+        return set_error(std::string(fn) + ": " + std::to_string(count) + " viewports, the stage has " + std::to_string(layers) + " layers");
+    for (uint32_t i = 0; i < count; ++i)
+        if (viewports[i] >= camera_count) return set_error(std::string(fn) + ": viewport " + std::to_string(viewports[i]) + " out of range");
+    return 0;
+}
+
+inline int check_scene_ready(const char* fn, size_t instance_count, bool accel_built) {
+    if (instance_count == 0) return set_error(std::string(fn) + ": no scene (trhip_scene_upload)");
+    if (!accel_built) return set_error(std::string(fn) + ": no acceleration structure: call trhip_scene_build_accel first");
+    return 0;
+}
+
+// body(first, n, list) for every chunk of the list: List is what one launch takes in its arguments (ViewportList of first_hit.h),
+// list.v[0 .. n) = viewports[first .. first + n).
+template <class List, class Body>
+void for_each_viewport_chunk(const uint32_t* viewports, uint32_t count, Body body) {
+    constexpr uint32_t chunk = sizeof(List::v) / sizeof(List::v[0]);
+    for (uint32_t first = 0; first < count; first += chunk) {
+        const uint32_t n = count - first < chunk ? count - first : chunk;
+        List list{};
+        for (uint32_t i = 0; i < n; ++i) list.v[i] = viewports[first + i];
+        body(first, n, list);
+    }
 }
 
 }  // namespace tr

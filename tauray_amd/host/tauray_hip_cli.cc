@@ -430,6 +430,49 @@ int main(int argc, char** argv)
         opt.samples_per_pass = std::min(opt.samples_per_pass, opt.samples_per_pixel);
         opt.active_viewport_count = viewports;
 
+        // the bake's options (sh-probes, dshgi): the path tracer's, with the probes' sample count and history ratio
+        auto sh_options = [&]
+        {
+            sh_renderer::options so;
+            so.max_ray_depth = opt.max_ray_depth; so.min_ray_dist = opt.min_ray_dist; so.rng_seed = opt.rng_seed; so.local_sampler = opt.local_sampler;
+            so.samples_per_probe = samples_per_probe; so.film = opt.film; so.film_radius = opt.film_radius; so.mis_mode = opt.mis_mode;
+            so.russian_roulette_delta = opt.russian_roulette_delta; so.temporal_ratio = dshgi_temporal_ratio; so.indirect_clamping = opt.indirect_clamping;
+            so.regularization_gamma = opt.regularization_gamma; so.sampling_weights = opt.sampling_weights;
+            so.bounce_mode = opt.bounce_mode; so.tri_light_mode = opt.tri_light_mode;
+            return so;
+        };
+        // The frames of a renderer of whole viewports on one device (dshgi, restir-di): make(dev, ss) builds it on the uploaded scene,
+        // scene_moved(r) runs after an animation step has been applied, print_timings(r) prints the lines of a frame under "DEVICE 0".
+        auto run_viewport_frames = [&](auto make, auto scene_moved, auto print_timings)
+        {
+            hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
+            headless out(hopt);
+            device dev(devices[0]);
+            scene_stage ss(dev, opt.scene);
+            ss.set_scene(scene);
+            auto r = make(dev, ss);
+            for(int f = -warmup; f < frames; ++f)
+            {
+                if(animated && f >= 0)
+                {   // update(s, dt, true) before the frame, the first one by dt = 0 (src/tauray.cc:1064-1092)
+                    if(!frames_given && !animator.is_playing()) break;
+                    animator.update(f == 0 ? 0 : update_dt);
+                    if(!frames_given && !animator.is_playing()) break;
+                    dev.sync();
+                    ss.apply(scene, f % 3 == 2);
+                    scene_moved(*r);
+                }
+                r->render();
+                dev.sync();
+                if(f < 0) continue;
+                if(timing)
+                {
+                    std::cout << "FRAME " << f << ":\n\tDEVICE 0:\n";
+                    print_timings(*r);
+                }
+                out.save(dev, r->display, (unsigned)f);
+            }
+        };
         if(renderer == "sh-probes")
         {   // sh_renderer (src/tauray.cc:423-433, src/sh_renderer.cc): bakes the scene's probe grids, one sh_path_tracer_stage per grid
             if(opt.bmfr || opt.taa || !opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)
@@ -442,12 +485,7 @@ int main(int argc, char** argv)
             if(scene.sh_grids.empty())
                 throw std::runtime_error("--renderer=sh-probes: " + scene_path + " has no light-probe grid (a node with TR_data.light_probe of type GRID)");
             for(sh_grid& g: scene.sh_grids) g.order = sh_order;      // src/tauray.cc:151
-            sh_renderer::options so;
-            so.max_ray_depth = opt.max_ray_depth; so.min_ray_dist = opt.min_ray_dist; so.rng_seed = opt.rng_seed; so.local_sampler = opt.local_sampler;
-            so.samples_per_probe = samples_per_probe; so.film = opt.film; so.film_radius = opt.film_radius; so.mis_mode = opt.mis_mode;
-            so.russian_roulette_delta = opt.russian_roulette_delta; so.temporal_ratio = dshgi_temporal_ratio; so.indirect_clamping = opt.indirect_clamping;
-            so.regularization_gamma = opt.regularization_gamma; so.sampling_weights = opt.sampling_weights;
-            so.bounce_mode = opt.bounce_mode; so.tri_light_mode = opt.tri_light_mode;
+            const sh_renderer::options so = sh_options();
             device dev(devices[0]);
             scene_stage ss(dev, opt.scene);
             ss.set_scene(scene);
@@ -487,11 +525,7 @@ int main(int argc, char** argv)
             for(sh_grid& g: scene.sh_grids) g.order = sh_order;      // src/tauray.cc:151
             dshgi_renderer::options go;
             go.direct = opt;
-            go.sh.max_ray_depth = opt.max_ray_depth; go.sh.min_ray_dist = opt.min_ray_dist; go.sh.rng_seed = opt.rng_seed; go.sh.local_sampler = opt.local_sampler;
-            go.sh.samples_per_probe = samples_per_probe; go.sh.film = opt.film; go.sh.film_radius = opt.film_radius; go.sh.mis_mode = opt.mis_mode;
-            go.sh.russian_roulette_delta = opt.russian_roulette_delta; go.sh.temporal_ratio = dshgi_temporal_ratio; go.sh.indirect_clamping = opt.indirect_clamping;
-            go.sh.regularization_gamma = opt.regularization_gamma; go.sh.sampling_weights = opt.sampling_weights;
-            go.sh.bounce_mode = opt.bounce_mode; go.sh.tri_light_mode = opt.tri_light_mode;
+            go.sh = sh_options();
             go.use_probe_visibility = use_probe_visibility;
             go.tonemap = opt.tonemap;
             if(!brdf_integration_path.empty())
@@ -502,36 +536,15 @@ int main(int argc, char** argv)
                 go.brdf_integration.resize(size_t(go.brdf_integration_width) * go.brdf_integration_height * 2);
                 for(size_t i = 0; i < go.brdf_integration.size() / 2; ++i) { go.brdf_integration[2 * i] = f[i * (size_t)channels]; go.brdf_integration[2 * i + 1] = f[i * (size_t)channels + 1]; }
             }
-            hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
-            headless out(hopt);
-            device dev(devices[0]);
-            scene_stage ss(dev, opt.scene);
-            ss.set_scene(scene);
-            dshgi_renderer gr(dev, ss, scene, size, go);
-            for(int f = -warmup; f < frames; ++f)
+            run_viewport_frames([&](device& dev, scene_stage& ss) { return std::make_unique<dshgi_renderer>(dev, ss, scene, size, go); },
+                                [&](dshgi_renderer& gr) { gr.set_scene(scene); },      // the instances pick their grids again
+                                [&](dshgi_renderer& gr)
             {
-                if(animated && f >= 0)
-                {   // update(s, dt, true) before the frame, the first one by dt = 0 (src/tauray.cc:1064-1092); the instances pick their grids again
-                    if(!frames_given && !animator.is_playing()) break;
-                    animator.update(f == 0 ? 0 : update_dt);
-                    if(!frames_given && !animator.is_playing()) break;
-                    dev.sync();
-                    ss.apply(scene, f % 3 == 2);
-                    gr.set_scene(scene);
-                }
-                gr.render();
-                dev.sync();
-                if(f < 0) continue;
-                if(timing)
-                {
-                    std::cout << "FRAME " << f << ":\n\tDEVICE 0:\n";
-                    for(auto& st: gr.sh.stages) { const trhip_sh_timings t = st->get_timings(); std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n"; }
-                    std::cout << "\t\t[direct (" << viewports << " viewports)] " << gr.direct->get_duration_ms() << " ms\n";
-                    const trhip_dshgi_timings t = gr.indirect->get_timings();
-                    std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n";
-                }
-                out.save(dev, gr.display, (unsigned)f);
-            }
+                for(auto& st: gr.sh.stages) { const trhip_sh_timings t = st->get_timings(); std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n"; }
+                std::cout << "\t\t[direct (" << viewports << " viewports)] " << gr.direct->get_duration_ms() << " ms\n";
+                const trhip_dshgi_timings t = gr.indirect->get_timings();
+                std::cout << "\t\t[" << t.name << "] " << t.total_ms << " ms\n";
+            });
             return 0;
         }
         if(renderer == "restir-di")
@@ -541,33 +554,13 @@ int main(int argc, char** argv)
             ro.restir.min_ray_dist = opt.min_ray_dist; ro.restir.rng_seed = (uint32_t)opt.rng_seed; ro.restir.projection = opt.projection;
             ro.tonemap = opt.tonemap;
             ro.restir.check();
-            hopt.size = size; hopt.output_prefix = prefix; hopt.display_count = viewports;
-            headless out(hopt);
-            device dev(devices[0]);
-            scene_stage ss(dev, opt.scene);
-            ss.set_scene(scene);
-            restir_di_renderer rr(dev, scene, size, ro);
-            for(int f = -warmup; f < frames; ++f)
+            run_viewport_frames([&](device& dev, scene_stage&) { return std::make_unique<restir_di_renderer>(dev, scene, size, ro); },
+                                [](restir_di_renderer&) {},
+                                [](restir_di_renderer& rr)
             {
-                if(animated && f >= 0)
-                {   // update(s, dt, true) before the frame, the first one by dt = 0 (src/tauray.cc:1064-1092)
-                    if(!frames_given && !animator.is_playing()) break;
-                    animator.update(f == 0 ? 0 : update_dt);
-                    if(!frames_given && !animator.is_playing()) break;
-                    dev.sync();
-                    ss.apply(scene, f % 3 == 2);
-                }
-                rr.render();
-                dev.sync();
-                if(f < 0) continue;
-                if(timing)
-                {
-                    const trhip_restir_di_timings t = rr.stage->get_timings();
-                    std::cout << "FRAME " << f << ":\n\tDEVICE 0:\n";
-                    std::cout << "\t\t[" << t.canonical_name << "] " << t.canonical_ms << " ms\n\t\t[" << t.spatial_name << "] " << t.spatial_ms << " ms\n";
-                }
-                out.save(dev, rr.display, (unsigned)f);
-            }
+                const trhip_restir_di_timings t = rr.stage->get_timings();
+                std::cout << "\t\t[" << t.canonical_name << "] " << t.canonical_ms << " ms\n\t\t[" << t.spatial_name << "] " << t.spatial_ms << " ms\n";
+            });
             return 0;
         }
         opt.max_frames_in_flight = frames_in_flight;

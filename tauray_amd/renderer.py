@@ -1188,7 +1188,32 @@ class DshgiStage(_PostStage):
         raise KeyError(name)
 
 
-class DshgiRenderer:
+class _ViewportFrameRenderer:
+    """What the single-device renderers of whole viewports share (DshgiRenderer, RestirDiRenderer): `size`, `viewports` (one per camera), the
+    `color` and `display` images of every viewport, the tonemap stage and the tail of a frame that runs it - all on one stream."""
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, tonemap: Optional[TonemapStage]):
+        self.ctx, self.ss, self.size = ctx, scene_stage, tuple(size)
+        self.viewports = max(len(scene.cameras), 1)
+        self.tonemap = tonemap or TonemapStage(ctx)
+        pixels = self.size[0] * self.size[1] * self.viewports
+        self.color, self.display = ctx.alloc(pixels * 16).zero(), ctx.alloc(pixels * 16).zero()
+
+    def _finish(self, stream, tonemap):
+        if tonemap:
+            self.tonemap.run(self.color, self.display, self.size[0], self.size[1], self.viewports, stream)
+
+    def download(self, which="color") -> np.ndarray:
+        self.ctx.sync()
+        buf = self.color if which == "color" else self.display
+        return buf.download((self.viewports, self.size[1], self.size[0], 4))
+
+    def close(self):
+        for b in (self.color, self.display):
+            b.free()
+
+
+class DshgiRenderer(_ViewportFrameRenderer):
     """dshgi_renderer (src/dshgi_renderer.{hh,cc}): per frame the scene's probe grids are baked (ShRenderer), the direct stage renders every
     viewport, the indirect light of the grids is added (DshgiStage), the frame is tonemapped - all on one stream.  The first bake has
     history 1, so the grids are complete before they are read.  `options`: the direct stage's PtOptionsC; `sh`: sh_options() of the bake;
@@ -1201,9 +1226,8 @@ class DshgiRenderer:
                  use_probe_visibility=False, brdf_integration=None, tonemap: Optional[TonemapStage] = None, record_surface=False):
         if not scene.sh_grids:
             raise ValueError("DshgiRenderer: the scene has no light-probe grid (TR_data.light_probe of type GRID)")
-        self.ctx, self.ss, self.size = ctx, scene_stage, tuple(size)
+        super().__init__(ctx, scene_stage, scene, size, tonemap)
         self.grids = list(scene.sh_grids)
-        self.viewports = max(len(scene.cameras), 1)
         self.sh = ShRenderer(ctx, scene_stage, self.grids, sh)
         order = self.sh.stages[0].order
         self.direct = DirectStage(ctx, scene_stage, copy_options(options, nee_triangles=0.0, nee_envmap=0.0),
@@ -1221,9 +1245,6 @@ class DshgiRenderer:
             table = ctx.alloc(host.nbytes).upload(host)
         self.indirect.set_brdf_integration(table, w, h)
         table.free()
-        self.tonemap = tonemap or TonemapStage(ctx)
-        pixels = self.size[0] * self.size[1] * self.viewports
-        self.color, self.display = ctx.alloc(pixels * 16).zero(), ctx.alloc(pixels * 16).zero()
         self.set_scene(scene)
 
     def set_scene(self, scene: SceneDesc):
@@ -1236,23 +1257,16 @@ class DshgiRenderer:
         self.direct.reset_accumulated_samples()
         self.direct.run(self.color, self.viewports, stream)
         self.indirect.run(np.arange(self.viewports), self.color, self.color, stream)
-        if tonemap:
-            self.tonemap.run(self.color, self.display, self.size[0], self.size[1], self.viewports, stream)
+        self._finish(stream, tonemap)
 
     def timings(self) -> dict:
         return {"bake": [st.timings() for st in self.sh.stages], "direct": self.direct.timings(), "indirect": self.indirect.timings()}
-
-    def download(self, which="color") -> np.ndarray:
-        self.ctx.sync()
-        buf = self.color if which == "color" else self.display
-        return buf.download((self.viewports, self.size[1], self.size[0], 4))
 
     def close(self):
         self.sh.close()
         self.direct.close()
         self.indirect.close()
-        for b in (self.color, self.display):
-            b.free()
+        super().close()
 
 
 def restir_di_options(**kw) -> dict:
@@ -1308,24 +1322,19 @@ class RestirDiStage(_PostStage):
         return self._download(code, shape, np.dtype(dtype))
 
 
-class RestirDiRenderer:
+class RestirDiRenderer(_ViewportFrameRenderer):
     """--renderer=restir-di: the ReSTIR DI stage renders every viewport, the frame is tonemapped - on one stream."""
 
     def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: Optional[dict] = None, projection=None,
                  tonemap: Optional[TonemapStage] = None):
-        self.ctx, self.ss, self.size = ctx, scene_stage, tuple(size)
-        self.viewports = max(len(scene.cameras), 1)
+        super().__init__(ctx, scene_stage, scene, size, tonemap)
         if projection is None:
             projection = scene.cameras[0].projection if scene.cameras else 0
         self.stage = RestirDiStage(ctx, scene_stage, self.size, self.viewports, options, projection)
-        self.tonemap = tonemap or TonemapStage(ctx)
-        pixels = self.size[0] * self.size[1] * self.viewports
-        self.color, self.display = ctx.alloc(pixels * 16).zero(), ctx.alloc(pixels * 16).zero()
 
     def render(self, stream=None, tonemap=True):
         self.stage.run(np.arange(self.viewports), self.color, stream)
-        if tonemap:
-            self.tonemap.run(self.color, self.display, self.size[0], self.size[1], self.viewports, stream)
+        self._finish(stream, tonemap)
 
     def reset(self):
         self.stage.reset()
@@ -1333,15 +1342,9 @@ class RestirDiRenderer:
     def timings(self) -> dict:
         return self.stage.timings()
 
-    def download(self, which="color") -> np.ndarray:
-        self.ctx.sync()
-        buf = self.color if which == "color" else self.display
-        return buf.download((self.viewports, self.size[1], self.size[0], 4))
-
     def close(self):
         self.stage.close()
-        for b in (self.color, self.display):
-            b.free()
+        super().close()
 
 
 @dataclass(frozen=True)

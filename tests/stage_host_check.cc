@@ -1,10 +1,13 @@
 // The host skeleton of the stage objects (tauray_amd/csrc/stage_host.h) on a machine without a device, for a run under the host sanitizers:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -o stage_host_check tests/stage_host_check.cc && ./stage_host_check
 // A derived stage is built and destroyed, create's failure tail releases it and reports "<fn>: <hip error>", a stage that has run no frame
-// gives zero timings without touching the device, and a download of the wrong size is refused with both sizes.  Prints "ok" and returns 0.
+// gives zero timings without touching the device, and a download of the wrong size is refused with both sizes.  The host side of a
+// viewport frame: the list check and the scene check say each of their refusals and accept what is valid, and a list is walked in chunks of
+// 64 with every entry in order.  Prints "ok" and returns 0.
 #include "../tauray_amd/csrc/stage_host.h"
 
 #include <cstdio>
+#include <utility>
 
 static std::string last_error;
 namespace tr {
@@ -16,11 +19,59 @@ DeviceScene* device_scene(trhip_device*) { return nullptr; }
 struct two_event_stage : tr::StageHost<> { float* image = nullptr; uint8_t* bytes = nullptr; };
 struct five_event_stage : tr::StageHost<5> { float* image[2] = {}; };
 struct timings { float total_ms; uint32_t frames; };
+struct list64 { uint32_t v[64]; };      // the shape of ViewportList (first_hit.h), which needs the device headers
+
+// The chunks of a list of `count` viewports 1000, 1001, ...; empty when an entry is out of place or a chunk's tail is not zero.
+static std::vector<std::pair<uint32_t, uint32_t>> chunks_of(uint32_t count)
+{
+    std::vector<uint32_t> viewports(count);
+    for(uint32_t i = 0; i < count; ++i) viewports[i] = 1000 + i;
+    std::vector<std::pair<uint32_t, uint32_t>> seen;
+    bool in_order = true;
+    tr::for_each_viewport_chunk<list64>(viewports.data(), count, [&](uint32_t first, uint32_t n, const list64& list) {
+        for(uint32_t i = 0; i < 64; ++i) in_order = in_order && list.v[i] == (i < n ? 1000 + first + i : 0);
+        seen.push_back({first, n});
+    });
+    if(!in_order) seen.clear();
+    return seen;
+}
 
 #define EXPECT(x) do { if(!(x)) { std::printf("stage_host_check: %s failed (line %d; last error: %s)\n", #x, __LINE__, last_error.c_str()); return 1; } } while(0)
 
 int main()
 {
+    // the viewport list of a frame: every refusal verbatim, the layer bound only where there is one, a valid list
+    {
+        const uint32_t list[3] = {0, 4, 2};
+        EXPECT(tr::check_viewport_list("check_render", nullptr, 3, 3, 5) == 1 && last_error == "check_render: null argument");
+        EXPECT(tr::check_viewport_list("check_render", list, 3, 2, 5) == 1 && last_error == "check_render: 3 viewports, the stage has 2 layers");
+        EXPECT(tr::check_viewport_list("check_render", list, 0, 2, 5) == 1 && last_error == "check_render: 0 viewports, the stage has 2 layers");
+        EXPECT(tr::check_viewport_list("check_render", list, 3, 3, 4) == 1 && last_error == "check_render: viewport 4 out of range");
+        EXPECT(tr::check_viewport_list("check_render", list, 3, 0, 4) == 1 && last_error == "check_render: viewport 4 out of range");
+        last_error.clear();
+        EXPECT(tr::check_viewport_list("check_render", list, 3, 3, 5) == 0 && tr::check_viewport_list("check_render", list, 3, 0, 5) == 0);
+        EXPECT(tr::check_viewport_list("check_render", list, 3, 64, 5) == 0 && tr::check_viewport_list("check_render", list, 0, 0, 5) == 0 && last_error.empty());
+    }
+    {
+        EXPECT(tr::check_scene_ready("check_render", 0, false) == 1 && last_error == "check_render: no scene (trhip_scene_upload)");
+        EXPECT(tr::check_scene_ready("check_render", 0, true) == 1 && last_error == "check_render: no scene (trhip_scene_upload)");
+        EXPECT(tr::check_scene_ready("check_render", 6, false) == 1 && last_error == "check_render: no acceleration structure: call trhip_scene_build_accel first");
+        last_error.clear();
+        EXPECT(tr::check_scene_ready("check_render", 6, true) == 0 && last_error.empty());
+    }
+    // a list in chunks of one launch
+    {
+        using seq = std::vector<std::pair<uint32_t, uint32_t>>;
+        EXPECT(chunks_of(0) == seq{});
+        EXPECT(chunks_of(1) == (seq{{0, 1}}));
+        EXPECT(chunks_of(63) == (seq{{0, 63}}));
+        EXPECT(chunks_of(64) == (seq{{0, 64}}));
+        EXPECT(chunks_of(65) == (seq{{0, 64}, {64, 1}}));
+        EXPECT(chunks_of(128) == (seq{{0, 64}, {64, 64}}));
+        EXPECT(chunks_of(129) == (seq{{0, 64}, {64, 64}, {128, 1}}));
+    }
+
+    // from here on: what happens without a device
     int devices = 0;
     if(hipGetDeviceCount(&devices) == hipSuccess && devices > 0) { std::printf("stage_host_check: this check is for a machine without a device\n"); return 2; }
 
@@ -71,6 +122,7 @@ int main()
         EXPECT(last_error == "check_download: unknown buffer");
         EXPECT(tr::stage_download("check_download", &s, host, 8, find) == 1 && last_error.rfind("hipSetDevice: ", 0) == 0);      // the right size: on to the device
     }
+
     std::printf("ok\n");
     return 0;
 }

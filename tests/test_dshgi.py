@@ -507,6 +507,37 @@ def test_surface_record_misses_and_composition(R, ctx):
 
 
 @pytest.mark.gpu
+def test_a_list_longer_than_one_launch(R, ctx):
+    """65 viewports are two launches, of 64 and of 1: layer 64 is layer 0 of a one-entry list of its viewport and layer 63 repeats layer 0,
+    bit for bit - colour, indirect term and surface record.  17 x 9 pixels leave the tile partial on both axes."""
+    rng = np.random.default_rng(17)
+    size, res, order = (17, 9), (2, 3, 5), 2
+    ss = _scene_stage(R, ctx, size)
+    half, table = _random_grid(rng, res, order), _random_table(rng)
+
+    def frame(views):
+        st = R.DshgiStage(ctx, ss, size, len(views), order, False, True)
+        image, tb = ctx.alloc(half.nbytes).upload(half), ctx.alloc(table.nbytes).upload(table)
+        st.set_grids([_grid_of(res)], [image])
+        st.set_instance_grids(np.zeros(len(ss.scene.instances), dtype=np.int32))
+        st.set_brdf_integration(tb, table.shape[1], table.shape[0])
+        out = ctx.alloc(size[0] * size[1] * len(views) * 16).zero()
+        st.run(views, None, out)
+        ctx.sync()
+        got = [out.download((len(views), size[1], size[0], 4)), st.download("indirect"), st.download("surface")]
+        st.close()
+        for b in (image, tb, out):
+            b.free()
+        return got
+
+    many, one = frame([0] * 64 + [1]), frame([1])
+    assert (many[2]["instance_id"][0] >= 0).any() and np.abs(many[1][0]).max() > 0
+    for a, b in zip(many, one):
+        assert a[64].tobytes() == b[0].tobytes() and a[63].tobytes() == a[0].tobytes()
+    assert many[1][64].tobytes() != many[1][0].tobytes(), "the two viewports see the same"
+
+
+@pytest.mark.gpu
 def test_same_bits_for_both_acceleration_structures(R, ctx):
     from tauray_amd import _lib
     rng = np.random.default_rng(9)

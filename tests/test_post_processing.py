@@ -120,3 +120,13 @@ def test_cpp_plan_is_the_same_plan(tmp_path):
         assert tuple(stages.split(",")) == py.stages and sorted(t for t in targets.split(",") if t != "-") == sorted(py.targets)
         assert (int(frame_order), int(fused), int(layers)) == (int(py.frame_order), int(py.fused_tonemap), py.output_layers)
     assert seen == set(ROWS)
+
+
+def test_stage_skeleton_under_the_host_sanitizers(tmp_path):
+    """tests/stage_host_check.cc: the stages' host skeleton and the host side of a viewport frame (stage_host.h), a stand-alone program built
+    with the address and undefined-behaviour sanitizers.  The skeleton half needs a machine without a device and says so where there is one; the viewport-frame half runs first, anywhere."""
+    exe = str(tmp_path / "stage_host_check")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
+                           "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "stage_host_check.cc")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert (r.returncode, r.stdout.strip()) in ((0, "ok"), (2, "stage_host_check: this check is for a machine without a device")), r.stdout + r.stderr

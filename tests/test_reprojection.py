@@ -472,6 +472,32 @@ def test_gbuffer_pass_is_the_feature_stage(R, ctx, scene_name, strategy):
     assert np.array_equal(_bits(t2["pos"].download((len(views), h, w, 4))), _bits(pos)) and not t2["normal"].download((len(views), h, w, 2)).any()
 
 
+@pytest.mark.gpu
+def test_gbuffer_pass_of_a_list_longer_than_one_launch(R, ctx):
+    """65 viewports are two launches, of 64 and of 1: layer 64 is layer 0 of a one-entry list of its viewport and layer 63 repeats layer 0,
+    bit for bit.  17 x 9 pixels leave the tile partial on both axes."""
+    size = (17, 9)
+    w, h = size
+    scene = _grid_scene(_glb("test.glb", size), 2, 1, 0.05)
+    ss = R.SceneStage(ctx, scene)
+    g = R.GbufferStage(ctx, ss, size, scene.cameras[0].projection)
+
+    def frame(views):
+        t = g.alloc_targets(len(views))
+        g.run(views, t)
+        ctx.sync()
+        got = [t["normal"].download((len(views), h, w, 2)), t["pos"].download((len(views), h, w, 4)), t["instance_id"].download((len(views), h, w), np.int32)]
+        for b in t.values():
+            b.free()
+        return got
+
+    many, one = frame([0] * 64 + [1]), frame([1])
+    assert (many[2][0] >= 0).any()
+    for a, b in zip(many, one):
+        assert a[64].tobytes() == b[0].tobytes() and a[63].tobytes() == a[0].tobytes()
+    assert many[1][64].tobytes() != many[1][0].tobytes(), "the two viewports see the same"
+
+
 # ---- 2. the path tracer on a viewport list
 @pytest.mark.gpu
 @pytest.mark.parametrize("sources", [[0, 4, 8], [0, 1, 5], [7, 2]])

@@ -949,6 +949,34 @@ def test_layouts_runs_reset_and_viewport_split_give_the_same_bits(R, ctx, rooms)
     rooms(size, as_strategy=0)
 
 
+@pytest.mark.gpu
+def test_a_list_longer_than_one_launch(R):
+    """65 viewports are two launches a pass, of 64 and of 1: layer 64 is layer 0 of a one-entry list of its viewport and layer 63 repeats
+    layer 0 (the sampler is seeded by the viewport, and without temporal reuse one frame has no history), bit for bit - colour, surface
+    record, canonical and history reservoirs.  17 x 9 pixels leave the tile partial on both axes."""
+    from tauray_amd import scene as S
+    size = (17, 9)
+    own = R.Context(0)      # the module's context holds the scene of `rooms`
+    ss = R.SceneStage(own, _room(S, size), as_strategy=0)
+
+    def frame(views):
+        st = R.RestirDiStage(own, ss, size, len(views), R.restir_di_options(candidates=4, spatial_samples=2, temporal_reuse=False, search_radius=4.0, rng_seed=3))
+        out = own.alloc(size[0] * size[1] * 16 * len(views)).zero()
+        st.run(views, out)
+        own.sync()
+        got = [out.download((len(views), size[1], size[0], 4))] + [st.download(n) for n in ("surface", "canonical", "history")]
+        out.free()
+        st.close()
+        return got
+
+    many, one = frame([0] * 64 + [1]), frame([1])
+    assert (many[1]["instance_id"][0] >= 0).any() and many[0][0][..., :3].max() > 0
+    for a, b in zip(many, one):
+        assert a[64].tobytes() == b[0].tobytes() and a[63].tobytes() == a[0].tobytes()
+    assert many[0][64].tobytes() != many[0][0].tobytes(), "the two viewports see the same"
+    own.close()
+
+
 EXPECTATION_CASES = {
     "1 candidate, no reuse": (dict(candidates=1, spatial_samples=0, temporal_reuse=False), 1, 64),
     "8 candidates, no reuse": (dict(candidates=8, spatial_samples=0, temporal_reuse=False), 1, 24),
