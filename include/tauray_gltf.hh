@@ -11,8 +11,10 @@
 // scale channels, LINEAR / STEP / CUBICSPLINE; src/gltf.cc:167-190,580-627) are kept in scene_data::animation and played by
 // tr::scene_animator below (src/animation.{hh,cc,tcc}, src/scene.cc:213-244).  Textures: PNG of any colour type, bit depth and
 // interlacing and baseline JPEG (include/tauray_image.hh), embedded or behind a relative / data: uri (src/gltf.cc:532-576); besides
-// .glb containers - the only form the reference opens - .gltf text files with their buffers.  Not read: morph targets,
-// progressive JPEG.  Same scope and same results as the Python mirror tauray_amd/gltf.py
+// .glb containers - the only form the reference opens - .gltf text files with their buffers.  Going past the reference, whose loader
+// skips them (src/gltf.cc:623): morph targets - the POSITION / NORMAL / TANGENT deltas of a primitive's `targets` (sparse accessors
+// included), default weights (node.weights, else mesh.weights, else zeros) in scene_data::morphed, and `weights` animation channels;
+// TEXCOORD_n / COLOR_n targets are not read (tauray_amd/csrc/morph.h).  Not read: progressive JPEG.  Same scope and same results as the Python mirror tauray_amd/gltf.py
 // (tests/test_cpp_host.py::test_cpp_glb_loader_matches_python_loader).
 #ifndef TAURAY_GLTF_HH
 #define TAURAY_GLTF_HH
@@ -444,24 +446,55 @@ struct glb_file
         throw std::runtime_error("glTF: image without bufferView or uri");
     }
 
-    // accessor as rows of doubles (exact for every component type glTF has)
+    // accessor as rows of doubles (exact for every component type glTF has): over its bufferView, with the `sparse` substitutions when it
+    // has them (over zeros without a bufferView)
     std::vector<double> accessor(int index, int& components, size_t& count) const
     {
         if(index < 0 || (size_t)index >= doc.at("accessors").size()) throw std::runtime_error("glTF: accessor index out of range");
         const json& a = doc.at("accessors").at((size_t)index);
-        const int view = a.integer("bufferView", -1);
-        if(view < 0 || (size_t)view >= doc.at("bufferViews").size()) throw std::runtime_error("glTF: bufferView index out of range");
-        const json& bv = doc.at("bufferViews").at((size_t)view);
-        const std::vector<uint8_t>& bin = buffer_of(bv);
+        const json* sparse = a.find("sparse");
         const int ct = a.integer("componentType", 0);
-        const std::string& type = a.at("type").str;
+        const json* type_json = a.find("type");
+        const std::string type = type_json ? type_json->str : std::string();
         components = type == "SCALAR" ? 1 : type == "VEC2" ? 2 : type == "VEC3" ? 3 : type == "VEC4" ? 4 : type == "MAT4" ? 16 : 0;
         const int sz = ct == 5120 || ct == 5121 ? 1 : ct == 5122 || ct == 5123 ? 2 : ct == 5125 || ct == 5126 ? 4 : 0;
         if(!components || !sz) throw std::runtime_error("glTF: unsupported accessor type");
+        const double d_count = a.number("count", 0);
+        std::vector<double> out;
+        if(!sparse || a.has("bufferView")) out = rows(a.integer("bufferView", -1), a.number("byteOffset", 0), ct, components, d_count, count);
+        else
+        {   // zeros are made up, not read: the file does not bound them
+            if(!(d_count >= 0 && d_count <= 16777216.0)) throw std::runtime_error("glTF: sparse accessor without a bufferView is too large");
+            count = (size_t)d_count;
+            out.assign(count * (size_t)components, 0.0);
+        }
+        if(!sparse) return out;
+        const json* ind = sparse->find("indices");
+        const json* val = sparse->find("values");
+        if(sparse->kind != json::OBJ || !ind || !val || ind->kind != json::OBJ || val->kind != json::OBJ) throw std::runtime_error("glTF: sparse accessor needs indices and values");
+        const double d_n = sparse->number("count", 0);
+        if(!(d_n >= 0 && d_n <= (double)count)) throw std::runtime_error("glTF: sparse count exceeds the accessor");
+        const int ict = ind->integer("componentType", 0);
+        if(ict != 5121 && ict != 5123 && ict != 5125) throw std::runtime_error("glTF: sparse indices must be unsigned integers");
+        size_t n = 0, nv = 0;
+        const std::vector<double> ii = rows(ind->integer("bufferView", -1), ind->number("byteOffset", 0), ict, 1, d_n, n);
+        const std::vector<double> vv = rows(val->integer("bufferView", -1), val->number("byteOffset", 0), ct, components, d_n, nv);
+        for(size_t k = 0; k < n; ++k) if(ii[k] >= (double)count) throw std::runtime_error("glTF: sparse index out of range");
+        for(size_t k = 0; k < n; ++k)      // in file order: a repeated index keeps its last value
+            for(int c = 0; c < components; ++c) out[(size_t)ii[k] * (size_t)components + (size_t)c] = vv[k * (size_t)components + (size_t)c];
+        return out;
+    }
+
+    // `d_count` rows of `components` values of component type `ct` at `d_ao` of a bufferView
+    std::vector<double> rows(int view, double d_ao, int ct, int components, double d_count, size_t& count) const
+    {
+        if(view < 0 || !doc.has("bufferViews") || (size_t)view >= doc.at("bufferViews").size()) throw std::runtime_error("glTF: bufferView index out of range");
+        const json& bv = doc.at("bufferViews").at((size_t)view);
+        const std::vector<uint8_t>& bin = buffer_of(bv);
+        const int sz = ct == 5120 || ct == 5121 ? 1 : ct == 5122 || ct == 5123 ? 2 : 4;
         // every number below comes from the file: checked as doubles before any of them becomes a size_t (a negative or huge double
         // cast to size_t is undefined), and the extent of the accessor is compared without a product that could wrap
-        const double d_count = a.number("count", 0), d_vo = bv.number("byteOffset", 0), d_ao = a.number("byteOffset", 0),
-                     d_len = bv.number("byteLength", 0), d_stride = bv.number("byteStride", 0);
+        const double d_vo = bv.number("byteOffset", 0), d_len = bv.number("byteLength", 0), d_stride = bv.number("byteStride", 0);
         const double lim = (double)bin.size();
         if(!(d_count >= 0 && d_vo >= 0 && d_ao >= 0 && d_len >= 0 && d_stride >= 0)) throw std::runtime_error("glTF: negative count, offset or stride");
         if(d_count > lim || d_vo > lim || d_ao > lim || d_len > lim) throw std::runtime_error("glTF: accessor exceeds its buffer");
@@ -542,7 +575,10 @@ inline material create_material(const glb_file& g, const json& mat)
     return m;
 }
 
-struct vertex_group { material mat; std::vector<vertex> vertices; std::vector<uint32_t> indices; std::vector<trhip_skin> skins; };
+// targets: morph targets of the group; dpos / dnrm / dtan: their target-major delta planes float[targets][vertices][3] (dnrm / dtan empty
+// when no target carries the attribute, zero where only some do)
+struct vertex_group { material mat; std::vector<vertex> vertices; std::vector<uint32_t> indices; std::vector<trhip_skin> skins;
+                      uint32_t targets = 0; std::vector<float> dpos, dnrm, dtan; };
 
 // mesh::calculate_normals (src/mesh.cc:113-143)
 inline void calculate_normals(std::vector<vertex>& v, const std::vector<uint32_t>& idx)
@@ -607,23 +643,25 @@ inline void calculate_tangents(std::vector<vertex>& v, const std::vector<uint32_
 struct gltf_animation
 {
     enum interpolation { LINEAR = 0, STEP, CUBICSPLINE };
-    // std::vector<animation::sample<T>>: microsecond ticks (src/gltf.cc:167-190), three or four components per key
+    // std::vector<animation::sample<T>>: microsecond ticks (src/gltf.cc:167-190), three or four components per key; a weights track has
+    // as many as the node's mesh has morph targets, so a key is of run-time width (max(width, 4) values, the rest zero)
+    using key = std::vector<double>;
     struct track
     {
         interpolation interp = LINEAR;
-        int width = 0;                                   // 3 (position, scaling) or 4 (orientation); 0 = no such track
+        int width = 0;                                   // 3 (position, scaling), 4 (orientation) or the target count (weights); 0 = no such track
         std::vector<int64_t> timestamps;
-        std::vector<std::array<double, 4>> data, in_tangent, out_tangent;
+        std::vector<key> data, in_tangent, out_tangent;
 
         // animation::interpolate (src/animation.tcc:39-77)
-        std::array<double, 4> sample(int64_t time, bool quaternion) const
+        key sample(int64_t time, bool quaternion) const
         {
             const size_t i = (size_t)(std::upper_bound(timestamps.begin(), timestamps.end(), time) - timestamps.begin());
             if(i == timestamps.size()) return data.back();
             if(i == 0) return data.front();
             const float frame_ticks = (float)(timestamps[i] - timestamps[i - 1]);
             const double ratio = (double)((float)(time - timestamps[i - 1]) / frame_ticks);
-            std::array<double, 4> r{};
+            key r(data[i - 1].size(), 0.0);
             if(interp == STEP) return data[i - 1];
             if(interp == CUBICSPLINE && !in_tangent.empty())
             {   // cubic_spline (src/math.tcc:24-35): coefficients in float, tangents scaled by the interval in seconds
@@ -634,8 +672,8 @@ struct gltf_animation
                     r[(size_t)k] = c1 * data[i - 1][(size_t)k] + c2 * (out_tangent[i - 1][(size_t)k] * scale) + c3 * data[i][(size_t)k] + c4 * (in_tangent[i][(size_t)k] * scale);
                 return r;
             }
-            const std::array<double, 4>& a = data[i - 1];
-            std::array<double, 4> b = data[i];
+            const key& a = data[i - 1];
+            key b = data[i];
             if(quaternion)
             {   // glm::slerp: the shorter arc, linear when the two nearly coincide
                 double cos_theta = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
@@ -654,11 +692,11 @@ struct gltf_animation
     // tr::animation: one named clip of one node
     struct clip
     {
-        track position, scaling, orientation;
+        track position, scaling, orientation, weights;
         int64_t loop_time() const
         {
             int64_t t = 0;
-            for(const track* tr: {&position, &scaling, &orientation}) if(tr->width && !tr->timestamps.empty()) t = std::max(t, tr->timestamps.back());
+            for(const track* tr: {&position, &scaling, &orientation, &weights}) if(tr->width && !tr->timestamps.empty()) t = std::max(t, tr->timestamps.back());
             return t;
         }
     };
@@ -673,6 +711,7 @@ struct gltf_animation
         // punctual lights on this node: kind, index in the scene's point (point lights, then spotlights) / directional array
         struct light { bool directional; uint32_t index; };
         std::vector<light> lights;
+        std::vector<double> weights;                    // morph-target weights a playing clip last wrote (empty: the loader's defaults hold)
         gltf_detail::mat4d local() const { return has_trs ? gltf_detail::trs_matrix(translation, rotation, scale) : matrix; }
     };
     struct skin { std::vector<int> joint_nodes; std::vector<gltf_detail::mat4d> inverse_bind; };      // parallel to scene_data::skinned
@@ -785,6 +824,27 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
                     }
                 }
             }
+            if(const json* targets = p.find("targets")) if(targets->size())
+            {   // target-major delta planes; an attribute only some targets carry is zero in the others
+                vg.targets = (uint32_t)targets->size();
+                const char* names[3] = {"POSITION", "NORMAL", "TANGENT"};
+                std::vector<float>* planes[3] = {&vg.dpos, &vg.dnrm, &vg.dtan};
+                for(int a = 0; a < 3; ++a)
+                {
+                    bool any = a == 0;
+                    for(const json& t: targets->arr) any = any || t.has(names[a]);
+                    if(!any) continue;
+                    planes[a]->assign((size_t)vg.targets * count * 3, 0.0f);
+                    for(size_t k = 0; k < targets->size(); ++k)
+                    {
+                        if(!targets->at(k).has(names[a])) continue;
+                        int c; size_t n;
+                        const std::vector<double> d = g.accessor(targets->at(k).integer(names[a], -1), c, n);
+                        if(n < count || c < 3) throw std::runtime_error(std::string("glTF: morph target ") + names[a] + " is shorter than POSITION");
+                        for(size_t i = 0; i < count; ++i) for(int x = 0; x < 3; ++x) (*planes[a])[(k * count + i) * 3 + (size_t)x] = (float)d[i * (size_t)c + (size_t)x];
+                    }
+                }
+            }
             groups.push_back(std::move(vg));
         }
         models.push_back(std::move(groups));
@@ -889,6 +949,17 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
                 in.light_base_id = -1; in.sh_grid_index = -1;
                 in.shadow_terminator_mul = (float)(1.0 / (1.0 - 0.5 * sto));
                 // glTF places skinned meshes at the origin; the loader enforces it (src/gltf.cc:777-784)
+                if(vg.targets)
+                {   // every node has a vertex span of its own, so two nodes of one mesh hold different weights
+                    scene_data::morphed_mesh mm;
+                    mm.instance = (uint32_t)instances.size(); mm.target_count = vg.targets; mm.node = node_index;
+                    mm.position_deltas = vg.dpos; mm.normal_deltas = vg.dnrm; mm.tangent_deltas = vg.dtan;
+                    const json& mesh = j.at("meshes").at((size_t)mesh_index);
+                    const json* w = node.has("weights") ? node.find("weights") : mesh.find("weights");
+                    if(w && w->size() != vg.targets) throw std::runtime_error("glTF: as many weights as morph targets");
+                    for(uint32_t k = 0; k < vg.targets; ++k) mm.weights.push_back(w ? (float)w->at(k).num : 0.0f);
+                    s.morphed.push_back(std::move(mm));
+                }
                 const bool skinned = node.has("skin") && !vg.skins.empty();
                 const mat4d model = skinned ? mat4d::identity() : glob;
                 if(skinned) skinned_pending.push_back(pending_skin{(uint32_t)instances.size(), node.integer("skin", 0), &vg.skins});
@@ -1010,11 +1081,23 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
             const json& target = chan.at("target");
             if(!target.has("node")) continue;
             const std::string& path_name = target.at("path").str;
-            const int width = path_name == "rotation" ? 4 : 3;
-            if(path_name != "translation" && path_name != "rotation" && path_name != "scale") continue;      // morph-target weights
+            int width = path_name == "rotation" ? 4 : 3;
+            if(path_name != "translation" && path_name != "rotation" && path_name != "scale" && path_name != "weights") continue;
+            if(path_name == "weights")
+            {   // as many scalars per key as the node's mesh has targets (its first primitive that has any)
+                width = 0;
+                const int tn = target.integer("node", -1);
+                if(tn >= 0 && (size_t)tn < list("nodes").size() && j.at("nodes").at((size_t)tn).has("mesh"))
+                {
+                    const int mi = j.at("nodes").at((size_t)tn).integer("mesh", -1);
+                    if(mi < 0 || (size_t)mi >= models.size()) throw std::runtime_error("glTF: mesh index out of range");
+                    for(const vertex_group& vg: models[(size_t)mi]) if(vg.targets) { width = (int)vg.targets; break; }
+                }
+                if(width == 0) continue;      // a node without morph targets has nothing to weigh
+            }
             const json& sampler = an.at("samplers").at((size_t)chan.integer("sampler", 0));
             gltf_animation::clip& cl = anim->clips[target.integer("node", 0)][an.has("name") ? an.at("name").str : std::string()];
-            gltf_animation::track& tr = path_name == "translation" ? cl.position : (path_name == "rotation" ? cl.orientation : cl.scaling);
+            gltf_animation::track& tr = path_name == "translation" ? cl.position : (path_name == "rotation" ? cl.orientation : (path_name == "scale" ? cl.scaling : cl.weights));
             tr = gltf_animation::track{};
             tr.width = width;
             const std::string interp = sampler.has("interpolation") ? sampler.at("interpolation").str : std::string("LINEAR");
@@ -1024,8 +1107,11 @@ inline scene_data load_glb(const std::string& path, uint32_t width, uint32_t hei
             const size_t n = count;
             for(size_t k = 0; k < n; ++k) tr.timestamps.push_back((int64_t)std::floor((double)((float)times[k] * 1000000.0f) + 0.5));
             const std::vector<double> values = g.accessor(sampler.integer("output", 0), comps, count);
-            auto key = [&](size_t index) { std::array<double, 4> v{}; for(int c = 0; c < width; ++c) v[(size_t)c] = (double)(float)values[index * (size_t)width + (size_t)c]; return v; };
-            const bool tangents = count >= 3 * n;
+            // keys of `width` values each, whatever the accessor's own element is (a weights output is n * T or 3 * n * T scalars)
+            const size_t keys = values.size() / (size_t)width;
+            auto key = [&](size_t index) { gltf_animation::key v((size_t)std::max(width, 4), 0.0); for(int c = 0; c < width; ++c) v[(size_t)c] = (double)(float)values[index * (size_t)width + (size_t)c]; return v; };
+            const bool tangents = keys >= 3 * n;
+            if(keys < n) throw std::runtime_error("glTF: animation output is shorter than its input");
             for(size_t k = 0; k < n; ++k)
             {
                 if(tangents) { tr.in_tangent.push_back(key(3 * k)); tr.data.push_back(key(3 * k + 1)); tr.out_tangent.push_back(key(3 * k + 2)); }
@@ -1249,7 +1335,7 @@ inline void step_camera_jitter(scene_data& s)
 // play(scene, name, loop, fallback) / update(scene, dt) / is_playing(scene) of src/scene.cc:213-244 with the controller of
 // src/animation.tcc:79-205 (a queue of one clip), over a scene load_glb produced: `tauray --animation[=name] --framerate F`.
 // update() rewrites scene_data::instances (model, model_normal; model_prev = last frame's model), ::cameras (previous_cameras =
-// last frame's), the joint matrices of ::skinned and the light records; scene_stage::apply / rt_renderer::update_scene send them
+// last frame's), the joint matrices of ::skinned, the weights of ::morphed and the light records; scene_stage::apply / rt_renderer::update_scene send them
 // to the device.
 // Punctual lights on moving nodes get a new position / direction in scene_data::point_lights / directional_lights.
 class scene_animator
@@ -1305,6 +1391,13 @@ public:
                 }
                 for(int k = 0; k < 4; ++k) node.rotation[k] = q[(size_t)k];
             }
+            if(c.current->weights.width) { const auto v = c.current->weights.sample(c.timer, false); node.weights.assign(v.begin(), v.begin() + c.current->weights.width); }
+        }
+        for(scene_data::morphed_mesh& mm: scene->morphed)
+        {   // the weights a clip wrote to the mesh's node, else the loader's defaults stay
+            const auto it = anim->nodes.find(mm.node);
+            if(it == anim->nodes.end() || it->second.weights.size() != mm.weights.size()) continue;
+            for(size_t k = 0; k < mm.weights.size(); ++k) mm.weights[k] = (float)it->second.weights[k];
         }
         instance* inst = reinterpret_cast<instance*>(scene->instances.data());
         const uint32_t n_inst = scene->instance_count();

@@ -242,6 +242,11 @@ struct scene_data
     // filled it in.  Not part of the .trsc dump.
     struct skinned_mesh { uint32_t instance = 0; std::vector<trhip_skin> skins; std::vector<float> joint_transforms; };
     std::vector<skinned_mesh> skinned;
+    // Vertex groups with morph targets (tauray_amd/csrc/morph.h): the target-major delta planes float[target_count][vertices][3] (normal /
+    // tangent planes empty when no target carries them), the weights now (the file's defaults until tr::scene_animator plays a `weights`
+    // channel) and the glTF node that drives them.  Not part of the .trsc dump, like the skins.
+    struct morphed_mesh { uint32_t instance = 0, target_count = 0; std::vector<float> position_deltas, normal_deltas, tangent_deltas, weights; int node = -1; };
+    std::vector<morphed_mesh> morphed;
     // What tr::scene_animator needs to play the file's animation clips (tauray_gltf.hh); null for scenes without a node tree.
     std::shared_ptr<gltf_animation> animation;
     std::vector<uint8_t> previous_cameras;       // camera_pair.previous of the current frame (empty = the cameras themselves)
@@ -326,11 +331,16 @@ public:
         check(trhip_scene_upload(dev->h, &d));
         // skinned meshes: the uploaded vertices are the bind pose; pose them before the build (the reference runs skinning.comp on
         // the first scene update, src/scene_stage.cc:1543-1567)
-        for(const scene_data::skinned_mesh& sk: s.skinned)
+        // morph targets come ahead of skinning (glTF 2.0 section 3.7.2.2): the skins are set first, so that a morphed and skinned mesh
+        // morphs its bind pose, the file's default weights are applied, and the rest pose skins the result
+        for(const scene_data::skinned_mesh& sk: s.skinned) set_skin(sk.instance, sk.skins.data(), (uint32_t)sk.skins.size());
+        for(const scene_data::morphed_mesh& mm: s.morphed)
         {
-            set_skin(sk.instance, sk.skins.data(), (uint32_t)sk.skins.size());
-            skin(sk.instance, sk.joint_transforms.data(), (uint32_t)(sk.joint_transforms.size() / 16));
+            set_morph_targets(mm.instance, mm.target_count, mm.position_deltas.data(), mm.normal_deltas.empty() ? nullptr : mm.normal_deltas.data(),
+                              mm.tangent_deltas.empty() ? nullptr : mm.tangent_deltas.data(), (uint32_t)(mm.position_deltas.size() / (3 * (size_t)std::max(mm.target_count, 1u))));
+            morph(mm.instance, mm.weights.data(), (uint32_t)mm.weights.size());
         }
+        for(const scene_data::skinned_mesh& sk: s.skinned) skin(sk.instance, sk.joint_transforms.data(), (uint32_t)(sk.joint_transforms.size() / 16));
         check(trhip_scene_set_accel_strategy(dev->h, opt.as_strategy));
         if(!opt.dynamic.empty())
         {
@@ -353,6 +363,13 @@ public:
     }
     // model::update_joints + shader/skinning.comp: column-major mat4 per joint
     void skin(uint32_t instance, const float* joint_transforms, uint32_t joint_count) { check(trhip_scene_skin(dev->h, instance, joint_transforms, joint_count)); }
+    // morph targets (tauray_amd/csrc/morph.h): delta planes float[target_count][vertex_count][3] (normals / tangents may be nullptr) over the
+    // instance's vertices as they stand, or over the bind pose of its skin (set_skin comes first); morph() evaluates them with new weights
+    void set_morph_targets(uint32_t instance, uint32_t target_count, const float* position_deltas, const float* normal_deltas, const float* tangent_deltas, uint32_t vertex_count)
+    {
+        check(trhip_scene_set_morph_targets(dev->h, instance, target_count, position_deltas, normal_deltas, tangent_deltas, vertex_count));
+    }
+    void morph(uint32_t instance, const float* weights, uint32_t weight_count) { check(trhip_scene_morph(dev->h, instance, weights, weight_count)); }
     void update_cameras(const void* camera_data_320, uint32_t count) { check(trhip_scene_update_cameras(dev->h, camera_data_320, count)); }
     // One frame's worth of scene changes (scene_stage::update after update(scene, dt), src/scene.cc:226-235): the instance records,
     // joint matrices and cameras of `s` - as tr::scene_animator::update left them - go to the device and the acceleration
@@ -360,6 +377,7 @@ public:
     void apply(const scene_data& s, bool rebuild = false)
     {
         update_instances(s.instances.data(), s.instance_count());
+        for(const scene_data::morphed_mesh& mm: s.morphed) morph(mm.instance, mm.weights.data(), (uint32_t)mm.weights.size());      // morph, then skin, then one refit
         for(const scene_data::skinned_mesh& sk: s.skinned) skin(sk.instance, sk.joint_transforms.data(), (uint32_t)(sk.joint_transforms.size() / 16));
         update_cameras(s.cameras.data(), s.camera_count());
         if(!s.previous_cameras.empty()) set_previous_cameras(s.previous_cameras.data(), (uint32_t)(s.previous_cameras.size() / 320));

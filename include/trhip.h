@@ -176,7 +176,21 @@ int trhip_scene_update_instances(trhip_device* dev, const void* instances, uint3
 typedef struct trhip_skin { uint32_t joints[4]; float weights[4]; } trhip_skin;
 int trhip_scene_set_skin(trhip_device* dev, uint32_t instance, const void* source_vertices, const trhip_skin* skins, uint32_t vertex_count);
 int trhip_scene_skin(trhip_device* dev, uint32_t instance, const float* joint_transforms, uint32_t joint_count);
-/* Reads back the (possibly skinned) 48-byte vertices of one instance; for tests and tools. */
+/* Morph targets (glTF 2.0 section 3.7.2.2; the reference's loader skips them).  trhip_scene_set_morph_targets gives the mesh of `instance`
+ * `target_count` targets: each plane is float[target_count][vertex_count][3], the POSITION deltas and - or NULL - the NORMAL and TANGENT
+ * (xyz) deltas.  The base they displace is a device copy of the instance's vertices as they stand, or of the bind pose of its skin when it
+ * has one: glTF morphs first and skins second, so trhip_scene_set_skin comes first and is refused on an instance that has targets.
+ * trhip_scene_morph evaluates base + sum of weights[k] * delta[k] over the non-zero weights, in the order tauray_amd/csrc/morph.h pins
+ * (normals and tangents renormalised, uv and tangent.w kept), and writes the result to the instance's vertices in the scene - then, like
+ * trhip_scene_skin, the acceleration structure is invalidated: follow with trhip_scene_refit_accel or trhip_scene_build_accel - or, on a
+ * skinned instance, to the skin's bind pose: the scene changes at the next trhip_scene_skin.  Instances that share the vertex span move
+ * together.  Under a two-level strategy a morphed instance is dynamic like a skinned one.  Refused: an instance out of range or without
+ * targets, a vertex_count other than the mesh's, no targets, null positions, a weight count other than target_count, and any value that
+ * is not finite.  A scene upload drops the targets, as it drops the skins. */
+int trhip_scene_set_morph_targets(trhip_device* dev, uint32_t instance, uint32_t target_count, const float* position_deltas, const float* normal_deltas,
+                                  const float* tangent_deltas, uint32_t vertex_count);
+int trhip_scene_morph(trhip_device* dev, uint32_t instance, const float* weights, uint32_t weight_count);
+/* Reads back the (possibly skinned or morphed) 48-byte vertices of one instance; for tests and tools. */
 int trhip_scene_get_vertices(trhip_device* dev, uint32_t instance, void* out_host, uint32_t max_count);
 /* After trhip_scene_update_instances: keeps the topology of the last build and recomputes the world triangles, every
  * child box (level by level, bottom-up) and the tri lights - an acceleration-structure *update* instead of a build

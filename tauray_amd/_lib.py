@@ -328,6 +328,8 @@ SYMBOLS = {
     "trhip_pt_set_shard": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "trhip_scene_set_skin": (_i, [_vp, _u32, _vp, _vp, _u32]),
     "trhip_scene_skin": (_i, [_vp, _u32, _vp, _u32]),
+    "trhip_scene_set_morph_targets": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _u32]),
+    "trhip_scene_morph": (_i, [_vp, _u32, _vp, _u32]),
     "trhip_scene_get_vertices": (_i, [_vp, _u32, _vp, _u32]),
     "trhip_scene_get_tri_lights": (_i, [_vp, _vp, _u32]),
     "trhip_pt_create": (_i, [_vp, C.POINTER(PtOptionsC), C.POINTER(_vp)]),

@@ -1,7 +1,8 @@
 """glTF animation clips for the scene loaders: tr::animation / animation_controller / animated
 (src/animation.{hh,cc,tcc}) and the part of src/scene.cc that plays them (play / update / is_playing, :213-244).
 
-A clip holds up to three tracks per node - position, scaling, orientation - sampled at integer microsecond ticks
+A clip holds up to four tracks per node - position, scaling, orientation and, going past the reference, the morph-target weights
+(glTF `weights` channels: a track of as many values per key as the node's mesh has targets) - sampled at integer microsecond ticks
 (src/gltf.cc:167-190 rounds the file's seconds).  `SceneAnimator` is what `tauray --animation[=name] --framerate F` does
 to a loaded scene per frame (src/tauray.cc:252-253, 1052-1092): advance every animated node's timer, rebuild the global
 transforms below it, and hand the renderer new instance records, cameras and joint matrices
@@ -50,7 +51,7 @@ class Track:
     """std::vector<animation::sample<T>> + its interpolation."""
     interpolation: int
     timestamps: List[int]            # microsecond ticks, ascending
-    data: np.ndarray                 # (n, 3) or (n, 4)
+    data: np.ndarray                 # (n, 3) or (n, 4); (n, targets) for a weights track
     in_tangent: Optional[np.ndarray] = None
     out_tangent: Optional[np.ndarray] = None
 
@@ -80,11 +81,12 @@ class Animation:
     position: Optional[Track] = None
     scaling: Optional[Track] = None
     orientation: Optional[Track] = None
+    weights: Optional[Track] = None
 
     @property
     def loop_time(self) -> int:
         """animation::determine_loop_time: the last timestamp of any track."""
-        return max([t.timestamps[-1] for t in (self.position, self.scaling, self.orientation) if t is not None and t.timestamps] + [0])
+        return max([t.timestamps[-1] for t in (self.position, self.scaling, self.orientation, self.weights) if t is not None and t.timestamps] + [0])
 
     def apply(self, trs: dict, time: int):
         """animation::apply: overwrite the node's translation / scale / rotation with the tracks' values at `time`."""
@@ -98,12 +100,18 @@ class Animation:
                 q = q / math.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3])
             trs["rotation"] = q
 
+    def apply_weights(self, time: int):
+        """The morph-target weights at `time` (interpolated like a translation), or None for a clip without a weights track."""
+        return None if self.weights is None else self.weights.sample(time)
+
 
 def read_track(timestamps_s: np.ndarray, values: np.ndarray, interpolation: int) -> Track:
     """read_animation_accessors (src/gltf.cc:167-190): ticks = round(seconds * 1e6); three values per key (in-tangent, value,
     out-tangent) when the output accessor holds that many."""
     ts = [int(math.floor(float(np.float32(t) * np.float32(1000000)) + 0.5)) for t in timestamps_s]      # C round() of a float product
     n = len(ts)
+    if len(values) < n:
+        raise ValueError("glTF: animation output is shorter than its input")
     if len(values) >= 3 * n:
         v = values[:3 * n].reshape(n, 3, -1)
         return Track(interpolation, ts, v[:, 1].copy(), v[:, 0].copy(), v[:, 2].copy())
@@ -131,8 +139,9 @@ class Controller:
         self.loop = loop
 
     def update(self, trs: dict, dt: int):
+        """Advances the clip and writes the node's translation / rotation / scale; returns the morph-target weights of this frame, or None."""
         if not self.playing:
-            return
+            return None
         self.timer += dt
         if self.loop:
             self.timer %= self.loop_time
@@ -140,8 +149,9 @@ class Controller:
             self.playing = False
             self.loop_time = 0
             self.timer = 0
-            return
+            return None
         self.current.apply(trs, self.timer)
+        return self.current.apply_weights(self.timer)
 
 
 @dataclass
@@ -154,6 +164,7 @@ class Node:
     instances: List[int] = field(default_factory=list)     # rigid instances placed by this node's global transform
     cameras: List[int] = field(default_factory=list)
     lights: List[tuple] = field(default_factory=list)      # (kind, index in its list, make(global transform) -> record)
+    weights: Optional[np.ndarray] = None                   # morph-target weights a playing clip last wrote (None: the loader's defaults hold)
 
     def local(self) -> np.ndarray:
         if self.trs is None:
@@ -189,7 +200,9 @@ class SceneAnimator:
         for n, c in self.controllers.items():
             node = desc.nodes[n]
             if node.trs is not None:
-                c.update(node.trs, dt_ticks)
+                w = c.update(node.trs, dt_ticks)
+                if w is not None:
+                    node.weights = w
         instances = desc.instances.copy()
         instances["model_prev"] = desc.instances["model"]
         point_lights, directional_lights = desc.point_lights.copy(), desc.directional_lights.copy()

@@ -632,6 +632,7 @@ int trhip_scene_set_skin(trhip_device* dev, uint32_t instance, const void* sourc
     const MeshSpan& sp = s.host_spans[instance];
     if (vertex_count != sp.vertex_count) return set_error("trhip_scene_set_skin: vertex_count differs from the instance's mesh");
     if (!skins && vertex_count) return set_error("trhip_scene_set_skin: null skins");
+    if (s.has_morph(instance)) return set_error("trhip_scene_set_skin: the instance has morph targets, whose base would be the skin's source (set the skin first)");
     HIPCHK(hipDeviceSynchronize());
     if (s.skin_slots.size() < s.instance_count) s.skin_slots.resize(s.instance_count);
     DeviceScene::SkinSlot& k = s.skin_slots[instance];
@@ -654,6 +655,55 @@ int trhip_scene_skin(trhip_device* dev, uint32_t instance, const float* joint_tr
     HIPCHK(hipDeviceSynchronize());   // frames in flight read the vertices
     if (int rc = skin_instance(s, instance, joint_transforms, joint_count, nullptr)) return rc;
     for (uint32_t i = 0; i < s.instance_count; ++i)      // every instance of the span moved: their BLAS (two-level structure)
+        if (memcmp(&s.host_spans[i], &s.host_spans[instance], sizeof(MeshSpan)) == 0) mark_skinned(s, i);
+    s.accel_built = false;
+    if (s.world_vertices) { (void)hipFree(s.world_vertices); s.world_vertices = nullptr; }
+    return 0;
+}
+int trhip_scene_set_morph_targets(trhip_device* dev, uint32_t instance, uint32_t target_count, const float* position_deltas, const float* normal_deltas,
+                                  const float* tangent_deltas, uint32_t vertex_count) {
+    // what the arguments alone decide comes first
+    if (target_count == 0) return set_error("trhip_scene_set_morph_targets: target_count is 0");
+    if (!position_deltas) return set_error("trhip_scene_set_morph_targets: null position deltas");
+    const size_t plane = (size_t)target_count * vertex_count * 3;
+    for (const float* p : {position_deltas, normal_deltas, tangent_deltas})
+        for (size_t k = 0; p && k < plane; ++k) if (!std::isfinite(p[k])) return set_error("trhip_scene_set_morph_targets: non-finite delta");
+    DEVCHK(dev);
+    DeviceScene& s = dev->scene;
+    if (instance >= s.instance_count) return set_error("trhip_scene_set_morph_targets: instance out of range");
+    const MeshSpan& sp = s.host_spans[instance];
+    if (vertex_count != sp.vertex_count) return set_error("trhip_scene_set_morph_targets: vertex_count differs from the instance's mesh");
+    HIPCHK(hipDeviceSynchronize());
+    if (s.morph_slots.size() < s.instance_count) s.morph_slots.resize(s.instance_count);
+    DeviceScene::MorphSlot& m = s.morph_slots[instance];
+    DeviceScene::free_morph(m);
+    m.target_count = target_count; m.vertex_count = vertex_count;
+    // the base: the instance's vertices as they stand, or the bind pose of its skin
+    const bool skinned = instance < s.skin_slots.size() && s.skin_slots[instance].source;
+    HIPCHK(hipMalloc(&m.base, std::max<size_t>(vertex_count, 1) * sizeof(Vertex)));      // an empty mesh has a slot too
+    if (vertex_count == 0) return 0;
+    HIPCHK(hipMemcpy(m.base, skinned ? s.skin_slots[instance].source : s.vertices + sp.vertex_offset, (size_t)vertex_count * sizeof(Vertex), hipMemcpyDeviceToDevice));
+    const float* host[3] = {position_deltas, normal_deltas, tangent_deltas};
+    float** device[3] = {&m.dpos, &m.dnrm, &m.dtan};
+    for (int k = 0; k < 3; ++k) {
+        if (!host[k]) continue;
+        HIPCHK(hipMalloc(device[k], plane * sizeof(float)));
+        HIPCHK(hipMemcpy(*device[k], host[k], plane * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+int trhip_scene_morph(trhip_device* dev, uint32_t instance, const float* weights, uint32_t weight_count) {
+    for (uint32_t k = 0; weights && k < weight_count; ++k)
+        if (!std::isfinite(weights[k])) return set_error("trhip_scene_morph: non-finite weight");
+    DEVCHK(dev);
+    DeviceScene& s = dev->scene;
+    if (!s.has_morph(instance)) return set_error("trhip_scene_morph: instance has no morph targets (trhip_scene_set_morph_targets)");
+    if (weight_count != s.morph_slots[instance].target_count || !weights)
+        return set_error("trhip_scene_morph: " + std::to_string(weight_count) + " weights for " + std::to_string(s.morph_slots[instance].target_count) + " targets");
+    HIPCHK(hipDeviceSynchronize());   // frames in flight read the vertices
+    if (int rc = morph_instance(s, instance, weights, weight_count, nullptr)) return rc;
+    if (instance < s.skin_slots.size() && s.skin_slots[instance].source) return 0;      // the scene changes at the next trhip_scene_skin
+    for (uint32_t i = 0; i < s.instance_count; ++i)      // as trhip_scene_skin: every instance of the span moved
         if (memcmp(&s.host_spans[i], &s.host_spans[instance], sizeof(MeshSpan)) == 0) mark_skinned(s, i);
     s.accel_built = false;
     if (s.world_vertices) { (void)hipFree(s.world_vertices); s.world_vertices = nullptr; }

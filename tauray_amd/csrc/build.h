@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "shading.h"
+#include "morph.h"
 
 namespace tr {
 
@@ -147,9 +148,24 @@ struct DeviceScene {
         for (SkinSlot& k : skin_slots) { if (k.source) (void)hipFree(k.source); if (k.skins) (void)hipFree(k.skins); if (k.joints) (void)hipFree(k.joints); }
         skin_slots.clear();
     }
+    // morph targets (morph.h): per instance a copy of the base vertices, the target-major delta planes (normals / tangents may be absent)
+    // and the active (index, weight) list of the last trhip_scene_morph
+    struct MorphSlot { Vertex* base = nullptr; float* dpos = nullptr; float* dnrm = nullptr; float* dtan = nullptr; MorphActive* active = nullptr;
+                       uint active_capacity = 0; uint target_count = 0; uint vertex_count = 0; };
+    std::vector<MorphSlot> morph_slots;
+    static void free_morph(MorphSlot& m) {
+        for (void* p : {(void*)m.base, (void*)m.dpos, (void*)m.dnrm, (void*)m.dtan, (void*)m.active}) if (p) (void)hipFree(p);
+        m = MorphSlot();
+    }
+    void free_morphs() {
+        for (MorphSlot& m : morph_slots) free_morph(m);
+        morph_slots.clear();
+    }
+    bool has_morph(uint instance) const { return instance < morph_slots.size() && morph_slots[instance].base; }
     void free_all() {
         free_accel();
         free_skins();
+        free_morphs();
         void* ptrs[] = {instances, spans, vertices, indices, point_lights, directional_lights, tex_infos, texels, envmap,
                         alias_table, cameras, prev_cameras, non_opaque, tri_prefix, world_spans, world_vertices, scratch, shade_tris, alpha_base, alpha_tris};
         for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -166,6 +182,7 @@ int build_shade_tris(DeviceScene& ds, int instance, hipStream_t stream);   // in
 int skin_instance(DeviceScene& ds, uint instance, const float* joint_transforms, uint joint_count, hipStream_t stream);   // skinning.comp
 int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);   // same tree, new boxes (after trhip_scene_update_instances)   // pre_transform.comp per instance
 void mark_skinned(DeviceScene& ds, uint instance);
+int morph_instance(DeviceScene& ds, uint instance, const float* weights, uint weight_count, hipStream_t stream);   // k_morph (morph.h)
 // The sphere-light tree after an upload or trhip_scene_update_lights (`moved`: the records changed) or trhip_scene_set_light_accel: chooses
 // the mode in effect, then builds, refits or drops the tree so that the device matches ds.host_point_lights.  Synchronous.
 int update_light_accel(DeviceScene& ds, bool moved);

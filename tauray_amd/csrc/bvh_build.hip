@@ -635,6 +635,42 @@ __global__ __launch_bounds__(BT) void k_skinning(uint vertex_count, const Vertex
     destination[i] = dst;
 }
 
+// glTF morph targets ahead of skinning: morph.h pins the order of operations (tests/morph_model.py repeats it bit for bit).  One lane per
+// vertex; the active list is the same for every lane (a uniform trip count), and lane i reads floats 3 i .. 3 i + 2 of an active target's
+// plane, so a wave reads 768 consecutive bytes per plane and target.  No atomics: two runs give the same bits.  Like k_skinning it writes
+// no previous positions (only the raster path of the reference reads them).
+__device__ inline f3 morph_accumulate(f3 acc, const float* plane, size_t vertex_count, uint i, const MorphActive* active, uint active_count) {
+    for (uint a = 0; a < active_count; ++a) {
+        const MorphActive m = active[a];
+        const float* d = plane + ((size_t)m.index * vertex_count + i) * 3u;
+        acc.x = acc.x + m.weight * d[0];      // two roundings each: the build has contraction off (Makefile)
+        acc.y = acc.y + m.weight * d[1];
+        acc.z = acc.z + m.weight * d[2];
+    }
+    return acc;
+}
+__device__ inline f3 morph_direction(f3 acc, f3 base) {
+    const float d = (acc.x * acc.x + acc.y * acc.y) + acc.z * acc.z;
+    const float len = sqrtf(d);      // sqrtf and / are correctly rounded in this build (the device library's intrinsic __fsqrt_rn is not)
+    return len > 0.0f ? F3(acc.x / len, acc.y / len, acc.z / len) : base;
+}
+__global__ __launch_bounds__(BT) void k_morph(uint vertex_count, const Vertex* base, const float* dpos, const float* dnrm, const float* dtan,
+                                              const MorphActive* active, uint active_count, Vertex* destination) {
+    uint i = blockIdx.x * BT + threadIdx.x;
+    if (i >= vertex_count) return;
+    const Vertex src = base[i];
+    Vertex dst = src;
+    if (active_count) {
+        dst.pos = morph_accumulate(src.pos, dpos, vertex_count, i, active, active_count);
+        if (dnrm) dst.normal = morph_direction(morph_accumulate(src.normal, dnrm, vertex_count, i, active, active_count), src.normal);
+        if (dtan) {
+            const f3 t = F3(src.tangent);
+            dst.tangent = F4(morph_direction(morph_accumulate(t, dtan, vertex_count, i, active, active_count), t), src.tangent.w);
+        }
+    }
+    destination[i] = dst;
+}
+
 __global__ __launch_bounds__(BT) void k_build_shade_tris(uint n_spans, const MeshSpan* spans, const Vertex* vertices, const uint* indices, ShadeTri* out, f4* tangents) {
     const MeshSpan sp = spans[blockIdx.y];
     const Vertex* vb = vertices + sp.vertex_offset;
@@ -723,6 +759,33 @@ int skin_instance(DeviceScene& ds, uint instance, const float* joint_transforms,
     HIPCHK(hipGetLastError());
     if (int rc = build_shade_tris(ds, (int)instance, stream)) return rc;
     HIPCHK(hipStreamSynchronize(stream));   // the host array may be reused by the caller
+    return 0;
+}
+
+// trhip_scene_morph behind its argument checks: compacts the non-zero weights into the slot's active list (grown like SkinSlot::joints) and
+// runs k_morph from the slot's base into the skin slot's source (glTF morphs before it skins: the scene's vertices change at the next
+// trhip_scene_skin) or, on an instance without a skin, into the instance's vertex span, followed by the shade-triangle rebuild of skin_instance.
+int morph_instance(DeviceScene& ds, uint instance, const float* weights, uint weight_count, hipStream_t stream) {
+    DeviceScene::MorphSlot& m = ds.morph_slots[instance];
+    std::vector<MorphActive> active;
+    for (uint k = 0; k < weight_count; ++k) if (weights[k] != 0.0f) active.push_back(MorphActive{k, weights[k]});
+    if (active.size() > m.active_capacity) {
+        if (m.active) (void)hipFree(m.active);
+        m.active = nullptr; m.active_capacity = 0;
+        HIPCHK(hipMalloc(&m.active, active.size() * sizeof(MorphActive)));
+        m.active_capacity = (uint)active.size();
+    }
+    if (!active.empty()) HIPCHK(hipMemcpyAsync(m.active, active.data(), active.size() * sizeof(MorphActive), hipMemcpyHostToDevice, stream));
+    const bool skinned = instance < ds.skin_slots.size() && ds.skin_slots[instance].source;
+    const MeshSpan& sp = ds.host_spans[instance];
+    Vertex* destination = skinned ? ds.skin_slots[instance].source : ds.vertices + sp.vertex_offset;
+    if (m.vertex_count) {
+        hipLaunchKernelGGL(k_morph, dim3((m.vertex_count + BT - 1) / BT), dim3(BT), 0, stream, m.vertex_count, m.base, m.dpos, m.dnrm, m.dtan, m.active,
+                           (uint)active.size(), destination);
+        HIPCHK(hipGetLastError());
+    }
+    if (!skinned) if (int rc = build_shade_tris(ds, (int)instance, stream)) return rc;
+    HIPCHK(hipStreamSynchronize(stream));   // `active` leaves scope
     return 0;
 }
 
@@ -1451,6 +1514,7 @@ static int build_two_level(DeviceScene& ds, hipStream_t stream, trhip_accel_info
     auto key = [&](uint i) { const MeshSpan& s = ds.host_spans[i]; return std::make_tuple(s.vertex_offset, s.vertex_count, s.index_offset, s.triangle_count); };
     std::vector<std::tuple<uint, uint, uint, uint>> skinned_keys;
     for (uint i = 0; i < NI && i < ds.skin_slots.size(); ++i) if (ds.skin_slots[i].source) skinned_keys.push_back(key(i));
+    for (uint i = 0; i < NI; ++i) if (ds.has_morph(i)) skinned_keys.push_back(key(i));      // a morphed mesh deforms like a skinned one
     std::vector<uint8_t> dyn(NI, 0);
     for (uint i = 0; i < NI; ++i)
         dyn[i] = (i < ds.dynamic_marks.size() && ds.dynamic_marks[i]) || std::find(skinned_keys.begin(), skinned_keys.end(), key(i)) != skinned_keys.end();

@@ -5,8 +5,10 @@ Host mirror of the reference's loader for the subset the path tracer needs
 meshes), followed by the instance flattening of scene_stage
 (src/scene_stage.cc:664-819: one instance per (model, vertex group), in node
 traversal order).  Supports KHR_lights_punctual, KHR_materials_transmission,
-KHR_materials_ior, KHR_materials_emissive_strength, Tauray's TR_data and skins
-(JOINTS_0 / WEIGHTS_0 + inverse bind matrices).  Textures: PNG of any colour type / bit depth / interlacing and baseline JPEG
+KHR_materials_ior, KHR_materials_emissive_strength, Tauray's TR_data, skins
+(JOINTS_0 / WEIGHTS_0 + inverse bind matrices), sparse accessors and - going past the reference, whose loader skips them - morph targets:
+the POSITION / NORMAL / TANGENT deltas of a primitive's `targets`, default weights (node.weights, else mesh.weights, else zeros) and `weights`
+animation channels; TEXCOORD_n / COLOR_n targets are not read (tauray_amd/csrc/morph.h).  Textures: PNG of any colour type / bit depth / interlacing and baseline JPEG
 (include/tauray_image.hh), embedded or behind a relative / data: uri.
 """
 from __future__ import annotations
@@ -24,6 +26,7 @@ from . import scene as S
 
 _COMP = {5120: ("i1", 1), 5121: ("u1", 1), 5122: ("<i2", 2), 5123: ("<u2", 2), 5125: ("<u4", 4), 5126: ("<f4", 4)}
 _NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
+_SPARSE_LIMIT = 1 << 24      # elements of a sparse accessor that has no bufferView (zeros are made up, not read: the file does not bound them)
 
 
 def decode_image(data: bytes) -> np.ndarray:
@@ -110,17 +113,45 @@ class _Glb:
         raise ValueError("glTF: image without bufferView or uri")
 
     def accessor(self, idx) -> np.ndarray:
+        """An accessor as rows: over its bufferView, with the `sparse` substitutions when it has them (over zeros without a bufferView)."""
         a = _item(self.json.get("accessors", []), idx, "accessor")
-        bv = _item(self.json.get("bufferViews", []), a.get("bufferView", -1), "bufferView")
-        if a["componentType"] not in _COMP or a["type"] not in _NCOMP:
+        sparse = a.get("sparse")
+        if a.get("componentType") not in _COMP or a.get("type") not in _NCOMP:
             raise ValueError("glTF: unsupported accessor type")
-        dt, sz = _COMP[a["componentType"]]
         nc = _NCOMP[a["type"]]
-        base = bv.get("byteOffset", 0) + a.get("byteOffset", 0)
-        stride = bv.get("byteStride", 0) or sz * nc
         count = a["count"]
+        if sparse is None or "bufferView" in a:
+            arr = self._rows(a.get("bufferView", -1), a.get("byteOffset", 0), a["componentType"], nc, count)
+        else:
+            if not isinstance(count, int) or count < 0 or count > _SPARSE_LIMIT:
+                raise ValueError("glTF: sparse accessor without a bufferView is too large")
+            arr = np.zeros((count, nc), dtype=_COMP[a["componentType"]][0])
+        if sparse is None:
+            return arr
+        if not isinstance(sparse, dict) or not isinstance(sparse.get("indices"), dict) or not isinstance(sparse.get("values"), dict):
+            raise ValueError("glTF: sparse accessor needs indices and values")
+        n = sparse.get("count", 0)
+        if not isinstance(n, int) or n < 0 or n > count:
+            raise ValueError("glTF: sparse count exceeds the accessor")
+        ind, val = sparse["indices"], sparse["values"]
+        if ind.get("componentType") not in (5121, 5123, 5125):
+            raise ValueError("glTF: sparse indices must be unsigned integers")
+        ii = self._rows(ind.get("bufferView", -1), ind.get("byteOffset", 0), ind["componentType"], 1, n).reshape(-1).astype(np.int64)
+        vv = self._rows(val.get("bufferView", -1), val.get("byteOffset", 0), a["componentType"], nc, n)
+        if n and ii.max() >= count:
+            raise ValueError("glTF: sparse index out of range")
+        arr = arr.copy()
+        arr[ii] = vv          # in file order: a repeated index keeps its last value
+        return arr
+
+    def _rows(self, view, byte_offset, component_type, nc, count) -> np.ndarray:
+        """`count` rows of `nc` components at `byte_offset` of a bufferView."""
+        bv = _item(self.json.get("bufferViews", []), view, "bufferView")
+        dt, sz = _COMP[component_type]
+        base = bv.get("byteOffset", 0) + byte_offset
+        stride = bv.get("byteStride", 0) or sz * nc
         buf = _item(self.buffers, bv.get("buffer", 0), "buffer")
-        if count < 0 or bv.get("byteOffset", 0) < 0 or a.get("byteOffset", 0) < 0 or bv.get("byteLength", 0) < 0 or bv.get("byteStride", 0) < 0:
+        if count < 0 or bv.get("byteOffset", 0) < 0 or byte_offset < 0 or bv.get("byteLength", 0) < 0 or bv.get("byteStride", 0) < 0:
             raise ValueError("glTF: negative count, offset or stride")
         # byteStride: 4 ... 252 and at least one element (glTF 2.0 section 5.11), 0 = tightly packed; as include/tauray_gltf.hh
         if bv.get("byteStride", 0) and not (sz * nc <= bv["byteStride"] <= 252):
@@ -128,7 +159,7 @@ class _Glb:
         # an accessor lives inside its bufferView, a bufferView inside its buffer (glTF 2.0 section 3.6.2)
         if bv.get("byteOffset", 0) + bv.get("byteLength", 0) > len(buf):
             raise ValueError("glTF: bufferView exceeds the buffer")
-        if count and a.get("byteOffset", 0) + stride * (count - 1) + sz * nc > bv.get("byteLength", 0):
+        if count and byte_offset + stride * (count - 1) + sz * nc > bv.get("byteLength", 0):
             raise ValueError("glTF: accessor exceeds its bufferView")
         if stride == sz * nc:
             arr = np.frombuffer(buf, dtype=dt, count=count * nc, offset=base).reshape(count, nc)
@@ -150,6 +181,17 @@ def _item(seq, index, what):
     if not isinstance(index, int) or isinstance(index, bool) or index < 0 or index >= len(seq):
         raise ValueError(f"glTF: {what} index out of range")
     return seq[index]
+
+
+def _target_count(j, node_index) -> int:
+    """Morph targets of the mesh a node shows (its first primitive that has any); 0 without a mesh or targets."""
+    nodes = j.get("nodes", [])
+    if not isinstance(node_index, int) or not 0 <= node_index < len(nodes) or "mesh" not in nodes[node_index]:
+        return 0
+    for p in _item(j.get("meshes", []), nodes[node_index]["mesh"], "mesh")["primitives"]:
+        if p.get("targets"):
+            return len(p["targets"])
+    return 0
 
 
 def _dot3(a, b):
@@ -319,14 +361,32 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
                     w = g.accessor(at["WEIGHTS_0"]).astype(np.float32)[:, :4]
                     ws = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
                     skin["weights"] = w / ws[:, None]
-            groups.append((mat, v, idx, skin))
+            morph = None
+            if p.get("targets"):        # target-major delta planes; an attribute only some targets carry is zero in the others
+                targets = p["targets"]
+                planes = {}
+                for name in ("POSITION", "NORMAL", "TANGENT"):
+                    if not any(name in t for t in targets):
+                        continue
+                    plane = np.zeros((len(targets), len(pos), 3), dtype=np.float32)
+                    for k, t in enumerate(targets):
+                        if name in t:
+                            d = g.accessor(t[name])
+                            if len(d) < len(pos) or d.shape[1] < 3:
+                                raise ValueError(f"glTF: morph target {name} is shorter than POSITION")
+                            plane[k] = d.astype(np.float32)[:len(pos), :3]
+                    planes[name] = plane
+                if "POSITION" not in planes:
+                    planes["POSITION"] = np.zeros((len(targets), len(pos), 3), dtype=np.float32)
+                morph = (planes["POSITION"], planes.get("NORMAL"), planes.get("TANGENT"))
+            groups.append((mat, v, idx, skin, morph))
         models.append(groups)
 
     inst_list, span_list, vert_list, idx_list = [], [], [], []
     point_lights, spot_lights, dir_lights, cameras = [], [], [], []
     voff = ioff = 0
     light_meta = {"angle": 0.0, "radius": 0.0}
-    node_globals, skinned_pending = {}, []
+    node_globals, skinned_pending, morphed = {}, [], []
     nodes, roots = {}, []
     sh_grids = []
 
@@ -375,7 +435,14 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
             sto = 0.0
             if tr and "mesh" in tr:
                 sto = float(tr["mesh"].get("shadow_terminator_offset", 0.0))
-            for mat, v, idx, skin in _item(models, node["mesh"], "mesh"):
+            for mat, v, idx, skin, morph in _item(models, node["mesh"], "mesh"):
+                if morph is not None:       # every node has a vertex span of its own, so two nodes of one mesh hold different weights
+                    mesh = j["meshes"][node["mesh"]]
+                    w = node.get("weights", mesh.get("weights", [0.0] * len(morph[0])))
+                    if len(w) != len(morph[0]):
+                        raise ValueError("glTF: as many weights as morph targets")
+                    morphed.append(S.MorphedMesh(instance=len(inst_list), position_deltas=morph[0], normal_deltas=morph[1], tangent_deltas=morph[2],
+                                                 weights=np.array(w, dtype=np.float64).astype(np.float32), node=node_index))
                 if "skin" in node and skin is not None:
                     # glTF places skinned meshes at the origin; the loader enforces it (src/gltf.cc:777-784)
                     skinned_pending.append((len(inst_list), node["skin"], skin))
@@ -450,12 +517,18 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
             sampler = anim["samplers"][chan["sampler"]]
             interp = A.INTERPOLATION.get(sampler.get("interpolation", "LINEAR"), A.LINEAR)
             path_name = target["path"]
-            if path_name not in ("translation", "rotation", "scale"):
-                continue            # morph-target weights
+            if path_name not in ("translation", "rotation", "scale", "weights"):
+                continue
+            key_width = 4 if path_name == "rotation" else 3
+            if path_name == "weights":      # as many scalars per key as the node's mesh has targets
+                key_width = _target_count(j, target["node"])
+                if key_width == 0:
+                    continue            # a node without morph targets has nothing to weigh
             clip = animations.setdefault(target["node"], {}).setdefault(anim.get("name", ""), A.Animation())
-            track = A.read_track(g.accessor(sampler["input"]).astype(np.float32).reshape(-1),
-                                 g.accessor(sampler["output"]).astype(np.float32).reshape(-1, 4 if path_name == "rotation" else 3), interp)
-            setattr(clip, {"translation": "position", "rotation": "orientation", "scale": "scaling"}[path_name], track)
+            values = g.accessor(sampler["output"]).astype(np.float32).reshape(-1)
+            values = values[:len(values) // key_width * key_width].reshape(-1, key_width)
+            track = A.read_track(g.accessor(sampler["input"]).astype(np.float32).reshape(-1), values, interp)
+            setattr(clip, {"translation": "position", "rotation": "orientation", "scale": "scaling", "weights": "weights"}[path_name], track)
 
     aspect = aspect_ratio if aspect_ratio > 0 else width / float(height)
     for cam in cameras:
@@ -476,6 +549,7 @@ def load_glb(path: str, width: int = 512, height: int = 512, aspect_ratio: float
     desc.nodes, desc.roots, desc.animations = nodes, roots, animations
     desc.spotlight_base = len(point_lights)
     desc.sh_grids = sh_grids
+    desc.morphed = morphed
     for inst, skin_index, skin in skinned_pending:
         sk = j["skins"][skin_index]
         joints = list(sk["joints"])

@@ -254,8 +254,14 @@ class SceneStage:
         self.previous_camera_data = None         # camera_pair.previous as last set (None: the cameras themselves)
         # skinned meshes: the uploaded vertices are the bind pose; pose them with the file's rest pose before the build
         # (the reference runs skinning.comp on the first scene update, src/scene_stage.cc:1543-1567)
+        # morph targets come ahead of skinning (glTF 2.0 section 3.7.2.2): the skins are set first, so that a morphed and skinned mesh
+        # morphs its bind pose, the file's default weights are applied, and the rest pose skins the result
         for sk in getattr(scene, "skinned", []):
             self.set_skin(sk.instance, sk.skins)
+        for mm in getattr(scene, "morphed", []):
+            self.set_morph_targets(mm.instance, mm.position_deltas, mm.normal_deltas, mm.tangent_deltas)
+            self.morph(mm.instance, scene.morph_weights(mm), refit=None)
+        for sk in getattr(scene, "skinned", []):
             self.skin(sk.instance, scene.joint_transforms(sk), refit=None)
         info = AccelInfoC()
         check(L.trhip_scene_set_accel_strategy(self.ctx.h, self.as_strategy))
@@ -311,6 +317,8 @@ class SceneStage:
         instances, cameras, node_globals = animator.update(dt_ticks)
         inst = np.ascontiguousarray(instances)
         check(_lib.lib().trhip_scene_update_instances(self.ctx.h, inst.ctypes.data, len(inst)))
+        for mm in self.scene.morphed:       # morph, then skin, then one refit
+            self.morph(mm.instance, self.scene.morph_weights(mm), refit=None)
         for sk in self.scene.skinned:
             self.skin(sk.instance, self.scene.joint_transforms(sk, node_globals), refit=None)
         self.update_cameras(cameras)
@@ -374,6 +382,27 @@ class SceneStage:
         acceleration-structure update (`refit`), a rebuild (`refit=False`) or nothing (`refit=None`: caller batches)."""
         j = np.ascontiguousarray(np.asarray(joint_transforms, dtype=np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
         check(_lib.lib().trhip_scene_skin(self.ctx.h, instance, j.ctypes.data, len(j)))
+        return None if refit is None else self._accel_after_change(refit)
+
+    def set_morph_targets(self, instance: int, position_deltas: np.ndarray, normal_deltas: Optional[np.ndarray] = None,
+                          tangent_deltas: Optional[np.ndarray] = None):
+        """trhip_scene_set_morph_targets: the mesh of `instance` gets the targets of the (T, V, 3) float32 delta planes (normals and tangents
+        optional); their base is the instance's vertices as they stand, or the bind pose of its skin (set the skin first)."""
+        planes = [None if p is None else np.ascontiguousarray(p, dtype=np.float32) for p in (position_deltas, normal_deltas, tangent_deltas)]
+        if planes[0] is None or planes[0].ndim != 3 or planes[0].shape[2] != 3:
+            raise ValueError("set_morph_targets: position deltas are (targets, vertices, 3)")
+        for p in planes[1:]:
+            if p is not None and p.shape != planes[0].shape:
+                raise ValueError("set_morph_targets: the planes differ in shape")
+        t, v, _ = planes[0].shape
+        ptr = [None if p is None else p.ctypes.data for p in planes]
+        check(_lib.lib().trhip_scene_set_morph_targets(self.ctx.h, instance, t, ptr[0], ptr[1], ptr[2], v))
+
+    def morph(self, instance: int, weights: np.ndarray, refit: Optional[bool] = True):
+        """trhip_scene_morph: base + sum of weights[k] * delta[k] (tauray_amd/csrc/morph.h) into the instance's vertices, or into its
+        skin's bind pose; then the acceleration-structure update (`refit`), a rebuild (`refit=False`) or nothing (`refit=None`)."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        check(_lib.lib().trhip_scene_morph(self.ctx.h, instance, w.ctypes.data if len(w) else None, len(w)))
         return None if refit is None else self._accel_after_change(refit)
 
     def vertices(self, instance: int) -> np.ndarray:

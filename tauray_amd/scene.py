@@ -362,6 +362,18 @@ class SkinnedMesh:
 
 
 @dataclass
+class MorphedMesh:
+    """A vertex group with morph targets (glTF 2.0 section 3.7.2.2; tauray_amd/csrc/morph.h): its instance, the target-major delta
+    planes, the default weights (node.weights, else mesh.weights, else zeros) and the glTF node whose `weights` animation drives it."""
+    instance: int
+    position_deltas: np.ndarray              # float32 (T, V, 3)
+    normal_deltas: Optional[np.ndarray]      # float32 (T, V, 3) or None: no target has NORMAL
+    tangent_deltas: Optional[np.ndarray]     # float32 (T, V, 3) or None: no target has TANGENT
+    weights: np.ndarray                      # float32 (T,)
+    node: int
+
+
+@dataclass
 class ShGrid:
     """sh_grid + its transformable (src/sh_grid.hh; TR_data.light_probe of type GRID, src/gltf.cc:462-481): a grid of light probes in the
     box the node's global transform maps [-1, 1]^3 onto."""
@@ -387,6 +399,7 @@ class SceneDesc:
     cameras: List[Camera] = field(default_factory=list)
     name: str = "scene"
     skinned: List["SkinnedMesh"] = field(default_factory=list)     # vertices of these instances are the bind pose
+    morphed: List["MorphedMesh"] = field(default_factory=list)     # vertices of these instances are the base of their morph targets
     node_globals: dict = field(default_factory=dict)               # glTF node index -> global transform of the rest pose
     nodes: dict = field(default_factory=dict)                      # glTF node index -> animation.Node (tree, local transform, instances, cameras)
     roots: list = field(default_factory=list)                      # root nodes of the file's scenes
@@ -400,6 +413,12 @@ class SceneDesc:
         """model::update_joints (src/model.cc:107-118): joint node's global transform * inverse bind matrix, (n, 4, 4)."""
         g = node_globals if node_globals is not None else self.node_globals
         return np.stack([np.asarray(g[n], dtype=np.float64) @ sk.inverse_bind[i] for i, n in enumerate(sk.joint_nodes)]).astype(np.float32)
+
+    def morph_weights(self, mm: "MorphedMesh") -> np.ndarray:
+        """The weights of a morphed mesh now: what a `weights` track last wrote to its node (animation.Animation.apply), else the defaults."""
+        node = self.nodes.get(mm.node)
+        w = node.weights if node is not None and node.weights is not None else mm.weights
+        return np.asarray(w, dtype=np.float64).astype(np.float32)
 
     @property
     def triangle_count(self) -> int:
