@@ -304,6 +304,9 @@ public:
     {
         int as_strategy = TRHIP_AS_ALL_MERGED;
         std::vector<uint8_t> dynamic;
+        // trhip_scene_set_deformation_motion: screen motion follows the deformation of skinned and morphed meshes;
+        // apply() then latches their positions before it morphs and skins.  Off: their rigid motion only, the reference's ray-traced path.
+        bool deformation_motion = false;
     };
     explicit scene_stage(device& dev): dev(&dev) {}
     scene_stage(device& dev, const options& opt): dev(&dev), opt(opt) {}
@@ -329,6 +332,8 @@ public:
         d.non_opaque = s.non_opaque.data();
         d.gather_emissive_triangles = s.gather_emissive_triangles;
         check(trhip_scene_upload(dev->h, &d));
+        // the device handle keeps the switch over uploads; set behind the upload, so that a plane is never filled for the scene that leaves
+        check(trhip_scene_set_deformation_motion(dev->h, opt.deformation_motion ? 1 : 0));
         // skinned meshes: the uploaded vertices are the bind pose; pose them before the build (the reference runs skinning.comp on
         // the first scene update, src/scene_stage.cc:1543-1567)
         // morph targets come ahead of skinning (glTF 2.0 section 3.7.2.2): the skins are set first, so that a morphed and skinned mesh
@@ -341,6 +346,7 @@ public:
             morph(mm.instance, mm.weights.data(), (uint32_t)mm.weights.size());
         }
         for(const scene_data::skinned_mesh& sk: s.skinned) skin(sk.instance, sk.joint_transforms.data(), (uint32_t)(sk.joint_transforms.size() / 16));
+        if(opt.deformation_motion) latch_positions();      // the plane was filled with the uploaded bind pose: a still scene has previous = current
         check(trhip_scene_set_accel_strategy(dev->h, opt.as_strategy));
         if(!opt.dynamic.empty())
         {
@@ -370,13 +376,20 @@ public:
         check(trhip_scene_set_morph_targets(dev->h, instance, target_count, position_deltas, normal_deltas, tangent_deltas, vertex_count));
     }
     void morph(uint32_t instance, const float* weights, uint32_t weight_count) { check(trhip_scene_morph(dev->h, instance, weights, weight_count)); }
+    // Motion of deforming meshes: the switch (kept over scenes), and the latch of the positions of every skinned or morphed mesh as the
+    // previous positions of the frame to come - once per frame, before morph() and skin(); nothing happens while the switch is off.
+    void set_deformation_motion(bool on) { check(trhip_scene_set_deformation_motion(dev->h, on ? 1 : 0)); opt.deformation_motion = on; }
+    void latch_positions() { check(trhip_scene_latch_positions(dev->h)); }
     void update_cameras(const void* camera_data_320, uint32_t count) { check(trhip_scene_update_cameras(dev->h, camera_data_320, count)); }
     // One frame's worth of scene changes (scene_stage::update after update(scene, dt), src/scene.cc:226-235): the instance records,
     // joint matrices and cameras of `s` - as tr::scene_animator::update left them - go to the device and the acceleration
-    // structure is updated once.
-    void apply(const scene_data& s, bool rebuild = false)
+    // structure is updated once.  With `deformation_motion` (by default: as the switch stands) the positions are latched first: latch,
+    // morph, skin, one refit.
+    void apply(const scene_data& s, bool rebuild = false) { apply(s, rebuild, opt.deformation_motion); }
+    void apply(const scene_data& s, bool rebuild, bool deformation_motion)
     {
         update_instances(s.instances.data(), s.instance_count());
+        if(deformation_motion) latch_positions();
         for(const scene_data::morphed_mesh& mm: s.morphed) morph(mm.instance, mm.weights.data(), (uint32_t)mm.weights.size());      // morph, then skin, then one refit
         for(const scene_data::skinned_mesh& sk: s.skinned) skin(sk.instance, sk.joint_transforms.data(), (uint32_t)(sk.joint_transforms.size() / 16));
         update_cameras(s.cameras.data(), s.camera_count());

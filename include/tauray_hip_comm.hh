@@ -151,6 +151,8 @@ public:
         if(n_slots > 1 && this->opt.accumulate)
             throw std::runtime_error("process_rt_renderer: accumulating frames depend on each other, frames in flight must be 1");
         if(comm_id) check_comm(trhip_comm_create(hip_device, nranks, rank, comm_id, &comm));
+        // every rank keeps and latches the previous positions of deforming meshes, like every rank skins them (scene_stage::apply)
+        scene_update.opt.deformation_motion = this->opt.scene.deformation_motion;
         scene_update.set_scene(scene);                                // the scene is replicated on every device (src/gpu_buffer.hh:63-116)
         layers = this->opt.active_viewport_count;
         set_dists(std::vector<double>((size_t)nranks, 1.0 / nranks));

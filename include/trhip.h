@@ -192,6 +192,24 @@ int trhip_scene_set_morph_targets(trhip_device* dev, uint32_t instance, uint32_t
 int trhip_scene_morph(trhip_device* dev, uint32_t instance, const float* weights, uint32_t weight_count);
 /* Reads back the (possibly skinned or morphed) 48-byte vertices of one instance; for tests and tools. */
 int trhip_scene_get_vertices(trhip_device* dev, uint32_t instance, void* out_host, uint32_t max_count);
+/* Motion of deforming meshes (off by default, and then every output is what it was without these calls).  The
+ * previous world position of a hit - feature outputs 6, 7 and 8, the screen_motion target of trhip_pt_render_targets, the temporal reuse
+ * of trhip_restir_di_* - is model_prev * interp(model-space positions); with the switch off the positions are the current ones (the
+ * reference's ray-traced path, shader/rt.glsl:73-79), so a skinned or morphed mesh reports only its rigid motion.  With the switch on they
+ * are the positions of the previous frame:
+ *   trhip_scene_set_deformation_motion(dev, on)  kept over uploads, like the acceleration-structure strategy.  On: allocates a plane
+ *       float[vertices][3] parallel to the scene's vertex array (12 bytes next to the 48 of a vertex) and fills it from the current
+ *       vertices, so until the first latch the motion is the rigid one; an upload while it is on reallocates and refills.  Off: frees it.
+ *   trhip_scene_latch_positions(dev)  copies, for every vertex span that has a skin or morph targets (a shared span once; on a morphed and
+ *       skinned instance its span, i.e. the skinned result), the positions as they stand in the scene into the plane.  Call it once per
+ *       frame, before trhip_scene_morph / trhip_scene_skin: two skin calls in a frame then leave the motion alone, and a mesh that is
+ *       not posed again gets previous = current.  Waits for the device first, as trhip_scene_skin does.  Static spans keep what the fill
+ *       gave them.  With the switch off it succeeds and does nothing.
+ *   trhip_scene_get_previous_positions(dev, instance, out, max_count)  reads back up to max_count float[3] of the instance's span of the
+ *       plane; for tests and tools.  Refused: null output, no scene, an instance out of range, the switch off. */
+int trhip_scene_set_deformation_motion(trhip_device* dev, int on);
+int trhip_scene_latch_positions(trhip_device* dev);
+int trhip_scene_get_previous_positions(trhip_device* dev, uint32_t instance, float* out_host, uint32_t max_count);
 /* After trhip_scene_update_instances: keeps the topology of the last build and recomputes the world triangles, every
  * child box (level by level, bottom-up) and the tri lights - an acceleration-structure *update* instead of a build
  * (src/acceleration_structure.cc:376-422).  Results are identical to a rebuild; traversal gets slower as the

@@ -331,6 +331,9 @@ SYMBOLS = {
     "trhip_scene_set_morph_targets": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _u32]),
     "trhip_scene_morph": (_i, [_vp, _u32, _vp, _u32]),
     "trhip_scene_get_vertices": (_i, [_vp, _u32, _vp, _u32]),
+    "trhip_scene_set_deformation_motion": (_i, [_vp, _i]),
+    "trhip_scene_latch_positions": (_i, [_vp]),
+    "trhip_scene_get_previous_positions": (_i, [_vp, _u32, _vp, _u32]),
     "trhip_scene_get_tri_lights": (_i, [_vp, _vp, _u32]),
     "trhip_pt_create": (_i, [_vp, C.POINTER(PtOptionsC), C.POINTER(_vp)]),
     "trhip_direct_create": (_i, [_vp, C.POINTER(PtOptionsC), C.POINTER(_vp)]),

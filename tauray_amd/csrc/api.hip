@@ -555,6 +555,7 @@ int trhip_scene_upload(trhip_device* dev, const trhip_scene_desc* d) {
     s.gather_emissive_triangles = d->gather_emissive_triangles;
     s.host_tri_light_count = d->gather_emissive_triangles ? tri_lights : 0;
     if (int rc = build_shade_tris(s, -1, nullptr)) return rc;
+    if (s.deformation_motion) if (int rc = fill_previous_positions(s, nullptr)) return rc;      // the switch is kept over uploads, the plane is not
     return update_light_accel(s, true);
 }
 
@@ -636,6 +637,7 @@ int trhip_scene_set_skin(trhip_device* dev, uint32_t instance, const void* sourc
     HIPCHK(hipDeviceSynchronize());
     if (s.skin_slots.size() < s.instance_count) s.skin_slots.resize(s.instance_count);
     DeviceScene::SkinSlot& k = s.skin_slots[instance];
+    s.latch_spans_valid = false;      // the span deforms from now on (trhip_scene_latch_positions)
     if (k.source) { (void)hipFree(k.source); k.source = nullptr; }
     if (k.skins) { (void)hipFree(k.skins); k.skins = nullptr; }
     k.vertex_count = vertex_count;
@@ -677,6 +679,7 @@ int trhip_scene_set_morph_targets(trhip_device* dev, uint32_t instance, uint32_t
     if (s.morph_slots.size() < s.instance_count) s.morph_slots.resize(s.instance_count);
     DeviceScene::MorphSlot& m = s.morph_slots[instance];
     DeviceScene::free_morph(m);
+    s.latch_spans_valid = false;      // as trhip_scene_set_skin
     m.target_count = target_count; m.vertex_count = vertex_count;
     // the base: the instance's vertices as they stand, or the bind pose of its skin
     const bool skinned = instance < s.skin_slots.size() && s.skin_slots[instance].source;
@@ -707,6 +710,35 @@ int trhip_scene_morph(trhip_device* dev, uint32_t instance, const float* weights
         if (memcmp(&s.host_spans[i], &s.host_spans[instance], sizeof(MeshSpan)) == 0) mark_skinned(s, i);
     s.accel_built = false;
     if (s.world_vertices) { (void)hipFree(s.world_vertices); s.world_vertices = nullptr; }
+    return 0;
+}
+int trhip_scene_set_deformation_motion(trhip_device* dev, int on) {
+    DEVCHK(dev);
+    DeviceScene& s = dev->scene;
+    if ((on != 0) == s.deformation_motion) return 0;
+    HIPCHK(hipDeviceSynchronize());   // frames in flight read the plane
+    s.deformation_motion = on != 0;
+    if (!on) { s.free_previous_positions(); return 0; }
+    return fill_previous_positions(s, nullptr);      // previous = current: until the first latch the motion is the rigid one
+}
+int trhip_scene_latch_positions(trhip_device* dev) {
+    DEVCHK(dev);
+    DeviceScene& s = dev->scene;
+    if (!s.deformation_motion || !s.prev_positions) return 0;
+    HIPCHK(hipDeviceSynchronize());   // frames in flight read the plane
+    return latch_positions(s, nullptr);
+}
+int trhip_scene_get_previous_positions(trhip_device* dev, uint32_t instance, float* out_host, uint32_t max_count) {
+    if (!out_host) return set_error("trhip_scene_get_previous_positions: null output");      // what the arguments alone decide comes first
+    DEVCHK(dev);
+    DeviceScene& s = dev->scene;
+    if (s.instance_count == 0) return set_error("trhip_scene_get_previous_positions: no scene (trhip_scene_upload)");
+    if (instance >= s.instance_count) return set_error("trhip_scene_get_previous_positions: instance out of range");
+    if (!s.deformation_motion) return set_error("trhip_scene_get_previous_positions: deformation motion is off (trhip_scene_set_deformation_motion)");
+    const MeshSpan& sp = s.host_spans[instance];
+    const uint n = std::min(max_count, sp.vertex_count);
+    HIPCHK(hipDeviceSynchronize());
+    if (n && s.prev_positions) HIPCHK(hipMemcpy(out_host, s.prev_positions + 3u * (size_t)sp.vertex_offset, (size_t)n * 3u * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 int trhip_scene_get_vertices(trhip_device* dev, uint32_t instance, void* out_host, uint32_t max_count) {

@@ -109,6 +109,13 @@ struct DeviceScene {
     uint sphere_light_count() const { uint c = 0; for (const PointLight& pl : host_point_lights) c += pl.radius != 0.0f ? 1u : 0u; return c; }
     // ---- emitter set of the terminal query (common.h EmitterSet): behind the records in `tris`, all-merged structure only
     uint emitter_count = 0xFFFFFFFFu;           // emitter triangles of the last build or refit; 0xFFFFFFFF = no set
+    // ---- motion of deforming meshes (trhip_scene_set_deformation_motion)
+    bool deformation_motion = false;            // kept over uploads
+    float* prev_positions = nullptr;            // float[vertex_count][3] parallel to `vertices`: the positions at the last latch; null = off
+    MeshSpan* latch_spans = nullptr;            // device list for k_latch_positions: the whole vertex array (the fill), then the deforming spans
+    uint latch_span_count = 0;                  // ... of the latter, each vertex range once
+    uint latch_span_most = 0;                   // ... and the vertex count of the longest
+    bool latch_spans_valid = false;             // false after trhip_scene_set_skin / trhip_scene_set_morph_targets
 
     SceneView view() const {
         SceneView v;
@@ -120,6 +127,7 @@ struct DeviceScene {
         v.instance_count = instance_count; v.point_light_count = point_light_count;
         v.directional_light_count = directional_light_count; v.tri_light_count = tri_light_count;
         v.env_w = env_w; v.env_h = env_h; v.wide_textures = wide_textures; v.tri_count = accel_built ? tri_count : 0; v.node_count = node_count;
+        v.prev_positions = prev_positions;
         return v;
     }
     void free_accel() {
@@ -162,16 +170,24 @@ struct DeviceScene {
         morph_slots.clear();
     }
     bool has_morph(uint instance) const { return instance < morph_slots.size() && morph_slots[instance].base; }
+    void free_previous_positions() {
+        if (prev_positions) (void)hipFree(prev_positions);
+        if (latch_spans) (void)hipFree(latch_spans);
+        prev_positions = nullptr; latch_spans = nullptr; latch_span_count = 0; latch_span_most = 0; latch_spans_valid = false;
+    }
     void free_all() {
         free_accel();
         free_skins();
         free_morphs();
+        free_previous_positions();
         void* ptrs[] = {instances, spans, vertices, indices, point_lights, directional_lights, tex_infos, texels, envmap,
                         alias_table, cameras, prev_cameras, non_opaque, tri_prefix, world_spans, world_vertices, scratch, shade_tris, alpha_base, alpha_tris};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         const int strategy = accel_strategy, light_mode = light_accel_requested;
+        const bool motion = deformation_motion;
         *this = DeviceScene();
         accel_strategy = strategy;
+        deformation_motion = motion;
         light_accel_requested = light_mode;
     }
 };
@@ -183,6 +199,10 @@ int skin_instance(DeviceScene& ds, uint instance, const float* joint_transforms,
 int refit_accel(DeviceScene& ds, hipStream_t stream, trhip_accel_info* info);   // same tree, new boxes (after trhip_scene_update_instances)   // pre_transform.comp per instance
 void mark_skinned(DeviceScene& ds, uint instance);
 int morph_instance(DeviceScene& ds, uint instance, const float* weights, uint weight_count, hipStream_t stream);   // k_morph (morph.h)
+// The previous-position plane: allocated and filled from every vertex of the scene (after an upload, or when the switch goes on), and
+// the latch of the spans that have a skin or morph targets (k_latch_positions).  Both synchronous.
+int fill_previous_positions(DeviceScene& ds, hipStream_t stream);
+int latch_positions(DeviceScene& ds, hipStream_t stream);
 // The sphere-light tree after an upload or trhip_scene_update_lights (`moved`: the records changed) or trhip_scene_set_light_accel: chooses
 // the mode in effect, then builds, refits or drops the tree so that the device matches ds.host_point_lights.  Synchronous.
 int update_light_accel(DeviceScene& ds, bool moved);

@@ -589,7 +589,8 @@ int ensure_world_vertices(DeviceScene& ds, hipStream_t stream) {
 // skin_mat = sum w_k * joint[k]; positions go through skin_mat, normals and tangents through transpose(inverse(skin_mat)).
 // GLSL leaves the arithmetic of inverse() to the driver; here it is the cofactor expansion over 2x2 sub-determinants
 // (only the upper-left 3x3 of the inverse reaches a direction), identical in oracle/oracle.cc so results match bit for bit.
-// The previous-position buffer the shader also fills is read by the raster path only (shader/forward.vert:28).
+// The previous-position buffer the shader also fills is read by the raster path only (shader/forward.vert:28); here the previous
+// positions are kept by k_latch_positions (below), once per frame and ahead of this kernel, when trhip_scene_set_deformation_motion is on.
 __global__ __launch_bounds__(BT) void k_skinning(uint vertex_count, const Vertex* source, const Skin* skins, const m4* joints, uint joint_count, Vertex* destination) {
     uint i = blockIdx.x * BT + threadIdx.x;
     if (i >= vertex_count) return;
@@ -638,7 +639,7 @@ __global__ __launch_bounds__(BT) void k_skinning(uint vertex_count, const Vertex
 // glTF morph targets ahead of skinning: morph.h pins the order of operations (tests/morph_model.py repeats it bit for bit).  One lane per
 // vertex; the active list is the same for every lane (a uniform trip count), and lane i reads floats 3 i .. 3 i + 2 of an active target's
 // plane, so a wave reads 768 consecutive bytes per plane and target.  No atomics: two runs give the same bits.  Like k_skinning it writes
-// no previous positions (only the raster path of the reference reads them).
+// no previous positions: k_latch_positions keeps them.
 __device__ inline f3 morph_accumulate(f3 acc, const float* plane, size_t vertex_count, uint i, const MorphActive* active, uint active_count) {
     for (uint a = 0; a < active_count; ++a) {
         const MorphActive m = active[a];
@@ -669,6 +670,22 @@ __global__ __launch_bounds__(BT) void k_morph(uint vertex_count, const Vertex* b
         }
     }
     destination[i] = dst;
+}
+
+// The previous positions of deforming meshes (trhip_scene_latch_positions): the positions of the listed spans as
+// they stand in the scene go to the plane surface_prev_pos reads (shading.h), float[vertex][3] parallel to the vertex array.  blockIdx.y
+// names the span, one lane per vertex; a lane reads the 12 bytes of a 48-byte vertex that are its position and writes 12 packed bytes,
+// so a wave writes 768 consecutive bytes.  Blocks past the end of a span shorter than the longest leave at once.  No atomics, no LDS.
+// Bounds: `spans` holds gridDim.y records whose vertex_offset + vertex_count the upload checked against the vertex array, and the plane
+// has a slot per vertex of that array.
+__global__ __launch_bounds__(BT) void k_latch_positions(const MeshSpan* spans, const Vertex* vertices, float* previous) {
+    const MeshSpan sp = spans[blockIdx.y];
+    const uint i = blockIdx.x * BT + threadIdx.x;
+    if (i >= sp.vertex_count) return;
+    const size_t v = (size_t)sp.vertex_offset + i;
+    const f3 p = vertices[v].pos;
+    float* out = previous + 3u * v;
+    out[0] = p.x; out[1] = p.y; out[2] = p.z;
 }
 
 __global__ __launch_bounds__(BT) void k_build_shade_tris(uint n_spans, const MeshSpan* spans, const Vertex* vertices, const uint* indices, ShadeTri* out, f4* tangents) {
@@ -786,6 +803,58 @@ int morph_instance(DeviceScene& ds, uint instance, const float* weights, uint we
     }
     if (!skinned) if (int rc = build_shade_tris(ds, (int)instance, stream)) return rc;
     HIPCHK(hipStreamSynchronize(stream));   // `active` leaves scope
+    return 0;
+}
+
+// The device list of k_latch_positions: record 0 is the whole vertex array (what the fill copies), behind it every vertex range that a
+// skin or morph targets deform, once (instances that share a span move together; a morphed and skinned instance is its span, the
+// skinned result).  Rebuilt when a skin or targets were set since the last time.
+static int update_latch_spans(DeviceScene& ds, hipStream_t stream) {
+    if (ds.latch_spans_valid) return 0;
+    std::vector<MeshSpan> list(1, MeshSpan{0u, ds.vertex_count, 0u, 0u});
+    std::vector<std::pair<uint, uint>> seen;
+    uint most = 0;
+    for (uint i = 0; i < ds.instance_count; ++i) {
+        if (!((i < ds.skin_slots.size() && ds.skin_slots[i].source) || ds.has_morph(i))) continue;
+        const MeshSpan& sp = ds.host_spans[i];
+        const std::pair<uint, uint> range(sp.vertex_offset, sp.vertex_count);
+        if (sp.vertex_count == 0 || std::find(seen.begin(), seen.end(), range) != seen.end()) continue;
+        seen.push_back(range);
+        list.push_back(MeshSpan{sp.vertex_offset, sp.vertex_count, 0u, 0u});
+        most = std::max(most, sp.vertex_count);
+    }
+    if (ds.latch_spans) { (void)hipFree(ds.latch_spans); ds.latch_spans = nullptr; }
+    ds.latch_span_count = 0; ds.latch_span_most = 0;
+    HIPCHK(hipMalloc(&ds.latch_spans, list.size() * sizeof(MeshSpan)));
+    HIPCHK(hipMemcpyAsync(ds.latch_spans, list.data(), list.size() * sizeof(MeshSpan), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));   // `list` leaves scope
+    ds.latch_span_count = (uint)list.size() - 1u;
+    ds.latch_span_most = most;
+    ds.latch_spans_valid = true;
+    return 0;
+}
+
+int fill_previous_positions(DeviceScene& ds, hipStream_t stream) {
+    ds.free_previous_positions();
+    if (ds.vertex_count == 0 || !ds.vertices) return 0;      // nothing to keep: surface_prev_pos is never reached either
+    HIPCHK(hipMalloc(&ds.prev_positions, (size_t)ds.vertex_count * 3u * sizeof(float)));
+    if (int rc = update_latch_spans(ds, stream)) return rc;
+    hipLaunchKernelGGL(k_latch_positions, dim3((ds.vertex_count + BT - 1) / BT, 1), dim3(BT), 0, stream, ds.latch_spans, ds.vertices, ds.prev_positions);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int latch_positions(DeviceScene& ds, hipStream_t stream) {
+    if (!ds.prev_positions) return 0;
+    if (int rc = update_latch_spans(ds, stream)) return rc;
+    if (ds.latch_span_count == 0) return 0;      // the listed spans are not empty
+    for (uint first = 0; first < ds.latch_span_count; first += 65535u) {      // gridDim.y is 16 bits wide
+        const uint count = std::min(65535u, ds.latch_span_count - first);
+        hipLaunchKernelGGL(k_latch_positions, dim3((ds.latch_span_most + BT - 1) / BT, count), dim3(BT), 0, stream, ds.latch_spans + 1 + first, ds.vertices, ds.prev_positions);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(stream));
     return 0;
 }
 

@@ -258,6 +258,10 @@ struct SceneView {
     uint env_w, env_h;
     uint tri_count, node_count;
     uint wide_textures;          // some texture of the scene is TEXTURE_FORMAT_RGBA16
+    // trhip_scene_set_deformation_motion: float[vertices][3] parallel to obj_vertices, the model-space positions as the last
+    // trhip_scene_latch_positions found them; null = off (surface_prev_pos interpolates the current positions).  Last, so that every
+    // other member keeps its offset in the kernel-argument segment.
+    const float* prev_positions;
 };
 // The TLAS leaf records of a two-level structure: behind the node_count node slots in the same allocation (SceneView stays as it is)
 TR_HD const TlasLeaf* tlas_leaves(const SceneView& sv) { return reinterpret_cast<const TlasLeaf*>(sv.nodes4 + sv.node_count); }

@@ -576,12 +576,24 @@ struct SurfacePoint {
 
 // CALC_PREV_VERTEX_POS (shader/rt.glsl:73-79): the hit point under the previous frame's model matrix.  Interpolates the
 // uploaded model-space vertices (also under PRE_TRANSFORMED_VERTICES, where the reference goes through inverse(model)).
+// With SceneView::prev_positions (trhip_scene_set_deformation_motion) the three positions come from that plane
+// instead - what a skinned or morphed mesh held at the last latch - through the same span and indices and with the same arithmetic; the
+// pointer is a kernel argument, so the branch is uniform over the grid.
 TR_DEV f3 surface_prev_pos(const SceneView& sv, int instance_id, int primitive_id, float bu, float bv) {
     const MeshSpan span = sv.obj_spans[instance_id];
     const uint* ix = sv.indices + span.index_offset + 3u * (uint)primitive_id;
-    const Vertex* vb = sv.obj_vertices + span.vertex_offset;
     const f3 b = F3(1.0f - bu - bv, bu, bv);
-    const f3 object_pos = vb[ix[0]].pos * b.x + vb[ix[1]].pos * b.y + vb[ix[2]].pos * b.z;
+    f3 object_pos;
+    if (sv.prev_positions) {
+        const float* pb = sv.prev_positions + 3u * (size_t)span.vertex_offset;
+        const float* p0 = pb + 3u * (size_t)ix[0];
+        const float* p1 = pb + 3u * (size_t)ix[1];
+        const float* p2 = pb + 3u * (size_t)ix[2];
+        object_pos = F3(p0[0], p0[1], p0[2]) * b.x + F3(p1[0], p1[1], p1[2]) * b.y + F3(p2[0], p2[1], p2[2]) * b.z;
+    } else {
+        const Vertex* vb = sv.obj_vertices + span.vertex_offset;
+        object_pos = vb[ix[0]].pos * b.x + vb[ix[1]].pos * b.y + vb[ix[2]].pos * b.z;
+    }
     return F3(mul(sv.instances[instance_id].model_prev, F4(object_pos, 1)));
 }
 

@@ -13,6 +13,7 @@
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
+//              [--animation[=NAME] --framerate=F [--deformation-motion]]   (screen motion follows skinned and morphed meshes as they deform)
 //              [--display=headless|looking-glass --lkg-params=viewports,midplane,depth,relative_dist
 //               --lkg-calibration=display_index,pitch,slope,center,fringe,viewCone,invView,verticalAngle,DPI,screenW,screenH,flipImageX,flipImageY,flipSubp]
 //              (a Looking Glass output: --width / --height are the size of one view, one composed screenW x screenH file per frame)
@@ -77,6 +78,9 @@ static const char* const usage_text =
     "                         the panel, as its calibration file has it (required: no display service is read here); positional or name=value\n"
     "  --tonemap=filmic|linear|gamma-correction|reinhard|reinhard-luminance --exposure=E --gamma=G\n"
     "  --animation[=NAME] --framerate=F --accumulation --envmap=FILE --camera-grid=w,h,x,y -t --skip-nan-check\n"
+    "  --deformation-motion   screen motion (--denoiser=bmfr, --taa, --temporal-reprojection, the temporal reuse of --renderer=restir-di) follows\n"
+    "                         skinned and morphed meshes as they deform: their positions are kept every frame before --animation poses them\n"
+    "                         (off: their rigid motion only; every renderer that plays --animation; nothing changes without a deforming mesh)\n"
     "  --fake-devices=N | --devices=0,1,... --distribution-strategy=scanline|shuffled-strips --frames-in-flight=N --frames-per-launch=N\n"
     "  --process-count=N --process-rank=R --device=D --comm-id=FILE [--comm-nonce=N] [--exchange=rccl|ipc] [--shard=views]\n"
     "  --dump-scene=out.trsc\n";
@@ -221,6 +225,7 @@ int main(int argc, char** argv)
             else if(a == "--animation") animation_flag = true;                                  // any clip a node has (src/tauray.cc:252-253)
             else if(starts(a, "--animation=")) { animation_flag = true; animation_name = val("--animation="); }
             else if(starts(a, "--framerate=")) framerate = std::stod(val("--framerate="));
+            else if(a == "--deformation-motion") opt.scene.deformation_motion = true;             // scene_stage::options (trhip_scene_set_deformation_motion)
             else if(starts(a, "--envmap=")) envmap_path = val("--envmap=");                        // lat-long .hdr (src/options.hh:125)
             else if(starts(a, "--warmup-frames=")) warmup = std::stoi(val("--warmup-frames="));
             else if(starts(a, "--renderer="))

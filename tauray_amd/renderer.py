@@ -204,9 +204,10 @@ class SceneStage:
     """scene_stage: uploads the flattened scene and builds the acceleration structure on the device."""
 
     def __init__(self, ctx: Context, scene: Optional[SceneDesc] = None, fast_trace_rebuilds: bool = False, as_strategy: int = 0,
-                 dynamic=None):
+                 dynamic=None, deformation_motion: bool = False):
         """`as_strategy`: trhip_scene_set_accel_strategy (0 all-merged, the default; 1 per-mesh; 2 static-merged-dynamic-per-mesh).
-        `dynamic`: per-instance marks (trhip_scene_set_dynamic_instances) of the scenes this stage is given, or None (all static)."""
+        `dynamic`: per-instance marks (trhip_scene_set_dynamic_instances) of the scenes this stage is given, or None (all static).
+        `deformation_motion`: set_deformation_motion for the scenes this stage is given, and what animate() and pose() do by default."""
         self.ctx = ctx
         self.scene = None
         self.accel = None
@@ -214,6 +215,7 @@ class SceneStage:
         self.fast_trace_rebuilds = fast_trace_rebuilds
         self.as_strategy = int(as_strategy)
         self.dynamic = None if dynamic is None else np.ascontiguousarray(np.asarray(dynamic).astype(np.uint8))
+        self.deformation_motion = bool(deformation_motion)
         if scene is not None:
             self.set_scene(scene)
 
@@ -249,6 +251,8 @@ class SceneStage:
         d.non_opaque = p(non_opaque)
         d.gather_emissive_triangles = 1 if getattr(scene, "tri_light_count", 0) > 0 else 0
         check(L.trhip_scene_upload(self.ctx.h, C.byref(d)))
+        # the device handle keeps the switch over uploads; set behind the upload, so that a plane is never filled for the scene that leaves
+        check(L.trhip_scene_set_deformation_motion(self.ctx.h, 1 if self.deformation_motion else 0))
         self.scene = scene
         self.camera_data = cams.copy()           # what the device renders with (update_cameras follows)
         self.previous_camera_data = None         # camera_pair.previous as last set (None: the cameras themselves)
@@ -263,6 +267,8 @@ class SceneStage:
             self.morph(mm.instance, scene.morph_weights(mm), refit=None)
         for sk in getattr(scene, "skinned", []):
             self.skin(sk.instance, scene.joint_transforms(sk), refit=None)
+        if self.deformation_motion:      # the plane was filled with the uploaded bind pose: a still scene has previous = current
+            self.latch_positions()
         info = AccelInfoC()
         check(L.trhip_scene_set_accel_strategy(self.ctx.h, self.as_strategy))
         if self.dynamic is not None:
@@ -302,21 +308,27 @@ class SceneStage:
         dl = np.ascontiguousarray(self.scene.directional_lights if directional_lights is None else directional_lights)
         check(_lib.lib().trhip_scene_update_lights(self.ctx.h, pl.ctypes.data if len(pl) else None, len(pl), dl.ctypes.data if len(dl) else None, len(dl)))
 
-    def pose(self, node_globals: dict, refit: bool = True):
+    def pose(self, node_globals: dict, refit: bool = True, deformation_motion: Optional[bool] = None):
         """New global transforms of the joint nodes (an animation step of the caller's): every skinned mesh is skinned again
-        and the acceleration structure updated."""
+        and the acceleration structure updated.  `deformation_motion`: latch the positions first (latch_positions); None = as the
+        switch stands."""
+        if self.deformation_motion if deformation_motion is None else deformation_motion:
+            self.latch_positions()
         for sk in self.scene.skinned:
             self.skin(sk.instance, self.scene.joint_transforms(sk, node_globals), refit=None)
         return self._accel_after_change(refit)
 
-    def animate(self, animator, dt_ticks: int, refit: bool = True):
+    def animate(self, animator, dt_ticks: int, refit: bool = True, deformation_motion: Optional[bool] = None):
         """One frame of a playing animation (update(scene, dt) of src/scene.cc:226-235 followed by scene_stage::update):
         `animator` (tauray_amd.animation.SceneAnimator over this stage's scene) advances by dt microseconds; the new instance
         records, cameras (with last frame's as camera_pair.previous) and joint matrices go to the device, and the acceleration
-        structure is updated once - refitted, or rebuilt with `refit=False`."""
+        structure is updated once - refitted, or rebuilt with `refit=False`.  With `deformation_motion` the positions of the deforming
+        meshes are latched first (latch_positions; None = as the switch, set_deformation_motion, stands): latch, morph, skin, one refit."""
         instances, cameras, node_globals = animator.update(dt_ticks)
         inst = np.ascontiguousarray(instances)
         check(_lib.lib().trhip_scene_update_instances(self.ctx.h, inst.ctypes.data, len(inst)))
+        if self.deformation_motion if deformation_motion is None else deformation_motion:
+            self.latch_positions()
         for mm in self.scene.morphed:       # morph, then skin, then one refit
             self.morph(mm.instance, self.scene.morph_weights(mm), refit=None)
         for sk in self.scene.skinned:
@@ -404,6 +416,25 @@ class SceneStage:
         w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
         check(_lib.lib().trhip_scene_morph(self.ctx.h, instance, w.ctypes.data if len(w) else None, len(w)))
         return None if refit is None else self._accel_after_change(refit)
+
+    def set_deformation_motion(self, on: bool):
+        """trhip_scene_set_deformation_motion: with it on, the previous world position of a hit on a skinned or morphed mesh (feature
+        outputs 6 to 8, the screen_motion target, the temporal reuse of ReSTIR DI) interpolates the positions latch_positions last kept,
+        not the current ones.  Kept over scenes; off by default."""
+        check(_lib.lib().trhip_scene_set_deformation_motion(self.ctx.h, 1 if on else 0))
+        self.deformation_motion = bool(on)
+
+    def latch_positions(self):
+        """trhip_scene_latch_positions: keeps the positions of every skinned or morphed mesh as they stand, as the previous positions of the
+        frame to come.  Once per frame, before morph() and skin(); nothing happens while the switch is off."""
+        check(_lib.lib().trhip_scene_latch_positions(self.ctx.h))
+
+    def previous_positions(self, instance: int) -> np.ndarray:
+        """trhip_scene_get_previous_positions: the (vertices, 3) float32 previous model-space positions of the instance's mesh."""
+        n = int(self.scene.spans[instance]["vertex_count"])
+        out = np.zeros((n, 3), dtype=np.float32)
+        check(_lib.lib().trhip_scene_get_previous_positions(self.ctx.h, instance, out.ctypes.data, n))
+        return out
 
     def vertices(self, instance: int) -> np.ndarray:
         from .scene import VERTEX
@@ -1221,8 +1252,14 @@ class _ViewportFrameRenderer:
     """What the single-device renderers of whole viewports share (DshgiRenderer, RestirDiRenderer): `size`, `viewports` (one per camera), the
     `color` and `display` images of every viewport, the tonemap stage and the tail of a frame that runs it - all on one stream."""
 
-    def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, tonemap: Optional[TonemapStage]):
+    def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, tonemap: Optional[TonemapStage],
+                 deformation_motion: Optional[bool] = None):
+        """`deformation_motion`: None leaves the scene stage's switch (SceneStage.set_deformation_motion) as it stands, else sets it - on
+        the caller's scene stage, for every stage that shares it: the switch belongs to the scene, not to this renderer (the C++
+        viewport-frame renderers have no such argument and take the switch from the scene stage they are given)."""
         self.ctx, self.ss, self.size = ctx, scene_stage, tuple(size)
+        if deformation_motion is not None:
+            scene_stage.set_deformation_motion(deformation_motion)
         self.viewports = max(len(scene.cameras), 1)
         self.tonemap = tonemap or TonemapStage(ctx)
         pixels = self.size[0] * self.size[1] * self.viewports
@@ -1252,10 +1289,11 @@ class DshgiRenderer(_ViewportFrameRenderer):
     see both and the indirect term carries their light."""
 
     def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: PtOptionsC, sh: Optional[dict] = None,
-                 use_probe_visibility=False, brdf_integration=None, tonemap: Optional[TonemapStage] = None, record_surface=False):
+                 use_probe_visibility=False, brdf_integration=None, tonemap: Optional[TonemapStage] = None, record_surface=False,
+                 deformation_motion: Optional[bool] = None):
         if not scene.sh_grids:
             raise ValueError("DshgiRenderer: the scene has no light-probe grid (TR_data.light_probe of type GRID)")
-        super().__init__(ctx, scene_stage, scene, size, tonemap)
+        super().__init__(ctx, scene_stage, scene, size, tonemap, deformation_motion)
         self.grids = list(scene.sh_grids)
         self.sh = ShRenderer(ctx, scene_stage, self.grids, sh)
         order = self.sh.stages[0].order
@@ -1355,8 +1393,8 @@ class RestirDiRenderer(_ViewportFrameRenderer):
     """--renderer=restir-di: the ReSTIR DI stage renders every viewport, the frame is tonemapped - on one stream."""
 
     def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: Optional[dict] = None, projection=None,
-                 tonemap: Optional[TonemapStage] = None):
-        super().__init__(ctx, scene_stage, scene, size, tonemap)
+                 tonemap: Optional[TonemapStage] = None, deformation_motion: Optional[bool] = None):
+        super().__init__(ctx, scene_stage, scene, size, tonemap, deformation_motion)
         if projection is None:
             projection = scene.cameras[0].projection if scene.cameras else 0
         self.stage = RestirDiStage(ctx, scene_stage, self.size, self.viewports, options, projection)
@@ -1646,6 +1684,7 @@ class RtRenderer:
     def __init__(self, ctx: Context, scene: SceneDesc, options: PtOptionsC, size, strategy=DISTRIBUTION_SCANLINE,
                  rank=0, world_size=1, viewports=1, tonemap: Optional[dict] = None, accumulate=False, use_torch=None,
                  shard="pixels", frames_in_flight=1, stage_cls=None, exchange=None, frames_per_launch=1, as_strategy=0, dynamic=None,
+                 deformation_motion=False,
                  denoiser=None, denoiser_settings=_lib.BMFR_DIFFUSE_ONLY, spatial_reprojection=None, temporal_reprojection=0.0,
                  taa=0, taa_edge_dilation=True, taa_anti_shimmer=False, looking_glass=None):
         """`shard`: what the ranks divide among themselves - "pixels" (the reference's distribution strategies, partial frames
@@ -1657,7 +1696,8 @@ class RtRenderer:
         layer groups, frame-major, and everything after the path tracing - exchange, stitch, tonemap - handles the B frames in
         one go.  For frames that do not accumulate; what the ranks of a pixel-sharded job use, whose launches are small.
         `as_strategy`, `dynamic`: the acceleration-structure strategy and dynamic marks of the scene stage (SceneStage; the C++
-        rt_renderer::options::scene).
+        rt_renderer::options::scene).  `deformation_motion`: the scene stage's switch (SceneStage.set_deformation_motion): its animate()
+        and pose() then latch the positions of skinned and morphed meshes, and screen motion follows their deformation.
         `denoiser`: None, or "bmfr" (the reference's --denoiser=bmfr, src/post_processing_renderer.cc:53-106): the path tracer renders the
         gbuffer entries the BMFR stage reads next to the colour target, every frame is a fresh frame of samples_per_pixel samples (the
         sample counter keeps counting), and post_process runs the stage before the tonemap stage (which is then a stage of its own: the
@@ -1725,7 +1765,7 @@ class RtRenderer:
             from .looking_glass import looking_glass_cameras
             looking_glass_cameras(scene, looking_glass.viewports, looking_glass.midplane, looking_glass.depth, looking_glass.relative_dist,
                                   looking_glass.calibration)
-        self.scene_update = SceneStage(ctx, scene, as_strategy=as_strategy, dynamic=dynamic)
+        self.scene_update = SceneStage(ctx, scene, as_strategy=as_strategy, dynamic=dynamic, deformation_motion=deformation_motion)
         if self.shard == "pixels":
             workloads = [1.0 / world_size] * world_size
             self.dists = self._device_dists(workloads)
