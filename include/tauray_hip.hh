@@ -926,7 +926,7 @@ public:
     trhip_dshgi* h = nullptr;
 };
 
-// What the single-device renderers of whole viewports share (dshgi_renderer, restir_di_renderer): the zeroed `color` and `display` images of
+// What the single-device renderers of whole viewports share (dshgi_renderer, restir_di_renderer, restir_gi_renderer): the zeroed `color` and `display` images of
 // every viewport (one per camera), the tonemap stage, the list of all viewports and the tail of a frame that tonemaps it.  A derived
 // renderer's destructor releases the stages that write the images; the images go after them.
 class viewport_frame_renderer
@@ -1130,6 +1130,109 @@ public:
 
 private:
     static const options& checked(const options& o) { o.restir.check(); return o; }      // the options are refused before anything is allocated
+};
+
+// ReSTIR GI (trhip_restir_gi_*; csrc/restir_gi.h pins the rule): one bounce of indirect light by reservoir resampling - per frame the
+// initial kernel (first hit, one cosine-hemisphere ray, a light sample at its hit), the temporal kernel (the history merge) and the spatial
+// kernel (neighbour merge, shading).  `size`, `layers`: the images of a frame.  The limits are listed in trhip.h and DESIGN.md section 25.
+class restir_gi_stage
+{
+public:
+    struct options
+    {
+        uint32_t spatial_samples = 2;     // --restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse
+        float search_radius = 32.0f;
+        float max_confidence = 16.0f;
+        bool temporal_reuse = true;
+        float min_ray_dist = 1e-4f;
+        uint32_t rng_seed = 0;
+        bool record = false;
+        int projection = 0;
+        // what trhip_restir_gi_create refuses, said without a device
+        void check() const
+        {
+            if(spatial_samples > 4) throw std::runtime_error("restir-gi: spatial_samples " + std::to_string(spatial_samples) + " is outside 0..4");
+            if(!(search_radius > 0.0f) || !(search_radius <= 1024.0f)) throw std::runtime_error("restir-gi: search_radius must be in (0, 1024]");
+            if(!(max_confidence >= 1.0f) || !std::isfinite(max_confidence)) throw std::runtime_error("restir-gi: max_confidence must be finite and at least 1");
+            if(!(min_ray_dist > 0.0f) || !std::isfinite(min_ray_dist)) throw std::runtime_error("restir-gi: min_ray_dist must be finite and positive");
+        }
+        // --restir-gi=...: positional or name=value; a field left out keeps its value
+        void parse(const std::string& text)
+        {
+            const char* const o = "--restir-gi";
+            const auto v = parse_struct_option(o, text, {"spatial_samples", "search_radius", "max_confidence", "temporal_reuse"});
+            const double n = struct_number(o, v, "spatial_samples", (double)spatial_samples);
+            if(!(n >= 0) || !(n <= 4) || n != std::floor(n)) throw std::runtime_error(std::string(o) + ": spatial_samples must be a whole number in 0..4");
+            spatial_samples = (uint32_t)n;
+            search_radius = (float)struct_number(o, v, "search_radius", search_radius);
+            max_confidence = (float)struct_number(o, v, "max_confidence", max_confidence);
+            auto it = v.find("temporal_reuse");
+            if(it != v.end())
+            {
+                const std::string& t = it->second;
+                if(t == "on" || t == "true" || t == "1") temporal_reuse = true;
+                else if(t == "off" || t == "false" || t == "0") temporal_reuse = false;
+                else throw std::runtime_error(std::string(o) + ": temporal_reuse=" + t + " is neither on nor off");
+            }
+            check();
+        }
+    };
+    restir_gi_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), size(size), layers(layers), opt(opt)
+    {
+        opt.check();
+        trhip_restir_gi_options o = {};
+        o.spatial_samples = opt.spatial_samples; o.search_radius = opt.search_radius; o.max_confidence = opt.max_confidence;
+        o.temporal_reuse = opt.temporal_reuse; o.min_ray_dist = opt.min_ray_dist; o.rng_seed = opt.rng_seed; o.record = opt.record;
+        check(trhip_restir_gi_create(dev.h, &o, size.x, size.y, layers, &h));
+    }
+    restir_gi_stage(const restir_gi_stage&) = delete;
+    ~restir_gi_stage() { trhip_restir_gi_destroy(h); }
+    // one frame of the listed viewports: out = in + indirect light (RGBA32F [viewports][h][w]; `in` null: (0, 0, 0, 1); `out` may be `in`)
+    void run(const std::vector<uint32_t>& viewports, const void* in, void* out, void* stream = nullptr)
+    {
+        check(trhip_restir_gi_render(h, opt.projection, viewports.data(), (uint32_t)viewports.size(), in, out, stream));
+    }
+    void reset() { check(trhip_restir_gi_reset(h)); }
+    trhip_restir_gi_timings get_timings() { trhip_restir_gi_timings t; check(trhip_restir_gi_get_timings(h, &t)); return t; }
+
+    device* dev;
+    uvec2 size;
+    uint32_t layers;
+    options opt;
+    trhip_restir_gi* h = nullptr;
+};
+
+// --renderer=restir-gi: the ReSTIR DI stage renders the direct light of every viewport, the ReSTIR GI stage adds one bounce of indirect
+// light to it, the frame is tonemapped - on one stream.
+class restir_gi_renderer: public viewport_frame_renderer
+{
+public:
+    struct options
+    {
+        restir_di_stage::options restir;        // the direct half (--restir)
+        restir_gi_stage::options restir_gi;     // the indirect half (--restir-gi)
+        tonemap_stage::options tonemap;
+    };
+    restir_gi_renderer(device& dev, const scene_data& scene, uvec2 size, const options& opt_)
+    : viewport_frame_renderer(dev, scene, size, checked(opt_).tonemap), opt(opt_)
+    {
+        direct.reset(new restir_di_stage(dev, size, viewports, opt.restir));
+        stage.reset(new restir_gi_stage(dev, size, viewports, opt.restir_gi));
+    }
+    ~restir_gi_renderer() { stage.reset(); direct.reset(); }
+    void render(void* stream = nullptr)
+    {
+        direct->run(viewport_list, color, stream);
+        stage->run(viewport_list, color, color, stream);
+        finish_frame(stream);
+    }
+
+    options opt;
+    std::unique_ptr<restir_di_stage> direct;
+    std::unique_ptr<restir_gi_stage> stage;
+
+private:
+    static const options& checked(const options& o) { o.restir.check(); o.restir_gi.check(); return o; }      // refused before anything is allocated
 };
 
 class load_balancer

@@ -1015,6 +1015,77 @@ int trhip_restir_di_get_timings(trhip_restir_di* stage, trhip_restir_di_timings*
 #define TRHIP_RESTIR_DI_FINAL 6       /* trhip_restir_di_final [layers][h][w] */
 int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
 
+/* ---- ReSTIR GI: reservoir resampling of one bounce of indirect light (after Ouyang et al. 2021 and the ReSTIR DI stage above, whose
+ * resampling rule it keeps; the reference has no such renderer, its --renderer=restir is ReSTIR PT and is not built here: this is
+ * `restir-gi` everywhere).  csrc/restir_gi.hip; the order of operations and of random draws is pinned in csrc/restir_gi.h.  A sample is
+ * a point x_s on a surface, its geometric normal n_s towards the pixel that found it and the radiance L_o it sent there.  Per frame and
+ * chunk of 64 viewports three launches:
+ *   initial    the first hit and its surface record (DI's), one cosine-hemisphere ray from it, the closest hit x_s, one light sample at
+ *              x_s drawn as sample_canonical draws it, with its shadow ray: L_o = contribution * visibility / light_pdf
+ *   temporal   no rays: the initial sample's weight (DI's rule with one candidate), and with temporal_reuse the merge of the history
+ *              reservoir of the stochastically reprojected pixel unless temporal_edge_detection rejects it
+ *   spatial    up to spatial_samples neighbours within search_radius, merged with pairwise MIS and the reconnection Jacobian, one shadow
+ *              ray per re-evaluation; out.rgb = in.rgb + contribution * visibility * uc_weight of the chosen sample, out.a = in.a
+ * The contribution of a sample at a surface is the ggx_bsdf_pdf lobes through modulate_bsdf for the direction to x_s, times L_o; 0 when
+ * the direction is below the surface's flat normal or behind n_s.  The stage's three random streams are disjoint from each other and
+ * from both of DI's (fourth sampler coordinate 0x80000000 + 3 * frame + pass).
+ * Limits:
+ *   1. L_o is the radiance x_s sent towards the pixel that found it and is not evaluated again for a pixel that reuses the sample: the
+ *      paper's Lambertian assumption, a bias on glossy secondary surfaces.
+ *   2. No transmission: the contribution is 0 below the flat normal.
+ *   3. A surface with roughness below 0.001 gets no specular indirect light (no delta lobes).
+ *   4. History samples are not validated again when geometry or lights move; max_confidence bounds their age.
+ *   5. Sphere lights are points, as in DI.  Cosine-hemisphere initial sampling only, one bounce, one device. */
+typedef struct trhip_restir_gi trhip_restir_gi;
+typedef struct trhip_restir_gi_options {
+    uint32_t spatial_samples;         /* 0..4 */
+    float search_radius;              /* pixels, > 0, at most 1024 */
+    float max_confidence;             /* >= 1, the clamp of the temporal merge */
+    int32_t temporal_reuse;           /* 0 / 1 */
+    float min_ray_dist;               /* > 0 */
+    uint32_t rng_seed;                /* raw; pcg() applied if non-zero, as the path tracer's */
+    int32_t record;                   /* keep the decision records (test hook) */
+} trhip_restir_gi_options;
+typedef struct trhip_restir_gi_reservoir {    /* the null sample has n_s = 0 and L_o = 0 */
+    float x_s[3], uc_weight;
+    float n_s[3], target_function;
+    float L_o[3], confidence;
+} trhip_restir_gi_reservoir;
+typedef struct trhip_restir_gi_initial {      /* per pixel; the last row is the temporal kernel's update_reservoir of the initial sample */
+    float draw[2], pdf; uint32_t traced;      /* unit .xy of the direction's draw; traced: the secondary ray was cast */
+    float dir[3], t;                          /* the secondary ray and its hit as trace_closest4 returns it, instance_id -1: none */
+    int32_t instance_id, primitive_id; float u, v;
+    uint32_t light_draw[4];                   /* the four words sample_canonical took at x_s */
+    float L_o[3], target;                     /* target: of the initial sample at the pixel (visibility 1) */
+    float weight, sel_draw; uint32_t selected, pad;
+} trhip_restir_gi_initial;
+typedef struct trhip_restir_gi_timings {      /* device ms of the last render */
+    float initial_ms, temporal_ms, spatial_ms, total_ms;
+    uint32_t frames;
+    char initial_name[64], temporal_name[64], spatial_name[64];    /* "restir gi initial", "restir gi temporal", "restir gi spatial" */
+} trhip_restir_gi_timings;
+/* Refuses a null device (there is no CPU fallback), zero or oversized dimensions and every option outside its range. */
+int trhip_restir_gi_create(trhip_device* dev, const trhip_restir_gi_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_restir_gi** out);
+void trhip_restir_gi_destroy(trhip_restir_gi* stage);
+int trhip_restir_gi_reset(trhip_restir_gi* stage);        /* forgets the history and restarts the frame counter */
+/* One frame of `count` viewports (at most the stage's layers), three launches per 64, asynchronous on `stream`: out_color_dev RGBA32F
+ * [count][h][w] = in_color_dev + indirect light; in_color_dev may be null ((0, 0, 0, 1) everywhere) or out_color_dev itself.  Refuses a
+ * device without a scene or acceleration structure and a viewport out of range.  History is kept per layer, the position in the list:
+ * with temporal_reuse, a list that differs from the last frame's is refused until trhip_restir_gi_reset. */
+int trhip_restir_gi_render(trhip_restir_gi* stage, int projection, const uint32_t* viewports, uint32_t count, const void* in_color_dev, void* out_color_dev,
+                           void* stream);
+int trhip_restir_gi_get_timings(trhip_restir_gi* stage, trhip_restir_gi_timings* out);   /* waits for the last render */
+#define TRHIP_RESTIR_GI_SURFACE 0     /* trhip_restir_di_surface [layers][h][w] of the last frame */
+#define TRHIP_RESTIR_GI_CANONICAL 1   /* trhip_restir_gi_reservoir [layers][h][w]: what the temporal kernel wrote */
+#define TRHIP_RESTIR_GI_HISTORY 2     /* trhip_restir_gi_reservoir [layers][h][w]: what the spatial kernel wrote */
+#define TRHIP_RESTIR_GI_INITIAL 3     /* trhip_restir_gi_initial [layers][h][w] (record only, as the five below) */
+#define TRHIP_RESTIR_GI_SECONDARY 4   /* trhip_restir_di_surface [layers][h][w]: x_s's surface record, instance_id -1 without a secondary hit */
+#define TRHIP_RESTIR_GI_LIGHT 5       /* trhip_restir_di_candidate [layers][h][w]: the light sample at x_s (weight, draw, selected are 0) */
+#define TRHIP_RESTIR_GI_TEMPORAL 6    /* trhip_restir_di_temporal [layers][h][w] */
+#define TRHIP_RESTIR_GI_SPATIAL 7     /* trhip_restir_di_spatial [layers][h][w][spatial_samples] */
+#define TRHIP_RESTIR_GI_FINAL 8       /* trhip_restir_di_final [layers][h][w] */
+int trhip_restir_gi_download(trhip_restir_gi* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
+
 #ifdef __cplusplus
 }
 #endif

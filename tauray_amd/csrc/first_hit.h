@@ -1,7 +1,9 @@
 // The first hit of a pixel of a listed viewport: the front half that k_feature (api.hip), k_gbuffer (reprojection.hip), k_dshgi_indirect
-// (dshgi.hip) and k_restir_di_canonical (restir_di.hip) share, and the launch shape of the three that take a viewport list.  The four
-// kernels call first_hit and first_hit_surface below and are built with the same flags (Makefile), so what one of them finds and shades
-// at a pixel is what the others do: k_feature's images are the reference the other three are tested against bit for bit.
+// (dshgi.hip), k_restir_di_canonical (restir_di.hip) and k_restir_gi_initial (restir_gi.hip) share, and the launch shape of the four that
+// take a viewport list.  The five kernels call first_hit and first_hit_surface below and are built with the same flags (Makefile), so
+// what one of them finds and shades at a pixel is what the others do: k_feature's images are the reference k_gbuffer, k_dshgi_indirect
+// and k_restir_di_canonical are tested against bit for bit, and k_restir_gi_initial's surface record is tested against
+// k_restir_di_canonical's.
 //   device  tile_pixel, ViewportList, first_hit, first_hit_surface
 //   host    whole_image_launch, tile_grid (they need LaunchCtx and dim3; the rest of a viewport frame's host side is in stage_host.h)
 #pragma once

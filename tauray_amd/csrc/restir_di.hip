@@ -44,81 +44,6 @@ struct RestirParams {
 
 #define TR_U(x) __float_as_uint(x)
 
-// sample_canonical (restir_di.glsl:251-354): select, fetch, compute, as sample_explicit_light.  The record stays in L for the contribution.
-TR_DEV RestirSample sample_canonical(const SceneView& sv, const RestirParams& P, u4 rnd, f3 pos, RestirLightRecord& L, float& light_pdf) {
-    f4 u = u4_to_unit(rnd);
-    enum { NONE = 0, POINT, TRI, DIR, ENV };
-    int kind = NONE;
-    if ((u.w -= P.prob_point) < 0) kind = POINT;
-    else if ((u.w -= P.prob_tri) < 0) kind = TRI;
-    else if ((u.w -= P.prob_dir) < 0) kind = DIR;
-    else if ((u.w -= P.prob_env) < 0) kind = ENV;
-    const int n_point = (int)sv.point_light_count, n_tri = (int)sv.tri_light_count, n_dir = (int)sv.directional_light_count;
-    // a class with probability > 0 has lights (nee_probabilities); the counts are tested all the same, no fetch goes past an array
-    if ((kind == POINT && n_point <= 0) || (kind == TRI && n_tri <= 0) || (kind == DIR && n_dir <= 0) || (kind == ENV && sv.environment_proj < 0)) kind = NONE;
-    asm volatile("" : "+v"(kind));
-    const int light_count = kind == POINT ? n_point : kind == TRI ? n_tri : n_dir;
-    const int light_index = clampi((int)((kind == POINT ? u.x : u.z) * light_count), 0, light_count - 1);
-    L.r0 = u4{0u, 0u, 0u, 0u}; L.r1 = L.r0; L.r2 = L.r0; L.r3 = L.r0;
-    int alias_i = 0;
-    if (kind == POINT) { const u4* rec = reinterpret_cast<const u4*>(sv.point_lights + light_index); L.r0 = rec[0]; L.r1 = rec[1]; L.r2 = rec[2]; L.r3 = rec[3]; }
-    if (kind == TRI) { const u4* rec = reinterpret_cast<const u4*>(sv.tri_lights + light_index); L.r0 = rec[0]; L.r1 = rec[1]; L.r2 = rec[2]; L.r3 = rec[3]; }
-    if (kind == DIR) { const u4* rec = reinterpret_cast<const u4*>(sv.directional_lights + light_index); L.r0 = rec[0]; L.r1 = rec[1]; }
-    u4 alias = {0u, 0u, 0u, 0u};
-    if (kind == ENV) {
-        const uint sx = sv.env_w, sy = sv.env_h;
-        const uint ipx = clampu(rnd.x / (0xFFFFFFFFu / sx), 0u, sx - 1u), ipy = clampu(rnd.y / (0xFFFFFFFFu / sy), 0u, sy - 1u);
-        alias_i = (int)(ipx + ipy * sx);
-        alias = *reinterpret_cast<const u4*>(sv.alias_table + alias_i);
-    }
-    L.valid = kind != NONE;
-#define TR_F(x) __uint_as_float(x)
-    RestirSample s = restir_null_sample();
-    light_pdf = 1.0f;
-    if (kind == POINT) {
-        s.type = 0u; s.index = (uint)light_index;
-        light_pdf = (1.0f / (float)light_count) * P.prob_point;
-    } else if (kind == TRI) {
-        s.type = 1u; s.index = (uint)light_index;
-        const f3 A = F3(TR_F(L.r0.x), TR_F(L.r0.y), TR_F(L.r0.z)) - pos, B = F3(TR_F(L.r0.w), TR_F(L.r1.x), TR_F(L.r1.y)) - pos, C = F3(TR_F(L.r1.z), TR_F(L.r1.w), TR_F(L.r2.x)) - pos;
-        float tri_pdf = 0.0f;
-        const f3 out_dir = sample_triangle_light<RoundedMath>(1, F2(u.x, u.y), A, B, C, tri_pdf);
-        const float out_length = ray_plane_intersection_dist(out_dir, A, B, C);
-        if (isinf(tri_pdf) || tri_pdf <= 0 || out_length <= P.min_ray_dist || any_nan(out_dir)) tri_pdf = 1e9f;
-        const f3 bary = get_barycentric_coords(out_dir * out_length, A, B, C);
-        s.data = F2(bary.x, bary.y);
-        light_pdf = (tri_pdf * (1.0f / (float)light_count)) * P.prob_tri;
-    } else if (kind == DIR) {
-        s.type = 2u; s.index = (uint)light_index;
-        const float dir_cutoff = TR_F(L.r1.w);
-        light_pdf = dir_cutoff >= 1.0f ? 1.0f : 1.0f / (2.0f * TR_PI * (1.0f - dir_cutoff));
-        light_pdf = (light_pdf / (float)light_count) * P.prob_dir;
-        s.data = F2(u.x, u.y);
-    } else if (kind == ENV) {
-        s.type = 3u; s.index = 0u;
-        const uint sx = sv.env_w, sy = sv.env_h, pixel_count = sx * sy;
-        int i = alias_i;
-        light_pdf = TR_F(alias.z);
-        if (rnd.z > alias.y) { i = (int)alias.x; light_pdf = TR_F(alias.w); }
-        const int ppx = (int)((uint)i % sx), ppy = (int)((uint)i / sx);
-        const f2 off = F2((float)(uint)(rnd.x * pixel_count), (float)(uint)(rnd.y * pixel_count)) * TR_INV_UINT32_MAX;
-        s.data = (F2((float)ppx, (float)ppy) + off) / F2((float)sx, (float)sy);
-        light_pdf = light_pdf * P.prob_env;
-    }
-#undef TR_F
-    return s;
-}
-
-template <bool TWO_LEVEL>
-TR_DEV float shadow_of(const SceneView& sv, const RestirParams& P, f3 pos, f3 contribution, f3 dir, float dist2, int* stack, int& overflow) {
-    float visibility = 0.0f;
-    if (restir_casts(contribution)) {
-        TraceStats st = {};
-        visibility = trace_shadow4<false, TWO_LEVEL>(sv, pos, dir, P.min_ray_dist, sqrtf(dist2) - P.min_ray_dist, stack, st, overflow);
-    }
-    return visibility;
-}
-
 // tile_pixel's launch shape (first_hit.h).
 // Two waves per SIMD: unbounded, the fp64 functions of RoundedMath took it to 256 VGPRs plus AGPR copies at one wave.
 template <bool TWO_LEVEL, bool TEMPORAL>
@@ -177,11 +102,11 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, Lau
             const u4 rnd = pcg4d(ls.rs);
             RestirLightRecord Lr;
             float light_pdf;
-            const RestirSample s = sample_canonical(sv, P, rnd, dom.pos, Lr, light_pdf);
+            const RestirSample s = restir_sample_canonical(sv, P, rnd, dom.pos, Lr, light_pdf);
             f3 light_dir, light_norm;
             float light_dist2;
             const f3 contrib = restir_contribution(sv, s, Lr, dom, light_dir, light_dist2, light_norm);
-            const float visibility = shadow_of<TWO_LEVEL>(sv, P, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
+            const float visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
             const float target = rgb_to_luminance(contrib * visibility);
             float weight = mis_weight * target / light_pdf;
             if (isnan(weight)) weight = 0.0f;
@@ -348,7 +273,7 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, Launc
                     f3 light_dir, light_norm;
                     float light_dist2;
                     const f3 contrib = restir_contribution(sv, n.ls, Ln, dom, light_dir, light_dist2, light_norm);
-                    const float visibility = shadow_of<TWO_LEVEL>(sv, P, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
+                    const float visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
                     const float target = rgb_to_luminance(contrib * visibility);
                     const f3 x = dom.pos + light_dir * sqrtf(light_dist2);
                     const float jacob = n.ls.type > 1u ? 1.0f : restir_jacobian(sample_domain.pos, dom.pos, x, light_norm);
@@ -366,7 +291,7 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, Launc
                     f3 light_dir, light_norm;
                     float light_dist2;
                     const f3 contrib = restir_contribution(sv, canonical.ls, Lc, sample_domain, light_dir, light_dist2, light_norm);
-                    const float visibility = shadow_of<TWO_LEVEL>(sv, P, sample_domain.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
+                    const float visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, sample_domain.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
                     const float alt_target = rgb_to_luminance(contrib * visibility);
                     const f3 x = sample_domain.pos + light_dir * sqrtf(light_dist2);
                     const float jacob = canonical.ls.type > 1u ? 1.0f : restir_jacobian(dom.pos, sample_domain.pos, x, light_norm);
@@ -398,7 +323,7 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, Launc
     f3 light_dir, light_norm;
     float light_dist2;
     const f3 contrib = restir_contribution(sv, r.ls, Lf, dom, light_dir, light_dist2, light_norm);
-    const float visibility = shadow_of<TWO_LEVEL>(sv, P, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
+    const float visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
     if (overflow) *overflow_flag = 1;
     const f3 shaded = contrib * visibility;
     restir_store(P.history + pix, restir_pack(r));

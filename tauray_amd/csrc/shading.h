@@ -43,12 +43,13 @@ TR_DEV f3 view_to_tangent_space(f3 view, const m3& tbn) {   // math.glsl:472-478
     if (tview.z < 1e-5f) tview = F3(tview.x, tview.y, fmax2(tview.z, 1e-5f));
     return normalize(tview);
 }
+template <class M = LibMath>
 TR_DEV f2 sample_concentric_disk(f2 u) {     // math.glsl:205-218
     f2 uo = 2.0f * u - 1.0f;
     f2 a = {fabsf(uo.x), fabsf(uo.y)};
     if (a.x < 0.0001f && a.y < 0.0001f) return F2(0);
     f2 rt = (a.x > a.y) ? F2(uo.x, TR_PI / 4 * (uo.y / uo.x)) : F2(uo.y, TR_PI / 2 - TR_PI / 4 * (uo.x / uo.y));
-    return rt.x * F2(tcos(rt.y), tsin(rt.y));
+    return rt.x * F2(M::cos(rt.y), M::sin(rt.y));
 }
 template <class M = LibMath>
 TR_DEV float sample_blackman_harris(float u) {   // math.glsl:220-228
@@ -79,8 +80,9 @@ TR_DEV f2 sample_regular_polygon(f2 u, float angle, uint sides) {   // math.glsl
     u = u.x + u.y > 1 ? 1 - u : u;
     return b * u.x + c * u.y;
 }
+template <class M = LibMath>
 TR_DEV f3 sample_cosine_hemisphere(f2 u) {   // math.glsl:294-298
-    f2 d = sample_concentric_disk(u);
+    f2 d = sample_concentric_disk<M>(u);
     return F3(d.x, d.y, sqrtf(fmax2(0.0f, 1 - dot(d, d))));
 }
 TR_DEV float pdf_cosine_hemisphere(f3 dir) { return fmax2(dir.z, 0.0f) * (1.0f / TR_PI); }

@@ -2,7 +2,7 @@
 // (its HIP device, its events, its frame counter, its device allocations) and the tails every entry point shares (finishing create,
 // destroy, the total time, a size-checked download).  Host only: nothing here is seen by a kernel.  A stage struct derives from StageHost
 // and keeps its own fields; argument validation, parameter packing and kernel launches stay in the stage's file.  The entry points that
-// render a list of viewports (gbuffer, dshgi, restir_di) share the checks and the chunk walk at the end of the file.
+// render a list of viewports (gbuffer, dshgi, restir_di, restir_gi) share the checks and the chunk walk at the end of the file.
 #pragma once
 #include <cstdint>
 #include <cstring>

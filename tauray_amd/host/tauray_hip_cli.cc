@@ -10,6 +10,7 @@
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
 //              [--renderer=restir-di [--restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse]]
+//              [--renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse] [--restir=...]]
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
@@ -60,6 +61,11 @@ static const char* const usage_text =
     "                         pixels are merged; one pass per frame (one device; works with --animation, --headless, --camera-grid, --tonemap,\n"
     "                         --envmap and -t; no denoiser, --taa, reprojection, --display=looking-glass or --samples-per-pixel above 1;\n"
     "                         --renderer=restir, the reference's ReSTIR PT, is not built)\n"
+    "  --renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse]   (2,32,16,on; positional or name=value)\n"
+    "                         ReSTIR GI: the direct light of --renderer=restir-di (--restir= configures it) plus one bounce of indirect light by\n"
+    "                         reservoir resampling - one cosine-hemisphere ray per pixel, the radiance its hit reflects kept as the sample; the\n"
+    "                         previous frame's reservoir and up to `spatial_samples` (0..4) neighbours within search_radius pixels are merged\n"
+    "                         (one device; works with and refuses what --renderer=restir-di does)\n"
     "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
     "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
     "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
@@ -104,6 +110,8 @@ int main(int argc, char** argv)
         std::string brdf_integration_path;
         restir_di_stage::options restir;                                    // --restir
         bool restir_given = false;
+        restir_gi_stage::options restir_gi;                                 // --restir-gi
+        bool restir_gi_given = false;
         std::vector<int> devices;
         bool timing = false;
         std::string dump_scene;
@@ -231,10 +239,11 @@ int main(int argc, char** argv)
             else if(starts(a, "--renderer="))
             {
                 renderer = val("--renderer=");
-                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes" && renderer != "dshgi" && renderer != "restir-di")
-                    throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes, dshgi, restir-di)");
+                if(renderer != "path-tracer" && renderer != "direct" && renderer != "sh-probes" && renderer != "dshgi" && renderer != "restir-di" && renderer != "restir-gi")
+                    throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes, dshgi, restir-di, restir-gi)");
             }
             else if(starts(a, "--restir=")) { restir.parse(val("--restir=")); restir_given = true; }
+            else if(starts(a, "--restir-gi=")) { restir_gi.parse(val("--restir-gi=")); restir_gi_given = true; }
             else if(a == "--use-probe-visibility") use_probe_visibility = true;
             else if(starts(a, "--brdf-integration=")) brdf_integration_path = val("--brdf-integration=");
             else if(starts(a, "--samples-per-probe="))
@@ -348,7 +357,19 @@ int main(int argc, char** argv)
         }
         if(scene_path.empty()) throw std::runtime_error(usage_text);
         if(renderer == "dshgi" && display == "looking-glass") throw std::runtime_error("--renderer=dshgi: no --display=looking-glass (the composition of a light field from it is not built)");
-        if(restir_given && renderer != "restir-di") throw std::runtime_error("--restir sets the options of --renderer=restir-di");
+        if(restir_given && renderer != "restir-di" && renderer != "restir-gi") throw std::runtime_error("--restir sets the options of --renderer=restir-di");
+        if(restir_gi_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi sets the options of --renderer=restir-gi");
+        if(renderer == "restir-gi")
+        {   // what the renderer does not do, said before a scene is read
+            if(opt.bmfr) throw std::runtime_error("--renderer=restir-gi: no --denoiser (the resampling is the noise reduction; the denoiser's feature targets are not written)");
+            if(opt.taa) throw std::runtime_error("--renderer=restir-gi: no --taa (the stages write no screen_motion target and their cameras do not jitter)");
+            if(!opt.spatial_reprojection.empty() || opt.temporal_reprojection > 0.0f)
+                throw std::runtime_error("--renderer=restir-gi: no --spatial-reprojection or --temporal-reprojection (the stages write no G-buffer targets)");
+            if(display == "looking-glass") throw std::runtime_error("--renderer=restir-gi: no --display=looking-glass (the composition of a light field from it is not built)");
+            if(opt.samples_per_pixel > 1) throw std::runtime_error("--renderer=restir-gi: one pass per frame, --samples-per-pixel must be 1 (the reservoirs carry the samples from frame to frame)");
+            if(devices.size() > 1 || fake_devices > 1) throw std::runtime_error("--renderer=restir-gi runs on one device: the reservoirs of neighbouring pixels and of the previous frame live on one device");
+            if(process_count > 0 || shard_views) throw std::runtime_error("--renderer=restir-gi runs in one process: no --process-count or --shard");
+        }
         if(renderer == "restir-di")
         {   // what the renderer does not do, said before a scene is read
             if(opt.bmfr) throw std::runtime_error("--renderer=restir-di: no --denoiser (the resampling is the noise reduction; the denoiser's feature targets are not written)");
@@ -446,7 +467,7 @@ int main(int argc, char** argv)
             so.bounce_mode = opt.bounce_mode; so.tri_light_mode = opt.tri_light_mode;
             return so;
         };
-        // The frames of a renderer of whole viewports on one device (dshgi, restir-di): make(dev, ss) builds it on the uploaded scene,
+        // The frames of a renderer of whole viewports on one device (dshgi, restir-di, restir-gi): make(dev, ss) builds it on the uploaded scene,
         // scene_moved(r) runs after an animation step has been applied, print_timings(r) prints the lines of a frame under "DEVICE 0".
         auto run_viewport_frames = [&](auto make, auto scene_moved, auto print_timings)
         {
@@ -565,6 +586,28 @@ int main(int argc, char** argv)
             {
                 const trhip_restir_di_timings t = rr.stage->get_timings();
                 std::cout << "\t\t[" << t.canonical_name << "] " << t.canonical_ms << " ms\n\t\t[" << t.spatial_name << "] " << t.spatial_ms << " ms\n";
+            });
+            return 0;
+        }
+        if(renderer == "restir-gi")
+        {
+            restir_gi_renderer::options ro;
+            ro.restir = restir;
+            ro.restir.min_ray_dist = opt.min_ray_dist; ro.restir.rng_seed = (uint32_t)opt.rng_seed; ro.restir.projection = opt.projection;
+            ro.restir_gi = restir_gi;
+            ro.restir_gi.min_ray_dist = opt.min_ray_dist; ro.restir_gi.rng_seed = (uint32_t)opt.rng_seed; ro.restir_gi.projection = opt.projection;
+            ro.tonemap = opt.tonemap;
+            ro.restir.check();
+            ro.restir_gi.check();
+            run_viewport_frames([&](device& dev, scene_stage&) { return std::make_unique<restir_gi_renderer>(dev, scene, size, ro); },
+                                [](restir_gi_renderer&) {},
+                                [](restir_gi_renderer& rr)
+            {
+                const trhip_restir_di_timings d = rr.direct->get_timings();
+                std::cout << "\t\t[" << d.canonical_name << "] " << d.canonical_ms << " ms\n\t\t[" << d.spatial_name << "] " << d.spatial_ms << " ms\n";
+                const trhip_restir_gi_timings t = rr.stage->get_timings();
+                std::cout << "\t\t[" << t.initial_name << "] " << t.initial_ms << " ms\n\t\t[" << t.temporal_name << "] " << t.temporal_ms << " ms\n\t\t["
+                          << t.spatial_name << "] " << t.spatial_ms << " ms\n";
             });
             return 0;
         }

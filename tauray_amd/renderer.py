@@ -1249,7 +1249,7 @@ class DshgiStage(_PostStage):
 
 
 class _ViewportFrameRenderer:
-    """What the single-device renderers of whole viewports share (DshgiRenderer, RestirDiRenderer): `size`, `viewports` (one per camera), the
+    """What the single-device renderers of whole viewports share (DshgiRenderer, RestirDiRenderer, RestirGiRenderer): `size`, `viewports` (one per camera), the
     `color` and `display` images of every viewport, the tonemap stage and the tail of a frame that runs it - all on one stream."""
 
     def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, tonemap: Optional[TonemapStage],
@@ -1410,6 +1410,91 @@ class RestirDiRenderer(_ViewportFrameRenderer):
         return self.stage.timings()
 
     def close(self):
+        self.stage.close()
+        super().close()
+
+
+def restir_gi_options(**kw) -> dict:
+    """trhip_restir_gi_options at the command line's defaults (--restir-gi=2,32,16,on)."""
+    o = dict(spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0, record=False)
+    unknown = set(kw) - set(o)
+    if unknown:
+        raise AttributeError(f"unknown ReSTIR GI option {sorted(unknown)}")
+    o.update(kw)
+    return o
+
+
+class RestirGiStage(_PostStage):
+    """ReSTIR GI (trhip_restir_gi_*, include/trhip.h; csrc/restir_gi.h pins the rule): one bounce of indirect light by reservoir
+    resampling - per frame the initial kernel (first hit, one cosine-hemisphere ray, a light sample at its hit), the temporal kernel (the
+    history merge, no rays) and the spatial kernel (neighbour merge, shading).  `size`: (w, h); `layers`: the viewports of a frame;
+    `options`: restir_gi_options()."""
+
+    PREFIX, TIMINGS = "restir_gi", _lib.RestirGiTimingsC
+    _RECORDS = {"surface": (_lib.RESTIR_GI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_GI_CANONICAL, _lib.RESTIR_GI_RESERVOIR_DTYPE),
+                "history": (_lib.RESTIR_GI_HISTORY, _lib.RESTIR_GI_RESERVOIR_DTYPE), "initial": (_lib.RESTIR_GI_INITIAL, _lib.RESTIR_GI_INITIAL_DTYPE),
+                "secondary": (_lib.RESTIR_GI_SECONDARY, _lib.RESTIR_DI_SURFACE_DTYPE), "light": (_lib.RESTIR_GI_LIGHT, _lib.RESTIR_DI_CANDIDATE_DTYPE),
+                "temporal": (_lib.RESTIR_GI_TEMPORAL, _lib.RESTIR_DI_TEMPORAL_DTYPE), "spatial": (_lib.RESTIR_GI_SPATIAL, _lib.RESTIR_DI_SPATIAL_DTYPE),
+                "final": (_lib.RESTIR_GI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE)}
+
+    def __init__(self, ctx: Optional[Context], scene_stage: Optional[SceneStage], size, layers=1, options: Optional[dict] = None, projection=0):
+        self.ctx, self.scene_stage, self.size, self.layers, self.projection = ctx, scene_stage, tuple(size), int(layers), int(projection)
+        o = self.options = restir_gi_options(**(options or {}))
+        opt = _lib.RestirGiOptionsC(max(int(o["spatial_samples"]), 0), float(o["search_radius"]), float(o["max_confidence"]), int(o["temporal_reuse"]),
+                                    float(o["min_ray_dist"]), int(o["rng_seed"]) & 0xFFFFFFFF, int(o["record"]))
+        if int(o["spatial_samples"]) < 0:
+            raise TrhipError("RestirGiStage: spatial_samples is a count")
+        self._create(getattr(ctx, "h", None), C.byref(opt), max(int(self.size[0]), 0), max(int(self.size[1]), 0), max(self.layers, 0))
+
+    def run(self, viewports, in_color, out, stream=None):
+        """One frame: `out` RGBA32F [len(viewports)][h][w] = `in_color` + the indirect light of the listed viewports; `in_color` None
+        counts as (0, 0, 0, 1), `out` may be `in_color`.  History is kept per position in the list: with temporal reuse the list stays
+        the same from frame to frame until `reset`."""
+        v = np.ascontiguousarray(viewports, dtype=np.uint32)
+        check(_lib.lib().trhip_restir_gi_render(self.h, self.projection, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size,
+                                                None if in_color is None else _ptr(in_color), _ptr(out), stream))
+
+    def reset(self):
+        """Forgets the history: the next frame is the first frame of a new stage."""
+        check(_lib.lib().trhip_restir_gi_reset(self.h))
+
+    def download(self, name: str) -> np.ndarray:
+        """A structured array [layers][h][w] ("spatial": one more axis) of "surface", "canonical", "history" and, with record, "initial",
+        "secondary", "light", "temporal", "spatial", "final"."""
+        code, dtype = self._RECORDS[name]
+        shape = (self.layers, self.size[1], self.size[0])
+        if name == "spatial":
+            shape += (int(self.options["spatial_samples"]),)
+        return self._download(code, shape, np.dtype(dtype))
+
+
+class RestirGiRenderer(_ViewportFrameRenderer):
+    """--renderer=restir-gi: the ReSTIR DI stage renders the direct light of every viewport, the ReSTIR GI stage adds one bounce of indirect
+    light to it, the frame is tonemapped - on one stream.  `di_options`: restir_di_options(); `options`: restir_gi_options()."""
+
+    def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: Optional[dict] = None, di_options: Optional[dict] = None,
+                 projection=None, tonemap: Optional[TonemapStage] = None, deformation_motion: Optional[bool] = None):
+        super().__init__(ctx, scene_stage, scene, size, tonemap, deformation_motion)
+        if projection is None:
+            projection = scene.cameras[0].projection if scene.cameras else 0
+        self.direct = RestirDiStage(ctx, scene_stage, self.size, self.viewports, di_options, projection)
+        self.stage = RestirGiStage(ctx, scene_stage, self.size, self.viewports, options, projection)
+
+    def render(self, stream=None, tonemap=True):
+        v = np.arange(self.viewports)
+        self.direct.run(v, self.color, stream)
+        self.stage.run(v, self.color, self.color, stream)
+        self._finish(stream, tonemap)
+
+    def reset(self):
+        self.direct.reset()
+        self.stage.reset()
+
+    def timings(self) -> dict:
+        return {"direct": self.direct.timings(), "indirect": self.stage.timings()}
+
+    def close(self):
+        self.direct.close()
         self.stage.close()
         super().close()
 
