@@ -1029,62 +1029,86 @@ public:
 // ReSTIR DI (trhip_restir_di_*; written after shader/restir_di.glsl and its two ray generation shaders): per frame the canonical kernel
 // (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).  `size`, `layers`: the images
 // of a frame.  The decisions where the shaders are stale or undefined are listed in trhip.h and DESIGN.md section 21.
+// The options the two ReSTIR stages share, their checks and their parsing; `who` is the renderer in a message ("restir-di"), `o` the
+// command-line option ("--restir").
+struct restir_shared_options
+{
+    uint32_t spatial_samples = 2;
+    float search_radius = 32.0f;
+    float max_confidence = 16.0f;
+    bool temporal_reuse = true;
+    float min_ray_dist = 1e-4f;
+    uint32_t rng_seed = 0;
+    bool record = false;
+    int projection = 0;
+
+protected:
+    // what trhip_restir_*_create refuses of these, said without a device
+    void check_shared(const std::string& who) const
+    {
+        if(spatial_samples > 4) throw std::runtime_error(who + ": spatial_samples " + std::to_string(spatial_samples) + " is outside 0..4");
+        if(!(search_radius > 0.0f) || !(search_radius <= 1024.0f)) throw std::runtime_error(who + ": search_radius must be in (0, 1024]");
+        if(!(max_confidence >= 1.0f) || !std::isfinite(max_confidence)) throw std::runtime_error(who + ": max_confidence must be finite and at least 1");
+        if(!(min_ray_dist > 0.0f) || !std::isfinite(min_ray_dist)) throw std::runtime_error(who + ": min_ray_dist must be finite and positive");
+    }
+    using fields = std::map<std::string, std::string>;
+    static void whole(const char* o, const fields& v, const char* name, uint32_t& field, double lo, double hi)
+    {
+        const double n = struct_number(o, v, name, (double)field);
+        if(!(n >= lo) || !(n <= hi) || n != std::floor(n))
+            throw std::runtime_error(std::string(o) + ": " + name + " must be a whole number in " + std::to_string((int)lo) + ".." + std::to_string((int)hi));
+        field = (uint32_t)n;
+    }
+    void parse_shared(const char* o, const fields& v)
+    {
+        whole(o, v, "spatial_samples", spatial_samples, 0, 4);
+        search_radius = (float)struct_number(o, v, "search_radius", search_radius);
+        max_confidence = (float)struct_number(o, v, "max_confidence", max_confidence);
+        auto it = v.find("temporal_reuse");
+        if(it != v.end())
+        {
+            const std::string& t = it->second;
+            if(t == "on" || t == "true" || t == "1") temporal_reuse = true;
+            else if(t == "off" || t == "false" || t == "0") temporal_reuse = false;
+            else throw std::runtime_error(std::string(o) + ": temporal_reuse=" + t + " is neither on nor off");
+        }
+    }
+    // the fields trhip_restir_di_options and trhip_restir_gi_options share
+    template<class C> void fill_shared(C& o) const
+    {
+        o.spatial_samples = spatial_samples; o.search_radius = search_radius; o.max_confidence = max_confidence;
+        o.temporal_reuse = temporal_reuse; o.min_ray_dist = min_ray_dist; o.rng_seed = rng_seed; o.record = record;
+    }
+};
+
 class restir_di_stage
 {
 public:
-    struct options
+    // Set the fields by name: the shared base's fields come first in aggregate order, `candidates` after them.
+    struct options: restir_shared_options
     {
         uint32_t candidates = 4;          // --restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse
-        uint32_t spatial_samples = 2;
-        float search_radius = 32.0f;
-        float max_confidence = 16.0f;
-        bool temporal_reuse = true;
-        float min_ray_dist = 1e-4f;
-        uint32_t rng_seed = 0;
-        bool record = false;
-        int projection = 0;
         // what trhip_restir_di_create refuses, said without a device
         void check() const
         {
             if(candidates < 1 || candidates > 32) throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " is outside 1..32");
-            if(spatial_samples > 4) throw std::runtime_error("restir-di: spatial_samples " + std::to_string(spatial_samples) + " is outside 0..4");
-            if(!(search_radius > 0.0f) || !(search_radius <= 1024.0f)) throw std::runtime_error("restir-di: search_radius must be in (0, 1024]");
-            if(!(max_confidence >= 1.0f) || !std::isfinite(max_confidence)) throw std::runtime_error("restir-di: max_confidence must be finite and at least 1");
-            if(!(min_ray_dist > 0.0f) || !std::isfinite(min_ray_dist)) throw std::runtime_error("restir-di: min_ray_dist must be finite and positive");
+            check_shared("restir-di");
         }
         // --restir=...: positional or name=value; a field left out keeps its value
         void parse(const std::string& text)
         {
             const char* const o = "--restir";
             const auto v = parse_struct_option(o, text, {"candidates", "spatial_samples", "search_radius", "max_confidence", "temporal_reuse"});
-            auto whole = [&](const char* name, uint32_t& field, double lo, double hi)
-            {
-                const double n = struct_number(o, v, name, (double)field);
-                if(!(n >= lo) || !(n <= hi) || n != std::floor(n))
-                    throw std::runtime_error(std::string(o) + ": " + name + " must be a whole number in " + std::to_string((int)lo) + ".." + std::to_string((int)hi));
-                field = (uint32_t)n;
-            };
-            whole("candidates", candidates, 1, 32);
-            whole("spatial_samples", spatial_samples, 0, 4);
-            search_radius = (float)struct_number(o, v, "search_radius", search_radius);
-            max_confidence = (float)struct_number(o, v, "max_confidence", max_confidence);
-            auto it = v.find("temporal_reuse");
-            if(it != v.end())
-            {
-                const std::string& t = it->second;
-                if(t == "on" || t == "true" || t == "1") temporal_reuse = true;
-                else if(t == "off" || t == "false" || t == "0") temporal_reuse = false;
-                else throw std::runtime_error(std::string(o) + ": temporal_reuse=" + t + " is neither on nor off");
-            }
+            whole(o, v, "candidates", candidates, 1, 32);
+            parse_shared(o, v);
             check();
         }
+        trhip_restir_di_options c_options() const { trhip_restir_di_options o = {}; o.candidates = candidates; fill_shared(o); return o; }
     };
     restir_di_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), size(size), layers(layers), opt(opt)
     {
         opt.check();
-        trhip_restir_di_options o = {};
-        o.candidates = opt.candidates; o.spatial_samples = opt.spatial_samples; o.search_radius = opt.search_radius; o.max_confidence = opt.max_confidence;
-        o.temporal_reuse = opt.temporal_reuse; o.min_ray_dist = opt.min_ray_dist; o.rng_seed = opt.rng_seed; o.record = opt.record;
+        const trhip_restir_di_options o = opt.c_options();
         check(trhip_restir_di_create(dev.h, &o, size.x, size.y, layers, &h));
     }
     restir_di_stage(const restir_di_stage&) = delete;
@@ -1138,51 +1162,23 @@ private:
 class restir_gi_stage
 {
 public:
-    struct options
+    struct options: restir_shared_options     // --restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse
     {
-        uint32_t spatial_samples = 2;     // --restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse
-        float search_radius = 32.0f;
-        float max_confidence = 16.0f;
-        bool temporal_reuse = true;
-        float min_ray_dist = 1e-4f;
-        uint32_t rng_seed = 0;
-        bool record = false;
-        int projection = 0;
         // what trhip_restir_gi_create refuses, said without a device
-        void check() const
-        {
-            if(spatial_samples > 4) throw std::runtime_error("restir-gi: spatial_samples " + std::to_string(spatial_samples) + " is outside 0..4");
-            if(!(search_radius > 0.0f) || !(search_radius <= 1024.0f)) throw std::runtime_error("restir-gi: search_radius must be in (0, 1024]");
-            if(!(max_confidence >= 1.0f) || !std::isfinite(max_confidence)) throw std::runtime_error("restir-gi: max_confidence must be finite and at least 1");
-            if(!(min_ray_dist > 0.0f) || !std::isfinite(min_ray_dist)) throw std::runtime_error("restir-gi: min_ray_dist must be finite and positive");
-        }
+        void check() const { check_shared("restir-gi"); }
         // --restir-gi=...: positional or name=value; a field left out keeps its value
         void parse(const std::string& text)
         {
             const char* const o = "--restir-gi";
-            const auto v = parse_struct_option(o, text, {"spatial_samples", "search_radius", "max_confidence", "temporal_reuse"});
-            const double n = struct_number(o, v, "spatial_samples", (double)spatial_samples);
-            if(!(n >= 0) || !(n <= 4) || n != std::floor(n)) throw std::runtime_error(std::string(o) + ": spatial_samples must be a whole number in 0..4");
-            spatial_samples = (uint32_t)n;
-            search_radius = (float)struct_number(o, v, "search_radius", search_radius);
-            max_confidence = (float)struct_number(o, v, "max_confidence", max_confidence);
-            auto it = v.find("temporal_reuse");
-            if(it != v.end())
-            {
-                const std::string& t = it->second;
-                if(t == "on" || t == "true" || t == "1") temporal_reuse = true;
-                else if(t == "off" || t == "false" || t == "0") temporal_reuse = false;
-                else throw std::runtime_error(std::string(o) + ": temporal_reuse=" + t + " is neither on nor off");
-            }
+            parse_shared(o, parse_struct_option(o, text, {"spatial_samples", "search_radius", "max_confidence", "temporal_reuse"}));
             check();
         }
+        trhip_restir_gi_options c_options() const { trhip_restir_gi_options o = {}; fill_shared(o); return o; }
     };
     restir_gi_stage(device& dev, uvec2 size, uint32_t layers, const options& opt): dev(&dev), size(size), layers(layers), opt(opt)
     {
         opt.check();
-        trhip_restir_gi_options o = {};
-        o.spatial_samples = opt.spatial_samples; o.search_radius = opt.search_radius; o.max_confidence = opt.max_confidence;
-        o.temporal_reuse = opt.temporal_reuse; o.min_ray_dist = opt.min_ray_dist; o.rng_seed = opt.rng_seed; o.record = opt.record;
+        const trhip_restir_gi_options o = opt.c_options();
         check(trhip_restir_gi_create(dev.h, &o, size.x, size.y, layers, &h));
     }
     restir_gi_stage(const restir_gi_stage&) = delete;

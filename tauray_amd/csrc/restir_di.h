@@ -82,25 +82,19 @@
 //   colour       contribution of the chosen sample here times its shadow ray's visibility;
 //                out = (contribution * uc_weight + emission, 1);  a pixel without a surface: the null reservoir and the direct stage's
 //                miss colour (k_direct: the visible directional lights in order, then the environment)
+//
+// Where the code is.  The sections reprojection, reuse, temporal, neighbours, spatial and jacobian, update_reservoir, visibility, the
+// surface record and the temporal, spatial and final decision records: restir_resample.h, once for this stage and ReSTIR GI.  Here:
+// the reservoir, the candidate record, sample_canonical, light_contribution and RestirDiKind, what restir_resample.h asks of a sample.
+// candidates, the miss colour and the emission of `colour`: the kernels (restir_di.hip).
 #pragma once
-#include "common.h"
-#include "shading.h"
-#include "trace.h"
+#include "restir_resample.h"
 
 namespace tr {
 
 constexpr uint RESTIR_NULL_INDEX = (1u << 30) - 1u;
-constexpr int RESTIR_MAX_CANDIDATES = 32, RESTIR_MAX_SPATIAL = 4;
+constexpr int RESTIR_MAX_CANDIDATES = 32;
 
-struct alignas(16) RestirSurface {       // trhip_restir_di_surface
-    f3 pos; int instance_id;
-    f3 mapped_normal; float metallic;
-    f3 flat_normal; float roughness;
-    f3 view; float transmittance;
-    f4 albedo;
-    f3 emission; float f0;
-    float ior_in, ior_out, pad0, pad1;
-};
 struct alignas(16) RestirReservoir {     // trhip_restir_di_reservoir
     float uc_weight, target_function; uint light; float confidence;
     f2 light_data; uint pad0, pad1;
@@ -110,112 +104,10 @@ struct RestirCandidateRecord {           // trhip_restir_di_candidate
     f3 contribution; float visibility;   // the unshadowed contribution
     float weight, draw; uint selected, pad;
 };
-struct RestirTemporalRecord {            // trhip_restir_di_temporal
-    int px, py; uint reuse; float prev_confidence;
-    float target, weight, draw; uint selected;
-};
-struct RestirSpatialRecord {             // trhip_restir_di_spatial
-    int px, py; uint good, selected;     // px = -1: an empty slot
-    float target_n, visibility_n, jacobian_n, m;
-    float wi, draw, target_c, visibility_c;
-    float jacobian_c, mis_canonical, pad0, pad1;
-};
-struct RestirFinalRecord {               // trhip_restir_di_final
-    f3 contribution; float visibility;   // the unshadowed contribution of the chosen sample
-    float canonical_m, wi, draw; uint selected;
-};
-static_assert(sizeof(RestirSurface) == 112 && sizeof(RestirReservoir) == 32 && sizeof(RestirCandidateRecord) == 48, "layout");
-static_assert(sizeof(RestirTemporalRecord) == 32 && sizeof(RestirSpatialRecord) == 64 && sizeof(RestirFinalRecord) == 32, "layout");
-
-// Word i of a record: the buffers are device allocations and every record is 16-byte aligned - one global (not flat) 16-byte load or store
-TR_HD u4 restir_word(const void* p, int i) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef uint v4u __attribute__((ext_vector_type(4)));
-    const v4u v = ((const v4u __attribute__((address_space(1)))*)p)[i];
-    return u4{v.x, v.y, v.z, v.w};
-#else
-    return ((const u4*)p)[i];
-#endif
-}
-TR_HD void restir_set_word(void* p, int i, u4 w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef uint v4u __attribute__((ext_vector_type(4)));
-    ((v4u __attribute__((address_space(1)))*)p)[i] = v4u{w.x, w.y, w.z, w.w};
-#else
-    ((u4*)p)[i] = w;
-#endif
-}
+static_assert(sizeof(RestirReservoir) == 32 && sizeof(RestirCandidateRecord) == 48, "layout");
 
 struct RestirSample { uint type, index; f2 data; };
-TR_DEV bool restir_is_null(const RestirSample& s) { return s.type == 0u && s.index == RESTIR_NULL_INDEX; }
 TR_DEV RestirSample restir_null_sample() { return {0u, RESTIR_NULL_INDEX, F2(0.0f)}; }
-
-struct RestirState {                     // `reservoir` (restir_di.glsl:29-37) without its contribution
-    RestirSample ls;
-    float target_function, weight_sum, uc_weight, confidence;
-};
-TR_DEV RestirState restir_create() { return {restir_null_sample(), 0.0f, 0.0f, 0.0f, 0.0f}; }
-TR_DEV bool restir_update(RestirState& r, const RestirSample& ls, float weight, float u) {    // update_reservoir (restir_di.glsl:118-131)
-    r.weight_sum = r.weight_sum + weight;
-    if (u * r.weight_sum < weight) { r.ls = ls; return true; }
-    return false;
-}
-TR_DEV float restir_uc_weight(const RestirState& r) { return r.weight_sum > 0.0f ? r.weight_sum / r.target_function : 0.0f; }
-
-TR_DEV RestirReservoir restir_pack(const RestirState& r) {
-    return {r.uc_weight, r.target_function, r.ls.type << 30 | r.ls.index, r.confidence, r.ls.data, 0u, 0u};
-}
-TR_DEV void restir_store(RestirReservoir* dst, const RestirReservoir& r) {
-    restir_set_word(dst, 0, u4{__float_as_uint(r.uc_weight), __float_as_uint(r.target_function), r.light, __float_as_uint(r.confidence)});
-    restir_set_word(dst, 1, u4{__float_as_uint(r.light_data.x), __float_as_uint(r.light_data.y), 0u, 0u});
-}
-TR_DEV RestirState restir_load(const RestirReservoir* src) {                                   // read_reservoir_buffer (:427-454)
-    const u4 a = restir_word(src, 0), b = restir_word(src, 1);
-    RestirState r;
-    r.uc_weight = __uint_as_float(a.x); r.target_function = __uint_as_float(a.y);
-    r.ls.type = a.z >> 30; r.ls.index = a.z & 0x3FFFFFFFu;
-    r.confidence = __uint_as_float(a.w);
-    r.ls.data = F2(__uint_as_float(b.x), __uint_as_float(b.y));
-    r.weight_sum = 0.0f;
-    return r;
-}
-
-// The part of a surface record light_contribution reads (the shader's `domain`)
-struct RestirDomain {
-    f3 pos, mapped_normal, flat_normal, view;
-    SampledMaterial mat;
-};
-TR_DEV void restir_store_surface(RestirSurface* dst, const RestirDomain& d, int instance_id) {
-#define TR_U(x) __float_as_uint(x)
-    restir_set_word(dst, 0, u4{TR_U(d.pos.x), TR_U(d.pos.y), TR_U(d.pos.z), (uint)instance_id});
-    restir_set_word(dst, 1, u4{TR_U(d.mapped_normal.x), TR_U(d.mapped_normal.y), TR_U(d.mapped_normal.z), TR_U(d.mat.metallic)});
-    restir_set_word(dst, 2, u4{TR_U(d.flat_normal.x), TR_U(d.flat_normal.y), TR_U(d.flat_normal.z), TR_U(d.mat.roughness)});
-    restir_set_word(dst, 3, u4{TR_U(d.view.x), TR_U(d.view.y), TR_U(d.view.z), TR_U(d.mat.transmittance)});
-    restir_set_word(dst, 4, u4{TR_U(d.mat.albedo.x), TR_U(d.mat.albedo.y), TR_U(d.mat.albedo.z), TR_U(d.mat.albedo.w)});
-    restir_set_word(dst, 5, u4{TR_U(d.mat.emission.x), TR_U(d.mat.emission.y), TR_U(d.mat.emission.z), TR_U(d.mat.f0)});
-    restir_set_word(dst, 6, u4{TR_U(d.mat.ior_in), TR_U(d.mat.ior_out), 0u, 0u});
-#undef TR_U
-}
-// Position, instance id and flat normal alone: what the neighbour search reads (two words)
-TR_DEV void restir_load_surface_head(const RestirSurface* src, f3& pos, int& instance_id, f3& flat_normal) {
-    const u4 a = restir_word(src, 0), c = restir_word(src, 2);
-    pos = F3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)); instance_id = (int)a.w;
-    flat_normal = F3(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z));
-}
-TR_DEV int restir_load_surface(const RestirSurface* src, RestirDomain& d) {
-    const u4 a = restir_word(src, 0), b = restir_word(src, 1), c = restir_word(src, 2), e = restir_word(src, 3), f = restir_word(src, 4), g = restir_word(src, 5),
-             h = restir_word(src, 6);
-#define TR_F(x) __uint_as_float(x)
-    d.pos = F3(TR_F(a.x), TR_F(a.y), TR_F(a.z));
-    d.mapped_normal = F3(TR_F(b.x), TR_F(b.y), TR_F(b.z)); d.mat.metallic = TR_F(b.w);
-    d.flat_normal = F3(TR_F(c.x), TR_F(c.y), TR_F(c.z)); d.mat.roughness = TR_F(c.w);
-    d.view = F3(TR_F(e.x), TR_F(e.y), TR_F(e.z)); d.mat.transmittance = TR_F(e.w);
-    d.mat.albedo = F4(TR_F(f.x), TR_F(f.y), TR_F(f.z), TR_F(f.w));
-    d.mat.emission = F3(TR_F(g.x), TR_F(g.y), TR_F(g.z)); d.mat.f0 = TR_F(g.w);
-    d.mat.ior_in = TR_F(h.x); d.mat.ior_out = TR_F(h.y);
-#undef TR_F
-    return (int)a.w;
-}
 
 // A light's record as sample_explicit_light (shade_kernel.h) fetches it: the kind and the record are decided first, then one masked fetch
 // per kind into the same four registers; the branches behind it only compute.  An environment sample has no record (the candidate
@@ -289,28 +181,43 @@ TR_DEV f3 restir_contribution(const SceneView& sv, const RestirSample& s, const 
     if (isnan(s.data.x) || isnan(s.data.y)) value = F3(0.0f);
     return value;
 }
-TR_DEV bool restir_casts(f3 c) { return c.x > 0.0f || c.y > 0.0f || c.z > 0.0f; }
 
-// reconnection_jacobian, mis_canonical, mis_noncanonical (restir_di.glsl:477-533)
-TR_DEV float restir_jacobian(f3 prev_src, f3 cur_src, f3 dst, f3 n) {
-    const f3 qdelta = prev_src - dst, rdelta = cur_src - dst;
-    const float lq = length(qdelta), lr = length(rdelta);
-    const float theta_q = fabsf(dot(n, qdelta)), theta_r = fabsf(dot(n, rdelta));
-    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 1.0f;
-    float v = (theta_r * (lq * lq * lq)) / (theta_q * (lr * lr * lr));
-    if (isinf(v) || isnan(v)) v = 0.0f;
-    return v;
-}
-TR_DEV float restir_mis_canonical(float c_conf, float o_conf, float total, float c_target, float c_in_other, float jacobian) {
-    if (c_target == 0.0f) return 0.0f;
-    const float w = c_conf * c_target;
-    return ((o_conf / total) * w) / (w + ((total - c_conf) * c_in_other) * jacobian);
-}
-TR_DEV float restir_mis_noncanonical(float c_conf, float o_conf, float total, float o_target, float o_in_canonical, float jacobian) {
-    if (o_target == 0.0f) return 0.0f;
-    const float w = (total - c_conf) * o_target;
-    return ((o_conf / total) * w) / (w + (c_conf * o_in_canonical) * jacobian);
-}
+// What restir_resample.h asks of a sample: a light sample (type, index, data)
+struct RestirDiKind {
+    using Sample = RestirSample;
+    using State = RestirState<Sample>;
+    using Reservoir = RestirReservoir;
+    struct Eval { f3 dir; float dist2; f3 normal; };
+    // The spatial merge reads a neighbour's surface behind the first traversal: at 256 VGPRs the kernels spill less
+    static constexpr bool SURFACE_LATE = true;
+    static TR_DEV State create() { return {restir_null_sample(), 0.0f, 0.0f, 0.0f, 0.0f}; }
+    static TR_DEV State load(const Reservoir* src) {                                           // read_reservoir_buffer (:427-454)
+        const u4 a = restir_word(src, 0), b = restir_word(src, 1);
+        State r;
+        r.uc_weight = __uint_as_float(a.x); r.target_function = __uint_as_float(a.y);
+        r.s.type = a.z >> 30; r.s.index = a.z & 0x3FFFFFFFu;
+        r.confidence = __uint_as_float(a.w);
+        r.s.data = F2(__uint_as_float(b.x), __uint_as_float(b.y));
+        r.weight_sum = 0.0f;
+        return r;
+    }
+    static TR_DEV void store(Reservoir* dst, const State& r) {                                 // write_reservoir_buffer (:411-425)
+        restir_set_word(dst, 0, u4{TR_U(r.uc_weight), TR_U(r.target_function), r.s.type << 30 | r.s.index, TR_U(r.confidence)});
+        restir_set_word(dst, 1, u4{TR_U(r.s.data.x), TR_U(r.s.data.y), 0u, 0u});
+    }
+    static TR_DEV float confidence(const Reservoir* src) { return __uint_as_float(restir_word(src, 0).w); }
+    static TR_DEV bool is_null(const Sample& s) { return s.type == 0u && s.index == RESTIR_NULL_INDEX; }
+    // the light's record is fetched per evaluation, not held across the spatial merge's loop
+    static TR_DEV f3 contribution(const SceneView& sv, const Sample& s, const RestirDomain& dom, Eval& e) {
+        const RestirLightRecord L = restir_fetch_light(sv, s);
+        return restir_contribution(sv, s, L, dom, e.dir, e.dist2, e.normal);
+    }
+    // the reconnection point is where the shadow ray ends; a directional or environment sample has none
+    static TR_DEV float jacobian(const Sample& s, const Eval& e, f3 from, f3 at) {
+        const f3 x = at + e.dir * sqrtf(e.dist2);
+        return s.type > 1u ? 1.0f : restir_jacobian(from, at, x, e.normal);
+    }
+};
 
 // sample_canonical (restir_di.glsl:251-354): select, fetch, compute, as sample_explicit_light.  The record stays in L for the contribution.
 // Params: the kernel parameters of the stage that draws (prob_point, prob_tri, prob_dir, prob_env: nee_probabilities; min_ray_dist) -
@@ -378,17 +285,6 @@ TR_DEV RestirSample restir_sample_canonical(const SceneView& sv, const Params& P
     }
 #undef TR_F
     return s;
-}
-
-// The shadow ray of a contribution (`visibility` above)
-template <bool TWO_LEVEL>
-TR_DEV float restir_shadow(const SceneView& sv, float min_ray_dist, f3 pos, f3 contribution, f3 dir, float dist2, int* stack, int& overflow) {
-    float visibility = 0.0f;
-    if (restir_casts(contribution)) {
-        TraceStats st = {};
-        visibility = trace_shadow4<false, TWO_LEVEL>(sv, pos, dir, min_ray_dist, sqrtf(dist2) - min_ray_dist, stack, st, overflow);
-    }
-    return visibility;
 }
 
 }  // namespace tr

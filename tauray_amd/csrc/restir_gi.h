@@ -68,6 +68,9 @@
 //   3. A surface with roughness below 0.001 gets no specular indirect light (ggx_bsdf_pdf's distribution is 0 there; no delta lobes).
 //   4. History samples are not validated again when geometry or lights move; max_confidence bounds their age.
 //   5. Sphere lights are points, as in DI.  Cosine-hemisphere initial sampling only, one bounce, one device.
+//
+// Where the code is.  temporal, spatial and what they take from restir_di.h: restir_resample.h, the same code as ReSTIR DI's.  Here: the
+// reservoir, the reprojection and initial records and RestirGiKind with `contribution`.  initial, resampling and colour: restir_gi.hip.
 #pragma once
 #include "restir_di.h"
 
@@ -94,60 +97,57 @@ struct RestirGiInitialRecord {           // trhip_restir_gi_initial
 static_assert(sizeof(RestirGiReservoir) == 48 && sizeof(RestirGiReproject) == 16 && sizeof(RestirGiInitialRecord) == 96, "layout");
 
 struct RestirGiSample { f3 x, n, L; };
-TR_DEV bool restir_gi_is_null(const RestirGiSample& s) {
-    return s.n.x == 0.0f && s.n.y == 0.0f && s.n.z == 0.0f && s.L.x == 0.0f && s.L.y == 0.0f && s.L.z == 0.0f;
-}
-TR_DEV RestirGiSample restir_gi_null_sample() { return {F3(0.0f), F3(0.0f), F3(0.0f)}; }
 
-struct RestirGiState {
-    RestirGiSample s;
-    float target_function, weight_sum, uc_weight, confidence;
-};
-TR_DEV RestirGiState restir_gi_create() { return {restir_gi_null_sample(), 0.0f, 0.0f, 0.0f, 0.0f}; }
-TR_DEV bool restir_gi_update(RestirGiState& r, const RestirGiSample& s, float weight, float u) {      // update_reservoir, as restir_update
-    r.weight_sum = r.weight_sum + weight;
-    if (u * r.weight_sum < weight) { r.s = s; return true; }
-    return false;
-}
-TR_DEV float restir_gi_uc_weight(const RestirGiState& r) { return r.weight_sum > 0.0f ? r.weight_sum / r.target_function : 0.0f; }
-
-TR_DEV void restir_gi_store(RestirGiReservoir* dst, const RestirGiState& r) {
-#define TR_U(x) __float_as_uint(x)
-    restir_set_word(dst, 0, u4{TR_U(r.s.x.x), TR_U(r.s.x.y), TR_U(r.s.x.z), TR_U(r.uc_weight)});
-    restir_set_word(dst, 1, u4{TR_U(r.s.n.x), TR_U(r.s.n.y), TR_U(r.s.n.z), TR_U(r.target_function)});
-    restir_set_word(dst, 2, u4{TR_U(r.s.L.x), TR_U(r.s.L.y), TR_U(r.s.L.z), TR_U(r.confidence)});
-#undef TR_U
-}
-TR_DEV RestirGiState restir_gi_load(const RestirGiReservoir* src) {
-    const u4 a = restir_word(src, 0), b = restir_word(src, 1), c = restir_word(src, 2);
+// What restir_resample.h asks of a sample: a point, its normal and the radiance it sent
+struct RestirGiKind {
+    using Sample = RestirGiSample;
+    using State = RestirState<Sample>;
+    using Reservoir = RestirGiReservoir;
+    struct Eval { f3 dir; float dist2; };
+    // The spatial merge reads a neighbour's surface ahead of the first traversal: read behind it, the wait showed
+    static constexpr bool SURFACE_LATE = false;
+    static TR_DEV State create() { return {{F3(0.0f), F3(0.0f), F3(0.0f)}, 0.0f, 0.0f, 0.0f, 0.0f}; }
+    static TR_DEV State load(const Reservoir* src) {
+        const u4 a = restir_word(src, 0), b = restir_word(src, 1), c = restir_word(src, 2);
 #define TR_F(x) __uint_as_float(x)
-    RestirGiState r;
-    r.s.x = F3(TR_F(a.x), TR_F(a.y), TR_F(a.z)); r.uc_weight = TR_F(a.w);
-    r.s.n = F3(TR_F(b.x), TR_F(b.y), TR_F(b.z)); r.target_function = TR_F(b.w);
-    r.s.L = F3(TR_F(c.x), TR_F(c.y), TR_F(c.z)); r.confidence = TR_F(c.w);
+        State r;
+        r.s.x = F3(TR_F(a.x), TR_F(a.y), TR_F(a.z)); r.uc_weight = TR_F(a.w);
+        r.s.n = F3(TR_F(b.x), TR_F(b.y), TR_F(b.z)); r.target_function = TR_F(b.w);
+        r.s.L = F3(TR_F(c.x), TR_F(c.y), TR_F(c.z)); r.confidence = TR_F(c.w);
 #undef TR_F
-    r.weight_sum = 0.0f;
-    return r;
-}
-
-// The contribution of a sample at a surface (`contribution` above): restir_contribution's tail behind the direction, times L_o
-TR_DEV f3 restir_gi_contribution(const RestirGiSample& s, const RestirDomain& dom, f3& dir, float& dist2) {
-    dir = F3(0.0f); dist2 = 0.0f;
-    if (restir_gi_is_null(s)) return F3(0.0f);
-    const f3 to = s.x - dom.pos;
-    dist2 = dot(to, to);
-    dir = normalize(to);
-    if (!(dist2 > 0.0f)) return F3(0.0f);
-    if (dot(dir, dom.flat_normal) < 1e-6f) return F3(0.0f);
-    if (dot(s.n, -dir) < 1e-6f) return F3(0.0f);
-    const m3 tbn = create_tangent_space(dom.mapped_normal);
-    const f3 shading_view = view_to_tangent_space(dom.view, tbn);
-    const f3 shading_light = mulT(dir, tbn);
-    Lobes lobes = {0, 0, 0, 0};
-    ggx_bsdf_pdf<RoundedMath>(shading_light, shading_view, dom.mat, lobes);
-    if (dot(dom.flat_normal, dir) < 0) { lobes.diffuse = 0; lobes.dielectric_reflection = 0; lobes.metallic_reflection = 0; }     // correct_lobes_for_normal_map
-    else lobes.transmission = 0;
-    return modulate_bsdf(dom.mat, lobes) * s.L;
-}
+        r.weight_sum = 0.0f;
+        return r;
+    }
+    static TR_DEV void store(Reservoir* dst, const State& r) {
+        restir_set_word(dst, 0, u4{TR_U(r.s.x.x), TR_U(r.s.x.y), TR_U(r.s.x.z), TR_U(r.uc_weight)});
+        restir_set_word(dst, 1, u4{TR_U(r.s.n.x), TR_U(r.s.n.y), TR_U(r.s.n.z), TR_U(r.target_function)});
+        restir_set_word(dst, 2, u4{TR_U(r.s.L.x), TR_U(r.s.L.y), TR_U(r.s.L.z), TR_U(r.confidence)});
+    }
+    static TR_DEV float confidence(const Reservoir* src) { return __uint_as_float(restir_word(src, 2).w); }
+    static TR_DEV bool is_null(const Sample& s) {
+        return s.n.x == 0.0f && s.n.y == 0.0f && s.n.z == 0.0f && s.L.x == 0.0f && s.L.y == 0.0f && s.L.z == 0.0f;
+    }
+    // `contribution` above: restir_contribution's tail behind the direction, times L_o
+    static TR_DEV f3 contribution(const SceneView&, const Sample& s, const RestirDomain& dom, Eval& e) {
+        e.dir = F3(0.0f); e.dist2 = 0.0f;
+        if (is_null(s)) return F3(0.0f);
+        const f3 to = s.x - dom.pos;
+        e.dist2 = dot(to, to);
+        e.dir = normalize(to);
+        if (!(e.dist2 > 0.0f)) return F3(0.0f);
+        if (dot(e.dir, dom.flat_normal) < 1e-6f) return F3(0.0f);
+        if (dot(s.n, -e.dir) < 1e-6f) return F3(0.0f);
+        const m3 tbn = create_tangent_space(dom.mapped_normal);
+        const f3 shading_view = view_to_tangent_space(dom.view, tbn);
+        const f3 shading_light = mulT(e.dir, tbn);
+        Lobes lobes = {0, 0, 0, 0};
+        ggx_bsdf_pdf<RoundedMath>(shading_light, shading_view, dom.mat, lobes);
+        if (dot(dom.flat_normal, e.dir) < 0) { lobes.diffuse = 0; lobes.dielectric_reflection = 0; lobes.metallic_reflection = 0; }     // correct_lobes_for_normal_map
+        else lobes.transmission = 0;
+        return modulate_bsdf(dom.mat, lobes) * s.L;
+    }
+    // the reconnection point and its normal are the sample's own
+    static TR_DEV float jacobian(const Sample& s, const Eval&, f3 from, f3 at) { return restir_jacobian(from, at, s.x, s.n); }
+};
 
 }  // namespace tr

@@ -1347,46 +1347,59 @@ def restir_di_options(**kw) -> dict:
     return o
 
 
-class RestirDiStage(_PostStage):
+class _RestirStage(_PostStage):
+    """What RestirDiStage and RestirGiStage share: `size`: (w, h); `layers`: the viewports of a frame; `options`: the stage's option dict.
+    _RECORDS: name -> (download code, dtype); _AXES: a record with one more axis -> the option that is its length."""
+
+    _RECORDS, _AXES = {}, {}
+
+    def _create_stage(self, ctx, scene_stage, size, layers, projection, opt):
+        """`opt`: the stage's trhip_restir_*_options."""
+        self.ctx, self.scene_stage, self.size, self.layers, self.projection = ctx, scene_stage, tuple(size), int(layers), int(projection)
+        self._create(getattr(ctx, "h", None), C.byref(opt), max(int(self.size[0]), 0), max(int(self.size[1]), 0), max(self.layers, 0))
+
+    def _render(self, viewports, *images_and_stream):
+        v = np.ascontiguousarray(viewports, dtype=np.uint32)
+        check(self._fn("render")(self.h, self.projection, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size, *images_and_stream))
+
+    def reset(self):
+        """Forgets the history: the next frame is the first frame of a new stage."""
+        check(self._fn("reset")(self.h))
+
+    def download(self, name: str) -> np.ndarray:
+        """A structured array [layers][h][w] (a name of _AXES: one more axis) of "surface", "canonical", "history" and, with record, the
+        decision records of _RECORDS."""
+        code, dtype = self._RECORDS[name]
+        shape = (self.layers, self.size[1], self.size[0])
+        if name in self._AXES:
+            shape += (int(self.options[self._AXES[name]]),)
+        return self._download(code, shape, np.dtype(dtype))
+
+
+class RestirDiStage(_RestirStage):
     """ReSTIR DI (trhip_restir_di_*, include/trhip.h; written after shader/restir_di.glsl and its two ray generation shaders): per frame
     the canonical kernel (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).
-    `size`: (w, h); `layers`: the viewports of a frame; `options`: restir_di_options()."""
+    `options`: restir_di_options(); with record, download() has "candidates", "temporal", "spatial", "final"."""
 
     PREFIX, TIMINGS = "restir_di", _lib.RestirDiTimingsC
     _RECORDS = {"surface": (_lib.RESTIR_DI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_DI_CANONICAL, _lib.RESTIR_DI_RESERVOIR_DTYPE),
                 "history": (_lib.RESTIR_DI_HISTORY, _lib.RESTIR_DI_RESERVOIR_DTYPE), "candidates": (_lib.RESTIR_DI_CANDIDATES, _lib.RESTIR_DI_CANDIDATE_DTYPE),
                 "temporal": (_lib.RESTIR_DI_TEMPORAL, _lib.RESTIR_DI_TEMPORAL_DTYPE), "spatial": (_lib.RESTIR_DI_SPATIAL, _lib.RESTIR_DI_SPATIAL_DTYPE),
                 "final": (_lib.RESTIR_DI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE)}
+    _AXES = {"candidates": "candidates", "spatial": "spatial_samples"}
 
     def __init__(self, ctx: Optional[Context], scene_stage: Optional[SceneStage], size, layers=1, options: Optional[dict] = None, projection=0):
-        self.ctx, self.scene_stage, self.size, self.layers, self.projection = ctx, scene_stage, tuple(size), int(layers), int(projection)
         o = self.options = restir_di_options(**(options or {}))
         opt = _lib.RestirDiOptionsC(max(int(o["candidates"]), 0), max(int(o["spatial_samples"]), 0), float(o["search_radius"]), float(o["max_confidence"]),
                                     int(o["temporal_reuse"]), float(o["min_ray_dist"]), int(o["rng_seed"]) & 0xFFFFFFFF, int(o["record"]))
         if int(o["candidates"]) < 0 or int(o["spatial_samples"]) < 0:
             raise TrhipError("RestirDiStage: candidates and spatial_samples are counts")
-        self._create(getattr(ctx, "h", None), C.byref(opt), max(int(self.size[0]), 0), max(int(self.size[1]), 0), max(self.layers, 0))
+        self._create_stage(ctx, scene_stage, size, layers, projection, opt)
 
     def run(self, viewports, out, stream=None):
         """One frame: `out` RGBA32F [len(viewports)][h][w] = contribution * uc_weight + emission of the listed viewports.  History is kept
         per position in the list: with temporal reuse the list stays the same from frame to frame until `reset`."""
-        v = np.ascontiguousarray(viewports, dtype=np.uint32)
-        check(_lib.lib().trhip_restir_di_render(self.h, self.projection, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size, _ptr(out), stream))
-
-    def reset(self):
-        """Forgets the history: the next frame is the first frame of a new stage."""
-        check(_lib.lib().trhip_restir_di_reset(self.h))
-
-    def download(self, name: str) -> np.ndarray:
-        """A structured array [layers][h][w] ("candidates", "spatial": one more axis) of "surface", "canonical", "history" and, with
-        record, "candidates", "temporal", "spatial", "final"."""
-        code, dtype = self._RECORDS[name]
-        shape = (self.layers, self.size[1], self.size[0])
-        if name == "candidates":
-            shape += (int(self.options["candidates"]),)
-        if name == "spatial":
-            shape += (int(self.options["spatial_samples"]),)
-        return self._download(code, shape, np.dtype(dtype))
+        self._render(viewports, _ptr(out), stream)
 
 
 class RestirDiRenderer(_ViewportFrameRenderer):
@@ -1424,11 +1437,11 @@ def restir_gi_options(**kw) -> dict:
     return o
 
 
-class RestirGiStage(_PostStage):
+class RestirGiStage(_RestirStage):
     """ReSTIR GI (trhip_restir_gi_*, include/trhip.h; csrc/restir_gi.h pins the rule): one bounce of indirect light by reservoir
     resampling - per frame the initial kernel (first hit, one cosine-hemisphere ray, a light sample at its hit), the temporal kernel (the
-    history merge, no rays) and the spatial kernel (neighbour merge, shading).  `size`: (w, h); `layers`: the viewports of a frame;
-    `options`: restir_gi_options()."""
+    history merge, no rays) and the spatial kernel (neighbour merge, shading).  `options`: restir_gi_options(); with record, download()
+    has "initial", "secondary", "light", "temporal", "spatial", "final"."""
 
     PREFIX, TIMINGS = "restir_gi", _lib.RestirGiTimingsC
     _RECORDS = {"surface": (_lib.RESTIR_GI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_GI_CANONICAL, _lib.RESTIR_GI_RESERVOIR_DTYPE),
@@ -1436,36 +1449,21 @@ class RestirGiStage(_PostStage):
                 "secondary": (_lib.RESTIR_GI_SECONDARY, _lib.RESTIR_DI_SURFACE_DTYPE), "light": (_lib.RESTIR_GI_LIGHT, _lib.RESTIR_DI_CANDIDATE_DTYPE),
                 "temporal": (_lib.RESTIR_GI_TEMPORAL, _lib.RESTIR_DI_TEMPORAL_DTYPE), "spatial": (_lib.RESTIR_GI_SPATIAL, _lib.RESTIR_DI_SPATIAL_DTYPE),
                 "final": (_lib.RESTIR_GI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE)}
+    _AXES = {"spatial": "spatial_samples"}
 
     def __init__(self, ctx: Optional[Context], scene_stage: Optional[SceneStage], size, layers=1, options: Optional[dict] = None, projection=0):
-        self.ctx, self.scene_stage, self.size, self.layers, self.projection = ctx, scene_stage, tuple(size), int(layers), int(projection)
         o = self.options = restir_gi_options(**(options or {}))
         opt = _lib.RestirGiOptionsC(max(int(o["spatial_samples"]), 0), float(o["search_radius"]), float(o["max_confidence"]), int(o["temporal_reuse"]),
                                     float(o["min_ray_dist"]), int(o["rng_seed"]) & 0xFFFFFFFF, int(o["record"]))
         if int(o["spatial_samples"]) < 0:
             raise TrhipError("RestirGiStage: spatial_samples is a count")
-        self._create(getattr(ctx, "h", None), C.byref(opt), max(int(self.size[0]), 0), max(int(self.size[1]), 0), max(self.layers, 0))
+        self._create_stage(ctx, scene_stage, size, layers, projection, opt)
 
     def run(self, viewports, in_color, out, stream=None):
         """One frame: `out` RGBA32F [len(viewports)][h][w] = `in_color` + the indirect light of the listed viewports; `in_color` None
         counts as (0, 0, 0, 1), `out` may be `in_color`.  History is kept per position in the list: with temporal reuse the list stays
         the same from frame to frame until `reset`."""
-        v = np.ascontiguousarray(viewports, dtype=np.uint32)
-        check(_lib.lib().trhip_restir_gi_render(self.h, self.projection, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size,
-                                                None if in_color is None else _ptr(in_color), _ptr(out), stream))
-
-    def reset(self):
-        """Forgets the history: the next frame is the first frame of a new stage."""
-        check(_lib.lib().trhip_restir_gi_reset(self.h))
-
-    def download(self, name: str) -> np.ndarray:
-        """A structured array [layers][h][w] ("spatial": one more axis) of "surface", "canonical", "history" and, with record, "initial",
-        "secondary", "light", "temporal", "spatial", "final"."""
-        code, dtype = self._RECORDS[name]
-        shape = (self.layers, self.size[1], self.size[0])
-        if name == "spatial":
-            shape += (int(self.options["spatial_samples"]),)
-        return self._download(code, shape, np.dtype(dtype))
+        self._render(viewports, None if in_color is None else _ptr(in_color), _ptr(out), stream)
 
 
 class RestirGiRenderer(_ViewportFrameRenderer):
