@@ -457,6 +457,10 @@ int trhip_pt_get_phase_counters(trhip_pt* pt, trhip_phase_counters* out);   /* s
  * that ran out of their 16-entry stack and tested every light in the loop instead (same hits, the loop's cost). */
 typedef struct trhip_light_counters { uint64_t sphere_tests, node_visits, walk_fallbacks; } trhip_light_counters;
 int trhip_pt_get_light_counters(trhip_pt* pt, trhip_light_counters* out);   /* synchronises the stream */
+/* The deepest per-ray traversal stack (entries, the one in a register included) that a trace launch has reached since the counters were
+ * last cleared; kept while work counting is on.  The first 1 + 16 entries of a ray live in a register and LDS, deeper ones in the spill
+ * memories (csrc/trace.h LaneStack), so a value above 17 says that the frames so far exercised those. */
+int trhip_pt_get_max_stack_depth(trhip_pt* pt, uint32_t* out);              /* synchronises the stream */
 /* The last bounce as a first-hit emitter query.  Every path ends at bounce max_bounces - 1, where a surface hit can
  * only add the emission of what was hit, so the last ray of a path needs to know whether it escapes, whether the nearest thing along it is
  * an emitter triangle, or that something else is in the way - and then neither what nor where.

@@ -330,6 +330,7 @@ SYMBOLS = {
     "trhip_pt_get_light_counters": (_i, [_vp, C.POINTER(LightCountersC)]),
     "trhip_pt_set_terminal_query": (_i, [_vp, _i]),
     "trhip_pt_get_terminal_counters": (_i, [_vp, C.POINTER(TerminalCountersC)]),
+    "trhip_pt_get_max_stack_depth": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "trhip_trace_terminal": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "trhip_stitch_batch": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, C.c_float, _vp]),
     "trhip_stream_create": (_i, [_vp, C.POINTER(C.c_void_p)]),

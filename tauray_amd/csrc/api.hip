@@ -143,7 +143,7 @@ __global__ __launch_bounds__(KB) void k_query_closest(SceneView sv, uint n, cons
         }
 #endif
         if (valid) out[i] = hit;
-        if (valid && include_lights) {     // sphere lights after the triangles, the ray read again (trace_lanes.h closest_lane)
+        if (valid && include_lights && sv.point_light_count != 0) {     // sphere lights after the triangles, the ray read again (trace_lanes.h closest_lane)
             const float tri_t = hit.instance_id >= 0 ? hit.t : r[7];
             uint ri = i;
             asm volatile("" : "+v"(ri));
@@ -958,6 +958,12 @@ int trhip_pt_get_light_counters(trhip_pt* pt, trhip_light_counters* out) {
     if (!out) return set_error("trhip_pt_get_light_counters: null output");
     DEVCHK(pt->dev);
     return pt->stage->get_light_counters(out, pt->stage->last_stream);
+}
+int trhip_pt_get_max_stack_depth(trhip_pt* pt, uint32_t* out) {
+    if (!pt) return set_error("null trhip_pt");
+    if (!out) return set_error("trhip_pt_get_max_stack_depth: null output");
+    DEVCHK(pt->dev);
+    return pt->stage->get_max_stack_depth(out, pt->stage->last_stream);
 }
 int trhip_pt_set_terminal_query(trhip_pt* pt, int mode) {
     if (!pt) return set_error("null trhip_pt");

@@ -43,6 +43,7 @@ public:
     int get_timings(trhip_timings* out);
     int get_phase_counters(trhip_phase_counters* out, hipStream_t stream);
     int get_light_counters(trhip_light_counters* out, hipStream_t stream);
+    int get_max_stack_depth(uint32_t* out, hipStream_t stream);
     int get_terminal_counters(trhip_terminal_counters* out, hipStream_t stream);
     int get_program(trhip_program_info* out);
     int terminal_query_in_effect() const;

@@ -110,12 +110,16 @@ TR_DEV bool tri_intersect(const RayPre& r, const TriRecord* tris, uint index, fl
     // (0.65 of its access rate), the VALUs are not (0.43).
     const f4* p = reinterpret_cast<const f4*>(reinterpret_cast<const char*>(tris) + (size_t)index * (uint)sizeof(TriRecord));
     const f4 q0 = p[0], q1 = p[1], q2 = p[2];       // x0 y0 z0 x1 | y1 z1 x2 y2 | z2 inst prim alpha
-    o.inst_flags = __float_as_uint(q2.y); o.prim = __float_as_uint(q2.z); o.alpha = __float_as_uint(q2.w);
+    // a caller that does not look at every word (the any-hit loops never read `prim`) would have the third load cut into the pieces it
+    // does read: two accesses for one.  The asm makes the four words one value that is used where the vertices are
+    float z2 = q2.x, w_inst = q2.y, w_prim = q2.z, w_alpha = q2.w;
+    asm volatile("" : "+v"(z2), "+v"(w_inst), "+v"(w_prim), "+v"(w_alpha));
+    o.inst_flags = __float_as_uint(w_inst); o.prim = __float_as_uint(w_prim); o.alpha = __float_as_uint(w_alpha);
     const uint kx4 = tri_component_offset(r.nkx), ky4 = tri_component_offset(r.nky), kz4 = tri_component_offset(r.nkz);
     auto pick = [](float x, float y, float z, uint k4) { const float xy = k4 == 4u ? y : x; return k4 == 8u ? z : xy; };
-    const float v0x = pick(q0.x, q0.y, q0.z, kx4), v1x = pick(q0.w, q1.x, q1.y, kx4), v2x = pick(q1.z, q1.w, q2.x, kx4);
-    const float v0y = pick(q0.x, q0.y, q0.z, ky4), v1y = pick(q0.w, q1.x, q1.y, ky4), v2y = pick(q1.z, q1.w, q2.x, ky4);
-    const float v0z = pick(q0.x, q0.y, q0.z, kz4), v1z = pick(q0.w, q1.x, q1.y, kz4), v2z = pick(q1.z, q1.w, q2.x, kz4);
+    const float v0x = pick(q0.x, q0.y, q0.z, kx4), v1x = pick(q0.w, q1.x, q1.y, kx4), v2x = pick(q1.z, q1.w, z2, kx4);
+    const float v0y = pick(q0.x, q0.y, q0.z, ky4), v1y = pick(q0.w, q1.x, q1.y, ky4), v2y = pick(q1.z, q1.w, z2, ky4);
+    const float v0z = pick(q0.x, q0.y, q0.z, kz4), v1z = pick(q0.w, q1.x, q1.y, kz4), v2z = pick(q1.z, q1.w, z2, kz4);
     TL(if (tlp) tlp->loads_issued();)
     const float Akz = v0z - r.op.z, Bkz = v1z - r.op.z, Ckz = v2z - r.op.z;
     const float Ax = (v0x - r.op.x) - r.Sx * Akz, Ay = (v0y - r.op.y) - r.Sy * Akz;
@@ -147,14 +151,22 @@ TR_DEV bool tri_intersect(const RayPre& r, const TriRecord* tris, uint index, fl
 // Per-lane traversal stack: the top entry in a register, the next TR_LDS_STACK in LDS, the rest in a private spill array.
 // `sp` must stay in a VGPR and the LDS access must stay a ds_read/ds_write: the spill array is therefore a separate
 // local (a struct member array drags the whole struct, sp included, into scratch) and pop() reads LDS
-// unconditionally (an if/else over the two memories is if-converted into a generic pointer + flat_load).
+// unconditionally, through a pointer typed as LDS (an if/else over the two memories through generic pointers is if-converted into a
+// select of pointers + flat_load).
 //
 // Round 5 (profiles/r5/trace_phase_timeline.txt): a wave gets an instruction issued every 6-7 clocks at six waves per SIMD whatever
 // its kind, and the three conditional pushes of a node phase + the pop were ~120 instructions and an LDS round trip - more clocks than
 // the four slab tests and the sort.  Now: entry sp - 1 lives in `tos`, rows 0 .. sp - 2 in memory; a node phase stores the old top and
 // up to two of the sorted children with three unconditional ds_writes (rows above the new top hold junk, which nothing reads), and a pop
-// hands out the register and refills it with a ds_read nobody waits for until the next pop or push.  Row -1 exists (the kernels
+// hands out the register and refills it with a ds_read whose result nothing in pop() uses.  Row -1 exists (the kernels
 // allocate one row more and pass the address of row 0): the store of the "old top" of an empty stack lands there.
+//
+// Round 22, as compiled (profiles/r22/anyhit_stack.txt): both push forms are selects for the new top and depth, one
+// ds_write2st64_b32 + one ds_write_b32, and the spill stores out of line behind one branch on the depth.  The pop's ds_read_b32 lands in
+// the register of `tos` and is not waited for behind the read.  In the closest-hit loops the wait stands in front of the next push's
+// store or the next pop; in the any-hit loops it stands at the head of the next iteration of the wave loop, where the compiler copies
+// the loop's values (some twenty instructions behind the read).  It would take a loop the structuriser leaves alone to move that one too.
+typedef __attribute__((address_space(3))) int lds_int;
 struct LaneStack {
     int* lds;           // &stack[0][lane_in_block]; stride TR_BLOCK; row -1 is writable
     int sp;             // entries, the one in `tos` included
@@ -192,29 +204,35 @@ struct LaneStack {
         }
     }
     // ... in slot order, for the any-hit loop (which descends into the first hit child and keeps the others in the order of their slots):
-    // `n` valid entries among (a, b, c), packed to the front
-    TR_DEV void push_packed(int* spill, int n, int a, int b, int c) {
-        if (sp + 2 <= TR_LDS_STACK) {
-            // bottom to top: old top, a, b | top = c (n = 3);  old top, a | top = b (n = 2);  old top | top = a (n = 1)
-            int* row = lds + (sp - 1) * TR_BLOCK;
-            row[0] = tos;
+    // `n` hit children behind the first; the last of them is `top`, the first two are a and b
+    TR_DEV void push_packed(int* spill, int n, int a, int b, int top) {
+        // bottom to top: old top, a, b | top (n = 3);  old top, a | top = b (n = 2);  old top | top = a (n = 1).
+        // The new top and depth are selects outside the branch on the depth, so that its two arms hold stores and nothing else: with
+        // `tos` and `sp` assigned in both, the arms were merged and the three conditional stores of the deep one became a dozen
+        // exec-mask blocks on the common path (profiles/r22/anyhit_stack.txt).
+        const int old = tos, r0 = sp - 1;
+        tos = n > 0 ? top : tos;
+        sp += n;
+        if (__builtin_expect(r0 + 2 < TR_LDS_STACK, 1)) {     // rows r0, r0 + 1, r0 + 2 are LDS rows
+            int* row = lds + r0 * TR_BLOCK;
+            row[0] = old;
             row[TR_BLOCK] = a;
             row[2 * TR_BLOCK] = b;
-            tos = n == 3 ? c : (n == 2 ? b : (n == 1 ? a : tos));
-            sp += n;
-        } else {
-            if (n > 0) push(spill, a);
-            if (n > 1) push(spill, b);
-            if (n > 2) push(spill, c);
+        } else {                // the rows a chain of n push() calls stores, each to its own memory
+            if (n > 0) store_row(spill, r0, old);
+            if (n > 1) store_row(spill, r0 + 1, a);
+            if (n > 2) store_row(spill, r0 + 2, b);
         }
     }
     TR_DEV int pop(const int* spill) {
-        const int out = tos;
+        int out = tos;
+        asm volatile("" : "+v"(out));     // the old top leaves its register here, ahead of the read that refills it
         sp--;
         const int r = sp - 1;       // the row that becomes the top: -1 (junk, never handed out) when the stack is empty now
-        int v = lds[(r < TR_LDS_STACK ? r : 0) * TR_BLOCK];
-        asm volatile("" : "+v"(v));   // pin the ds_read: no select-of-pointers + flat_load
-        if (r >= TR_LDS_STACK) v = spill[r - TR_LDS_STACK < TR_SPILL_STACK ? r - TR_LDS_STACK : TR_SPILL_STACK - 1];
+        // the column through a pointer that can only be LDS: the read stays a ds_read whatever is done with its result, and nothing
+        // here uses the result - where the wait for it ends up: see above
+        int v = ((const lds_int*)lds)[(r < TR_LDS_STACK ? r : 0) * TR_BLOCK];
+        if (__builtin_expect(r >= TR_LDS_STACK, 0)) v = spill[r - TR_LDS_STACK < TR_SPILL_STACK ? r - TR_LDS_STACK : TR_SPILL_STACK - 1];
         tos = v;
         return out;
     }
@@ -239,11 +257,16 @@ struct TraceStats {
 // vertices used to be fetched one behind the other (same values, same expressions: common.h, bvh_build.hip alpha_word).
 TR_DEV float candidate_alpha(const SceneView& sv, uint word, float bu, float bv) {
     if (!(word & 0x80000000u)) return __uint_as_float(word);
-    const AlphaTri a = sv.alpha_tris[word & 0x7FFFFFFFu];
-    float alpha = a.factor;
-    if (a.tex >= 0) {
+    // both 16-byte halves of the record are asked for together, ahead of the test of `tex`: left alone, the compiler fetches (factor, tex)
+    // first and the uvs only behind that test, a second dependent round trip for every textured candidate
+    const f4* p = reinterpret_cast<const f4*>(sv.alpha_tris + (word & 0x7FFFFFFFu));
+    const f4 lo = p[0], hi = p[1];        // uv0 uv1 | uv2 factor tex
+    float u0x = lo.x, u0y = lo.y, u1x = lo.z, u1y = lo.w, u2x = hi.x, u2y = hi.y, alpha = hi.z, texw = hi.w;
+    asm volatile("" : "+v"(u0x), "+v"(u0y), "+v"(u1x), "+v"(u1y), "+v"(u2x), "+v"(u2y), "+v"(alpha), "+v"(texw));
+    const int tex = __float_as_int(texw);
+    if (tex >= 0) {
         const float b0 = 1.0f - bu - bv;
-        alpha *= sample_texture_alpha(sv, a.tex, a.uv0 * b0 + a.uv1 * bu + a.uv2 * bv);
+        alpha *= sample_texture_alpha(sv, tex, F2(u0x, u0y) * b0 + F2(u1x, u1y) * bu + F2(u2x, u2y) * bv);
     }
     return alpha;
 }
@@ -311,10 +334,12 @@ TR_DEV bool shadow_descend(const Hit4& h, LaneStack& stk, int* spill, int& node)
     int c0 = h.c[0], c1 = h.c[1], c2 = h.c[2], c3 = h.c[3];
     asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
     const int first = h0 ? c0 : (h1 ? c1 : (h2 ? c2 : c3));
-    // the hit children behind the first, packed to the front: a = the second hit, b = the third, c = the fourth
+    // the hit children behind the first, packed to the front: a = the second hit, b = the third; `last` = the last hit, which becomes the
+    // top of the stack (two hits: a; three: b; four: c3)
     const int a = (h0 && h1) ? c1 : ((h2 && (h0 != h1)) ? c2 : c3);
     const int b = (h0 && h1 && h2) ? c2 : c3;
-    stk.push_packed(spill, n - 1, a, b, c3);
+    const int last = h3 ? c3 : (h2 ? c2 : c1);
+    stk.push_packed(spill, n - 1, a, b, last);
     node = first;
     return true;
 }

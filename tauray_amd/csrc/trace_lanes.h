@@ -77,7 +77,7 @@ TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffe
     }
     const float tri_t = hit.instance_id >= 0 ? hit.t : __builtin_huge_valf();
     pb.hit[id] = make_int4(hit.instance_id, hit.primitive_id, __float_as_int(hit.u), __float_as_int(hit.v));
-    if (!(P.opt.hide_lights && bounce == 0)) {
+    if (sv.point_light_count != 0 && !(P.opt.hide_lights && bounce == 0)) {    // scalar tests: a scene without such lights reads nothing again
         // sphere lights (trace.h trace_sphere_lights) once the triangle hit is stored, with the ray read again: neither the registers that
         // brought it to the traversal nor the hit are held across its loops for this (the asm keeps the compiler from reusing the first load)
         uint rid = id;

@@ -613,6 +613,12 @@ class PathTracerStage:
         check(_lib.lib().trhip_pt_get_light_counters(self.h, C.byref(c)))
         return {n: int(getattr(c, n)) for n, _ in LightCountersC._fields_}
 
+    def max_stack_depth(self) -> int:
+        """trhip_pt_get_max_stack_depth: the deepest per-ray traversal stack since the counters were cleared (counted under count_work)."""
+        d = C.c_uint32(0)
+        check(_lib.lib().trhip_pt_get_max_stack_depth(self.h, C.byref(d)))
+        return int(d.value)
+
     def set_terminal_query(self, mode: int):
         """trhip_pt_set_terminal_query: _lib.TERMINAL_QUERY_AUTO (the default: the last bounce is a first-hit emitter query where the
         scene allows it) or TERMINAL_QUERY_OFF.  Frames and ray counts do not depend on the mode."""
