@@ -477,6 +477,24 @@ int trhip_pt_set_terminal_query(trhip_pt* pt, int mode);
  * trhip_counters, only counted while work counting is on, cleared by trhip_pt_reset_counters. */
 typedef struct trhip_terminal_counters { uint64_t blocked_rays, fallback_rays; uint32_t in_effect, emitter_triangles, threshold, pad; } trhip_terminal_counters;
 int trhip_pt_get_terminal_counters(trhip_pt* pt, trhip_terminal_counters* out);   /* synchronises the stream */
+/* The primary start: how the paths of a pass start.  A path's start - camera ray, sampler state, any-hit seed, Sobol
+ * index - is a function of its launch id, the frame parameters and the camera.
+ *   TRHIP_PRIMARY_START_AUTO (the default): a pass launches no ray generation kernel.  The closest-hit launch of bounce 0 computes the start
+ *     in the lanes that trace the ray and stores the path state for the kernels behind it; the queue lengths and work cursors of a lane are
+ *     zeroed by the resolve launch of the pass before.  In effect for a path-tracer stage that renders
+ *     the command-line option set with the ahead-of-time kernels (trhip_pt_get_program: kind 1) over an all-merged structure, with
+ *     samples_per_pass == 1, while neither work counting nor detailed timing is on (trhip_pt_set_profiling); not for a probe stage or the
+ *     direct stage.  Otherwise, and under
+ *   TRHIP_PRIMARY_START_OFF, every pass starts with the ray generation launch (one for all lanes of a short frame).
+ * Frames and ray counts do not depend on the mode; it may change between frames.  Until it is set, TRHIP_PRIMARY_START=auto|off chooses it
+ * (A/B tools; any other value fails trhip_pt_render). */
+#define TRHIP_PRIMARY_START_AUTO 0
+#define TRHIP_PRIMARY_START_OFF 1
+int trhip_pt_set_primary_start(trhip_pt* pt, int mode);
+/* mode: what was set (-1: nothing, the environment decides).  in_effect: what the stage's next frame does.  last_frame: what the last frame
+ * rendered did (-1: none yet). */
+typedef struct trhip_primary_start_info { int32_t mode, in_effect, last_frame, pad; } trhip_primary_start_info;
+int trhip_pt_get_primary_start(trhip_pt* pt, trhip_primary_start_info* out);
 /* Peak vector-instruction issue rate of the device as it runs now: a loop of independent v_fma_f32 at eight waves per SIMD,
  * in 10^9 wave-level instructions per second (MI355X_MICROARCH.md: 2 cycles per wave64 instruction on a SIMD-32; the clock is
  * what the box sustains).  The peak of the VALU roofline in bench.py; about 2 ms of device time. */
@@ -832,6 +850,7 @@ int trhip_sh_get_grids(trhip_sh* stage, void** grid_dev, void** grid_half_dev);
 #define TRHIP_SH_GRID_HALF 1          /* RGBA16F, the same layout */
 int trhip_sh_download(trhip_sh* stage, int which, void* host, size_t bytes);   /* synchronises the device */
 int trhip_sh_get_counters(trhip_sh* stage, trhip_counters* out);   /* rays traced, cumulative (trhip_pt_get_counters of the bounce loop); synchronises the stream */
+int trhip_sh_get_primary_start(trhip_sh* stage, trhip_primary_start_info* out);   /* trhip_pt_get_primary_start of the bounce loop: a probe stage has a ray generation of its own, the mode is never in effect */
 int trhip_sh_get_timings(trhip_sh* stage, trhip_sh_timings* out);  /* waits for the last render */
 int trhip_sh_set_profiling(trhip_sh* stage, int count_work, int detailed_timing);   /* tool hook: trhip_pt_set_profiling of the bounce loop */
 int trhip_sh_reset_counters(trhip_sh* stage);                      /* tool hook: trhip_pt_reset_counters of the bounce loop; synchronises the stream */

@@ -76,6 +76,15 @@ TERMINAL_QUERY_AUTO, TERMINAL_QUERY_OFF = 0, 1
 HIT_BLOCKED = -2      # instance_id of a blocked ray in the hits of trhip_trace_terminal
 
 
+# trhip_pt_set_primary_start
+PRIMARY_START_AUTO, PRIMARY_START_OFF = 0, 1
+
+
+class PrimaryStartInfoC(C.Structure):
+    """trhip_primary_start_info: the mode that was set (-1 none), what the next frame does, what the last frame did (-1 none yet)."""
+    _fields_ = [("mode", C.c_int32), ("in_effect", C.c_int32), ("last_frame", C.c_int32), ("pad", C.c_int32)]
+
+
 class PtOptionsC(C.Structure):
     """== path_tracer_stage::options (reference src/path_tracer_stage.hh:13-30), flattened."""
     _fields_ = [
@@ -330,6 +339,8 @@ SYMBOLS = {
     "trhip_pt_get_light_counters": (_i, [_vp, C.POINTER(LightCountersC)]),
     "trhip_pt_set_terminal_query": (_i, [_vp, _i]),
     "trhip_pt_get_terminal_counters": (_i, [_vp, C.POINTER(TerminalCountersC)]),
+    "trhip_pt_set_primary_start": (_i, [_vp, _i]),
+    "trhip_pt_get_primary_start": (_i, [_vp, C.POINTER(PrimaryStartInfoC)]),
     "trhip_pt_get_max_stack_depth": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "trhip_trace_terminal": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "trhip_stitch_batch": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, C.c_float, _vp]),
@@ -424,6 +435,7 @@ SYMBOLS = {
     "trhip_sh_download": (_i, [_vp, _i, _vp, C.c_size_t]),
     "trhip_sh_get_counters": (_i, [_vp, C.POINTER(CountersC)]),
     "trhip_sh_get_timings": (_i, [_vp, C.POINTER(ShTimingsC)]),
+    "trhip_sh_get_primary_start": (_i, [_vp, C.POINTER(PrimaryStartInfoC)]),
     "trhip_sh_set_profiling": (_i, [_vp, _i, _i]),
     "trhip_sh_reset_counters": (_i, [_vp]),
     "trhip_dshgi_create": (_i, [_vp, C.POINTER(DshgiOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),

@@ -972,6 +972,21 @@ int trhip_pt_set_terminal_query(trhip_pt* pt, int mode) {
     pt->stage->terminal_query = mode;
     return 0;
 }
+int trhip_pt_set_primary_start(trhip_pt* pt, int mode) {
+    if (!pt) return set_error("null trhip_pt");
+    if (mode != TRHIP_PRIMARY_START_AUTO && mode != TRHIP_PRIMARY_START_OFF)
+        return set_error("trhip_pt_set_primary_start: unknown mode " + std::to_string(mode) + " (0 auto, 1 off)");
+    pt->stage->primary_start = mode;
+    return 0;
+}
+int trhip_pt_get_primary_start(trhip_pt* pt, trhip_primary_start_info* out) {
+    if (!pt) return set_error("null trhip_pt");
+    if (!out) return set_error("trhip_pt_get_primary_start: null output");
+    const int e = pt->stage->primary_start_in_effect();
+    if (e < 0) return set_error("trhip_pt_get_primary_start: TRHIP_PRIMARY_START is not auto or off");
+    out->mode = pt->stage->primary_start; out->in_effect = e; out->last_frame = pt->stage->last_primary_start; out->pad = 0;
+    return 0;
+}
 int trhip_pt_get_terminal_counters(trhip_pt* pt, trhip_terminal_counters* out) {
     if (!pt) return set_error("null trhip_pt");
     if (!out) return set_error("trhip_pt_get_terminal_counters: null output");

@@ -47,6 +47,8 @@ public:
     int get_terminal_counters(trhip_terminal_counters* out, hipStream_t stream);
     int get_program(trhip_program_info* out);
     int terminal_query_in_effect() const;
+    int primary_start_in_effect() const;
+    bool shades_with_cli_set() const;
 
     DeviceScene* scene;
     trhip_pt_options opt;
@@ -66,6 +68,8 @@ public:
     int ieee_shading = -1;           // trhip_pt_set_shading_arithmetic: 1 = k_shade at IEEE fp32 for every option set, 0 = Vulkan-grade arithmetic for the command-line set, -1 = TRHIP_SHADE_FAST decides
     int specialize = -1;             // trhip_pt_set_specialization: 1 = a shading program compiled for this stage's option set (hipRTC / kernel cache), 0 = the general kernels, -1 = TRHIP_SPECIALIZE decides (default on)
     int terminal_query = -1;         // trhip_pt_set_terminal_query: TRHIP_TERMINAL_QUERY_AUTO / _OFF, -1 = TRHIP_TERMINAL_QUERY decides (default auto)
+    int primary_start = -1;          // trhip_pt_set_primary_start: TRHIP_PRIMARY_START_AUTO / _OFF, -1 = TRHIP_PRIMARY_START decides (default auto)
+    int last_primary_start = -1;     // whether the last frame rendered started its paths that way (-1: no frame yet)
     bool direct = false;             // direct_stage instead of path_tracer_stage (trhip_direct_create)
     // sh_path_tracer_stage instead (trhip_sh_create): render() traces the batch `probes` names - k_sh_raygen instead of k_raygen, the bounce
     // loop with hidden lights and the first-bounce clamp on the general kernels, no resolve (sh_probes.hip projects the path state)

@@ -73,7 +73,10 @@ __global__ __launch_bounds__(KB) void k_accumulate_sample(PtParams P, PathBuffer
     const uint i = blockIdx.x * KB + threadIdx.x;
     if (i < P.n_ids) accumulate_sample_path(P, pb, i + P.id_offset);
 }
+// The last launch of a lane's pass, behind every kernel that reads the lane's queue lengths and work cursors: block 0 leaves them zeroed
+// for the lane's next pass, which may start without a k_raygen launch (the primary start).
 __global__ __launch_bounds__(KB) void k_resolve(PtParams P, PathBuffers pb) {
+    if (blockIdx.x == 0) for (uint k = threadIdx.x; k < P.bounce_words; k += KB) pb.bounce[k] = 0;
     const uint i = blockIdx.x * KB + threadIdx.x;
     if (i < P.n_ids) resolve_path(P, pb, i + P.id_offset);
 }

@@ -368,6 +368,14 @@ int trhip_sh_get_counters(trhip_sh* s, trhip_counters* out) {
     return s->pt->get_counters(out, s->last_stream);
 }
 
+int trhip_sh_get_primary_start(trhip_sh* s, trhip_primary_start_info* out) {      // trhip_pt_get_primary_start of the bounce loop: never in effect
+    if (!s || !out) return set_error("trhip_sh_get_primary_start: null argument");
+    const int e = s->pt->primary_start_in_effect();
+    if (e < 0) return set_error("trhip_sh_get_primary_start: TRHIP_PRIMARY_START is not auto or off");
+    out->mode = s->pt->primary_start; out->in_effect = e; out->last_frame = s->pt->last_primary_start; out->pad = 0;
+    return 0;
+}
+
 int trhip_sh_set_profiling(trhip_sh* s, int count_work, int detailed_timing) {
     if (!s) return set_error("trhip_sh_set_profiling: null stage");
     s->pt->count_work = count_work; s->pt->detailed_timing = detailed_timing;

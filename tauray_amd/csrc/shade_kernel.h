@@ -229,6 +229,53 @@ struct SpecMacros {
     }
 };
 #endif
+// get_world_camera_ray (path_tracer.glsl:504-533) with the sampler draws ahead of it (path_tracer.rgen:88-101, path_tracer.glsl:376-384).
+// How the path of launch id `i` starts: a pure function of the id, the launch parameters (option set already pinned) and the camera.
+// The one place that derives it: k_raygen stores what it returns, and the primary closest-hit launch (trace_lanes.h)
+// calls it in the lanes that trace the ray.  Integer hashing and fp32 arithmetic without contraction; every caller is compiled at IEEE
+// fp32 (path_tracer.hip, and shade_spec.hip's ray generation), so the bits are the same wherever it runs.
+struct PathStart {
+    bool valid;            // get_pixel_pos: false for the launch ids of a shard past its last pixel (everything below is then zero)
+    f3 origin, dir;        // the camera ray
+    u4 rng;                // random_sampler.seed after the film, lens and seed draws
+    uint seed;             // payload.random_seed of bounce 0 (PathBuffers::misc.x)
+    uint sobol_index;      // PathBuffers::misc.y
+};
+TR_DEV PathStart path_start(const SceneView& sv, const PtParams& P, uint i) {
+    PathStart s;
+    s.origin = F3(0); s.dir = F3(0); s.rng = u4{0, 0, 0, 0}; s.seed = 0; s.sobol_index = 0;
+    uint lx, ly, lz;
+    launch_coord(P.L, i, lx, ly, lz);
+    int px, py;
+    s.valid = get_pixel_pos(P.L, lx, ly, px, py);
+    if (!s.valid) return s;
+    LocalSampler ls = init_local_sampler(u4{(uint)px, (uint)py, global_viewport(P, lz), P.rng_sample}, sample_counter_of(P, lz),
+                                         P.rng_seed, P.opt.sampler);
+    f2 cam_offset = F2(0.0f);
+    if (P.opt.film != 0) {   // control.antialiasing == 1
+        f4 r = u4_to_unit(pcg4d(ls.rs));   // generate_film_sample
+        if (P.opt.film == 1) cam_offset = F2(r.x, r.y) * 2.0f - 1.0f;
+        else cam_offset = sample_blackman_harris_concentric_disk(F2(r.x, r.y)) * 2.0f;
+        cam_offset = cam_offset * (2.0f * P.opt.film_radius);
+    }
+    f2 dof_u = F2(0.5f);
+    if (P.opt.depth_of_field) { f4 r = u4_to_unit(pcg4d(ls.rs)); dof_u = F2(r.x, r.y); }
+    get_screen_camera_ray(P.L, px, py, sv.cameras[global_viewport(P, lz)], P.opt.projection, P.opt.depth_of_field != 0, cam_offset, dof_u, s.origin, s.dir);
+    s.seed = pcg4d(ls.rs).x;      // payload.random_seed = pcg4d(lsampler.rs.seed).x  (path_tracer.glsl:384)
+    s.sobol_index = ls.sobol_index;
+    s.rng = ls.rs;
+    return s;
+}
+// The path state ahead of bounce 0 as the bounce kernels read it: the start plus the constants of path_tracer.glsl:376-384.  A launch id
+// without a pixel gets its dead flag and nothing else.
+TR_DEV void store_path_start(const PathBuffers& pb, uint i, const PathStart& s) {
+    pb.misc[i] = u4{s.seed, s.sobol_index, i, s.valid ? 0u : 1u};
+    if (!s.valid) return;
+    pb.org_pdf[i] = F4(s.origin, 0.0f);          // bsdf_pdf = 0
+    pb.dir_reg[i] = F4(s.dir, 1.0f);             // regularization = 1
+    pb.atten_alpha[i] = F4(1, 1, 1, 1);          // attenuation = 1
+    pb.rng[i] = s.rng;
+}
 // What one bounce of one path leaves for the kernel that called it: whether the path goes on, and its shadow ray if it cast one
 // (contrib *= shadow_ray(...) happens in the trace kernel, including the clamp on the occluded value).
 struct ShadeOut {
@@ -522,7 +569,7 @@ TR_DEV void shade_bounce(const SceneView& sv_, const PtParams& P_, const PathBuf
 }
 
 // ---------------------------------------------------------------------------------------------------
-// path_tracer.rgen:88-101 + get_world_camera_ray (path_tracer.glsl:504-533)
+// path_tracer.rgen:88-101
 template <typename S>
 TR_DEV void raygen_paths(const SceneView& sv, const PtParams& P_, const PathBuffers& pb) {
     PtParams P = P_;
@@ -531,36 +578,11 @@ TR_DEV void raygen_paths(const SceneView& sv, const PtParams& P_, const PathBuff
     uint i = blockIdx.x * KB + threadIdx.x;
     if (i >= P.n_ids) return;
     i += P.id_offset;
-    uint lx, ly, lz;
-    launch_coord(P.L, i, lx, ly, lz);
-    int px, py;
-    bool valid = get_pixel_pos(P.L, lx, ly, px, py);
-    u4 misc = {0, 0, i, valid ? 0u : 1u};
     if (P.sample_in_pass == 0 && !P.fused_resolve) {
         pb.sum_color[i] = F4(0, 0, 0, 1);
         if (pb.sum_diffuse) { pb.sum_diffuse[i] = F4(0); pb.sum_reflection[i] = F4(0); }
     }
-    if (!valid) { pb.misc[i] = misc; return; }
-    LocalSampler ls = init_local_sampler(u4{(uint)px, (uint)py, global_viewport(P, lz), P.rng_sample}, sample_counter_of(P, lz),
-                                         P.rng_seed, P.opt.sampler);
-    f2 cam_offset = F2(0.0f);
-    if (P.opt.film != 0) {   // control.antialiasing == 1
-        f4 r = u4_to_unit(pcg4d(ls.rs));   // generate_film_sample
-        if (P.opt.film == 1) cam_offset = F2(r.x, r.y) * 2.0f - 1.0f;
-        else cam_offset = sample_blackman_harris_concentric_disk(F2(r.x, r.y)) * 2.0f;
-        cam_offset = cam_offset * (2.0f * P.opt.film_radius);
-    }
-    f2 dof_u = F2(0.5f);
-    if (P.opt.depth_of_field) { f4 r = u4_to_unit(pcg4d(ls.rs)); dof_u = F2(r.x, r.y); }
-    f3 origin, dir;
-    get_screen_camera_ray(P.L, px, py, sv.cameras[global_viewport(P, lz)], P.opt.projection, P.opt.depth_of_field != 0, cam_offset, dof_u, origin, dir);
-    misc.x = pcg4d(ls.rs).x;      // payload.random_seed = pcg4d(lsampler.rs.seed).x  (path_tracer.glsl:384)
-    misc.y = ls.sobol_index;
-    pb.org_pdf[i] = F4(origin, 0.0f);            // bsdf_pdf = 0
-    pb.dir_reg[i] = F4(dir, 1.0f);               // regularization = 1
-    pb.atten_alpha[i] = F4(1, 1, 1, 1);          // attenuation = 1
-    pb.rng[i] = ls.rs;
-    pb.misc[i] = misc;
+    store_path_start(pb, i, path_start(sv, P, i));
 }
 template <typename S = SpecGeneral>
 __global__ __launch_bounds__(KB) void k_raygen(SceneView sv, PtParams P, PathBuffers pb) { raygen_paths<S>(sv, P, pb); }

@@ -4,6 +4,7 @@
 #include "trace.h"
 #include "trace_quad.h"
 #include "pt_state.h"
+#include "shade_kernel.h"      // path_start
 
 namespace tr {
 
@@ -17,11 +18,42 @@ namespace {
 // emitter queries.  A path whose ray is blocked is over - its last k_shade pass would add exactly nothing - and gets neither a hit
 // record nor a place in `next_queue`; the others (escaped, reached an emitter, traced as an ordinary closest hit because
 // terminal_early_ok failed) are appended there with one ballot and one atomic per wave, and the bounce's k_shade runs over that queue.
+//
+// PRIMARY (the launch of bounce 0 while the primary start is in effect): no k_raygen ran.  Every lane derives its
+// path's start from its launch id (shade_kernel.h path_start - the function k_raygen calls), traces the camera ray out of registers and
+// stores the path state k_raygen would have stored, for the kernels behind it (primary_ray, called by the kernel ahead of this function).
+// All of that is over before the traversal loop starts.
 struct TerminalCounts { uint blocked, fallback; };
-template <bool COUNT, bool TWO_LEVEL = false, bool TERMINAL = false>
+// The head of the argument segment of a kernel that calls closest_lane<.., PRIMARY>: (SceneView, PtParams, ...) by value
+// (k_trace_closest_primary, path_tracer.hip, which asserts it)
+struct PrimaryKernArgs { SceneView sv; PtParams P; };
+// What closest_lane<.., PRIMARY> traces: the camera ray of path `id`, as primary_ray left it
+struct PrimaryRay { bool valid; uint id, seed; f3 origin, dir; };
+// The start of the path of slot `qi` of a lane's launch ids (shade_kernel.h path_start), stored as k_raygen stores it.
+// S: the option set the start is compiled for (SpecCli leaves the uniform-random sampler, the point film and no lens).
+template <typename S>
+TR_DEV PrimaryRay primary_ray(const SceneView& sv, const PathBuffers& pb, uint qi, uint n) {
+    PrimaryRay r = {false, 0u, 0u, F3(0), F3(0)};
+    if (qi >= n) return r;
+    // The parameters afresh out of the kernel-argument segment, through a pointer the optimiser cannot see through (as k_shade does,
+    // shade_kernel.h TR_SHADE_FRESH_ARGS): from the kernel's own `P` the compiler hoists the start's invariants - the pieces of the
+    // divisions by the launch size, the film and lens constants - out of the wave's chunk loop and spills them around the traversal.
+    typedef const PrimaryKernArgs __attribute__((address_space(4)))* KernArgPtr;
+    KernArgPtr ka = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    PtParams P;
+    load_kernarg(P, &ka->P);
+    S::pin(P);
+    r.id = qi + P.id_offset;
+    const PathStart s = path_start(sv, P, r.id);
+    store_path_start(pb, r.id, s);
+    r.valid = s.valid; r.seed = s.seed; r.origin = s.origin; r.dir = s.dir;
+    return r;
+}
+template <bool COUNT, bool TWO_LEVEL = false, bool TERMINAL = false, bool PRIMARY = false>
 TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffers& pb, int bounce, const uint* queue, uint qi, uint n, int* lds_stack,
                          const QuadCtx& qc, TraceStats& st, int& overflow, uint& max_vis, uint& rays, uint* next_queue = nullptr, uint* next_count = nullptr,
-                         TerminalCounts* tc = nullptr) {
+                         TerminalCounts* tc = nullptr, const PrimaryRay* pr = nullptr) {
     bool valid = qi < n;
     uint id = 0;
     u4 misc = {0, 0, 0, 1};
@@ -50,6 +82,8 @@ TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffe
     // the ray is fetched together with the path's flags, not behind them: one round trip less before the traversal starts, and a
     // queue holds live paths only (the flag matters at bounce 0, where the ids are all launch ids)
     TL(const unsigned long long tl_chunk = tl_now();)
+    if constexpr (PRIMARY) { valid = pr->valid; id = pr->id; misc.x = pr->seed; o = F4(pr->origin, 0.0f); d = F4(pr->dir, 1.0f); }
+    else
     if (valid) { id = queue ? queue[qi] : qi + P.id_offset; misc = pb.misc[id]; o = pb.org_pdf[id]; d = pb.dir_reg[id]; valid = !(misc.w & 1u); }
     TL(tl_data_arrived(); tl_misc(qc.tl, 3, tl_now() - tl_chunk);)
     // payload.random_seed of this trace: k_raygen stored the seed of bounce 0, every closest-hit trace advances it once
@@ -79,7 +113,8 @@ TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffe
     pb.hit[id] = make_int4(hit.instance_id, hit.primitive_id, __float_as_int(hit.u), __float_as_int(hit.v));
     if (sv.point_light_count != 0 && !(P.opt.hide_lights && bounce == 0)) {    // scalar tests: a scene without such lights reads nothing again
         // sphere lights (trace.h trace_sphere_lights) once the triangle hit is stored, with the ray read again: neither the registers that
-        // brought it to the traversal nor the hit are held across its loops for this (the asm keeps the compiler from reusing the first load)
+        // brought it to the traversal nor the hit are held across its loops for this (the asm keeps the compiler from reusing the first load).
+        // The primary instance reads back what this lane stored ahead of its traversal.
         uint rid = id;
         asm volatile("" : "+v"(rid));
         const f3 lo = F3(pb.org_pdf[rid]), ld = F3(pb.dir_reg[rid]);
@@ -93,6 +128,15 @@ TR_DEV void closest_lane(const SceneView& sv, const PtParams& P, const PathBuffe
 }
 
 // LDS and global scratch of a wave's quad tail
+TR_DEV QuadCtx make_quad_ctx_of(int* s_stack, int* s_owner, const PathBuffers& pb, uint tid) {      // ... of thread `tid` of the block
+    QuadCtx qc;
+    TL(qc.tl = nullptr;)
+    const uint wave = tid >> 6;
+    qc.wave_stack = s_stack + (tid & ~63u);
+    qc.owner_tab = s_owner + wave * TR_OWNER_WORDS;
+    qc.spill = pb.qspill + ((size_t)blockIdx.x * (KB / 64) + wave) * (16u * TR_QSPILL);
+    return qc;
+}
 TR_DEV QuadCtx make_quad_ctx(int* s_stack, int* s_owner, const PathBuffers& pb TL(, uint* s_tl = nullptr)) {
     QuadCtx qc;
     TL(qc.tl = s_tl ? s_tl + (threadIdx.x >> 6) * TL_WORDS : nullptr;)

@@ -631,6 +631,18 @@ class PathTracerStage:
         check(_lib.lib().trhip_pt_get_terminal_counters(self.h, C.byref(c)))
         return {n: int(getattr(c, n)) for n, _ in TerminalCountersC._fields_ if n != "pad"}
 
+    def set_primary_start(self, mode: int):
+        """trhip_pt_set_primary_start: _lib.PRIMARY_START_AUTO (the default: no ray generation launch, the closest-hit launch of bounce 0
+        computes the camera rays, where the stage allows it) or PRIMARY_START_OFF.  Frames and ray counts do not depend on the mode."""
+        check(_lib.lib().trhip_pt_set_primary_start(self.h, mode))
+
+    def primary_start(self) -> dict:
+        """trhip_pt_get_primary_start: mode (what was set, -1 none), in_effect (what the next frame does), last_frame (what the last frame
+        rendered did, -1 none yet)."""
+        p = _lib.PrimaryStartInfoC()
+        check(_lib.lib().trhip_pt_get_primary_start(self.h, C.byref(p)))
+        return {"mode": int(p.mode), "in_effect": bool(p.in_effect), "last_frame": int(p.last_frame)}
+
     def timings(self) -> dict:
         t = TimingsC()
         check(_lib.lib().trhip_pt_get_timings(self.h, C.byref(t)))
@@ -1140,6 +1152,12 @@ class ShPathTracerStage(_PostStage):
         c = CountersC()
         check(_lib.lib().trhip_sh_get_counters(self.h, C.byref(c)))
         return {n: getattr(c, n) for n, _ in c._fields_}
+
+    def primary_start(self) -> dict:
+        """trhip_sh_get_primary_start: as PathTracerStage.primary_start; a probe stage always starts its paths with its own ray generation."""
+        p = _lib.PrimaryStartInfoC()
+        check(_lib.lib().trhip_sh_get_primary_start(self.h, C.byref(p)))
+        return {"mode": int(p.mode), "in_effect": bool(p.in_effect), "last_frame": int(p.last_frame)}
 
     def set_profiling(self, count_work=False, detailed_timing=False):
         check(_lib.lib().trhip_sh_set_profiling(self.h, int(count_work), int(detailed_timing)))
