@@ -1156,16 +1156,32 @@ private:
     static const options& checked(const options& o) { o.restir.check(); return o; }      // the options are refused before anything is allocated
 };
 
-// ReSTIR GI (trhip_restir_gi_*; csrc/restir_gi.h pins the rule): one bounce of indirect light by reservoir resampling - per frame the
-// initial kernel (first hit, one cosine-hemisphere ray, a light sample at its hit), the temporal kernel (the history merge) and the spatial
-// kernel (neighbour merge, shading).  `size`, `layers`: the images of a frame.  The limits are listed in trhip.h and DESIGN.md section 25.
+// ReSTIR GI (trhip_restir_gi_*; csrc/restir_gi.h pins the rule): indirect light by reservoir resampling - per frame the initial kernel
+// (first hit, one cosine-hemisphere ray, a light sample at its hit and, with bounces > 1, the path continued from there), the temporal
+// kernel (the history merge) and the spatial kernel (neighbour merge, shading).  `size`, `layers`: the images of a frame.  The limits are
+// listed in trhip.h and DESIGN.md sections 25 and 30.
 class restir_gi_stage
 {
 public:
     struct options: restir_shared_options     // --restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse
     {
-        // what trhip_restir_gi_create refuses, said without a device
-        void check() const { check_shared("restir-gi"); }
+        uint32_t bounces = 1;                 // --restir-gi-bounces=N: the vertices of a sample's path behind the pixel (trhip_restir_gi_set_bounces)
+        // what trhip_restir_gi_create and trhip_restir_gi_set_bounces refuse, said without a device
+        void check() const
+        {
+            if(bounces < 1 || bounces > 8) throw std::runtime_error("restir-gi: bounces " + std::to_string(bounces) + " is outside 1..8");
+            check_shared("restir-gi");
+        }
+        // --restir-gi-bounces=N
+        void parse_bounces(const std::string& text)
+        {
+            size_t end = 0;
+            unsigned long n = 0;
+            try { n = std::stoul(text, &end); } catch(std::exception&) { end = 0; }
+            if(text.empty() || end != text.size() || text[0] == '-' || n < 1 || n > 8)
+                throw std::runtime_error("--restir-gi-bounces: " + text + " is not a whole number in 1..8");
+            bounces = (uint32_t)n;
+        }
         // --restir-gi=...: positional or name=value; a field left out keeps its value
         void parse(const std::string& text)
         {
@@ -1180,6 +1196,11 @@ public:
         opt.check();
         const trhip_restir_gi_options o = opt.c_options();
         check(trhip_restir_gi_create(dev.h, &o, size.x, size.y, layers, &h));
+        if(opt.bounces != 1 && trhip_restir_gi_set_bounces(h, opt.bounces) != 0)
+        {
+            trhip_restir_gi_destroy(h);
+            check(1);
+        }
     }
     restir_gi_stage(const restir_gi_stage&) = delete;
     ~restir_gi_stage() { trhip_restir_gi_destroy(h); }
@@ -1198,8 +1219,8 @@ public:
     trhip_restir_gi* h = nullptr;
 };
 
-// --renderer=restir-gi: the ReSTIR DI stage renders the direct light of every viewport, the ReSTIR GI stage adds one bounce of indirect
-// light to it, the frame is tonemapped - on one stream.
+// --renderer=restir-gi: the ReSTIR DI stage renders the direct light of every viewport, the ReSTIR GI stage adds indirect light to it
+// (options.restir_gi.bounces: how far a sample's path goes on), the frame is tonemapped - on one stream.
 class restir_gi_renderer: public viewport_frame_renderer
 {
 public:

@@ -1038,7 +1038,7 @@ int trhip_restir_di_get_timings(trhip_restir_di* stage, trhip_restir_di_timings*
 #define TRHIP_RESTIR_DI_FINAL 6       /* trhip_restir_di_final [layers][h][w] */
 int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
 
-/* ---- ReSTIR GI: reservoir resampling of one bounce of indirect light (after Ouyang et al. 2021 and the ReSTIR DI stage above, whose
+/* ---- ReSTIR GI: reservoir resampling of indirect light (after Ouyang et al. 2021 and the ReSTIR DI stage above, whose
  * resampling rule it keeps; the reference has no such renderer, its --renderer=restir is ReSTIR PT and is not built here: this is
  * `restir-gi` everywhere).  csrc/restir_gi.hip; the order of operations and of random draws is pinned in csrc/restir_gi.h.  A sample is
  * a point x_s on a surface, its geometric normal n_s towards the pixel that found it and the radiance L_o it sent there.  Per frame and
@@ -1052,13 +1052,16 @@ int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size
  * The contribution of a sample at a surface is the ggx_bsdf_pdf lobes through modulate_bsdf for the direction to x_s, times L_o; 0 when
  * the direction is below the surface's flat normal or behind n_s.  The stage's three random streams are disjoint from each other and
  * from both of DI's (fourth sampler coordinate 0x80000000 + 3 * frame + pass).
+ * With trhip_restir_gi_set_bounces(B > 1) the initial launch continues the path from x_s over B - 1 further vertices, each found by a
+ * cosine-hemisphere ray from the one before it and lit by one light sample of its own: L_o = the sum over the vertices of throughput *
+ * light sample (no emission, no Russian roulette); the null-sample test, the target and the reservoirs take that sum.
  * Limits:
  *   1. L_o is the radiance x_s sent towards the pixel that found it and is not evaluated again for a pixel that reuses the sample: the
  *      paper's Lambertian assumption, a bias on glossy secondary surfaces.
  *   2. No transmission: the contribution is 0 below the flat normal.
  *   3. A surface with roughness below 0.001 gets no specular indirect light (no delta lobes).
  *   4. History samples are not validated again when geometry or lights move; max_confidence bounds their age.
- *   5. Sphere lights are points, as in DI.  Cosine-hemisphere initial sampling only, one bounce, one device. */
+ *   5. Sphere lights are points, as in DI.  Cosine-hemisphere sampling only, at most 8 bounces without Russian roulette, one device. */
 typedef struct trhip_restir_gi trhip_restir_gi;
 typedef struct trhip_restir_gi_options {
     uint32_t spatial_samples;         /* 0..4 */
@@ -1079,9 +1082,20 @@ typedef struct trhip_restir_gi_initial {      /* per pixel; the last row is the 
     float dir[3], t;                          /* the secondary ray and its hit as trace_closest4 returns it, instance_id -1: none */
     int32_t instance_id, primitive_id; float u, v;
     uint32_t light_draw[4];                   /* the four words sample_canonical took at x_s */
-    float L_o[3], target;                     /* target: of the initial sample at the pixel (visibility 1) */
+    float L_o[3], target;                     /* L_o: the sum over the path's vertices; target: of the initial sample at the pixel (visibility 1) */
     float weight, sel_draw; uint32_t selected, pad;
 } trhip_restir_gi_initial;
+typedef struct trhip_restir_gi_path {         /* per pixel and extra vertex k + 1 = 2 .. bounces; nine aligned 16-byte words */
+    float draw[2], pdf; uint32_t traced;      /* unit .xy of the direction's draw at vertex k, its pdf; traced: the ray was cast */
+    float dir[3], t;                          /* the ray from vertex k and its hit as trace_closest4 returns it, instance_id -1: none */
+    int32_t instance_id, primitive_id; float u, v;
+    uint32_t light_draw[4];                   /* the four words sample_canonical took at vertex k + 1 */
+    uint32_t light; float light_data[2], light_pdf;    /* the light sample as trhip_restir_di_candidate has it; no sample: index 2^30 - 1 */
+    float contribution[3], visibility;
+    float factor[3], pad0;                    /* contribution of vertex k + 1 (radiance 1) at vertex k, / pdf */
+    float throughput[3], pad1;                /* T_{k+1}; 0 where no hit formed it */
+    float L_o[3], pad2;                       /* the running sum behind this vertex */
+} trhip_restir_gi_path;
 typedef struct trhip_restir_gi_timings {      /* device ms of the last render */
     float initial_ms, temporal_ms, spatial_ms, total_ms;
     uint32_t frames;
@@ -1091,6 +1105,10 @@ typedef struct trhip_restir_gi_timings {      /* device ms of the last render */
 int trhip_restir_gi_create(trhip_device* dev, const trhip_restir_gi_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_restir_gi** out);
 void trhip_restir_gi_destroy(trhip_restir_gi* stage);
 int trhip_restir_gi_reset(trhip_restir_gi* stage);        /* forgets the history and restarts the frame counter */
+/* The vertices of a sample's path behind the pixel, 1..8; 1 after create: L_o is one light sample at x_s.  Refuses a count outside 1..8,
+ * a null stage, and, while the stage holds history (a frame since create or reset), another count than the history's: a reservoir does
+ * not mix the samples of two estimators.  With record the path records are allocated here. */
+int trhip_restir_gi_set_bounces(trhip_restir_gi* stage, uint32_t bounces);
 /* One frame of `count` viewports (at most the stage's layers), three launches per 64, asynchronous on `stream`: out_color_dev RGBA32F
  * [count][h][w] = in_color_dev + indirect light; in_color_dev may be null ((0, 0, 0, 1) everywhere) or out_color_dev itself.  Refuses a
  * device without a scene or acceleration structure and a viewport out of range.  History is kept per layer, the position in the list:
@@ -1107,6 +1125,8 @@ int trhip_restir_gi_get_timings(trhip_restir_gi* stage, trhip_restir_gi_timings*
 #define TRHIP_RESTIR_GI_TEMPORAL 6    /* trhip_restir_di_temporal [layers][h][w] */
 #define TRHIP_RESTIR_GI_SPATIAL 7     /* trhip_restir_di_spatial [layers][h][w][spatial_samples] */
 #define TRHIP_RESTIR_GI_FINAL 8       /* trhip_restir_di_final [layers][h][w] */
+#define TRHIP_RESTIR_GI_PATH 9        /* trhip_restir_gi_path [layers][h][w][bounces - 1] (record and bounces > 1 only, as the one below) */
+#define TRHIP_RESTIR_GI_PATH_SURFACE 10   /* trhip_restir_di_surface [layers][h][w][bounces - 1]: the extra vertices, instance_id -1 where the lane had ended */
 int trhip_restir_gi_download(trhip_restir_gi* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
 
 #ifdef __cplusplus

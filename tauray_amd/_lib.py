@@ -294,13 +294,18 @@ class RestirGiTimingsC(C.Structure):
 # trhip_restir_gi_download and the records behind the codes (include/trhip.h); the surface, candidate, temporal, spatial and final
 # records are ReSTIR DI's
 (RESTIR_GI_SURFACE, RESTIR_GI_CANONICAL, RESTIR_GI_HISTORY, RESTIR_GI_INITIAL, RESTIR_GI_SECONDARY, RESTIR_GI_LIGHT, RESTIR_GI_TEMPORAL,
- RESTIR_GI_SPATIAL, RESTIR_GI_FINAL) = range(9)
+ RESTIR_GI_SPATIAL, RESTIR_GI_FINAL, RESTIR_GI_PATH, RESTIR_GI_PATH_SURFACE) = range(11)
+RESTIR_GI_MAX_BOUNCES = 8
 RESTIR_GI_SAMPLER_W = 0x80000000      # the fourth sampler coordinate of the stage's streams (csrc/restir_gi.h)
 RESTIR_GI_RESERVOIR_DTYPE = [("x_s", "<f4", 3), ("uc_weight", "<f4"), ("n_s", "<f4", 3), ("target_function", "<f4"), ("L_o", "<f4", 3),
                              ("confidence", "<f4")]
 RESTIR_GI_INITIAL_DTYPE = [("draw", "<f4", 2), ("pdf", "<f4"), ("traced", "<u4"), ("dir", "<f4", 3), ("t", "<f4"), ("instance_id", "<i4"),
                            ("primitive_id", "<i4"), ("u", "<f4"), ("v", "<f4"), ("light_draw", "<u4", 4), ("L_o", "<f4", 3), ("target", "<f4"),
                            ("weight", "<f4"), ("sel_draw", "<f4"), ("selected", "<u4"), ("pad", "<u4")]
+RESTIR_GI_PATH_DTYPE = [("draw", "<f4", 2), ("pdf", "<f4"), ("traced", "<u4"), ("dir", "<f4", 3), ("t", "<f4"), ("instance_id", "<i4"),
+                        ("primitive_id", "<i4"), ("u", "<f4"), ("v", "<f4"), ("light_draw", "<u4", 4), ("light", "<u4"), ("light_data", "<f4", 2),
+                        ("light_pdf", "<f4"), ("contribution", "<f4", 3), ("visibility", "<f4"), ("factor", "<f4", 3), ("pad0", "<f4"),
+                        ("throughput", "<f4", 3), ("pad1", "<f4"), ("L_o", "<f4", 3), ("pad2", "<f4")]
 
 
 # every symbol include/trhip.h declares: (name, restype, argtypes)
@@ -457,6 +462,7 @@ SYMBOLS = {
     "trhip_restir_gi_create": (_i, [_vp, C.POINTER(RestirGiOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),
     "trhip_restir_gi_destroy": (None, [_vp]),
     "trhip_restir_gi_reset": (_i, [_vp]),
+    "trhip_restir_gi_set_bounces": (_i, [_vp, _u32]),
     "trhip_restir_gi_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _vp, _vp, _vp]),
     "trhip_restir_gi_get_timings": (_i, [_vp, C.POINTER(RestirGiTimingsC)]),
     "trhip_restir_gi_download": (_i, [_vp, _i, _vp, C.c_size_t]),

@@ -1,4 +1,4 @@
-// ReSTIR GI - reservoir resampling of one bounce of indirect light (after Ouyang, Liu, Kettunen, Pharr and Pantaleoni, "ReSTIR GI: Path
+// ReSTIR GI - reservoir resampling of indirect light (after Ouyang, Liu, Kettunen, Pharr and Pantaleoni, "ReSTIR GI: Path
 // Resampling for Real-Time Path Tracing", 2021, and restir_di.h, whose resampling rule it keeps): constants, layouts, the order of
 // operations and the order of random draws of k_restir_gi_initial, k_restir_gi_temporal and k_restir_gi_spatial (restir_gi.hip) behind the
 // entry points trhip_restir_gi_* (include/trhip.h).  The reference has no such renderer; the rule is this project's own.
@@ -19,14 +19,17 @@
 //                     reprojected pixel position before the stochastic rounding, and length(ray origin - pos)
 //   decision records  (options.record) RestirGiInitialRecord [pixel], x_s's RestirSurface [pixel], its light sample as a
 //                     RestirCandidateRecord [pixel] (weight, draw, selected stay 0), RestirTemporalRecord [pixel], RestirSpatialRecord
-//                     [pixel][spatial_samples], RestirFinalRecord [pixel]  (the last three: restir_di.h's)
+//                     [pixel][spatial_samples], RestirFinalRecord [pixel]  (the last three: restir_di.h's); with bounces > 1 a
+//                     RestirGiPathRecord and the vertex's RestirSurface [pixel][bounces - 1], one per extra vertex x_2 ... x_bounces
 //
 // Random draws.  sampler = init_local_sampler((px, py, viewport, 0x80000000), 3 * frame + pass, pcg(rng_seed) or 0, uniform) (rng.h),
 // pass = 0, 1, 2 in the initial, temporal and spatial kernel, frame = the stage's frame counter: three streams disjoint from each other
 // and, for less than 2^30 frames, from both of DI's at every frame (DI's fourth coordinate is 2 * frame + pass, below 2^31; a fourth
 // coordinate of 1 would not do: 1 + 3 * frame + pass meets DI's 2 * frame' + pass').  A draw is pcg4d(sampler.rs); "unit" =
 // float(word) * 2^-32 per component.  Order:
-//   initial    one draw (unit .xy: the direction); if the secondary ray hits: one draw (the four words: sample_canonical at x_s)
+//   initial    one draw (unit .xy: the direction); if the secondary ray hits: one draw (the four words: sample_canonical at x_s);
+//              [bounces > 1, behind those two, per extra vertex while the lane is alive: one draw (unit .xy: the direction), and
+//              if the throughput survives: one draw (the four words: sample_canonical at the new vertex)]
 //   temporal   [TEMPORAL: one draw, unit .xy: the reprojection]  one draw (unit .x: the selection of the initial sample)
 //              [reuse: one draw, unit .x: the temporal merge]
 //   spatial    2 * SPATIAL draws (unit .xy: the offsets), per slot that holds a neighbour whose sample is not null one draw (unit .x),
@@ -43,7 +46,22 @@
 //                probabilities, its light_contribution at x_s's record and its shadow ray, as DI's candidate;
 //                L_o = (contribution * visibility) / light_pdf per component, 0 if any component is NaN or inf; x_s's own emission is
 //                not part of it (it is direct light at the pixel).  An L_o without a positive component: the null sample.
-//                The sample is (x_s.pos, x_s.flat_normal, L_o).
+//                The sample is (x_s.pos, x_s.flat_normal, L_o).  This is bounces = 1.
+//   path         bounces = B > 1 (trhip_restir_gi_set_bounces): L_o is the radiance of a path continued from x_1 := x_s, a vertex
+//                treating the next one exactly as the pixel treats x_s.  dom_1 = x_s's surface record, T_1 = (1, 1, 1), L_o = NEE_1 =
+//                the L_o above.  For k = 1 .. B - 1 while the lane is alive: one draw u; local = sample_cosine_hemisphere<RoundedMath>(u.xy);
+//                dir_k = create_tangent_space(dom_k.mapped_normal) * local; pdf_k = pdf_cosine_hemisphere(local);
+//                dot(dir_k, dom_k.flat_normal) < 1e-6f or pdf_k <= 0 ends the lane; else trace_closest4 from dom_k.pos along dir_k from
+//                min_ray_dist to infinity; a miss ends the lane (what that ray sees is direct light at x_k, which NEE_k estimates); a
+//                hit is dom_{k+1} = first_hit_surface(sv, hit, dir_k, dom_k.pos) with view = normalize(x_{k+1} - x_k);
+//                f_k = contribution of the sample (x_{k+1}, dom_{k+1}.flat_normal, (1, 1, 1)) at dom_k, / pdf_k per component;
+//                T_{k+1} = T_k * f_k per component; a T_{k+1} with a NaN or inf component or without a positive one ends the lane;
+//                else one draw, the four words of sample_canonical at x_{k+1}, its light_contribution at dom_{k+1} and its shadow ray
+//                as at x_1: NEE_{k+1} = (contribution * visibility) / light_pdf, non-finite -> 0; L_o = L_o + T_{k+1} * NEE_{k+1}.
+//                The emission of a vertex is never added (it is direct light at the vertex before it, which that vertex's light
+//                sample covers); no Russian roulette; cosine sampling only; limits 2 and 3 hold at every vertex.  The test for the
+//                null sample, the target and the recorded L_o take the final sum: a path whose first light sample is black can
+//                still carry light.
 //   contribution of a sample at a surface: to = x_s - pos; dist2 = dot(to, to); dir = normalize(to); normal = n_s.  0 (with dir = 0,
 //                dist2 = 0) for the null sample;  0 when not dist2 > 0, when dot(dir, flat_normal) < 1e-6f or when
 //                dot(n_s, -dir) < 1e-6f;  else tbn, shading_view, shading_light, ggx_bsdf_pdf<RoundedMath>, correct_lobes_for_normal_map
@@ -67,10 +85,11 @@
 //   2. No transmission: the contribution is 0 below the flat normal.
 //   3. A surface with roughness below 0.001 gets no specular indirect light (ggx_bsdf_pdf's distribution is 0 there; no delta lobes).
 //   4. History samples are not validated again when geometry or lights move; max_confidence bounds their age.
-//   5. Sphere lights are points, as in DI.  Cosine-hemisphere initial sampling only, one bounce, one device.
+//   5. Sphere lights are points, as in DI.  Cosine-hemisphere sampling only, at most 8 bounces without Russian roulette, one device.
 //
 // Where the code is.  temporal, spatial and what they take from restir_di.h: restir_resample.h, the same code as ReSTIR DI's.  Here: the
-// reservoir, the reprojection and initial records and RestirGiKind with `contribution`.  initial, resampling and colour: restir_gi.hip.
+// reservoir, the reprojection, initial and path records and RestirGiKind with `contribution`.  initial, resampling and colour:
+// restir_gi.hip; `path`: restir_gi_path.hip (restir_gi_path.h: the kernels' parameters, shared by the two).
 #pragma once
 #include "restir_di.h"
 
@@ -94,7 +113,19 @@ struct RestirGiInitialRecord {           // trhip_restir_gi_initial
     f3 L_o; float target;                // target: of the initial sample at the pixel
     float weight, sel_draw; uint selected, pad;   // the temporal kernel's update_reservoir of the initial sample
 };
-static_assert(sizeof(RestirGiReservoir) == 48 && sizeof(RestirGiReproject) == 16 && sizeof(RestirGiInitialRecord) == 96, "layout");
+struct alignas(16) RestirGiPathRecord {  // trhip_restir_gi_path: extra vertex k + 1 of `path`, nine aligned 16-byte words
+    f2 draw; float pdf; uint traced;     // unit .xy of dir_k's draw, pdf_k; traced: the ray was cast
+    f3 dir; float t;                     // dir_k and its hit (instance_id -1: none), as trace_closest4 returns it
+    int instance_id, primitive_id; float u, v;
+    u4 light_draw;                       // the four words sample_canonical took at x_{k+1} (0 where the lane ended before)
+    uint light; f2 light_data; float light_pdf;      // the light sample as RestirCandidateRecord has it (RESTIR_NULL_INDEX: none)
+    f3 contribution; float visibility;
+    f3 factor; float pad0;               // f_k
+    f3 throughput; float pad1;           // T_{k+1} (0 where no hit formed it)
+    f3 L_o; float pad2;                  // the running sum behind this vertex
+};
+static_assert(sizeof(RestirGiReservoir) == 48 && sizeof(RestirGiReproject) == 16 && sizeof(RestirGiInitialRecord) == 96 && sizeof(RestirGiPathRecord) == 144, "layout");
+constexpr uint RESTIR_GI_MAX_BOUNCES = 8u;
 
 struct RestirGiSample { f3 x, n, L; };
 

@@ -1,7 +1,9 @@
-// ReSTIR GI for gfx950 - reservoir resampling of one bounce of indirect light, behind the entry points trhip_restir_gi_* of include/trhip.h.
+// ReSTIR GI for gfx950 - reservoir resampling of indirect light, behind the entry points trhip_restir_gi_* of include/trhip.h.
 //   k_restir_gi_initial    per pixel of every viewport: the first hit and its surface (first_hit.h), the surface record, one
 //                          cosine-hemisphere ray and its closest hit x_s, x_s's surface, one light sample there with its shadow ray: the
 //                          initial sample (x_s, n_s, L_o), its pdf and its target; the reprojected position for the temporal kernel
+//   k_restir_gi_initial_path  (restir_gi_path.hip) the same with L_o continued from x_s over bounces - 1 further vertices, launched in
+//                          k_restir_gi_initial's place by a stage with bounces > 1 (`path` of restir_gi.h)
 //   k_restir_gi_temporal   no rays: the initial sample's resampling weight, the reprojection and the merge of the history reservoir
 //   k_restir_gi_spatial    the neighbour search, the pairwise-MIS merge of the neighbours' canonical reservoirs (two shadow rays a
 //                          neighbour), the chosen sample's shading (one more), the history reservoir and the colour added to `in`
@@ -9,36 +11,16 @@
 // temporal and the spatial merge and the host skeleton are restir_resample.h's, shared with ReSTIR DI.  Three
 // kernels, not DI's two: the initial kernel holds two closest-hit traversals and two shade_surface calls, and the merge that follows needs
 // none of their registers.  IEEE fp32 without contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.
+#include <algorithm>
 #include <string>
 #include <vector>
 
-#include "restir_gi.h"
+#include "restir_gi_path.h"
 
 namespace tr {
 namespace {
 
-constexpr int KB = TR_BLOCK;
 using Kind = RestirGiKind;
-
-struct RestirGiParams {
-    float search_radius, max_confidence, min_ray_dist;
-    float prob_point, prob_tri, prob_dir, prob_env;
-    uint rng_seed, frame;              // pcg(rng_seed) or 0; the stage's frame counter
-    int has_history;
-    RestirSurface* surface;            // this frame's half
-    const RestirSurface* prev_surface; // the other half
-    RestirGiReservoir* canonical;
-    RestirGiReservoir* history;
-    RestirGiReproject* reproject;      // null without temporal reuse
-    const f4* in;                      // null: (0, 0, 0, 1)
-    f4* out;
-    RestirGiInitialRecord* rec_initial;         // null unless options.record, as the five below
-    RestirSurface* rec_secondary;
-    RestirCandidateRecord* rec_light;
-    RestirTemporalRecord* rec_temporal;
-    RestirSpatialRecord* rec_spatial;
-    RestirFinalRecord* rec_final;
-};
 
 TR_DEV bool finite3(f3 v) { return !(isnan(v.x) || isnan(v.y) || isnan(v.z) || isinf(v.x) || isinf(v.y) || isinf(v.z)); }
 
@@ -230,8 +212,6 @@ __global__ __launch_bounds__(KB, 2) void k_restir_gi_spatial(SceneView sv, Launc
     if (P.rec_final) restir_write_final(P.rec_final + pix, frec);
 }
 
-using RestirGiKernel = void (*)(SceneView, LaunchCtx, int, ViewportList, RestirGiParams, uint*);
-
 template <bool TWO_LEVEL>
 RestirGiKernel spatial_kernel(uint32_t spatial) {
     switch (spatial) {
@@ -257,9 +237,13 @@ struct trhip_restir_gi : RestirStageHost<4> {
     RestirGiInitialRecord* rec_initial = nullptr;
     RestirSurface* rec_secondary = nullptr;
     RestirCandidateRecord* rec_light = nullptr;
+    uint32_t bounces = 1;                          // trhip_restir_gi_set_bounces
+    RestirGiPathRecord* rec_path = nullptr;        // [pixels][bounces - 1]; null unless options.record and bounces > 1, as the one below
+    RestirSurface* rec_path_surface = nullptr;
 };
 
-static_assert(sizeof(trhip_restir_gi_reservoir) == sizeof(RestirGiReservoir) && sizeof(trhip_restir_gi_initial) == sizeof(RestirGiInitialRecord), "downloads are the kernels' records");
+static_assert(sizeof(trhip_restir_gi_reservoir) == sizeof(RestirGiReservoir) && sizeof(trhip_restir_gi_initial) == sizeof(RestirGiInitialRecord) &&
+              sizeof(trhip_restir_gi_path) == sizeof(RestirGiPathRecord), "downloads are the kernels' records");
 
 extern "C" {
 
@@ -280,14 +264,54 @@ void trhip_restir_gi_destroy(trhip_restir_gi* s) { stage_destroy(s); }
 
 int trhip_restir_gi_reset(trhip_restir_gi* s) { return restir_reset(API, s); }
 
+int trhip_restir_gi_set_bounces(trhip_restir_gi* s, uint32_t bounces) {
+    const std::string fn = std::string(API) + "_set_bounces";
+    if (bounces < 1u || bounces > RESTIR_GI_MAX_BOUNCES) return set_error(fn + ": bounces " + std::to_string(bounces) + " is outside 1..8");
+    if (!s) return set_error(fn + ": null stage");
+    // a reservoir must not mix the samples of two estimators silently
+    if (s->frame > 0 && bounces != s->bounces)
+        return set_error(fn + ": the stage holds history of " + std::to_string(s->bounces) + " bounces: call " + API + "_reset first");
+    if (bounces == s->bounces) return 0;
+    if (s->opt.record) {     // the path records have one entry per extra vertex
+        DEVCHK(s->hip_device);
+        HIPCHK(hipDeviceSynchronize());
+        for (void* old : {(void*)s->rec_path, (void*)s->rec_path_surface}) {
+            if (!old) continue;
+            s->allocations.erase(std::find(s->allocations.begin(), s->allocations.end(), old));
+            HIPCHK(hipFree(old));
+        }
+        s->rec_path = nullptr; s->rec_path_surface = nullptr;
+        s->bounces = 1;
+        if (bounces > 1u) {
+            const size_t n = s->pixels() * (bounces - 1u);
+            s->alloc_zeroed(s->rec_path, n * sizeof(RestirGiPathRecord));
+            s->alloc_zeroed(s->rec_path_surface, n * sizeof(RestirSurface));
+            if (s->err == hipSuccess) s->err = hipDeviceSynchronize();
+            if (s->err != hipSuccess) {
+                const hipError_t e = s->err;
+                s->err = hipSuccess;
+                return set_error(fn + ": " + hipGetErrorString(e));
+            }
+        }
+    }
+    s->bounces = bounces;
+    return 0;
+}
+
 int trhip_restir_gi_render(trhip_restir_gi* s, int projection, const uint32_t* viewports, uint32_t count, const void* in_color_dev, void* out_color_dev, void* stream) {
     DeviceScene* scene = nullptr;
     if (int r = restir_begin_render(API, s, viewports, count, out_color_dev, scene)) return r;
     RestirGiParams base{};
     restir_fill_params(base, *s, *scene);
     const bool temporal = s->opt.temporal_reuse != 0;
+    const bool path = s->bounces > 1u;
+    // restir_run_passes fills the parameters of every chunk of a pass, then the next pass's: the first `chunks` fills are the initial pass's
+    constexpr uint32_t per_launch = sizeof(ViewportList::v) / sizeof(ViewportList::v[0]);
+    const uint32_t chunks = (count + per_launch - 1u) / per_launch;
+    uint32_t filled = 0;
     const RestirGiKernel kernels[3] = {
-        scene->two_level ? k_restir_gi_initial<true> : k_restir_gi_initial<false>,
+        path ? restir_gi_initial_path_kernel(scene->two_level)
+             : (scene->two_level ? k_restir_gi_initial<true> : k_restir_gi_initial<false>),
         temporal ? k_restir_gi_temporal<true> : k_restir_gi_temporal<false>,
         scene->two_level ? spatial_kernel<true>(s->opt.spatial_samples) : spatial_kernel<false>(s->opt.spatial_samples)};
     return restir_run_passes(s, scene, projection, viewports, count, (hipStream_t)stream, base, kernels, 3, [&](RestirGiParams& P, size_t off) {
@@ -298,6 +322,9 @@ int trhip_restir_gi_render(trhip_restir_gi* s, int projection, const uint32_t* v
         P.rec_initial = s->rec_initial ? s->rec_initial + off : nullptr;
         P.rec_secondary = s->rec_secondary ? s->rec_secondary + off : nullptr;
         P.rec_light = s->rec_light ? s->rec_light + off : nullptr;
+        if (path && filled++ < chunks)
+            restir_gi_set_path_args(P, {s->bounces, s->rec_path ? s->rec_path + off * (s->bounces - 1u) : nullptr,
+                                        s->rec_path_surface ? s->rec_path_surface + off * (s->bounces - 1u) : nullptr});
     });
 }
 
@@ -315,9 +342,13 @@ int trhip_restir_gi_get_timings(trhip_restir_gi* s, trhip_restir_gi_timings* out
 
 int trhip_restir_gi_download(trhip_restir_gi* s, int which, void* host, size_t bytes) {
     const int shared[4] = {TRHIP_RESTIR_GI_SURFACE, TRHIP_RESTIR_GI_TEMPORAL, TRHIP_RESTIR_GI_SPATIAL, TRHIP_RESTIR_GI_FINAL};
-    return restir_download(API, s, which, host, bytes, which >= TRHIP_RESTIR_GI_INITIAL && which <= TRHIP_RESTIR_GI_FINAL, shared,
+    const bool path = which == TRHIP_RESTIR_GI_PATH || which == TRHIP_RESTIR_GI_PATH_SURFACE;
+    if (s && host && path && s->opt.record && s->bounces == 1u) return set_error(std::string(API) + "_download: a stage of one bounce has no path records");
+    return restir_download(API, s, which, host, bytes, which >= TRHIP_RESTIR_GI_INITIAL && which <= TRHIP_RESTIR_GI_PATH_SURFACE, shared,
         [&](size_t n, const void*& src, size_t& size) {
             switch (which) {
+                case TRHIP_RESTIR_GI_PATH: src = s->rec_path; size = n * (s->bounces - 1u) * sizeof(RestirGiPathRecord); return true;
+                case TRHIP_RESTIR_GI_PATH_SURFACE: src = s->rec_path_surface; size = n * (s->bounces - 1u) * sizeof(RestirSurface); return true;
                 case TRHIP_RESTIR_GI_CANONICAL: src = s->canonical; size = n * sizeof(RestirGiReservoir); return true;
                 case TRHIP_RESTIR_GI_HISTORY: src = s->history; size = n * sizeof(RestirGiReservoir); return true;
                 case TRHIP_RESTIR_GI_INITIAL: src = s->rec_initial; size = n * sizeof(RestirGiInitialRecord); return true;

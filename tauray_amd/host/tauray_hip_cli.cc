@@ -10,7 +10,7 @@
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
 //              [--renderer=restir-di [--restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse]]
-//              [--renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse] [--restir=...]]
+//              [--renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse] [--restir-gi-bounces=N] [--restir=...]]
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
 //              [--taa=N[,edge-dilation=on|off][,anti-shimmer=on|off]]
@@ -66,6 +66,9 @@ static const char* const usage_text =
     "                         reservoir resampling - one cosine-hemisphere ray per pixel, the radiance its hit reflects kept as the sample; the\n"
     "                         previous frame's reservoir and up to `spatial_samples` (0..4) neighbours within search_radius pixels are merged\n"
     "                         (one device; works with and refuses what --renderer=restir-di does)\n"
+    "  --restir-gi-bounces=N  the vertices of a ReSTIR GI sample's path behind the pixel, 1..8 (1): above 1 the radiance of a sample is that of a\n"
+    "                         path continued from the ray's hit by cosine-hemisphere bounces with one light sample at each vertex, no\n"
+    "                         Russian roulette (--max-ray-depth is not read by this renderer)\n"
     "  --renderer=path-tracer|direct --max-ray-depth=N --samples-per-pixel=N --sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3 --rng-seed=N\n"
     "  --denoiser=none|bmfr   bmfr: blockwise multi-order feature regression between the path tracer and the tonemap stage\n"
     "                         (one device or --shard=views; works with --animation and --headless; svgf is not built)\n"
@@ -111,7 +114,7 @@ int main(int argc, char** argv)
         restir_di_stage::options restir;                                    // --restir
         bool restir_given = false;
         restir_gi_stage::options restir_gi;                                 // --restir-gi
-        bool restir_gi_given = false;
+        bool restir_gi_given = false, restir_gi_bounces_given = false;       // --restir-gi-bounces
         std::vector<int> devices;
         bool timing = false;
         std::string dump_scene;
@@ -244,6 +247,7 @@ int main(int argc, char** argv)
             }
             else if(starts(a, "--restir=")) { restir.parse(val("--restir=")); restir_given = true; }
             else if(starts(a, "--restir-gi=")) { restir_gi.parse(val("--restir-gi=")); restir_gi_given = true; }
+            else if(starts(a, "--restir-gi-bounces=")) { restir_gi.parse_bounces(val("--restir-gi-bounces=")); restir_gi_bounces_given = true; }
             else if(a == "--use-probe-visibility") use_probe_visibility = true;
             else if(starts(a, "--brdf-integration=")) brdf_integration_path = val("--brdf-integration=");
             else if(starts(a, "--samples-per-probe="))
@@ -359,6 +363,7 @@ int main(int argc, char** argv)
         if(renderer == "dshgi" && display == "looking-glass") throw std::runtime_error("--renderer=dshgi: no --display=looking-glass (the composition of a light field from it is not built)");
         if(restir_given && renderer != "restir-di" && renderer != "restir-gi") throw std::runtime_error("--restir sets the options of --renderer=restir-di");
         if(restir_gi_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi sets the options of --renderer=restir-gi");
+        if(restir_gi_bounces_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi-bounces sets the path length of --renderer=restir-gi");
         if(renderer == "restir-gi")
         {   // what the renderer does not do, said before a scene is read
             if(opt.bmfr) throw std::runtime_error("--renderer=restir-gi: no --denoiser (the resampling is the noise reduction; the denoiser's feature targets are not written)");

@@ -1452,8 +1452,9 @@ class RestirDiRenderer(_ViewportFrameRenderer):
 
 
 def restir_gi_options(**kw) -> dict:
-    """trhip_restir_gi_options at the command line's defaults (--restir-gi=2,32,16,on)."""
-    o = dict(spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0, record=False)
+    """trhip_restir_gi_options at the command line's defaults (--restir-gi=2,32,16,on), and `bounces` (--restir-gi-bounces=1), which
+    the stage applies through trhip_restir_gi_set_bounces."""
+    o = dict(spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0, record=False, bounces=1)
     unknown = set(kw) - set(o)
     if unknown:
         raise AttributeError(f"unknown ReSTIR GI option {sorted(unknown)}")
@@ -1462,17 +1463,19 @@ def restir_gi_options(**kw) -> dict:
 
 
 class RestirGiStage(_RestirStage):
-    """ReSTIR GI (trhip_restir_gi_*, include/trhip.h; csrc/restir_gi.h pins the rule): one bounce of indirect light by reservoir
-    resampling - per frame the initial kernel (first hit, one cosine-hemisphere ray, a light sample at its hit), the temporal kernel (the
-    history merge, no rays) and the spatial kernel (neighbour merge, shading).  `options`: restir_gi_options(); with record, download()
-    has "initial", "secondary", "light", "temporal", "spatial", "final"."""
+    """ReSTIR GI (trhip_restir_gi_*, include/trhip.h; csrc/restir_gi.h pins the rule): indirect light by reservoir resampling - per
+    frame the initial kernel (first hit, one cosine-hemisphere ray, a light sample at its hit and, with bounces > 1, the path continued
+    from there), the temporal kernel (the history merge, no rays) and the spatial kernel (neighbour merge, shading).  `options`:
+    restir_gi_options(); with record, download() has "initial", "secondary", "light", "temporal", "spatial", "final" and, with
+    bounces > 1, "path" and "path_surface" ([layers][h][w][bounces - 1])."""
 
     PREFIX, TIMINGS = "restir_gi", _lib.RestirGiTimingsC
     _RECORDS = {"surface": (_lib.RESTIR_GI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_GI_CANONICAL, _lib.RESTIR_GI_RESERVOIR_DTYPE),
                 "history": (_lib.RESTIR_GI_HISTORY, _lib.RESTIR_GI_RESERVOIR_DTYPE), "initial": (_lib.RESTIR_GI_INITIAL, _lib.RESTIR_GI_INITIAL_DTYPE),
                 "secondary": (_lib.RESTIR_GI_SECONDARY, _lib.RESTIR_DI_SURFACE_DTYPE), "light": (_lib.RESTIR_GI_LIGHT, _lib.RESTIR_DI_CANDIDATE_DTYPE),
                 "temporal": (_lib.RESTIR_GI_TEMPORAL, _lib.RESTIR_DI_TEMPORAL_DTYPE), "spatial": (_lib.RESTIR_GI_SPATIAL, _lib.RESTIR_DI_SPATIAL_DTYPE),
-                "final": (_lib.RESTIR_GI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE)}
+                "final": (_lib.RESTIR_GI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE), "path": (_lib.RESTIR_GI_PATH, _lib.RESTIR_GI_PATH_DTYPE),
+                "path_surface": (_lib.RESTIR_GI_PATH_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE)}
     _AXES = {"spatial": "spatial_samples"}
 
     def __init__(self, ctx: Optional[Context], scene_stage: Optional[SceneStage], size, layers=1, options: Optional[dict] = None, projection=0):
@@ -1481,7 +1484,27 @@ class RestirGiStage(_RestirStage):
                                     float(o["min_ray_dist"]), int(o["rng_seed"]) & 0xFFFFFFFF, int(o["record"]))
         if int(o["spatial_samples"]) < 0:
             raise TrhipError("RestirGiStage: spatial_samples is a count")
+        bounces, o["bounces"] = int(o["bounces"]), 1
         self._create_stage(ctx, scene_stage, size, layers, projection, opt)
+        if bounces != 1:
+            try:
+                self.set_bounces(bounces)
+            except TrhipError:
+                self.close()
+                raise
+
+    def set_bounces(self, bounces: int):
+        """The vertices of a sample's path behind the pixel, 1..8 (trhip_restir_gi_set_bounces); refused while there is history."""
+        if not 0 <= int(bounces) <= 0xFFFFFFFF:
+            raise TrhipError("RestirGiStage: bounces is a count")
+        check(self._fn("set_bounces")(self.h, int(bounces)))
+        self.options["bounces"] = int(bounces)
+
+    def download(self, name: str) -> np.ndarray:
+        if name in ("path", "path_surface"):
+            code, dtype = self._RECORDS[name]
+            return self._download(code, (self.layers, self.size[1], self.size[0], int(self.options["bounces"]) - 1), np.dtype(dtype))
+        return super().download(name)
 
     def run(self, viewports, in_color, out, stream=None):
         """One frame: `out` RGBA32F [len(viewports)][h][w] = `in_color` + the indirect light of the listed viewports; `in_color` None
@@ -1491,8 +1514,9 @@ class RestirGiStage(_RestirStage):
 
 
 class RestirGiRenderer(_ViewportFrameRenderer):
-    """--renderer=restir-gi: the ReSTIR DI stage renders the direct light of every viewport, the ReSTIR GI stage adds one bounce of indirect
-    light to it, the frame is tonemapped - on one stream.  `di_options`: restir_di_options(); `options`: restir_gi_options()."""
+    """--renderer=restir-gi: the ReSTIR DI stage renders the direct light of every viewport, the ReSTIR GI stage adds indirect light to it
+    (`bounces` of its options: how far a sample's path goes on), the frame is tonemapped - on one stream.  `di_options`:
+    restir_di_options(); `options`: restir_gi_options()."""
 
     def __init__(self, ctx: Context, scene_stage: SceneStage, scene: SceneDesc, size, options: Optional[dict] = None, di_options: Optional[dict] = None,
                  projection=None, tonemap: Optional[TonemapStage] = None, deformation_motion: Optional[bool] = None):

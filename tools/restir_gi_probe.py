@@ -7,8 +7,11 @@
 against the path tracer's converged frame (the mean of 4096 frames at 1 spp, non-finite samples left out), and of the GI stage alone with and without reuse
 against its own converged indirect light, as tests/test_restir_gi.py asserts on.  No threshold: the comparison points are the same
 commit's DI stage and path tracer in the same process, and the record, profiles/r20/restir_gi.txt, is the next change's baseline.
+With --bounces 1,2,3,4 the stage at its defaults is timed once per listed path length (trhip_restir_gi_set_bounces) next to the path
+tracer at the matching max_bounces (bounces + 2), and --quality adds, per listed length above 1, the GI stage's image mean and the two
+mean squared errors against its own converged image at that length (profiles/r24/restir_gi_bounces.txt).
 
-usage: python tools/restir_gi_probe.py [--lights 64] [--frames 20] [--warmup 5] [--quality]
+usage: python tools/restir_gi_probe.py [--lights 64] [--frames 20] [--warmup 5] [--quality] [--bounces 1,2,3,4]
 """
 import argparse
 import os
@@ -31,7 +34,11 @@ def main():
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--quality", action="store_true")
+    ap.add_argument("--bounces", default="1", help="comma-separated path lengths of the GI stage, each 1..8")
     a = ap.parse_args()
+    lengths = [int(b) for b in a.bounces.split(",")]
+    if not lengths or any(b < 1 or b > 8 for b in lengths):
+        ap.error("--bounces: every length is a whole number in 1..8")
 
     from tauray_amd import _lib, renderer as R, scenes
     from tauray_amd.distribution import DISTRIBUTION_DUPLICATE, DistributionParams
@@ -46,8 +53,9 @@ def main():
     print("   device ms, median (min ... max)")
     out = ctx.alloc(w * h * 16).zero()
 
-    def restir_gi(spatial, temporal=True):
-        st = R.RestirGiStage(ctx, ss, (w, h), 1, R.restir_gi_options(spatial_samples=spatial, temporal_reuse=temporal, min_ray_dist=base.min_ray_dist), base.projection)
+    def restir_gi(spatial, temporal=True, bounces=1):
+        st = R.RestirGiStage(ctx, ss, (w, h), 1, R.restir_gi_options(spatial_samples=spatial, temporal_reuse=temporal, min_ray_dist=base.min_ray_dist, bounces=bounces),
+                             base.projection)
         rows = []
         for f in range(a.warmup + a.frames):
             st.run([0], None, out)
@@ -88,6 +96,11 @@ def main():
     print(f"restir-di stage at its defaults (4 candidates, 2 spatial samples): {spread(restir_di())}")
     for bounces in (2, 3):
         print(f"path tracer, 1 spp, max_bounces {bounces}: {spread(path_tracer(bounces))}")
+    if lengths != [1]:
+        for b in lengths:
+            i, t, s, total = restir_gi(2, True, b)
+            print(f"restir-gi bounces {b} at its defaults: [restir gi initial] {spread(i)}  stage {spread(total)}  |  path tracer, 1 spp, max_bounces {b + 2}: "
+                  f"{spread(path_tracer(b + 2))}")
     out.free()
 
     if a.quality:
@@ -145,6 +158,23 @@ def main():
         print(f"   (the path tracer sees the sphere lights as spheres, the two stages light with points: part of the renderer's error is that difference, not noise)")
         print(f"MSE of the indirect light against the GI stage's own converged image ({N} frames without reuse): defaults, frame 8: {np.mean(mse['gi']):.4e}; "
               f"no reuse: {np.mean(mse['gi_alone']):.4e}; ratio {np.mean(mse['gi']) / np.mean(mse['gi_alone']):.3f}")
+        for b in (b for b in lengths if b > 1):
+            own, N = np.zeros((qh, qw, 3)), 1024
+            for seed in range(1001, 1001 + N):
+                st = R.RestirGiStage(ctx, qs, (qw, qh), 1, R.restir_gi_options(rng_seed=seed, min_ray_dist=base.min_ray_dist, spatial_samples=0, temporal_reuse=False, bounces=b))
+                st.run([0], None, buf)
+                own += buf.download((qh, qw, 4))[..., :3].astype(np.float64) / N
+                st.close()
+            err = dict(gi=[], gi_alone=[])
+            for seed in range(1, 9):
+                for name, options, frames in (("gi", {}, 9), ("gi_alone", dict(spatial_samples=0, temporal_reuse=False), 1)):
+                    st = R.RestirGiStage(ctx, qs, (qw, qh), 1, R.restir_gi_options(rng_seed=seed, min_ray_dist=base.min_ray_dist, bounces=b, **options))
+                    for _ in range(frames):
+                        st.run([0], None, buf)
+                    err[name].append(np.mean((buf.download((qh, qw, 4))[..., :3].astype(np.float64) - own) ** 2))
+                    st.close()
+            print(f"bounces {b}: indirect image mean {own.mean():.4e} ({own.mean() / gi_ref.mean():.3f} x one bounce's, {N} frames without reuse); MSE against it: "
+                  f"defaults, frame 8: {np.mean(err['gi']):.4e}; no reuse: {np.mean(err['gi_alone']):.4e}; ratio {np.mean(err['gi']) / np.mean(err['gi_alone']):.3f}")
 
 
 if __name__ == "__main__":
