@@ -32,6 +32,7 @@ int stream_pool_class(hipStream_t s, int* cls, bool blocking = false);
 int stream_pool_pipe_classes(int* classes_out, int* streams_out);      // distinct classes this process reaches on the current device
 
 struct PathBuffers;
+struct PtParams;
 
 class PtStage {
 public:
@@ -86,6 +87,17 @@ private:
     struct Impl;
     Impl* impl;
     bool timing_pending = false;
+    // the steps of render(), in its order (path_tracer.hip)
+    struct Frame;
+    struct LaneCtx;
+    int validate_call(uint viewports) const;
+    void make_params(PtParams& P, const trhip_pt_targets& targets, uint target_w, uint target_h, uint viewports, uint launch_w, uint launch_h) const;
+    void report_lane_pipes(int n_lanes, hipStream_t stream);
+    int render_direct(Frame& f);
+    int enqueue_item(Frame& f, const struct EnqueueItem& it);
+    void enqueue_raygen(Frame& f, LaneCtx& c);
+    int enqueue_bounce(Frame& f, LaneCtx& c, int bounce, int sample);
+    int enqueue_finish(Frame& f, int lane, int pass);
     int ensure_buffers(size_t n, bool lobe_sums);
     int resolve_pending();
     void free_buffers();

@@ -186,3 +186,15 @@ def test_headers_are_plain_c(tmp_path):
     assert r.returncode == 0, r.stderr
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.split()[:3] == ["96", "24", "48"], out.stdout + out.stderr
+
+
+def test_frame_schedule_without_a_device(tmp_path):
+    """tests/pt_schedule_check.cc: the path tracer's frame schedule (csrc/pt_schedule.h: plan_frame, the enqueue order, the switches and the rule
+    for the caller's stream class) against values worked out by hand, a stand-alone program built with the address and undefined-behaviour
+    sanitizers.  The header needs no HIP: plain g++, no library, no device."""
+    import subprocess
+    exe = str(tmp_path / "pt_schedule_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(ROOT, "tests", "pt_schedule_check.cc")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert (r.returncode, r.stdout.strip()) == (0, "ok"), r.stdout + r.stderr

@@ -200,3 +200,33 @@ def test_pinned_pipe_classes_skip_the_experiment(tmp_path):
     p = subprocess.run([sys.executable, "-c", code, ROOT], env=dict(os.environ, TRHIP_PIPE_CLASSES="0,1,2,3"), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert p.stdout.strip().splitlines()[-1] == "[0, 1, 2, 3, 0, 1] -1 4", p.stdout
+
+
+@pytest.mark.gpu
+def test_the_class_of_the_callers_stream_is_not_carried_to_another_stream(R, ctx):
+    """The pipe class of the caller's stream belongs to the stream it was measured on: a one-lane frame on another stream in between (which
+    classifies nothing) must not leave the first stream's class attached to the second."""
+    import numpy as np
+    from conftest import GOLDEN
+    from tauray_amd.distribution import DISTRIBUTION_DUPLICATE, DistributionParams
+    from tauray_amd.gltf import load_glb
+    W = H = 64
+    A, B = ctx.create_stream(), ctx.create_stream()
+    try:
+        if ctx.stream_pipe_class(A) == ctx.stream_pipe_class(B):
+            pytest.skip("the two streams are of one pipe class")
+        scene = load_glb(os.path.join(GOLDEN, "test.glb"), W, H)
+        pt = R.PathTracerStage(ctx, R.SceneStage(ctx, scene), R.options_for_scene(scene, max_bounces=3), DistributionParams((W, H), DISTRIBUTION_DUPLICATE, 0, 1, True))
+        color = ctx.alloc(W * H * 16).zero()
+        for lanes, stream in ((4, A), (1, B), (4, B)):
+            pt.set_lanes(lanes)
+            pt.run(color, stream=stream)
+            ctx.sync(stream)
+            assert np.isfinite(color.download((H, W, 4))).all()
+        lanes, pipes = pt.lane_pipes()
+        assert lanes == 4 and pipes[0] == ctx.stream_pipe_class(B), (pipes, ctx.stream_pipe_class(A), ctx.stream_pipe_class(B))
+        if ctx.info()["pipe_classes"] >= 4:
+            assert len(set(pipes)) == 4 and -1 not in pipes, pipes
+    finally:
+        ctx.destroy_stream(A)
+        ctx.destroy_stream(B)
