@@ -1088,11 +1088,22 @@ public:
     struct options: restir_shared_options
     {
         uint32_t candidates = 4;          // --restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse
-        // what trhip_restir_di_create refuses, said without a device
+        int visibility = TRHIP_RESTIR_VISIBILITY_PER_TARGET;      // --restir-visibility=per-target|shared|sampled (trhip_restir_di_set_visibility)
+        // what trhip_restir_di_create and trhip_restir_di_set_visibility refuse, said without a device
         void check() const
         {
             if(candidates < 1 || candidates > 32) throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " is outside 1..32");
+            if(visibility < TRHIP_RESTIR_VISIBILITY_PER_TARGET || visibility > TRHIP_RESTIR_VISIBILITY_SAMPLED)
+                throw std::runtime_error("restir-di: visibility " + std::to_string(visibility) + " is outside 0..2");
             check_shared("restir-di");
+        }
+        // --restir-visibility=MODE
+        void parse_visibility(const std::string& text)
+        {
+            if(text == "per-target") visibility = TRHIP_RESTIR_VISIBILITY_PER_TARGET;
+            else if(text == "shared") visibility = TRHIP_RESTIR_VISIBILITY_SHARED;
+            else if(text == "sampled") visibility = TRHIP_RESTIR_VISIBILITY_SAMPLED;
+            else throw std::runtime_error("--restir-visibility: " + text + " is none of per-target, shared, sampled");
         }
         // --restir=...: positional or name=value; a field left out keeps its value
         void parse(const std::string& text)
@@ -1110,6 +1121,11 @@ public:
         opt.check();
         const trhip_restir_di_options o = opt.c_options();
         check(trhip_restir_di_create(dev.h, &o, size.x, size.y, layers, &h));
+        if(opt.visibility != TRHIP_RESTIR_VISIBILITY_PER_TARGET && trhip_restir_di_set_visibility(h, opt.visibility) != 0)
+        {
+            trhip_restir_di_destroy(h);
+            check(1);
+        }
     }
     restir_di_stage(const restir_di_stage&) = delete;
     ~restir_di_stage() { trhip_restir_di_destroy(h); }
@@ -1119,6 +1135,8 @@ public:
         check(trhip_restir_di_render(h, opt.projection, viewports.data(), (uint32_t)viewports.size(), out, stream));
     }
     void reset() { check(trhip_restir_di_reset(h)); }
+    // another mode than the history's is refused until reset()
+    void set_visibility(int mode) { check(trhip_restir_di_set_visibility(h, mode)); opt.visibility = mode; }
     trhip_restir_di_timings get_timings() { trhip_restir_di_timings t; check(trhip_restir_di_get_timings(h, &t)); return t; }
 
     device* dev;

@@ -942,10 +942,10 @@ int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t s
  * built here: this is `restir-di` everywhere).  csrc/restir_di.hip; the order of operations and of random draws is pinned in
  * csrc/restir_di.h.  Per frame and chunk of 64 viewports two launches:
  *   canonical  the first hit of the pixel centre's ray, its surface record, `candidates` light samples drawn as sample_canonical draws
- *              them and resampled (RIS) with target = luminance(light_contribution * shadow ray); with temporal_reuse the history
+ *              them and resampled (RIS) with target = luminance(light_contribution * shadow ray) (decision 17: the ray is a mode); with temporal_reuse the history
  *              reservoir of the stochastically reprojected pixel is merged by confidence unless temporal_edge_detection rejects it
  *   spatial    up to spatial_samples neighbours within search_radius, merged with pairwise MIS and the reconnection Jacobian, one shadow
- *              ray per re-evaluation; the chosen sample is shaded: colour = contribution * uc_weight + emission, alpha 1
+ *              ray per re-evaluation (decision 17: the ray is a mode); the chosen sample is shaded with one more, in every mode: colour = contribution * uc_weight + emission, alpha 1
  * Decisions where the shaders are stale, undefined or depart from this library:
  *   1. BSDF: the ggx_bsdf_pdf lobes through modulate_bsdf, as the direct stage's light sample gets them, shading_view.z clamped to 1e-5
  *      (restir_di.glsl:234-244 calls a ggx_brdf signature that no longer exists).
@@ -955,7 +955,8 @@ int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t s
  *      negative resampling weight).
  *   5. The two kernels draw from disjoint random streams (sampler coordinate w = 2 * frame and 2 * frame + 1, plus rng_seed as
  *      init_local_sampler adds it); the shaders seed both passes alike.  The order of draws within a kernel is the shaders'.
- *   6. Only the default visibility path: a shadow ray inside every target function (no SHARED_VISIBILITY / SAMPLE_VISIBILITY).
+ *   6. The default visibility path is a shadow ray inside every target function; the shaders' SHARED_VISIBILITY and SAMPLE_VISIBILITY
+ *      are the modes `shared` and `sampled` of trhip_restir_di_set_visibility (decisions 17 to 22).
  *   7. An empty neighbour slot is skipped (restir_di_spatial.rgen:145-149 reads out of bounds and adds 0).
  *   8. The first frame after create or reset has no history; history light indices refer to the current frame's light arrays, an index
  *      past the end counts as the null sample.
@@ -971,7 +972,25 @@ int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t s
  *  16. sin, cos, pow and atan2 of the resampling code (light sampling, light_contribution, the neighbour offsets) are the double function of
  *      the float argument rounded once, not the device library's sinf / cosf / powf / atan2f: GLSL leaves their accuracy open, and this is
  *      the one rounding a host model can repeat bit for bit - in all but the rarest case, a double result so near a float rounding boundary
- *      that two libraries' doubles fall on either side of it.  The first hit is shaded as every other stage shades it. */
+ *      that two libraries' doubles fall on either side of it.  The first hit is shaded as every other stage shades it.
+ *  17. Visibility modes.  per-target (0, the default) casts candidates + 2 * spatial_samples + 1 shadow rays a pixel.  shared (1): no
+ *      target function traces - candidates, the neighbour's sample here, the canonical sample at the neighbour - and the only ray is the
+ *      chosen sample's shading.  sampled (2): as shared, plus one ray for the sample the candidates chose.  An untraced target's
+ *      visibility factor, recorded as such, is 1 where decision 14 would cast a ray and 0 otherwise, so
+ *      target = luminance(contribution * visibility) describes every mode.  No mode adds, removes or reorders a random draw.
+ *  18. sampled: behind the candidates' uc_weight and ahead of the temporal merge the reservoir's sample is evaluated once more at the
+ *      pixel and traced by decision 14 (no ray and visibility 0 for the null sample), then uc_weight *= visibility
+ *      (restir_di_canonical_and_temporal.rgen:115-122).  The temporal merge is the same in every mode.
+ *  19. shared and sampled: a bad neighbour takes no slot (restir_di_spatial.rgen:123-129 is compiled out); the first spatial_samples good
+ *      ones are held in draw order; the 2 * spatial_samples offset draws stay.
+ *  20. The shading ray stays in every mode.  sampled: uc_weight *= visibility ahead of the history reservoir, and the colour is
+ *      contribution * visibility * uc_weight + emission with that multiplied weight (restir_di_spatial.rgen:266-269,281).  Limit: under a
+ *      partly transparent occluder (0 < visibility < 1) `sampled` counts the factor once per pass that traced it; it is exact for opaque
+ *      occluders only.
+ *  21. shared is unbiased like per-target (a target without visibility is a valid target; the traced ray is in the integrand).  sampled
+ *      is biased wherever visibility differs between the pixels that share a sample: the paper's biased variant.
+ *  22. A reservoir does not mix the samples of two target functions: the mode changes only while the stage holds no history.  ReSTIR GI's
+ *      own kernels keep their visibility path whatever the mode of the ReSTIR DI stage beside them. */
 typedef struct trhip_restir_di trhip_restir_di;
 typedef struct trhip_restir_di_options {
     uint32_t candidates;              /* 1..32 light samples per pixel (RIS_SAMPLE_COUNT) */
@@ -1015,6 +1034,10 @@ typedef struct trhip_restir_di_final {        /* per pixel: the chosen sample's 
     float contribution[3], visibility;
     float canonical_m, wi, draw; uint32_t selected;
 } trhip_restir_di_final;
+typedef struct trhip_restir_di_sampled {      /* per pixel: decision 18's shadow ray (1, none traced, in the modes per-target and shared) and the candidates' uc_weight it
+                                               * multiplied (shared: that weight, multiplied by nothing; per-target: 0) */
+    float visibility, uc_weight_before; uint32_t pad[2];
+} trhip_restir_di_sampled;
 typedef struct trhip_restir_di_timings {      /* device ms of the last render */
     float canonical_ms, spatial_ms, total_ms;
     uint32_t frames;
@@ -1024,6 +1047,12 @@ typedef struct trhip_restir_di_timings {      /* device ms of the last render */
 int trhip_restir_di_create(trhip_device* dev, const trhip_restir_di_options* opt, uint32_t width, uint32_t height, uint32_t layers, trhip_restir_di** out);
 void trhip_restir_di_destroy(trhip_restir_di* stage);
 int trhip_restir_di_reset(trhip_restir_di* stage);        /* forgets the history and restarts the frame counter */
+/* The visibility mode (decisions 17 to 22); a stage is created per-target.  Refuses a null stage, a mode outside 0..2 and, while the stage
+ * holds history (a frame rendered since create or reset), any mode but the history's. */
+#define TRHIP_RESTIR_VISIBILITY_PER_TARGET 0
+#define TRHIP_RESTIR_VISIBILITY_SHARED 1
+#define TRHIP_RESTIR_VISIBILITY_SAMPLED 2
+int trhip_restir_di_set_visibility(trhip_restir_di* stage, int mode);
 /* One frame of `count` viewports (at most the stage's layers), two launches per 64, asynchronous on `stream`: out_color_dev RGBA32F
  * [count][h][w].  Refuses a device without a scene or acceleration structure and a viewport out of range.  History is kept per layer, the
  * position in the list: with temporal_reuse, a list that differs from the last frame's is refused until trhip_restir_di_reset. */
@@ -1036,6 +1065,7 @@ int trhip_restir_di_get_timings(trhip_restir_di* stage, trhip_restir_di_timings*
 #define TRHIP_RESTIR_DI_TEMPORAL 4    /* trhip_restir_di_temporal [layers][h][w] */
 #define TRHIP_RESTIR_DI_SPATIAL 5     /* trhip_restir_di_spatial [layers][h][w][spatial_samples] */
 #define TRHIP_RESTIR_DI_FINAL 6       /* trhip_restir_di_final [layers][h][w] */
+#define TRHIP_RESTIR_DI_SAMPLED 7     /* trhip_restir_di_sampled [layers][h][w] (record only) */
 int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
 
 /* ---- ReSTIR GI: reservoir resampling of indirect light (after Ouyang et al. 2021 and the ReSTIR DI stage above, whose

@@ -262,7 +262,9 @@ class RestirDiTimingsC(C.Structure):
 
 # trhip_restir_di_download and the records behind the codes (include/trhip.h)
 (RESTIR_DI_SURFACE, RESTIR_DI_CANONICAL, RESTIR_DI_HISTORY, RESTIR_DI_CANDIDATES, RESTIR_DI_TEMPORAL, RESTIR_DI_SPATIAL,
- RESTIR_DI_FINAL) = range(7)
+ RESTIR_DI_FINAL, RESTIR_DI_SAMPLED) = range(8)
+# trhip_restir_di_set_visibility: the modes by their command-line names
+RESTIR_VISIBILITY = {"per-target": 0, "shared": 1, "sampled": 2}
 RESTIR_DI_NULL_INDEX = (1 << 30) - 1
 RESTIR_DI_SURFACE_DTYPE = [("pos", "<f4", 3), ("instance_id", "<i4"), ("mapped_normal", "<f4", 3), ("metallic", "<f4"), ("flat_normal", "<f4", 3),
                            ("roughness", "<f4"), ("view", "<f4", 3), ("transmittance", "<f4"), ("albedo", "<f4", 4), ("emission", "<f4", 3),
@@ -278,6 +280,7 @@ RESTIR_DI_SPATIAL_DTYPE = [("px", "<i4"), ("py", "<i4"), ("good", "<u4"), ("sele
                            ("jacobian_c", "<f4"), ("mis_canonical", "<f4"), ("pad", "<f4", 2)]
 RESTIR_DI_FINAL_DTYPE = [("contribution", "<f4", 3), ("visibility", "<f4"), ("canonical_m", "<f4"), ("wi", "<f4"), ("draw", "<f4"),
                          ("selected", "<u4")]
+RESTIR_DI_SAMPLED_DTYPE = [("visibility", "<f4"), ("uc_weight_before", "<f4"), ("pad", "<u4", 2)]
 
 
 class RestirGiOptionsC(C.Structure):
@@ -456,6 +459,7 @@ SYMBOLS = {
     "trhip_restir_di_create": (_i, [_vp, C.POINTER(RestirDiOptionsC), _u32, _u32, _u32, C.POINTER(_vp)]),
     "trhip_restir_di_destroy": (None, [_vp]),
     "trhip_restir_di_reset": (_i, [_vp]),
+    "trhip_restir_di_set_visibility": (_i, [_vp, _i]),
     "trhip_restir_di_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _vp, _vp]),
     "trhip_restir_di_get_timings": (_i, [_vp, C.POINTER(RestirDiTimingsC)]),
     "trhip_restir_di_download": (_i, [_vp, _i, _vp, C.c_size_t]),

@@ -83,6 +83,36 @@
 //                out = (contribution * uc_weight + emission, 1);  a pixel without a surface: the null reservoir and the direct stage's
 //                miss colour (k_direct: the visible directional lights in order, then the environment)
 //
+// Visibility modes (trhip_restir_di_set_visibility; the shaders' SHARED_VISIBILITY and SAMPLE_VISIBILITY, the visibility reuse of Bitterli
+// et al. 2020; a template parameter of both kernels).  Mode 0, per-target, is everything above: candidates + 2 * SPATIAL + 1 shadow rays
+// a pixel.  Mode 1, shared: one ray, the chosen sample's shading.  Mode 2, sampled: two, the sample the candidates chose and the shading.
+//   1 candidates   modes 1 and 2: the loop traces nothing.  The factor of the target, which is also the candidate record's `visibility`,
+//                  is 1 where `visibility` above would cast a ray (the contribution has a component > 0) and 0 otherwise, so
+//                  target = rgb_to_luminance(contribution * visibility) describes every mode.  Weights, draws, their order and
+//                  update_reservoir are unchanged; no mode adds or removes a draw.
+//   2 sampled      mode 2, behind uc_weight = restir_uc_weight(r) and ahead of the temporal merge
+//                  (restir_di_canonical_and_temporal.rgen:115-122): the reservoir's sample is evaluated once more at the pixel's surface
+//                  (the loop keeps neither direction nor distance; the same inputs give the same bits) and one shadow ray is cast as
+//                  `visibility` says - none, and 0, for the null sample or a contribution without a positive component - then
+//                  uc_weight = uc_weight * visibility.  The `sampled` record holds that visibility and the weight ahead of the multiply;
+//                  in modes 0 and 1 visibility is 1, no ray; in mode 0 nothing is multiplied either, the record is (1, 0) on every
+//                  pixel and the host writes it (the mode-0 kernels are the code they were).  A pixel without a surface:
+//                  (mode 2 ? 0 : 1, 0).
+//   3 temporal     unchanged in every mode: it never traced.
+//   4 neighbours   modes 1 and 2: a bad neighbour takes no slot (restir_di_spatial.rgen:123-129 is compiled out), only the first
+//                  SPATIAL good ones are held, in draw order.  The 2 * SPATIAL offset draws stay.
+//   5 spatial      modes 1 and 2: neither re-evaluation traces; the factor and visibility_n / visibility_c follow point 1.
+//   6 colour       the shadow ray stays in every mode.  Mode 2 (restir_di_spatial.rgen:266-269,281): uc_weight = uc_weight * visibility
+//                  ahead of the history store, out = ((contribution * visibility) * uc_weight + emission, 1) with that multiplied weight.
+//                  Limit: under a partly transparent occluder (0 < visibility < 1) mode 2 counts the factor once per pass that traced
+//                  it; it is exact for opaque occluders only, where visibility * visibility = visibility.
+//   7 bias         mode 1 is unbiased like mode 0: a target without visibility is still a valid target (positive wherever the
+//                  integrand is), and the one traced ray is in the integrand.  Mode 2 is BIASED wherever visibility differs between the
+//                  pixels that share a sample: a sample zeroed at the pixel that drew it is lost to neighbours and later frames that
+//                  would have seen the light.  It is the paper's biased variant.
+//   8 ReSTIR GI    does not change: restir_spatial_merge's SHARED_VISIBILITY parameter defaults to false, the code as it was.
+// A reservoir does not mix the samples of two target functions: the mode changes only while the stage holds no history.
+//
 // Where the code is.  The sections reprojection, reuse, temporal, neighbours, spatial and jacobian, update_reservoir, visibility, the
 // surface record and the temporal, spatial and final decision records: restir_resample.h, once for this stage and ReSTIR GI.  Here:
 // the reservoir, the candidate record, sample_canonical, light_contribution and RestirDiKind, what restir_resample.h asks of a sample.
@@ -104,7 +134,11 @@ struct RestirCandidateRecord {           // trhip_restir_di_candidate
     f3 contribution; float visibility;   // the unshadowed contribution
     float weight, draw; uint selected, pad;
 };
-static_assert(sizeof(RestirReservoir) == 32 && sizeof(RestirCandidateRecord) == 48, "layout");
+struct alignas(16) RestirSampledRecord { // trhip_restir_di_sampled
+    float visibility, uc_weight_before;  // `visibility modes` point 2: the ray of the candidates' choice and the weight it multiplied
+    uint pad0, pad1;
+};
+static_assert(sizeof(RestirReservoir) == 32 && sizeof(RestirCandidateRecord) == 48 && sizeof(RestirSampledRecord) == 16, "layout");
 
 struct RestirSample { uint type, index; f2 data; };
 TR_DEV RestirSample restir_null_sample() { return {0u, RESTIR_NULL_INDEX, F2(0.0f)}; }

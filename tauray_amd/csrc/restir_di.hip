@@ -1,15 +1,20 @@
 // ReSTIR DI for gfx950 - reservoir resampling of direct light, written after the reference's shader/restir_di.glsl,
 // shader/restir_di_canonical_and_temporal.rgen and shader/restir_di_spatial.rgen, behind the entry points trhip_restir_di_* of include/trhip.h.
 //   k_restir_di_canonical  per pixel of every viewport: the first hit and its surface (first_hit.h), the surface
-//                          record, RIS over `candidates` light samples (a shadow ray in every target function), the temporal merge of
+//                          record, RIS over `candidates` light samples (per-target: a shadow ray in every target function), the temporal merge of
 //                          the reprojected pixel's history reservoir
 //   k_restir_di_spatial    per pixel: the neighbour search, the pairwise-MIS merge of the neighbours' canonical reservoirs (two shadow rays
-//                          a neighbour), the chosen sample's shading (one more), the history reservoir and the colour
+//                          a neighbour in the per-target mode, none in the others), the chosen sample's shading (one more, in every
+//                          mode), the history reservoir and the colour
+// VISIBILITY (trhip_restir_di_set_visibility; `visibility modes` of restir_di.h) is a template parameter of both: 0, per-target, traces
+// inside every target function; with 1 and 2 the candidate loop and the per-slot loop hold no traversal at all, 2 traces the candidates'
+// choice once behind the loop.
 // Constants, layouts, the order of operations and the order of random draws: restir_di.h.  The temporal and the spatial merge and the
 // host skeleton are restir_resample.h's, shared with ReSTIR GI.  Both kernels are IEEE fp32, evaluated without
 // contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  The front half is first_hit.h's, the one
 // k_gbuffer and k_feature call.
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "restir_di.h"
@@ -36,11 +41,17 @@ struct RestirParams {
     RestirSpatialRecord* rec_spatial;
     RestirFinalRecord* rec_final;
 };
+// The shared and the sampled mode's kernels take one pointer more; the per-target kernels keep the arguments, and with them the code, they had
+struct RestirParamsSampled : RestirParams {
+    RestirSampledRecord* rec_sampled;           // null unless options.record
+};
+template <int VISIBILITY>
+using ParamsOf = std::conditional_t<VISIBILITY == 0, RestirParams, RestirParamsSampled>;
 
 // tile_pixel's launch shape (first_hit.h).
 // Two waves per SIMD: unbounded, the fp64 functions of RoundedMath took it to 256 VGPRs plus AGPR copies at one wave.
-template <bool TWO_LEVEL, bool TEMPORAL>
-__global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, LaunchCtx L, int projection, ViewportList list, RestirParams P, uint* overflow_flag) {
+template <bool TWO_LEVEL, bool TEMPORAL, int VISIBILITY>
+__global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, LaunchCtx L, int projection, ViewportList list, ParamsOf<VISIBILITY> P, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
     int* const s_stack = s_stack_rows + TR_STACK_ROW0;
     int px, py;
@@ -82,7 +93,8 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, Lau
             f3 light_dir, light_norm;
             float light_dist2;
             const f3 contrib = restir_contribution(sv, s, Lr, dom, light_dir, light_dist2, light_norm);
-            const float visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
+            const float visibility = VISIBILITY != 0 ? restir_untraced(contrib)
+                                                     : restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, light_dir, light_dist2, s_stack + threadIdx.x, overflow);
             const float target = rgb_to_luminance(contrib * visibility);
             float weight = mis_weight * target / light_pdf;
             if (isnan(weight)) weight = 0.0f;
@@ -98,8 +110,22 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, Lau
             }
         }
         r.uc_weight = restir_uc_weight(r);
+        // SAMPLE_VISIBILITY (restir_di_canonical_and_temporal.rgen:115-122): one ray for the sample the candidates chose.  Its direction
+        // and distance come from evaluating it once more, the loop keeps neither
+        // (the per-target instances are the code they were: they write no `sampled` record, the host holds its constant)
+        float sampled_visibility = 1.0f;
+        if (VISIBILITY == 2) {
+            Kind::Eval e;
+            const f3 contrib = Kind::contribution(sv, r.s, dom, e);
+            sampled_visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, e.dir, e.dist2, s_stack + threadIdx.x, overflow);
+        }
+        if constexpr (VISIBILITY != 0)
+            if (P.rec_sampled) restir_set_word(P.rec_sampled + pix, 0, u4{TR_U(sampled_visibility), TR_U(r.uc_weight), 0u, 0u});
+        if (VISIBILITY == 2) r.uc_weight = r.uc_weight * sampled_visibility;
 
         if (TEMPORAL) restir_temporal_merge<Kind>(sv, L, rp, P.history + layer * layer_px, dom, P.max_confidence, ls, r, trec);
+    } else if constexpr (VISIBILITY != 0) {      // no surface: the null sample
+        if (P.rec_sampled) restir_set_word(P.rec_sampled + pix, 0, u4{TR_U(VISIBILITY == 2 ? 0.0f : 1.0f), 0u, 0u, 0u});
     }
     if (overflow) *overflow_flag = 1;
     restir_store_surface(P.surface + pix, dom, hit.instance_id >= 0 ? hit.instance_id : -1);
@@ -107,8 +133,8 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_canonical(SceneView sv, Lau
     if (P.rec_temporal) restir_write_temporal(P.rec_temporal + pix, trec);
 }
 
-template <bool TWO_LEVEL, int SPATIAL>
-__global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, LaunchCtx L, int projection, ViewportList list, RestirParams P, uint* overflow_flag) {
+template <bool TWO_LEVEL, int SPATIAL, int VISIBILITY>
+__global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, LaunchCtx L, int projection, ViewportList list, ParamsOf<VISIBILITY> P, uint* overflow_flag) {
     __shared__ int s_stack_rows[TR_STACK_WORDS];
     int* const s_stack = s_stack_rows + TR_STACK_ROW0;
     int px, py;
@@ -150,7 +176,7 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, Launc
     RestirFinalRecord frec = {F3(0.0f), 0.0f, 0.0f, 0.0f, 0.0f, 0u};
     if (SPATIAL > 0) {
         const LocalSampler ls = init_local_sampler(u4{(uint)px, (uint)py, viewport, 0u}, 2u * P.frame + 1u, P.rng_seed, SAMPLER_UNIFORM);
-        const RestirMerged<Kind> m = restir_spatial_merge<Kind, TWO_LEVEL, SPATIAL>(sv, L, sv.cameras[viewport], P.search_radius, P.min_ray_dist,
+        const RestirMerged<Kind> m = restir_spatial_merge<Kind, TWO_LEVEL, SPATIAL, VISIBILITY != 0>(sv, L, sv.cameras[viewport], P.search_radius, P.min_ray_dist,
             P.surface + layer * layer_px, P.canonical + layer * layer_px, P.rec_spatial, px, py, pix, dom, canonical, ls, s_stack + threadIdx.x, overflow);
         r = m.r; frec = m.frec; overflow = m.overflow;
     }
@@ -159,22 +185,28 @@ __global__ __launch_bounds__(KB, 2) void k_restir_di_spatial(SceneView sv, Launc
     const float visibility = restir_shadow<TWO_LEVEL>(sv, P.min_ray_dist, dom.pos, contrib, e.dir, e.dist2, s_stack + threadIdx.x, overflow);
     if (overflow) *overflow_flag = 1;
     const f3 shaded = contrib * visibility;
+    if (VISIBILITY == 2) r.uc_weight = r.uc_weight * visibility;      // restir_di_spatial.rgen:266-269: ahead of the history and of the colour
     Kind::store(P.history + pix, r);
     P.out[pix] = F4(shaded * r.uc_weight + dom.mat.emission, 1.0f);
     frec.contribution = contrib; frec.visibility = visibility;
     if (P.rec_final) restir_write_final(P.rec_final + pix, frec);
 }
 
-using RestirKernel = void (*)(SceneView, LaunchCtx, int, ViewportList, RestirParams, uint*);
+template <int VISIBILITY>
+using RestirKernel = void (*)(SceneView, LaunchCtx, int, ViewportList, ParamsOf<VISIBILITY>, uint*);
 
-template <bool TWO_LEVEL>
-RestirKernel spatial_kernel(uint32_t spatial) {
+template <bool TWO_LEVEL, int VISIBILITY>
+RestirKernel<VISIBILITY> canonical_kernel(bool temporal) {
+    return temporal ? k_restir_di_canonical<TWO_LEVEL, true, VISIBILITY> : k_restir_di_canonical<TWO_LEVEL, false, VISIBILITY>;
+}
+template <bool TWO_LEVEL, int VISIBILITY>
+RestirKernel<VISIBILITY> spatial_kernel(uint32_t spatial) {
     switch (spatial) {
-        case 0: return k_restir_di_spatial<TWO_LEVEL, 0>;
-        case 1: return k_restir_di_spatial<TWO_LEVEL, 1>;
-        case 2: return k_restir_di_spatial<TWO_LEVEL, 2>;
-        case 3: return k_restir_di_spatial<TWO_LEVEL, 3>;
-        default: return k_restir_di_spatial<TWO_LEVEL, 4>;
+        case 0: return k_restir_di_spatial<TWO_LEVEL, 0, VISIBILITY>;
+        case 1: return k_restir_di_spatial<TWO_LEVEL, 1, VISIBILITY>;
+        case 2: return k_restir_di_spatial<TWO_LEVEL, 2, VISIBILITY>;
+        case 3: return k_restir_di_spatial<TWO_LEVEL, 3, VISIBILITY>;
+        default: return k_restir_di_spatial<TWO_LEVEL, 4, VISIBILITY>;
     }
 }
 
@@ -189,11 +221,42 @@ struct trhip_restir_di : RestirStageHost<3> {
     trhip_restir_di_options opt = {};
     RestirReservoir *canonical = nullptr, *history = nullptr;
     RestirCandidateRecord* rec_candidates = nullptr;
+    RestirSampledRecord* rec_sampled = nullptr;      // per-target: (1, 0) on every pixel, written by fill_sampled_constant, no kernel
+    int visibility = TRHIP_RESTIR_VISIBILITY_PER_TARGET;      // trhip_restir_di_set_visibility
 };
 
 static_assert(sizeof(trhip_restir_di_surface) == sizeof(RestirSurface) && sizeof(trhip_restir_di_reservoir) == sizeof(RestirReservoir), "downloads are the kernels' records");
 static_assert(sizeof(trhip_restir_di_candidate) == sizeof(RestirCandidateRecord) && sizeof(trhip_restir_di_temporal) == sizeof(RestirTemporalRecord), "downloads are the kernels' records");
 static_assert(sizeof(trhip_restir_di_spatial) == sizeof(RestirSpatialRecord) && sizeof(trhip_restir_di_final) == sizeof(RestirFinalRecord), "downloads are the kernels' records");
+static_assert(sizeof(trhip_restir_di_sampled) == sizeof(RestirSampledRecord), "downloads are the kernels' records");
+
+// The per-target mode's `sampled` record: no ray and nothing multiplied, (visibility 1, uc_weight_before 0) on every pixel.  Written where
+// the mode is decided - at create and when the setter goes back to per-target - never in a frame.  Waits for the device.
+static hipError_t fill_sampled_constant(trhip_restir_di* s) {
+    const std::vector<RestirSampledRecord> ones(s->pixels(), RestirSampledRecord{1.0f, 0.0f, 0u, 0u});
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(s->rec_sampled, ones.data(), ones.size() * sizeof(RestirSampledRecord), hipMemcpyHostToDevice);
+    return e;
+}
+
+// A frame in one visibility mode: a mode's instances hold only that mode's code
+template <int VISIBILITY>
+static int restir_di_render_mode(trhip_restir_di* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
+    ParamsOf<VISIBILITY> base{};
+    base.candidates = (int)s->opt.candidates;
+    restir_fill_params(base, *s, *scene);
+    const bool temporal = s->opt.temporal_reuse != 0;
+    const RestirKernel<VISIBILITY> kernels[2] = {
+        scene->two_level ? canonical_kernel<true, VISIBILITY>(temporal) : canonical_kernel<false, VISIBILITY>(temporal),
+        scene->two_level ? spatial_kernel<true, VISIBILITY>(s->opt.spatial_samples) : spatial_kernel<false, VISIBILITY>(s->opt.spatial_samples)};
+    // The canonical kernels of every chunk first, then the spatial ones
+    return restir_run_passes(s, scene, projection, viewports, count, (hipStream_t)stream, base, kernels, 2, [&](ParamsOf<VISIBILITY>& P, size_t off) {
+        P.canonical = s->canonical + off; P.history = s->history + off;
+        P.out = (f4*)out_color_dev + off;
+        P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
+        if constexpr (VISIBILITY != 0) P.rec_sampled = s->rec_sampled ? s->rec_sampled + off : nullptr;
+    });
+}
 
 extern "C" {
 
@@ -207,7 +270,11 @@ int trhip_restir_di_create(trhip_device* dev, const trhip_restir_di_options* opt
         [&](trhip_restir_di* s, size_t n) {
             s->alloc_zeroed(s->canonical, n * sizeof(RestirReservoir));
             s->alloc_zeroed(s->history, n * sizeof(RestirReservoir));
-            if (opt->record) s->alloc_zeroed(s->rec_candidates, n * opt->candidates * sizeof(RestirCandidateRecord));
+            if (opt->record) {
+                s->alloc_zeroed(s->rec_candidates, n * opt->candidates * sizeof(RestirCandidateRecord));
+                s->alloc_zeroed(s->rec_sampled, n * sizeof(RestirSampledRecord));
+                if (s->err == hipSuccess) s->err = fill_sampled_constant(s);      // a stage is created per-target
+            }
         });
 }
 
@@ -215,23 +282,30 @@ void trhip_restir_di_destroy(trhip_restir_di* s) { stage_destroy(s); }
 
 int trhip_restir_di_reset(trhip_restir_di* s) { return restir_reset(API, s); }
 
+int trhip_restir_di_set_visibility(trhip_restir_di* s, int mode) {
+    static const char* const names[3] = {"per-target", "shared", "sampled"};
+    const std::string fn = std::string(API) + "_set_visibility";
+    if (!s) return set_error(fn + ": null stage");
+    if (mode < TRHIP_RESTIR_VISIBILITY_PER_TARGET || mode > TRHIP_RESTIR_VISIBILITY_SAMPLED) return set_error(fn + ": mode " + std::to_string(mode) + " is outside 0..2");
+    // a reservoir must not mix the samples of two target functions silently
+    if (s->frame > 0 && mode != s->visibility)
+        return set_error(fn + ": the stage holds history of the " + names[s->visibility] + " mode: call " + API + "_reset first");
+    if (mode == TRHIP_RESTIR_VISIBILITY_PER_TARGET && mode != s->visibility && s->rec_sampled) {      // the other modes' kernels wrote the record
+        DEVCHK(s->hip_device);
+        HIPCHK(fill_sampled_constant(s));
+    }
+    s->visibility = mode;
+    return 0;
+}
+
 int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
     DeviceScene* scene = nullptr;
     if (int r = restir_begin_render(API, s, viewports, count, out_color_dev, scene)) return r;
-    RestirParams base{};
-    base.candidates = (int)s->opt.candidates;
-    restir_fill_params(base, *s, *scene);
-    const bool temporal = s->opt.temporal_reuse != 0;
-    const RestirKernel kernels[2] = {
-        scene->two_level ? (temporal ? k_restir_di_canonical<true, true> : k_restir_di_canonical<true, false>)
-                         : (temporal ? k_restir_di_canonical<false, true> : k_restir_di_canonical<false, false>),
-        scene->two_level ? spatial_kernel<true>(s->opt.spatial_samples) : spatial_kernel<false>(s->opt.spatial_samples)};
-    // The canonical kernels of every chunk first, then the spatial ones
-    return restir_run_passes(s, scene, projection, viewports, count, (hipStream_t)stream, base, kernels, 2, [&](RestirParams& P, size_t off) {
-        P.canonical = s->canonical + off; P.history = s->history + off;
-        P.out = (f4*)out_color_dev + off;
-        P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
-    });
+    switch (s->visibility) {
+        case TRHIP_RESTIR_VISIBILITY_PER_TARGET: return restir_di_render_mode<0>(s, scene, projection, viewports, count, out_color_dev, stream);
+        case TRHIP_RESTIR_VISIBILITY_SHARED: return restir_di_render_mode<1>(s, scene, projection, viewports, count, out_color_dev, stream);
+        default: return restir_di_render_mode<2>(s, scene, projection, viewports, count, out_color_dev, stream);
+    }
 }
 
 int trhip_restir_di_get_timings(trhip_restir_di* s, trhip_restir_di_timings* out) {
@@ -246,11 +320,12 @@ int trhip_restir_di_get_timings(trhip_restir_di* s, trhip_restir_di_timings* out
 
 int trhip_restir_di_download(trhip_restir_di* s, int which, void* host, size_t bytes) {
     const int shared[4] = {TRHIP_RESTIR_DI_SURFACE, TRHIP_RESTIR_DI_TEMPORAL, TRHIP_RESTIR_DI_SPATIAL, TRHIP_RESTIR_DI_FINAL};
-    return restir_download(API, s, which, host, bytes, which >= TRHIP_RESTIR_DI_CANDIDATES && which <= TRHIP_RESTIR_DI_FINAL, shared,
+    return restir_download(API, s, which, host, bytes, which >= TRHIP_RESTIR_DI_CANDIDATES && which <= TRHIP_RESTIR_DI_SAMPLED, shared,
         [&](size_t n, const void*& src, size_t& size) {
             switch (which) {
                 case TRHIP_RESTIR_DI_CANONICAL: src = s->canonical; size = n * sizeof(RestirReservoir); return true;
                 case TRHIP_RESTIR_DI_HISTORY: src = s->history; size = n * sizeof(RestirReservoir); return true;
+                case TRHIP_RESTIR_DI_SAMPLED: src = s->rec_sampled; size = n * sizeof(RestirSampledRecord); return true;
                 case TRHIP_RESTIR_DI_CANDIDATES: src = s->rec_candidates; size = n * s->opt.candidates * sizeof(RestirCandidateRecord); return true;
                 default: return false;
             }

@@ -137,6 +137,9 @@ TR_DEV float restir_shadow(const SceneView& sv, float min_ray_dist, f3 pos, f3 c
     return visibility;
 }
 
+// The visibility of a target function that traces nothing (`visibility modes` of restir_di.h): 1 where restir_shadow would cast a ray
+TR_DEV float restir_untraced(f3 contribution) { return restir_casts(contribution) ? 1.0f : 0.0f; }
+
 // reconnection_jacobian, mis_canonical, mis_noncanonical (restir_di.glsl:477-533)
 TR_DEV float restir_jacobian(f3 prev_src, f3 cur_src, f3 dst, f3 n) {
     const f3 qdelta = prev_src - dst, rdelta = cur_src - dst;
@@ -253,9 +256,12 @@ TR_DEV void restir_clear_records(RestirFinalRecord* rec_final, RestirSpatialReco
 // far.  The scene view, the launch and what the pixel holds come in by value, and the merged reservoir, the canonical merge's record and
 // the traversals' overflow go out by value: through references the loop is compiled against memory it cannot tell from the records it
 // writes, and that schedule stays when it is inlined.  `cam` stays a reference into the scene's camera array.
+// SHARED_VISIBILITY (restir_di.h's `visibility modes`, the shader's define of that name): neither re-evaluation
+// traces - its visibility is restir_untraced - and a bad neighbour takes no slot.  The default, false, is the code as it was: ReSTIR GI
+// and ReSTIR DI's per-target mode instantiate that.
 template <class Kind>
 struct RestirMerged { typename Kind::State r; RestirFinalRecord frec; int overflow; };
-template <class Kind, bool TWO_LEVEL, int SPATIAL>
+template <class Kind, bool TWO_LEVEL, int SPATIAL, bool SHARED_VISIBILITY = false>
 TR_DEV RestirMerged<Kind> restir_spatial_merge(const SceneView sv, const LaunchCtx L, const CameraData& cam, float search_radius, float min_ray_dist,
                                                const RestirSurface* surfaces, const typename Kind::Reservoir* canonicals, RestirSpatialRecord* rec_spatial,
                                                int px, int py, size_t pix, const RestirDomain dom, const typename Kind::State canonical, LocalSampler ls,
@@ -289,7 +295,7 @@ TR_DEV RestirMerged<Kind> restir_spatial_merge(const SceneView sv, const LaunchC
         if (!bad && good_neighbors < SPATIAL) {
             set_slot(sx, sy, good_bits, good_neighbors, nx, ny, true);
             ++good_neighbors;
-        } else if (bad && good_neighbors + bad_neighbors < SPATIAL) {
+        } else if (!SHARED_VISIBILITY && bad && good_neighbors + bad_neighbors < SPATIAL) {     // restir_di_spatial.rgen:123-129
             ++bad_neighbors;
             set_slot(sx, sy, good_bits, SPATIAL - bad_neighbors, nx, ny, false);
         }
@@ -320,7 +326,8 @@ TR_DEV RestirMerged<Kind> restir_spatial_merge(const SceneView sv, const LaunchC
             if (!Kind::is_null(n.s)) {
                 typename Kind::Eval e;
                 const f3 contrib = Kind::contribution(sv, n.s, dom, e);
-                const float visibility = restir_shadow<TWO_LEVEL>(sv, min_ray_dist, dom.pos, contrib, e.dir, e.dist2, stack, overflow);
+                const float visibility = SHARED_VISIBILITY ? restir_untraced(contrib)
+                                                           : restir_shadow<TWO_LEVEL>(sv, min_ray_dist, dom.pos, contrib, e.dir, e.dist2, stack, overflow);
                 const float target = rgb_to_luminance(contrib * visibility);
                 const float jacob = Kind::jacobian(n.s, e, sample_domain.pos, dom.pos);
                 const float m = restir_mis_noncanonical(canonical.confidence, n.confidence, total_confidence, n.target_function, target, jacob);
@@ -336,7 +343,8 @@ TR_DEV RestirMerged<Kind> restir_spatial_merge(const SceneView sv, const LaunchC
                 if (Kind::SURFACE_LATE) restir_load_surface(surfaces + npix, sample_domain);
                 typename Kind::Eval e;
                 const f3 contrib = Kind::contribution(sv, canonical.s, sample_domain, e);
-                const float visibility = restir_shadow<TWO_LEVEL>(sv, min_ray_dist, sample_domain.pos, contrib, e.dir, e.dist2, stack, overflow);
+                const float visibility = SHARED_VISIBILITY ? restir_untraced(contrib)
+                                                           : restir_shadow<TWO_LEVEL>(sv, min_ray_dist, sample_domain.pos, contrib, e.dir, e.dist2, stack, overflow);
                 const float alt_target = rgb_to_luminance(contrib * visibility);
                 const float jacob = Kind::jacobian(canonical.s, e, dom.pos, sample_domain.pos);
                 const float mc = restir_mis_canonical(canonical.confidence, n.confidence, total_confidence, canonical.target_function, alt_target, jacob);

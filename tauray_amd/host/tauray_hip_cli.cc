@@ -10,6 +10,7 @@
 //              reinhard|reinhard-luminance] [--exposure=1] [--gamma=2.2] [--sampler=uniform-random|sobol-owen|sobol-z2|sobol-z3]
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
 //              [--renderer=restir-di [--restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse]]
+//              [--restir-visibility=per-target|shared|sampled]   (with --renderer=restir-di and restir-gi)
 //              [--renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse] [--restir-gi-bounces=N] [--restir=...]]
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
@@ -66,6 +67,10 @@ static const char* const usage_text =
     "                         reservoir resampling - one cosine-hemisphere ray per pixel, the radiance its hit reflects kept as the sample; the\n"
     "                         previous frame's reservoir and up to `spatial_samples` (0..4) neighbours within search_radius pixels are merged\n"
     "                         (one device; works with and refuses what --renderer=restir-di does)\n"
+    "  --restir-visibility=per-target|shared|sampled   (per-target) where ReSTIR DI traces shadow rays, with --renderer=restir-di and restir-gi:\n"
+    "                         per-target: inside every target function, candidates + 2 * spatial_samples + 1 rays a pixel; shared: only the\n"
+    "                         chosen sample's shading, 1 ray, unbiased; sampled: also the sample the candidates chose, 2 rays, biased where\n"
+    "                         visibility differs between the pixels that share a sample\n"
     "  --restir-gi-bounces=N  the vertices of a ReSTIR GI sample's path behind the pixel, 1..8 (1): above 1 the radiance of a sample is that of a\n"
     "                         path continued from the ray's hit by cosine-hemisphere bounces with one light sample at each vertex, no\n"
     "                         Russian roulette (--max-ray-depth is not read by this renderer)\n"
@@ -112,7 +117,7 @@ int main(int argc, char** argv)
         bool use_probe_visibility = false;                                  // --use-probe-visibility, --brdf-integration (src/options.hh, data/brdf_integration.exr)
         std::string brdf_integration_path;
         restir_di_stage::options restir;                                    // --restir
-        bool restir_given = false;
+        bool restir_given = false, restir_visibility_given = false;         // --restir-visibility
         restir_gi_stage::options restir_gi;                                 // --restir-gi
         bool restir_gi_given = false, restir_gi_bounces_given = false;       // --restir-gi-bounces
         std::vector<int> devices;
@@ -246,6 +251,7 @@ int main(int argc, char** argv)
                     throw std::runtime_error("unknown renderer " + renderer + " (path-tracer, direct, sh-probes, dshgi, restir-di, restir-gi)");
             }
             else if(starts(a, "--restir=")) { restir.parse(val("--restir=")); restir_given = true; }
+            else if(starts(a, "--restir-visibility=")) { restir.parse_visibility(val("--restir-visibility=")); restir_visibility_given = true; }
             else if(starts(a, "--restir-gi=")) { restir_gi.parse(val("--restir-gi=")); restir_gi_given = true; }
             else if(starts(a, "--restir-gi-bounces=")) { restir_gi.parse_bounces(val("--restir-gi-bounces=")); restir_gi_bounces_given = true; }
             else if(a == "--use-probe-visibility") use_probe_visibility = true;
@@ -362,6 +368,8 @@ int main(int argc, char** argv)
         if(scene_path.empty()) throw std::runtime_error(usage_text);
         if(renderer == "dshgi" && display == "looking-glass") throw std::runtime_error("--renderer=dshgi: no --display=looking-glass (the composition of a light field from it is not built)");
         if(restir_given && renderer != "restir-di" && renderer != "restir-gi") throw std::runtime_error("--restir sets the options of --renderer=restir-di");
+        if(restir_visibility_given && renderer != "restir-di" && renderer != "restir-gi")
+            throw std::runtime_error("--restir-visibility sets the visibility mode of --renderer=restir-di");
         if(restir_gi_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi sets the options of --renderer=restir-gi");
         if(restir_gi_bounces_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi-bounces sets the path length of --renderer=restir-gi");
         if(renderer == "restir-gi")

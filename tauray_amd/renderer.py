@@ -1361,14 +1361,22 @@ class DshgiRenderer(_ViewportFrameRenderer):
 
 
 def restir_di_options(**kw) -> dict:
-    """trhip_restir_di_options at the command line's defaults (--restir=4,2,32,16,on)."""
+    """trhip_restir_di_options at the command line's defaults (--restir=4,2,32,16,on), and `visibility` (--restir-visibility=per-target):
+    "per-target", "shared" or "sampled", which the stage applies through trhip_restir_di_set_visibility."""
     o = dict(candidates=4, spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0,
-             record=False)
+             record=False, visibility="per-target")
     unknown = set(kw) - set(o)
     if unknown:
         raise AttributeError(f"unknown ReSTIR DI option {sorted(unknown)}")
     o.update(kw)
+    _restir_visibility_mode(o["visibility"])
     return o
+
+
+def _restir_visibility_mode(name) -> int:
+    if name not in _lib.RESTIR_VISIBILITY:
+        raise ValueError(f"unknown ReSTIR DI visibility mode {name!r} ({', '.join(_lib.RESTIR_VISIBILITY)})")
+    return _lib.RESTIR_VISIBILITY[name]
 
 
 class _RestirStage(_PostStage):
@@ -1403,13 +1411,13 @@ class _RestirStage(_PostStage):
 class RestirDiStage(_RestirStage):
     """ReSTIR DI (trhip_restir_di_*, include/trhip.h; written after shader/restir_di.glsl and its two ray generation shaders): per frame
     the canonical kernel (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).
-    `options`: restir_di_options(); with record, download() has "candidates", "temporal", "spatial", "final"."""
+    `options`: restir_di_options(); with record, download() has "candidates", "temporal", "spatial", "final", "sampled"."""
 
     PREFIX, TIMINGS = "restir_di", _lib.RestirDiTimingsC
     _RECORDS = {"surface": (_lib.RESTIR_DI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_DI_CANONICAL, _lib.RESTIR_DI_RESERVOIR_DTYPE),
                 "history": (_lib.RESTIR_DI_HISTORY, _lib.RESTIR_DI_RESERVOIR_DTYPE), "candidates": (_lib.RESTIR_DI_CANDIDATES, _lib.RESTIR_DI_CANDIDATE_DTYPE),
                 "temporal": (_lib.RESTIR_DI_TEMPORAL, _lib.RESTIR_DI_TEMPORAL_DTYPE), "spatial": (_lib.RESTIR_DI_SPATIAL, _lib.RESTIR_DI_SPATIAL_DTYPE),
-                "final": (_lib.RESTIR_DI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE)}
+                "final": (_lib.RESTIR_DI_FINAL, _lib.RESTIR_DI_FINAL_DTYPE), "sampled": (_lib.RESTIR_DI_SAMPLED, _lib.RESTIR_DI_SAMPLED_DTYPE)}
     _AXES = {"candidates": "candidates", "spatial": "spatial_samples"}
 
     def __init__(self, ctx: Optional[Context], scene_stage: Optional[SceneStage], size, layers=1, options: Optional[dict] = None, projection=0):
@@ -1418,7 +1426,20 @@ class RestirDiStage(_RestirStage):
                                     int(o["temporal_reuse"]), float(o["min_ray_dist"]), int(o["rng_seed"]) & 0xFFFFFFFF, int(o["record"]))
         if int(o["candidates"]) < 0 or int(o["spatial_samples"]) < 0:
             raise TrhipError("RestirDiStage: candidates and spatial_samples are counts")
+        visibility, o["visibility"] = o["visibility"], "per-target"
         self._create_stage(ctx, scene_stage, size, layers, projection, opt)
+        if visibility != "per-target":
+            try:
+                self.set_visibility(visibility)
+            except TrhipError:
+                self.close()
+                raise
+
+    def set_visibility(self, visibility: str):
+        """The visibility mode, "per-target", "shared" or "sampled" (trhip_restir_di_set_visibility); another mode than the history's
+        is refused while there is history."""
+        check(self._fn("set_visibility")(self.h, _restir_visibility_mode(visibility)))
+        self.options["visibility"] = visibility
 
     def run(self, viewports, out, stream=None):
         """One frame: `out` RGBA32F [len(viewports)][h][w] = contribution * uc_weight + emission of the listed viewports.  History is kept

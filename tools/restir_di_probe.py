@@ -6,7 +6,12 @@ median with the spread (min ... max) next to it.  With --quality it also prints 
 image that tests/test_restir_di.py asserts on (128 x 72, 8 seeds).  No threshold: the record, profiles/r16/restir_di.txt, is the next
 change's baseline.
 
-usage: python tools/restir_di_probe.py [--lights 64] [--frames 20] [--warmup 5] [--quality]
+With --visibility MODE[,MODE...] (per-target, shared, sampled: trhip_restir_di_set_visibility) a block of rows per mode follows: the five
+configurations above, the candidate sweep on to 32 and --restir=32,4; with --quality also the mode's MSE at the defaults and, for shared
+and sampled when per-target is among the modes, at the candidate count of the sweep whose stage time is closest to per-target's at the
+defaults.  The record: profiles/r26/restir_di_visibility.txt.
+
+usage: python tools/restir_di_probe.py [--lights 64] [--frames 20] [--warmup 5] [--quality] [--visibility MODE[,MODE...]]
 """
 import argparse
 import os
@@ -29,7 +34,9 @@ def main():
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--quality", action="store_true")
+    ap.add_argument("--visibility", default="", help="per-target, shared, sampled: a block of rows per mode")
     a = ap.parse_args()
+    modes = [m for m in a.visibility.split(",") if m]
 
     from tauray_amd import _lib, renderer as R, scenes
     from tauray_amd.distribution import DISTRIBUTION_DUPLICATE, DistributionParams
@@ -44,8 +51,8 @@ def main():
     print("   device ms, median (min ... max)")
     out = ctx.alloc(w * h * 16).zero()
 
-    def restir(candidates, spatial):
-        st = R.RestirDiStage(ctx, ss, (w, h), 1, R.restir_di_options(candidates=candidates, spatial_samples=spatial, min_ray_dist=base.min_ray_dist), base.projection)
+    def restir(candidates, spatial, **more):
+        st = R.RestirDiStage(ctx, ss, (w, h), 1, R.restir_di_options(candidates=candidates, spatial_samples=spatial, min_ray_dist=base.min_ray_dist, **more), base.projection)
         rows = []
         for f in range(a.warmup + a.frames):
             st.run([0], out)
@@ -74,6 +81,13 @@ def main():
         print(f"restir-di candidates {candidates} spatial_samples {spatial}: [restir di canonical] {spread(c)}  [restir di spatial] {spread(s)}  stage {spread(t)}")
     for spp in (1, 4, 8):
         print(f"direct stage samples_per_pixel {spp}: {spread(direct(spp))}")
+    stage_ms = {}       # (mode, candidates) at two spatial samples -> median stage ms
+    for mode in modes:
+        for candidates, spatial in ((1, 2), (4, 2), (8, 2), (32, 2), (4, 0), (4, 4), (32, 4)):
+            c, s, t = restir(candidates, spatial, visibility=mode)
+            if spatial == 2:
+                stage_ms[(mode, candidates)] = float(np.median(t))
+            print(f"restir-di visibility {mode} candidates {candidates} spatial_samples {spatial}: [restir di canonical] {spread(c)}  [restir di spatial] {spread(s)}  stage {spread(t)}")
     out.free()
 
     if a.quality:
@@ -90,16 +104,29 @@ def main():
             st.close()
             return img
         ref = direct_image(4096, 999)
-        mse_r, mse_d = [], []
-        for seed in range(1, 9):
-            st = R.RestirDiStage(ctx, qs, (qw, qh), 1, R.restir_di_options(rng_seed=seed, min_ray_dist=base.min_ray_dist))
+
+        def restir_mse(seed, **more):
+            st = R.RestirDiStage(ctx, qs, (qw, qh), 1, R.restir_di_options(rng_seed=seed, min_ray_dist=base.min_ray_dist, **more))
             for _ in range(9):
                 st.run([0], buf)
-            mse_r.append(np.mean((buf.download((qh, qw, 4))[..., :3].astype(np.float64) - ref) ** 2))
+            mse = np.mean((buf.download((qh, qw, 4))[..., :3].astype(np.float64) - ref) ** 2)
             st.close()
+            return mse
+        mse_r, mse_d = [], []
+        for seed in range(1, 9):
+            mse_r.append(restir_mse(seed))
             mse_d.append(np.mean((direct_image(4, seed) - ref) ** 2))
         print(f"quality at {qw} x {qh}, 8 seeds, MSE against the direct stage at 4096 spp: restir-di defaults, frame 8: {np.mean(mse_r):.4e}; direct stage at 4 spp: {np.mean(mse_d):.4e}; "
               f"ratio {np.mean(mse_r) / np.mean(mse_d):.3f}")
+        for mode in modes:
+            counts = [4]
+            if mode != "per-target" and ("per-target", 4) in stage_ms:
+                counts.append(min((1, 4, 8, 32), key=lambda c: abs(stage_ms[(mode, c)] - stage_ms[("per-target", 4)])))
+            for candidates in counts:
+                mse = [restir_mse(seed, visibility=mode, candidates=candidates) for seed in range(1, 9)]
+                note = "" if candidates == 4 else f" (the count whose stage time, {stage_ms[(mode, candidates)]:.3f} ms, is closest to per-target's {stage_ms[('per-target', 4)]:.3f} ms at the defaults)"
+                print(f"quality at {qw} x {qh}, 8 seeds, visibility {mode}, candidates {candidates}{note}, frame 8: MSE {np.mean(mse):.4e} "
+                      f"(per seed {np.min(mse):.4e} ... {np.max(mse):.4e}); against the direct stage at 4 spp: ratio {np.mean(mse) / np.mean(mse_d):.3f}")
 
 
 if __name__ == "__main__":
