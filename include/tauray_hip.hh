@@ -1089,13 +1089,37 @@ public:
     {
         uint32_t candidates = 4;          // --restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse
         int visibility = TRHIP_RESTIR_VISIBILITY_PER_TARGET;      // --restir-visibility=per-target|shared|sampled (trhip_restir_di_set_visibility)
-        // what trhip_restir_di_create and trhip_restir_di_set_visibility refuse, said without a device
+        // --restir-light-selection=uniform|power[,fraction] (trhip_restir_di_set_light_selection): how a point or triangle light candidate is
+        // drawn, and the share of the power mode's pdf that stays uniform
+        int light_selection = TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM;
+        float uniform_fraction = 0.1f;
+        // what trhip_restir_di_create, trhip_restir_di_set_visibility and trhip_restir_di_set_light_selection refuse, said without a device
         void check() const
         {
             if(candidates < 1 || candidates > 32) throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " is outside 1..32");
             if(visibility < TRHIP_RESTIR_VISIBILITY_PER_TARGET || visibility > TRHIP_RESTIR_VISIBILITY_SAMPLED)
                 throw std::runtime_error("restir-di: visibility " + std::to_string(visibility) + " is outside 0..2");
+            if(light_selection < TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM || light_selection > TRHIP_RESTIR_LIGHT_SELECTION_POWER)
+                throw std::runtime_error("restir-di: light_selection " + std::to_string(light_selection) + " is outside 0..1");
+            if(!(uniform_fraction > 0.0f) || !(uniform_fraction <= 1.0f)) throw std::runtime_error("restir-di: uniform_fraction must be in (0, 1]");
             check_shared("restir-di");
+        }
+        // --restir-light-selection=uniform|power[,fraction]
+        void parse_light_selection(const std::string& text)
+        {
+            const size_t comma = text.find(',');
+            const std::string name = text.substr(0, comma);
+            if(name == "uniform") light_selection = TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM;
+            else if(name == "power") light_selection = TRHIP_RESTIR_LIGHT_SELECTION_POWER;
+            else throw std::runtime_error("--restir-light-selection: " + name + " is neither uniform nor power");
+            if(comma == std::string::npos) return;
+            const std::string number = text.substr(comma + 1);
+            size_t end = 0;
+            float f = 0.0f;
+            try { f = std::stof(number, &end); } catch(std::exception&) { end = 0; }
+            if(number.empty() || end != number.size() || !(f > 0.0f) || !(f <= 1.0f))
+                throw std::runtime_error("--restir-light-selection: the uniform fraction " + number + " is not a number in (0, 1]");
+            uniform_fraction = f;
         }
         // --restir-visibility=MODE
         void parse_visibility(const std::string& text)
@@ -1121,7 +1145,8 @@ public:
         opt.check();
         const trhip_restir_di_options o = opt.c_options();
         check(trhip_restir_di_create(dev.h, &o, size.x, size.y, layers, &h));
-        if(opt.visibility != TRHIP_RESTIR_VISIBILITY_PER_TARGET && trhip_restir_di_set_visibility(h, opt.visibility) != 0)
+        if((opt.visibility != TRHIP_RESTIR_VISIBILITY_PER_TARGET && trhip_restir_di_set_visibility(h, opt.visibility) != 0) ||
+           (opt.light_selection != TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM && trhip_restir_di_set_light_selection(h, opt.light_selection, opt.uniform_fraction) != 0))
         {
             trhip_restir_di_destroy(h);
             check(1);
@@ -1137,6 +1162,14 @@ public:
     void reset() { check(trhip_restir_di_reset(h)); }
     // another mode than the history's is refused until reset()
     void set_visibility(int mode) { check(trhip_restir_di_set_visibility(h, mode)); opt.visibility = mode; }
+    // "power" builds the table from the scene's lights as they are and waits for the device; a change is refused while there is history
+    void set_light_selection(int mode, float uniform_fraction = 0.1f)
+    {
+        check(trhip_restir_di_set_light_selection(h, mode, uniform_fraction));
+        opt.light_selection = mode; opt.uniform_fraction = uniform_fraction;
+    }
+    // after the scene's lights or instances changed: rebuilds the power mode's table unless the lights' weights are those it holds (then false)
+    bool refresh_light_selection() { uint32_t rebuilt = 0; check(trhip_restir_di_refresh_light_selection(h, &rebuilt)); return rebuilt != 0; }
     trhip_restir_di_timings get_timings() { trhip_restir_di_timings t; check(trhip_restir_di_get_timings(h, &t)); return t; }
 
     device* dev;
@@ -1161,6 +1194,8 @@ public:
         stage.reset(new restir_di_stage(dev, size, viewports, opt.restir));
     }
     ~restir_di_renderer() { stage.reset(); }
+    // a frame of an animated scene, ahead of render(): the lights may have moved with their nodes (nothing for the uniform selection)
+    void scene_moved() { stage->refresh_light_selection(); }
     void render(void* stream = nullptr)
     {
         stage->run(viewport_list, color, stream);
@@ -1255,6 +1290,7 @@ public:
         stage.reset(new restir_gi_stage(dev, size, viewports, opt.restir_gi));
     }
     ~restir_gi_renderer() { stage.reset(); direct.reset(); }
+    void scene_moved() { direct->refresh_light_selection(); }      // as restir_di_renderer
     void render(void* stream = nullptr)
     {
         direct->run(viewport_list, color, stream);

@@ -990,7 +990,28 @@ int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t s
  *  21. shared is unbiased like per-target (a target without visibility is a valid target; the traced ray is in the integrand).  sampled
  *      is biased wherever visibility differs between the pixels that share a sample: the paper's biased variant.
  *  22. A reservoir does not mix the samples of two target functions: the mode changes only while the stage holds no history.  ReSTIR GI's
- *      own kernels keep their visibility path whatever the mode of the ReSTIR DI stage beside them. */
+ *      own kernels keep their visibility path whatever the mode of the ReSTIR DI stage beside them.
+ *  23. Light selection (trhip_restir_di_set_light_selection).  uniform (0, the default) draws a point or triangle
+ *      light as sample_canonical does, index = clamp(int(u * n), 0, n - 1) with pdf 1 / n.  power (1) draws it in proportion to a weight:
+ *      a point or spot light's is luminance(color) - the spot cone and the radius are ignored -, a triangle light's
+ *      luminance(r9g9b9e5_to_rgb(emission_factor)) * (0.5 * |cross(pos[1] - pos[0], pos[2] - pos[0])|) - the emission texture is
+ *      ignored -, a negative, NaN or infinite weight is 0.  Directional lights, the environment and the four class probabilities
+ *      (decision 15) keep their rule.
+ *  24. Inside a class of n lights p_i = (1 - f) * w_i / sum(w) + f / n with the caller's uniform_fraction f in (0, 1]; 1 / n when
+ *      sum(w) = 0.  The uniform share is what keeps the estimator unbiased where the weight is blind - textures, cones, a table that is
+ *      stale because lights moved since it was built -: a light that contributes has a positive pdf.
+ *  25. The table: one 16-byte alias entry per light, the point lights' table then the triangle lights', each over its own n slots,
+ *      built on the host (include/tauray_alias.hh) in the work-list order and threshold encoding of the environment map's table, in
+ *      double steps; pdf and alias_pdf are float(p_i) of the slot and of its alias.
+ *  26. The draw: p = uint64(word) * n, slot = p >> 32, low = uint32(p), word = the draw's x for a point and z for a triangle light (the
+ *      words uniform selection reads); e = table[slot]; low > e.probability takes e.alias_id with e.alias_pdf, else the slot with
+ *      e.pdf; light_pdf = pdf * prob_point, or (tri_pdf * pdf) * prob_tri with the point on the triangle from x and y as ever.  No
+ *      draw is added or removed.  Limit: a light's frequency differs from its recorded pdf by at most n / 2^32 relative, the
+ *      granularity of `low` and of the slot.
+ *  27. The pdf of a candidate is no part of a reservoir, so the table may be rebuilt while the stage holds history
+ *      (trhip_restir_di_refresh_light_selection); the mode and the fraction change only without history: uc_weight does not mix two
+ *      candidate distributions silently (as decision 22).
+ *  28. ReSTIR GI's kernels draw the light sample at a secondary hit uniformly whatever the selection of the ReSTIR DI stage beside them. */
 typedef struct trhip_restir_di trhip_restir_di;
 typedef struct trhip_restir_di_options {
     uint32_t candidates;              /* 1..32 light samples per pixel (RIS_SAMPLE_COUNT) */
@@ -1053,6 +1074,18 @@ int trhip_restir_di_reset(trhip_restir_di* stage);        /* forgets the history
 #define TRHIP_RESTIR_VISIBILITY_SHARED 1
 #define TRHIP_RESTIR_VISIBILITY_SAMPLED 2
 int trhip_restir_di_set_visibility(trhip_restir_di* stage, int mode);
+/* The light selection (decisions 23 to 28); a stage is created uniform.  Refuses a null stage, a mode outside 0..1, a uniform_fraction
+ * outside (0, 1] or NaN (checked, and otherwise ignored, for uniform), power on a device without a scene and, while the stage holds
+ * history, any change of mode or fraction.  With power it builds the table from the scene's lights as they are: the weights kernel, a
+ * download, the host builder, an upload; it waits for the device. */
+#define TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM 0
+#define TRHIP_RESTIR_LIGHT_SELECTION_POWER 1
+int trhip_restir_di_set_light_selection(trhip_restir_di* stage, int mode, float uniform_fraction);
+/* Rebuilds the table after the scene's lights or instances changed; allowed while the stage holds history (decision 27).  The build is
+ * skipped when the lights' weights are byte-equal to those the table was built from: *rebuilt (may be null) is 1 or 0.  Waits for the
+ * device.  A uniform stage: nothing, 0.  trhip_restir_di_render refuses, in power mode, a scene whose point or triangle light count
+ * differs from the table's until this call; it never builds or synchronises on its own. */
+int trhip_restir_di_refresh_light_selection(trhip_restir_di* stage, uint32_t* rebuilt);
 /* One frame of `count` viewports (at most the stage's layers), two launches per 64, asynchronous on `stream`: out_color_dev RGBA32F
  * [count][h][w].  Refuses a device without a scene or acceleration structure and a viewport out of range.  History is kept per layer, the
  * position in the list: with temporal_reuse, a list that differs from the last frame's is refused until trhip_restir_di_reset. */
@@ -1066,6 +1099,8 @@ int trhip_restir_di_get_timings(trhip_restir_di* stage, trhip_restir_di_timings*
 #define TRHIP_RESTIR_DI_SPATIAL 5     /* trhip_restir_di_spatial [layers][h][w][spatial_samples] */
 #define TRHIP_RESTIR_DI_FINAL 6       /* trhip_restir_di_final [layers][h][w] */
 #define TRHIP_RESTIR_DI_SAMPLED 7     /* trhip_restir_di_sampled [layers][h][w] (record only) */
+#define TRHIP_RESTIR_DI_LIGHT_WEIGHTS 8   /* float [n_point + n_tri]: the weights the table was built from (power selection; with and without record) */
+#define TRHIP_RESTIR_DI_LIGHT_TABLE 9     /* 16-byte alias entries { uint32 alias_id, probability; float pdf, alias_pdf }, same order */
 int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
 
 /* ---- ReSTIR GI: reservoir resampling of indirect light (after Ouyang et al. 2021 and the ReSTIR DI stage above, whose

@@ -55,6 +55,29 @@
 //                weight = (1.0f / (float(candidates) + prev_confidence)) * target / pdf, NaN -> 0;  update_reservoir:
 //                weight_sum += weight; selected = u * weight_sum < weight (then the reservoir takes sample and target);  confidence += 1
 //                after the loop uc_weight = weight_sum > 0 ? weight_sum / target : 0
+//   light selection (trhip_restir_di_set_light_selection; uniform, the default, is `candidates` above word for word; power, decisions 23 to 28
+//                of trhip.h, changes how the index of a point or triangle candidate is drawn and what its pdf is, nothing else):
+//                weights   fp32, one per light (k_restir_light_weights, restir_di_power.hip): point or spot light rgb_to_luminance(color) -
+//                          the spot cone and the radius are ignored; triangle light rgb_to_luminance(r9g9b9e5_to_rgb(emission_factor)) *
+//                          (0.5f * length(cross(pos[1] - pos[0], pos[2] - pos[0]))) - the emission texture is ignored; a weight that is
+//                          negative, NaN or infinite is 0.  Directional lights, the environment and the class probabilities keep their rule.
+//                pdf       inside a class of n lights p_i = (1 - f) * w_i / sum(w) + f / n in double (sum: one running double sum in
+//                          slot order), f = uniform_fraction in (0, 1]; 1 / n when sum(w) = 0.  The uniform share keeps the estimator
+//                          unbiased where the weight is blind (textures, cones, a table that is stale because lights moved since it was
+//                          built): a light that contributes has a positive pdf.
+//                table     one AliasEntry per light, the point lights' table then the triangle lights', each over its own n slots, built on
+//                          the host (include/tauray_alias.hh) from n * p_i in the work-list order and the threshold encoding of the
+//                          environment map's table; the steps are doubles, not floats: a float n * p_i is off by up to 2^-25 relative, and
+//                          the thresholds are asked to reproduce p_i to 2^-30.  pdf / alias_pdf = float(p_i) of the slot and of its alias.
+//                draw      point: p = uint64(rnd.x) * n, slot = p >> 32, low = uint32(p); e = table[slot], one 16-byte load ahead of the
+//                          light record's; low > e.probability: index = e.alias_id, pdf = e.alias_pdf, else index = slot, pdf = e.pdf;
+//                          light_pdf = pdf * prob_point.  triangle: the same with rnd.z and the table's second part,
+//                          light_pdf = (tri_pdf * pdf) * prob_tri; u.xy still place the point on the triangle.  No draw is added or
+//                          removed, the streams stay where they are.  Limit: a light's frequency differs from its recorded pdf by at most
+//                          n / 2^32 relative, the granularity of `low` and of the slot.
+//                The pdf enters only the candidate weight target / pdf: the merges, the Jacobians, the MIS terms and the reservoirs never
+//                see it, so the table may be rebuilt while there is history (trhip_restir_di_refresh_light_selection); mode and fraction
+//                change only without history.  ReSTIR GI's light sample at a secondary hit (restir_gi.hip) stays uniform.
 //   reprojection m = get_camera_projection(previous camera, surface_prev_pos).xy;  m.y = 1.0f - m.y;  m = m * size - 0.5f;  im = int(m)
 //                (truncation);  off = m - float(im);  pixel = im + (off.x < u.x ? 0 : 1, off.y < u.y ? 0 : 1)   (restir_di.glsl:138-153)
 //   reuse        there is history, the pixel is on screen, and not (dot(prev.mapped_normal, mapped_normal) < 0.95f or

@@ -9,6 +9,8 @@
 // VISIBILITY (trhip_restir_di_set_visibility; `visibility modes` of restir_di.h) is a template parameter of both: 0, per-target, traces
 // inside every target function; with 1 and 2 the candidate loop and the per-slot loop hold no traversal at all, 2 traces the candidates'
 // choice once behind the loop.
+// The power-proportional light selection (trhip_restir_di_set_light_selection; `light selection` of restir_di.h) has its canonical kernel
+// and its weights kernel in restir_di_power.hip; its host side - the table, the setter, the refresh, the power mode's frame - is here.
 // Constants, layouts, the order of operations and the order of random draws: restir_di.h.  The temporal and the spatial merge and the
 // host skeleton are restir_resample.h's, shared with ReSTIR GI.  Both kernels are IEEE fp32, evaluated without
 // contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  The front half is first_hit.h's, the one
@@ -17,7 +19,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "restir_di.h"
+#include "restir_di_power.h"
+#include "../../include/tauray_alias.hh"
 
 namespace tr {
 namespace {
@@ -223,7 +226,19 @@ struct trhip_restir_di : RestirStageHost<3> {
     RestirCandidateRecord* rec_candidates = nullptr;
     RestirSampledRecord* rec_sampled = nullptr;      // per-target: (1, 0) on every pixel, written by fill_sampled_constant, no kernel
     int visibility = TRHIP_RESTIR_VISIBILITY_PER_TARGET;      // trhip_restir_di_set_visibility
+    // trhip_restir_di_set_light_selection (restir_di.h `light selection`).  The weights and the table are the stage's own allocations, grown
+    // with the scene's light count; host_weights are the weights the table was built from, table_points / table_tris its two classes.
+    int selection = TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM;
+    float uniform_fraction = 0.1f;
+    float* light_weights = nullptr;
+    AliasEntry* light_table = nullptr;
+    size_t light_capacity = 0;
+    bool has_table = false;
+    uint32_t table_points = 0, table_tris = 0;
+    std::vector<float> host_weights;
+    ~trhip_restir_di() { (void)hipFree(light_weights); (void)hipFree(light_table); }
 };
+static_assert(sizeof(alias_entry) == sizeof(AliasEntry), "the host builder's entry is the kernels'");
 
 static_assert(sizeof(trhip_restir_di_surface) == sizeof(RestirSurface) && sizeof(trhip_restir_di_reservoir) == sizeof(RestirReservoir), "downloads are the kernels' records");
 static_assert(sizeof(trhip_restir_di_candidate) == sizeof(RestirCandidateRecord) && sizeof(trhip_restir_di_temporal) == sizeof(RestirTemporalRecord), "downloads are the kernels' records");
@@ -256,6 +271,69 @@ static int restir_di_render_mode(trhip_restir_di* s, DeviceScene* scene, int pro
         P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
         if constexpr (VISIBILITY != 0) P.rec_sampled = s->rec_sampled ? s->rec_sampled + off : nullptr;
     });
+}
+
+// A frame of the power mode: the canonical pass is restir_di_power.hip's kernel with a parameter block of its own, the spatial pass the
+// instance the uniform mode launches (it never sees a candidate's pdf)
+template <int VISIBILITY>
+static int restir_di_render_power(trhip_restir_di* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    RestirPowerParams cbase{};
+    cbase.candidates = (int)s->opt.candidates;
+    restir_fill_params(cbase, *s, *scene);
+    cbase.light_table = s->light_table;
+    ParamsOf<VISIBILITY> sbase{};
+    sbase.candidates = (int)s->opt.candidates;
+    restir_fill_params(sbase, *s, *scene);
+    const RestirPowerKernel canonical = restir_di_power_canonical_kernel(scene->two_level, s->opt.temporal_reuse != 0, VISIBILITY);
+    const RestirKernel<VISIBILITY> spatial = scene->two_level ? spatial_kernel<true, VISIBILITY>(s->opt.spatial_samples) : spatial_kernel<false, VISIBILITY>(s->opt.spatial_samples);
+    if (int r = restir_begin_frame(s, st)) return r;
+    if (int r = restir_run_pass(s, scene, projection, viewports, count, st, cbase, canonical, 0, [&](RestirPowerParams& P, size_t off) {
+            P.canonical = s->canonical + off; P.history = s->history + off;
+            P.out = (f4*)out_color_dev + off;
+            P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
+            P.rec_sampled = VISIBILITY != 0 && s->rec_sampled ? s->rec_sampled + off : nullptr;
+        })) return r;
+    if (int r = restir_run_pass(s, scene, projection, viewports, count, st, sbase, spatial, 1, [&](ParamsOf<VISIBILITY>& P, size_t off) {
+            P.canonical = s->canonical + off; P.history = s->history + off;
+            P.out = (f4*)out_color_dev + off;
+            P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
+            if constexpr (VISIBILITY != 0) P.rec_sampled = s->rec_sampled ? s->rec_sampled + off : nullptr;
+        })) return r;
+    return restir_end_frame(s, viewports, count);
+}
+
+// The table of the power mode from the scene's lights as they are now: the weights kernel, a download, the host builder
+// (tauray_alias.hh), an upload.  Waits for the device, twice: a frame in flight reads the table.  force = false skips the build when
+// the weights are byte-equal to those the table holds.
+static int build_light_table(trhip_restir_di* s, const std::string& fn, bool force, uint32_t* rebuilt) {
+    if (rebuilt) *rebuilt = 0;
+    DEVCHK(s->hip_device);
+    DeviceScene* scene = device_scene(s->dev);
+    if (int r = check_scene_ready(fn.c_str(), scene->instance_count, scene->accel_built)) return r;
+    const uint32_t n_point = scene->point_light_count, n_tri = scene->tri_light_count;
+    const size_t n = (size_t)n_point + n_tri;
+    if (n > s->light_capacity || !s->light_table) {
+        HIPCHK(hipDeviceSynchronize());
+        (void)hipFree(s->light_weights); (void)hipFree(s->light_table);
+        s->light_weights = nullptr; s->light_table = nullptr; s->light_capacity = 0; s->has_table = false;
+        const size_t cap = n > 0 ? n : 1;
+        HIPCHK(hipMalloc((void**)&s->light_weights, cap * sizeof(float)));
+        HIPCHK(hipMalloc((void**)&s->light_table, cap * sizeof(AliasEntry)));
+        s->light_capacity = cap;
+    }
+    std::vector<float> weights(n);
+    HIPCHK(restir_launch_light_weights(scene->view(), s->light_weights, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (n) HIPCHK(hipMemcpy(weights.data(), s->light_weights, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (!force && s->has_table && n_point == s->table_points && n_tri == s->table_tris &&
+        (n == 0 || memcmp(weights.data(), s->host_weights.data(), n * sizeof(float)) == 0)) return 0;
+    const std::vector<alias_entry> table = build_light_selection_table(weights.data(), n_point, n_tri, s->uniform_fraction);
+    if (n) HIPCHK(hipMemcpy(s->light_table, table.data(), n * sizeof(alias_entry), hipMemcpyHostToDevice));
+    s->host_weights = weights;
+    s->table_points = n_point; s->table_tris = n_tri; s->has_table = true;
+    if (rebuilt) *rebuilt = 1;
+    return 0;
 }
 
 extern "C" {
@@ -298,9 +376,48 @@ int trhip_restir_di_set_visibility(trhip_restir_di* s, int mode) {
     return 0;
 }
 
+int trhip_restir_di_set_light_selection(trhip_restir_di* s, int mode, float uniform_fraction) {
+    static const char* const names[2] = {"uniform", "power"};
+    const std::string fn = std::string(API) + "_set_light_selection";
+    if (!s) return set_error(fn + ": null stage");
+    if (mode < TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM || mode > TRHIP_RESTIR_LIGHT_SELECTION_POWER) return set_error(fn + ": mode " + std::to_string(mode) + " is outside 0..1");
+    if (!(uniform_fraction > 0.0f) || !(uniform_fraction <= 1.0f)) return set_error(fn + ": uniform_fraction must be in (0, 1]");
+    // a reservoir's uc_weight must not mix two candidate distributions silently
+    if (s->frame > 0 && (mode != s->selection || uniform_fraction != s->uniform_fraction))
+        return set_error(fn + ": the stage holds history of the " + names[s->selection] + " selection with uniform_fraction " + std::to_string(s->uniform_fraction) +
+                         ": call " + API + "_reset first");
+    if (mode == TRHIP_RESTIR_LIGHT_SELECTION_POWER) {
+        const float before = s->uniform_fraction;
+        s->uniform_fraction = uniform_fraction;
+        if (int r = build_light_table(s, fn, true, nullptr)) { s->uniform_fraction = before; return r; }
+    }
+    s->uniform_fraction = uniform_fraction;
+    s->selection = mode;
+    return 0;
+}
+
+int trhip_restir_di_refresh_light_selection(trhip_restir_di* s, uint32_t* rebuilt) {
+    const std::string fn = std::string(API) + "_refresh_light_selection";
+    if (rebuilt) *rebuilt = 0;
+    if (!s) return set_error(fn + ": null stage");
+    if (s->selection != TRHIP_RESTIR_LIGHT_SELECTION_POWER) return 0;
+    return build_light_table(s, fn, false, rebuilt);
+}
+
 int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
     DeviceScene* scene = nullptr;
     if (int r = restir_begin_render(API, s, viewports, count, out_color_dev, scene)) return r;
+    if (s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER) {
+        if (scene->point_light_count != s->table_points || scene->tri_light_count != s->table_tris)
+            return set_error(std::string(API) + "_render: the scene has " + std::to_string(scene->point_light_count) + " point and " + std::to_string(scene->tri_light_count) +
+                             " triangle lights, the light selection table was built for " + std::to_string(s->table_points) + " and " + std::to_string(s->table_tris) +
+                             ": call " + API + "_refresh_light_selection first");
+        switch (s->visibility) {
+            case TRHIP_RESTIR_VISIBILITY_PER_TARGET: return restir_di_render_power<0>(s, scene, projection, viewports, count, out_color_dev, stream);
+            case TRHIP_RESTIR_VISIBILITY_SHARED: return restir_di_render_power<1>(s, scene, projection, viewports, count, out_color_dev, stream);
+            default: return restir_di_render_power<2>(s, scene, projection, viewports, count, out_color_dev, stream);
+        }
+    }
     switch (s->visibility) {
         case TRHIP_RESTIR_VISIBILITY_PER_TARGET: return restir_di_render_mode<0>(s, scene, projection, viewports, count, out_color_dev, stream);
         case TRHIP_RESTIR_VISIBILITY_SHARED: return restir_di_render_mode<1>(s, scene, projection, viewports, count, out_color_dev, stream);
@@ -320,12 +437,17 @@ int trhip_restir_di_get_timings(trhip_restir_di* s, trhip_restir_di_timings* out
 
 int trhip_restir_di_download(trhip_restir_di* s, int which, void* host, size_t bytes) {
     const int shared[4] = {TRHIP_RESTIR_DI_SURFACE, TRHIP_RESTIR_DI_TEMPORAL, TRHIP_RESTIR_DI_SPATIAL, TRHIP_RESTIR_DI_FINAL};
+    // the weights and the table of the power mode are no decision records: they are there with and without `record`
+    if (s && (which == TRHIP_RESTIR_DI_LIGHT_WEIGHTS || which == TRHIP_RESTIR_DI_LIGHT_TABLE) && !(s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER && s->has_table))
+        return set_error(std::string(API) + "_download: the stage has no light selection table (" + API + "_set_light_selection)");
     return restir_download(API, s, which, host, bytes, which >= TRHIP_RESTIR_DI_CANDIDATES && which <= TRHIP_RESTIR_DI_SAMPLED, shared,
         [&](size_t n, const void*& src, size_t& size) {
             switch (which) {
                 case TRHIP_RESTIR_DI_CANONICAL: src = s->canonical; size = n * sizeof(RestirReservoir); return true;
                 case TRHIP_RESTIR_DI_HISTORY: src = s->history; size = n * sizeof(RestirReservoir); return true;
                 case TRHIP_RESTIR_DI_SAMPLED: src = s->rec_sampled; size = n * sizeof(RestirSampledRecord); return true;
+                case TRHIP_RESTIR_DI_LIGHT_WEIGHTS: src = s->light_weights; size = ((size_t)s->table_points + s->table_tris) * sizeof(float); return true;
+                case TRHIP_RESTIR_DI_LIGHT_TABLE: src = s->light_table; size = ((size_t)s->table_points + s->table_tris) * sizeof(AliasEntry); return true;
                 case TRHIP_RESTIR_DI_CANDIDATES: src = s->rec_candidates; size = n * s->opt.candidates * sizeof(RestirCandidateRecord); return true;
                 default: return false;
             }

@@ -453,31 +453,47 @@ void restir_fill_params(Params& base, const Stage& s, const DeviceScene& scene) 
 
 // The frame: every chunk's kernel of one pass, then the next pass (a chunk's launch reads only its own layers); ev[pass + 1] behind pass.
 // fill(P, off) sets the stage's own pointers of a chunk that starts `off` pixels into the images; the shared ones are set here.
+// The three steps are functions of their own for a frame whose passes take different parameter blocks (ReSTIR DI's power-proportional
+// light selection: restir_di_power.h); restir_run_passes is the frame of one block.
+template <class Stage>
+int restir_begin_frame(Stage* s, hipStream_t st) {
+    HIPCHK(hipEventRecord(s->ev[0], st));
+    return 0;
+}
 template <class Stage, class Params, class Fill>
-int restir_run_passes(Stage* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, hipStream_t st, const Params& base,
-                      void (*const* kernels)(SceneView, LaunchCtx, int, ViewportList, Params, uint*), int passes, Fill fill) {
+int restir_run_pass(Stage* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, hipStream_t st, const Params& base,
+                    void (*kernel)(SceneView, LaunchCtx, int, ViewportList, Params, uint*), int pass, Fill fill) {
     const LaunchCtx L = whole_image_launch(s->w, s->h);
     const size_t layer_px = (size_t)s->w * s->h;
     const int cur = (int)(s->frame & 1u);
-    HIPCHK(hipEventRecord(s->ev[0], st));
-    for (int pass = 0; pass < passes; ++pass) {
-        for_each_viewport_chunk<ViewportList>(viewports, count, [&](uint32_t first, uint32_t n, const ViewportList& list) {
-            Params P = base;
-            const size_t off = first * layer_px;
-            P.surface = s->surface[cur] + off; P.prev_surface = s->surface[cur ^ 1] + off;
-            P.rec_temporal = s->rec_temporal ? s->rec_temporal + off : nullptr;
-            P.rec_spatial = s->rec_spatial ? s->rec_spatial + off * s->opt.spatial_samples : nullptr;
-            P.rec_final = s->rec_final ? s->rec_final + off : nullptr;
-            fill(P, off);
-            hipLaunchKernelGGL(kernels[pass], tile_grid(s->w, s->h, n), dim3(TR_BLOCK), 0, st, scene->view(), L, projection, list, P, device_overflow_flag(s->dev));
-        });
-        HIPCHK(hipEventRecord(s->ev[pass + 1], st));
-    }
+    for_each_viewport_chunk<ViewportList>(viewports, count, [&](uint32_t first, uint32_t n, const ViewportList& list) {
+        Params P = base;
+        const size_t off = first * layer_px;
+        P.surface = s->surface[cur] + off; P.prev_surface = s->surface[cur ^ 1] + off;
+        P.rec_temporal = s->rec_temporal ? s->rec_temporal + off : nullptr;
+        P.rec_spatial = s->rec_spatial ? s->rec_spatial + off * s->opt.spatial_samples : nullptr;
+        P.rec_final = s->rec_final ? s->rec_final + off : nullptr;
+        fill(P, off);
+        hipLaunchKernelGGL(kernel, tile_grid(s->w, s->h, n), dim3(TR_BLOCK), 0, st, scene->view(), L, projection, list, P, device_overflow_flag(s->dev));
+    });
+    HIPCHK(hipEventRecord(s->ev[pass + 1], st));
+    return 0;
+}
+template <class Stage>
+int restir_end_frame(Stage* s, const uint32_t* viewports, uint32_t count) {
     HIPCHK(hipGetLastError());
     s->frames += 1;
     s->frame += 1;
     s->viewports.assign(viewports, viewports + count);
     return 0;
+}
+template <class Stage, class Params, class Fill>
+int restir_run_passes(Stage* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, hipStream_t st, const Params& base,
+                      void (*const* kernels)(SceneView, LaunchCtx, int, ViewportList, Params, uint*), int passes, Fill fill) {
+    if (int r = restir_begin_frame(s, st)) return r;
+    for (int pass = 0; pass < passes; ++pass)
+        if (int r = restir_run_pass(s, scene, projection, viewports, count, st, base, kernels[pass], pass, fill)) return r;
+    return restir_end_frame(s, viewports, count);
 }
 
 // trhip_restir_*_download: shared[] = the stage's codes of the surface, temporal, spatial and final records; decision: `which` is a

@@ -11,6 +11,7 @@
 //              [--rng-seed=0] [--accumulation] [-t] [--skip-nan-check] [--warmup-frames=0] [--frames-in-flight=1] [--frames-per-launch=1]
 //              [--renderer=restir-di [--restir=candidates,spatial_samples,search_radius,max_confidence,temporal_reuse]]
 //              [--restir-visibility=per-target|shared|sampled]   (with --renderer=restir-di and restir-gi)
+//              [--restir-light-selection=uniform|power[,fraction]]   (with --renderer=restir-di and restir-gi)
 //              [--renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse] [--restir-gi-bounces=N] [--restir=...]]
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
@@ -71,6 +72,9 @@ static const char* const usage_text =
     "                         per-target: inside every target function, candidates + 2 * spatial_samples + 1 rays a pixel; shared: only the\n"
     "                         chosen sample's shading, 1 ray, unbiased; sampled: also the sample the candidates chose, 2 rays, biased where\n"
     "                         visibility differs between the pixels that share a sample\n"
+    "  --restir-light-selection=uniform|power[,fraction]   (uniform) how ReSTIR DI draws a point or triangle light candidate, with\n"
+    "                         --renderer=restir-di and restir-gi: uniform: every light of its class alike; power: in proportion to the\n"
+    "                         lights' power through an alias table, the share `fraction` (0.1, in (0, 1]) of the pdf kept uniform\n"
     "  --restir-gi-bounces=N  the vertices of a ReSTIR GI sample's path behind the pixel, 1..8 (1): above 1 the radiance of a sample is that of a\n"
     "                         path continued from the ray's hit by cosine-hemisphere bounces with one light sample at each vertex, no\n"
     "                         Russian roulette (--max-ray-depth is not read by this renderer)\n"
@@ -118,6 +122,7 @@ int main(int argc, char** argv)
         std::string brdf_integration_path;
         restir_di_stage::options restir;                                    // --restir
         bool restir_given = false, restir_visibility_given = false;         // --restir-visibility
+        bool restir_light_selection_given = false;                          // --restir-light-selection
         restir_gi_stage::options restir_gi;                                 // --restir-gi
         bool restir_gi_given = false, restir_gi_bounces_given = false;       // --restir-gi-bounces
         std::vector<int> devices;
@@ -252,6 +257,7 @@ int main(int argc, char** argv)
             }
             else if(starts(a, "--restir=")) { restir.parse(val("--restir=")); restir_given = true; }
             else if(starts(a, "--restir-visibility=")) { restir.parse_visibility(val("--restir-visibility=")); restir_visibility_given = true; }
+            else if(starts(a, "--restir-light-selection=")) { restir.parse_light_selection(val("--restir-light-selection=")); restir_light_selection_given = true; }
             else if(starts(a, "--restir-gi=")) { restir_gi.parse(val("--restir-gi=")); restir_gi_given = true; }
             else if(starts(a, "--restir-gi-bounces=")) { restir_gi.parse_bounces(val("--restir-gi-bounces=")); restir_gi_bounces_given = true; }
             else if(a == "--use-probe-visibility") use_probe_visibility = true;
@@ -370,6 +376,8 @@ int main(int argc, char** argv)
         if(restir_given && renderer != "restir-di" && renderer != "restir-gi") throw std::runtime_error("--restir sets the options of --renderer=restir-di");
         if(restir_visibility_given && renderer != "restir-di" && renderer != "restir-gi")
             throw std::runtime_error("--restir-visibility sets the visibility mode of --renderer=restir-di");
+        if(restir_light_selection_given && renderer != "restir-di" && renderer != "restir-gi")
+            throw std::runtime_error("--restir-light-selection sets the light selection of --renderer=restir-di");
         if(restir_gi_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi sets the options of --renderer=restir-gi");
         if(restir_gi_bounces_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi-bounces sets the path length of --renderer=restir-gi");
         if(renderer == "restir-gi")
@@ -594,7 +602,7 @@ int main(int argc, char** argv)
             ro.tonemap = opt.tonemap;
             ro.restir.check();
             run_viewport_frames([&](device& dev, scene_stage&) { return std::make_unique<restir_di_renderer>(dev, scene, size, ro); },
-                                [](restir_di_renderer&) {},
+                                [](restir_di_renderer& rr) { rr.scene_moved(); },
                                 [](restir_di_renderer& rr)
             {
                 const trhip_restir_di_timings t = rr.stage->get_timings();
@@ -613,7 +621,7 @@ int main(int argc, char** argv)
             ro.restir.check();
             ro.restir_gi.check();
             run_viewport_frames([&](device& dev, scene_stage&) { return std::make_unique<restir_gi_renderer>(dev, scene, size, ro); },
-                                [](restir_gi_renderer&) {},
+                                [](restir_gi_renderer& rr) { rr.scene_moved(); },
                                 [](restir_gi_renderer& rr)
             {
                 const trhip_restir_di_timings d = rr.direct->get_timings();

@@ -1362,14 +1362,17 @@ class DshgiRenderer(_ViewportFrameRenderer):
 
 def restir_di_options(**kw) -> dict:
     """trhip_restir_di_options at the command line's defaults (--restir=4,2,32,16,on), and `visibility` (--restir-visibility=per-target):
-    "per-target", "shared" or "sampled", which the stage applies through trhip_restir_di_set_visibility."""
+    "per-target", "shared" or "sampled", which the stage applies through trhip_restir_di_set_visibility, and `light_selection`
+    (--restir-light-selection=uniform): "uniform" or "power" with `uniform_fraction` in (0, 1], applied through
+    trhip_restir_di_set_light_selection."""
     o = dict(candidates=4, spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0,
-             record=False, visibility="per-target")
+             record=False, visibility="per-target", light_selection="uniform", uniform_fraction=0.1)
     unknown = set(kw) - set(o)
     if unknown:
         raise AttributeError(f"unknown ReSTIR DI option {sorted(unknown)}")
     o.update(kw)
     _restir_visibility_mode(o["visibility"])
+    _restir_light_selection_mode(o["light_selection"], o["uniform_fraction"])
     return o
 
 
@@ -1377,6 +1380,14 @@ def _restir_visibility_mode(name) -> int:
     if name not in _lib.RESTIR_VISIBILITY:
         raise ValueError(f"unknown ReSTIR DI visibility mode {name!r} ({', '.join(_lib.RESTIR_VISIBILITY)})")
     return _lib.RESTIR_VISIBILITY[name]
+
+
+def _restir_light_selection_mode(name, uniform_fraction) -> int:
+    if name not in _lib.RESTIR_LIGHT_SELECTION:
+        raise ValueError(f"unknown ReSTIR DI light selection {name!r} ({', '.join(_lib.RESTIR_LIGHT_SELECTION)})")
+    if not 0.0 < float(uniform_fraction) <= 1.0:      # a NaN fails both comparisons
+        raise ValueError(f"ReSTIR DI uniform_fraction {uniform_fraction!r} is outside (0, 1]")
+    return _lib.RESTIR_LIGHT_SELECTION[name]
 
 
 class _RestirStage(_PostStage):
@@ -1411,7 +1422,8 @@ class _RestirStage(_PostStage):
 class RestirDiStage(_RestirStage):
     """ReSTIR DI (trhip_restir_di_*, include/trhip.h; written after shader/restir_di.glsl and its two ray generation shaders): per frame
     the canonical kernel (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).
-    `options`: restir_di_options(); with record, download() has "candidates", "temporal", "spatial", "final", "sampled"."""
+    `options`: restir_di_options(); with record, download() has "candidates", "temporal", "spatial", "final", "sampled"; with the power
+    light selection, "light_weights" (float [n_point + n_tri]) and "light_table" (the alias entries in the same order)."""
 
     PREFIX, TIMINGS = "restir_di", _lib.RestirDiTimingsC
     _RECORDS = {"surface": (_lib.RESTIR_DI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_DI_CANONICAL, _lib.RESTIR_DI_RESERVOIR_DTYPE),
@@ -1427,19 +1439,51 @@ class RestirDiStage(_RestirStage):
         if int(o["candidates"]) < 0 or int(o["spatial_samples"]) < 0:
             raise TrhipError("RestirDiStage: candidates and spatial_samples are counts")
         visibility, o["visibility"] = o["visibility"], "per-target"
+        selection, o["light_selection"] = o["light_selection"], "uniform"
         self._create_stage(ctx, scene_stage, size, layers, projection, opt)
-        if visibility != "per-target":
-            try:
+        try:
+            if visibility != "per-target":
                 self.set_visibility(visibility)
-            except TrhipError:
-                self.close()
-                raise
+            if selection != "uniform":
+                self.set_light_selection(selection, o["uniform_fraction"])
+        except TrhipError:
+            self.close()
+            raise
 
     def set_visibility(self, visibility: str):
         """The visibility mode, "per-target", "shared" or "sampled" (trhip_restir_di_set_visibility); another mode than the history's
         is refused while there is history."""
         check(self._fn("set_visibility")(self.h, _restir_visibility_mode(visibility)))
         self.options["visibility"] = visibility
+
+    def set_light_selection(self, light_selection: str, uniform_fraction: float = 0.1):
+        """How a point or triangle light candidate is drawn, "uniform" or "power" (trhip_restir_di_set_light_selection): in proportion to
+        the lights' power with the share `uniform_fraction` of the pdf uniform.  "power" builds the table from the scene's lights as
+        they are and waits for the device; a change is refused while there is history."""
+        check(self._fn("set_light_selection")(self.h, _restir_light_selection_mode(light_selection, uniform_fraction), float(uniform_fraction)))
+        self.options["light_selection"], self.options["uniform_fraction"] = light_selection, float(uniform_fraction)
+
+    def refresh_light_selection(self) -> bool:
+        """Rebuilds the power selection's table after the scene's lights or instances changed (trhip_restir_di_refresh_light_selection);
+        allowed while there is history.  True when the table was rebuilt, False when the lights' weights were those it holds (or the
+        stage is uniform).  Waits for the device."""
+        rebuilt = C.c_uint32(0)
+        check(self._fn("refresh_light_selection")(self.h, C.byref(rebuilt)))
+        return bool(rebuilt.value)
+
+    def download(self, name: str) -> np.ndarray:
+        if name in ("light_weights", "light_table"):
+            weights = name == "light_weights"
+            code, dtype = (_lib.RESTIR_DI_LIGHT_WEIGHTS, np.float32) if weights else (_lib.RESTIR_DI_LIGHT_TABLE, _lib.RESTIR_DI_LIGHT_TABLE_DTYPE)
+            n = len(self.scene_stage.scene.point_lights) + int(self.scene_stage.accel["tri_light_count"])
+            # one entry more than the table has: an empty table still has an address to copy to
+            return self._download_prefix(code, n, np.dtype(dtype))
+        return super().download(name)
+
+    def _download_prefix(self, code, n, dtype) -> np.ndarray:
+        out = np.empty(n + 1, dtype=dtype)
+        check(self._fn("download")(self.h, code, out.ctypes.data, n * dtype.itemsize))
+        return out[:n]
 
     def run(self, viewports, out, stream=None):
         """One frame: `out` RGBA32F [len(viewports)][h][w] = contribution * uc_weight + emission of the listed viewports.  History is kept
@@ -1456,8 +1500,11 @@ class RestirDiRenderer(_ViewportFrameRenderer):
         if projection is None:
             projection = scene.cameras[0].projection if scene.cameras else 0
         self.stage = RestirDiStage(ctx, scene_stage, self.size, self.viewports, options, projection)
+        self._animated = bool(scene.animations)
 
     def render(self, stream=None, tonemap=True):
+        if self._animated:      # the lights may have moved with their nodes: a no-op for the uniform selection
+            self.stage.refresh_light_selection()
         self.stage.run(np.arange(self.viewports), self.color, stream)
         self._finish(stream, tonemap)
 
@@ -1546,9 +1593,12 @@ class RestirGiRenderer(_ViewportFrameRenderer):
             projection = scene.cameras[0].projection if scene.cameras else 0
         self.direct = RestirDiStage(ctx, scene_stage, self.size, self.viewports, di_options, projection)
         self.stage = RestirGiStage(ctx, scene_stage, self.size, self.viewports, options, projection)
+        self._animated = bool(scene.animations)
 
     def render(self, stream=None, tonemap=True):
         v = np.arange(self.viewports)
+        if self._animated:      # as RestirDiRenderer
+            self.direct.refresh_light_selection()
         self.direct.run(v, self.color, stream)
         self.stage.run(v, self.color, self.color, stream)
         self._finish(stream, tonemap)

@@ -301,6 +301,21 @@ def sponza_lights(n_lights: int, seed: int = 1, width: int = 1920, height: int =
     return desc
 
 
+def sponza_lights_powers(n_lights: int, seed: int = 1, width: int = 1920, height: int = 1080, decades: float = 3.0) -> S.SceneDesc:
+    """`sponza_lights` with the lamps' powers spread log-uniformly over `decades` decades: every colour of sponza_lights is multiplied by
+    10 ** (-decades * u), u uniform per lamp, and all of them by one factor that keeps the sum of the colours, so that the image keeps
+    its brightness.  Positions, radii and cones are sponza_lights'.  For the power-proportional light selection of ReSTIR DI
+    (tools/restir_light_selection_probe.py): a few strong lamps among many weak ones.  Deterministic for (n_lights, seed, decades)."""
+    desc = sponza_lights(n_lights, seed, width, height)
+    if n_lights:
+        rng = np.random.default_rng([seed, n_lights, 0x90E25])
+        colour = desc.point_lights["color"].astype(np.float64)
+        spread = colour * (10.0 ** (-decades * rng.uniform(size=n_lights)))[:, None]
+        desc.point_lights["color"] = spread * (colour.sum() / spread.sum())
+    desc.name = f"sponza_lights_powers(n_lights={n_lights}, seed={seed}, decades={decades:g})"
+    return desc
+
+
 def scene_hash(desc: S.SceneDesc) -> str:
     h = hashlib.sha256()
     for a in (desc.instances, desc.spans, desc.vertices, desc.indices, desc.directional_lights, desc.point_lights):
