@@ -1093,7 +1093,11 @@ public:
         // drawn, and the share of the power mode's pdf that stays uniform
         int light_selection = TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM;
         float uniform_fraction = 0.1f;
-        // what trhip_restir_di_create, trhip_restir_di_set_visibility and trhip_restir_di_set_light_selection refuse, said without a device
+        // --restir-bsdf-candidates=N (trhip_restir_di_set_bsdf_candidates): candidates a pixel draws from its surface's BSDF behind the light
+        // candidates, 0..8, at most 32 together
+        uint32_t bsdf_candidates = 0;
+        // what trhip_restir_di_create, trhip_restir_di_set_visibility, trhip_restir_di_set_light_selection and
+        // trhip_restir_di_set_bsdf_candidates refuse, said without a device
         void check() const
         {
             if(candidates < 1 || candidates > 32) throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " is outside 1..32");
@@ -1102,6 +1106,9 @@ public:
             if(light_selection < TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM || light_selection > TRHIP_RESTIR_LIGHT_SELECTION_POWER)
                 throw std::runtime_error("restir-di: light_selection " + std::to_string(light_selection) + " is outside 0..1");
             if(!(uniform_fraction > 0.0f) || !(uniform_fraction <= 1.0f)) throw std::runtime_error("restir-di: uniform_fraction must be in (0, 1]");
+            if(bsdf_candidates > 8) throw std::runtime_error("restir-di: bsdf_candidates " + std::to_string(bsdf_candidates) + " is outside 0..8");
+            if(candidates + bsdf_candidates > 32)
+                throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " + bsdf_candidates " + std::to_string(bsdf_candidates) + " is above 32");
             check_shared("restir-di");
         }
         // --restir-light-selection=uniform|power[,fraction]
@@ -1120,6 +1127,16 @@ public:
             if(number.empty() || end != number.size() || !(f > 0.0f) || !(f <= 1.0f))
                 throw std::runtime_error("--restir-light-selection: the uniform fraction " + number + " is not a number in (0, 1]");
             uniform_fraction = f;
+        }
+        // --restir-bsdf-candidates=N
+        void parse_bsdf_candidates(const std::string& text)
+        {
+            size_t end = 0;
+            long n = -1;
+            try { n = std::stol(text, &end); } catch(std::exception&) { end = 0; }
+            if(text.empty() || end != text.size() || n < 0 || n > 8)
+                throw std::runtime_error("--restir-bsdf-candidates: " + text + " is not a whole number in 0..8");
+            bsdf_candidates = (uint32_t)n;
         }
         // --restir-visibility=MODE
         void parse_visibility(const std::string& text)
@@ -1146,7 +1163,8 @@ public:
         const trhip_restir_di_options o = opt.c_options();
         check(trhip_restir_di_create(dev.h, &o, size.x, size.y, layers, &h));
         if((opt.visibility != TRHIP_RESTIR_VISIBILITY_PER_TARGET && trhip_restir_di_set_visibility(h, opt.visibility) != 0) ||
-           (opt.light_selection != TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM && trhip_restir_di_set_light_selection(h, opt.light_selection, opt.uniform_fraction) != 0))
+           (opt.light_selection != TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM && trhip_restir_di_set_light_selection(h, opt.light_selection, opt.uniform_fraction) != 0) ||
+           (opt.bsdf_candidates != 0 && trhip_restir_di_set_bsdf_candidates(h, opt.bsdf_candidates) != 0))
         {
             trhip_restir_di_destroy(h);
             check(1);
@@ -1168,6 +1186,8 @@ public:
         check(trhip_restir_di_set_light_selection(h, mode, uniform_fraction));
         opt.light_selection = mode; opt.uniform_fraction = uniform_fraction;
     }
+    // a change is refused while there is history
+    void set_bsdf_candidates(uint32_t n) { check(trhip_restir_di_set_bsdf_candidates(h, n)); opt.bsdf_candidates = n; }
     // after the scene's lights or instances changed: rebuilds the power mode's table unless the lights' weights are those it holds (then false)
     bool refresh_light_selection() { uint32_t rebuilt = 0; check(trhip_restir_di_refresh_light_selection(h, &rebuilt)); return rebuilt != 0; }
     trhip_restir_di_timings get_timings() { trhip_restir_di_timings t; check(trhip_restir_di_get_timings(h, &t)); return t; }

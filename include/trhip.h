@@ -1011,7 +1011,40 @@ int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t s
  *  27. The pdf of a candidate is no part of a reservoir, so the table may be rebuilt while the stage holds history
  *      (trhip_restir_di_refresh_light_selection); the mode and the fraction change only without history: uc_weight does not mix two
  *      candidate distributions silently (as decision 22).
- *  28. ReSTIR GI's kernels draw the light sample at a secondary hit uniformly whatever the selection of the ReSTIR DI stage beside them. */
+ *  28. ReSTIR GI's kernels draw the light sample at a secondary hit uniformly whatever the selection of the ReSTIR DI stage beside them.
+ *  29. BSDF candidates (trhip_restir_di_set_bsdf_candidates; Bitterli et al. 2020 section 3.1, Talbot's RIS).  Behind
+ *      the L = options.candidates light candidates, drawn exactly as before, the canonical pass draws B = bsdf_candidates (0..8, L + B <= 32,
+ *      default 0) candidates from the surface's BSDF; M = L + B.  A BSDF candidate takes two draws from the pass's stream, null or not:
+ *      one whose four unit words are ggx_bsdf_sample's `ur`, one whose unit x is update_reservoir's selection draw.  The temporal
+ *      merge's draw follows them.
+ *  30. Its direction: tbn, shading_view and mat as the contribution builds them (z of the view clamped to 1e-5);
+ *      ggx_bsdf_sample<RoundedMath>(ur, shading_view, mat, out_dir), dir = normalize(tbn * out_dir).  p_b(x) is one function of (surface,
+ *      world direction) for candidates of both techniques, the value of ggx_bsdf_pdf<RoundedMath>(dir * tbn, shading_view, mat); the pdf
+ *      the sampler returns is not used (the two disagree on the transmission lobe).
+ *  31. A BSDF candidate is the null sample with weight 0 and traces nothing when out_dir has a NaN or is 0, when p_b is not > 0 - this
+ *      includes zero roughness, whose specular lobe is a delta: mirrors gain nothing - or when dot(dir, flat_normal) < 1e-6, where the
+ *      contribution is 0 under decision 5's rule: transmitted directions find no direct light.
+ *  32. Otherwise one closest-hit ray (pos, dir, min_ray_dist, inf).  A hit on an instance with light_base_id >= 0 is the triangle sample
+ *      (type 1, index = light_base_id + primitive, light_data = (1 - u - v, u): light_data.x weighs pos[0] and .y pos[1], a hit's u and v
+ *      weigh vertices 1 and 2); a miss with an environment is the environment sample (type 3, index 0, light_data = the lat-long uv of
+ *      dir: x = atan2(dir.z, dir.x) / (2 pi) + 0.5, y = atan2(-dir.y, sqrt(dir.x^2 + dir.z^2)) / pi + 0.5, RoundedMath's atan2); a
+ *      non-emissive hit, a miss without an environment and an index past the triangle light count are the null sample.
+ *  33. The found sample is fetched and evaluated like any other, so its contribution is what a light candidate of that identity gets.
+ *      Its visibility factor is 1 where the contribution has a positive component and 0 otherwise in every visibility mode: the
+ *      closest-hit ray is the visibility, no shadow ray is added.  Limit: an environment sample's direction is rebuilt from its uv and
+ *      differs from the traced one by rounding.  Rays a pixel: B closest-hit rays more than decision 17 counts, in every mode.
+ *  34. p_l(x), the pdf with which the light technique produces the sample's identity: a light candidate's light_pdf; for a triangle
+ *      found by a BSDF ray (tri_pdf * sel) * prob_tri with tri_pdf the solid-angle pdf of that triangle from pos (sample_canonical's
+ *      formula and 1e9 rule, the ray's length that of the contribution's direction to the triangle's plane), sel = 1 / n_tri or, under
+ *      power selection, table[n_point + index].pdf; for an environment sample table[pixel].pdf * prob_env with pixel =
+ *      clamp(floor(uv * size)), sample_canonical's layout (not latlong_direction_to_pixel_id's + 0.5).  A class of probability 0: 0.
+ *      p_b of a light candidate: 0 for point and directional samples, which the BSDF technique cannot produce; decision 30's function
+ *      at the contribution's direction for triangle and environment samples.
+ *  35. The balance heuristic: denom = float(L) * p_l + float(B) * p_b; weight = ((float(M) / (float(M) + prev_confidence)) * target) /
+ *      denom; a NaN weight or denom <= 0 gives 0.  confidence += 1 per candidate of either technique.  Everything behind the loops -
+ *      uc_weight, the sampled mode's ray, the temporal merge - is unchanged.  With B = 0 the stage launches the kernels it launched.
+ *  36. The pdfs enter only the candidate weight.  bsdf_candidates changes only while the stage holds no history (as decisions 22 and
+ *      27).  ReSTIR GI's kernels are untouched.  Out of scope: sphere lights (the stage lights them as points), delta lobes. */
 typedef struct trhip_restir_di trhip_restir_di;
 typedef struct trhip_restir_di_options {
     uint32_t candidates;              /* 1..32 light samples per pixel (RIS_SAMPLE_COUNT) */
@@ -1059,6 +1092,14 @@ typedef struct trhip_restir_di_sampled {      /* per pixel: decision 18's shadow
                                                * multiplied (shared: that weight, multiplied by nothing; per-target: 0) */
     float visibility, uc_weight_before; uint32_t pad[2];
 } trhip_restir_di_sampled;
+typedef struct trhip_restir_di_bsdf_candidate {   /* per candidate of a stage with BSDF candidates, next to trhip_restir_di_candidate (whose pdf is p_l) */
+    uint32_t technique;               /* 0: a light candidate, 1: a BSDF candidate */
+    float dir[3];                     /* light: the contribution's direction; BSDF: the traced one, 0 when the sampler gave none */
+    float p_b;
+    int32_t instance_id, primitive_id;   /* the BSDF ray's hit; instance -1 and t -1: a miss, nothing traced or a light candidate */
+    float u, v, t;
+    float denom; uint32_t traced;     /* 1: the closest-hit ray was cast */
+} trhip_restir_di_bsdf_candidate;
 typedef struct trhip_restir_di_timings {      /* device ms of the last render */
     float canonical_ms, spatial_ms, total_ms;
     uint32_t frames;
@@ -1081,6 +1122,11 @@ int trhip_restir_di_set_visibility(trhip_restir_di* stage, int mode);
 #define TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM 0
 #define TRHIP_RESTIR_LIGHT_SELECTION_POWER 1
 int trhip_restir_di_set_light_selection(trhip_restir_di* stage, int mode, float uniform_fraction);
+/* The BSDF candidates a pixel draws behind its light candidates (decisions 29 to 36); a stage is created with 0, and with 0 it launches
+ * the kernels it always launched.  Refuses a null stage, n > 8, candidates + n > 32 and, while the stage holds history, any change; it
+ * is accepted again after trhip_restir_di_reset.  With record it allocates the records of candidates + n candidates a pixel and waits
+ * for the device. */
+int trhip_restir_di_set_bsdf_candidates(trhip_restir_di* stage, uint32_t n);
 /* Rebuilds the table after the scene's lights or instances changed; allowed while the stage holds history (decision 27).  The build is
  * skipped when the lights' weights are byte-equal to those the table was built from: *rebuilt (may be null) is 1 or 0.  Waits for the
  * device.  A uniform stage: nothing, 0.  trhip_restir_di_render refuses, in power mode, a scene whose point or triangle light count
@@ -1094,13 +1140,14 @@ int trhip_restir_di_get_timings(trhip_restir_di* stage, trhip_restir_di_timings*
 #define TRHIP_RESTIR_DI_SURFACE 0     /* trhip_restir_di_surface [layers][h][w] of the last frame */
 #define TRHIP_RESTIR_DI_CANONICAL 1   /* trhip_restir_di_reservoir [layers][h][w]: what the canonical kernel wrote */
 #define TRHIP_RESTIR_DI_HISTORY 2     /* trhip_restir_di_reservoir [layers][h][w]: what the spatial kernel wrote */
-#define TRHIP_RESTIR_DI_CANDIDATES 3  /* trhip_restir_di_candidate [layers][h][w][candidates] (record only, as the three below) */
+#define TRHIP_RESTIR_DI_CANDIDATES 3  /* trhip_restir_di_candidate [layers][h][w][candidates + bsdf_candidates] (record only, as the three below) */
 #define TRHIP_RESTIR_DI_TEMPORAL 4    /* trhip_restir_di_temporal [layers][h][w] */
 #define TRHIP_RESTIR_DI_SPATIAL 5     /* trhip_restir_di_spatial [layers][h][w][spatial_samples] */
 #define TRHIP_RESTIR_DI_FINAL 6       /* trhip_restir_di_final [layers][h][w] */
 #define TRHIP_RESTIR_DI_SAMPLED 7     /* trhip_restir_di_sampled [layers][h][w] (record only) */
 #define TRHIP_RESTIR_DI_LIGHT_WEIGHTS 8   /* float [n_point + n_tri]: the weights the table was built from (power selection; with and without record) */
 #define TRHIP_RESTIR_DI_LIGHT_TABLE 9     /* 16-byte alias entries { uint32 alias_id, probability; float pdf, alias_pdf }, same order */
+#define TRHIP_RESTIR_DI_BSDF_CANDIDATES 10 /* trhip_restir_di_bsdf_candidate [layers][h][w][candidates + bsdf_candidates] (record only; refused with 0 BSDF candidates) */
 int trhip_restir_di_download(trhip_restir_di* stage, int which, void* host, size_t bytes);   /* test hook; synchronises the device */
 
 /* ---- ReSTIR GI: reservoir resampling of indirect light (after Ouyang et al. 2021 and the ReSTIR DI stage above, whose

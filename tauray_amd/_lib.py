@@ -262,12 +262,15 @@ class RestirDiTimingsC(C.Structure):
 
 # trhip_restir_di_download and the records behind the codes (include/trhip.h)
 (RESTIR_DI_SURFACE, RESTIR_DI_CANONICAL, RESTIR_DI_HISTORY, RESTIR_DI_CANDIDATES, RESTIR_DI_TEMPORAL, RESTIR_DI_SPATIAL,
- RESTIR_DI_FINAL, RESTIR_DI_SAMPLED, RESTIR_DI_LIGHT_WEIGHTS, RESTIR_DI_LIGHT_TABLE) = range(10)
+ RESTIR_DI_FINAL, RESTIR_DI_SAMPLED, RESTIR_DI_LIGHT_WEIGHTS, RESTIR_DI_LIGHT_TABLE, RESTIR_DI_BSDF_CANDIDATES) = range(11)
 # trhip_restir_di_set_visibility: the modes by their command-line names
 RESTIR_VISIBILITY = {"per-target": 0, "shared": 1, "sampled": 2}
 # trhip_restir_di_set_light_selection: the modes by their command-line names; the table's 16-byte entries (download code 9)
 RESTIR_LIGHT_SELECTION = {"uniform": 0, "power": 1}
 RESTIR_DI_LIGHT_TABLE_DTYPE = [("alias_id", "<u4"), ("probability", "<u4"), ("pdf", "<f4"), ("alias_pdf", "<f4")]
+# trhip_restir_di_bsdf_candidate (download code 10): one per candidate of a stage with BSDF candidates
+RESTIR_DI_BSDF_CANDIDATE_DTYPE = [("technique", "<u4"), ("dir", "<f4", 3), ("p_b", "<f4"), ("instance_id", "<i4"), ("primitive_id", "<i4"), ("u", "<f4"),
+                                  ("v", "<f4"), ("t", "<f4"), ("denom", "<f4"), ("traced", "<u4")]
 RESTIR_DI_NULL_INDEX = (1 << 30) - 1
 RESTIR_DI_SURFACE_DTYPE = [("pos", "<f4", 3), ("instance_id", "<i4"), ("mapped_normal", "<f4", 3), ("metallic", "<f4"), ("flat_normal", "<f4", 3),
                            ("roughness", "<f4"), ("view", "<f4", 3), ("transmittance", "<f4"), ("albedo", "<f4", 4), ("emission", "<f4", 3),
@@ -465,6 +468,7 @@ SYMBOLS = {
     "trhip_restir_di_set_visibility": (_i, [_vp, _i]),
     "trhip_restir_di_set_light_selection": (_i, [_vp, _i, C.c_float]),
     "trhip_restir_di_refresh_light_selection": (_i, [_vp, C.POINTER(_u32)]),
+    "trhip_restir_di_set_bsdf_candidates": (_i, [_vp, _u32]),
     "trhip_restir_di_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _vp, _vp]),
     "trhip_restir_di_get_timings": (_i, [_vp, C.POINTER(RestirDiTimingsC)]),
     "trhip_restir_di_download": (_i, [_vp, _i, _vp, C.c_size_t]),

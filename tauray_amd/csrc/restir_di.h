@@ -78,6 +78,37 @@
 //                The pdf enters only the candidate weight target / pdf: the merges, the Jacobians, the MIS terms and the reservoirs never
 //                see it, so the table may be rebuilt while there is history (trhip_restir_di_refresh_light_selection); mode and fraction
 //                change only without history.  ReSTIR GI's light sample at a secondary hit (restir_gi.hip) stays uniform.
+//   bsdf candidates (trhip_restir_di_set_bsdf_candidates; decisions 29 to 36 of trhip.h; k_restir_di_canonical_bsdf, restir_di_bsdf.hip;
+//                L = candidates, B = bsdf_candidates in 0..8, L + B <= 32, M = L + B; B = 0, the default, is `candidates` word for word
+//                and the kernels that were; with B > 0 the L light candidates are drawn as above, then the B BSDF candidates):
+//                1 draws     per BSDF candidate, null or not: one draw (the four unit words: ggx_bsdf_sample's ur), one draw (unit .x: the
+//                            selection).  The temporal merge's draw follows.
+//                2 direction tbn = create_tangent_space(mapped_normal), shading_view = view_to_tangent_space(view, tbn), mat: as
+//                            `contribution`;  ggx_bsdf_sample<RoundedMath>(ur, shading_view, mat, out_dir, ..);  dir = normalize(tbn * out_dir)
+//                3 p_b       p_b(surface, dir) = the value of ggx_bsdf_pdf<RoundedMath>(dir * tbn, shading_view, mat, lobes), for candidates of
+//                            both techniques.  The pdf ggx_bsdf_sample returns is not used.
+//                4 null      out_dir has a NaN or is 0; p_b is not > 0 (zero roughness: mirrors gain nothing); dot(dir, flat_normal) < 1e-6f:
+//                            the null sample, weight 0, nothing traced.
+//                5 ray       trace_closest4<1, false, TWO_LEVEL>(pos, dir, min_ray_dist, inf).  Hit, instance.light_base_id >= 0 and
+//                            index = light_base_id + primitive < tri_light_count: (type 1, index, data = (1.0f - u - v, u)).  Miss and an
+//                            environment: (type 3, 0, data = (atan2(dir.z, dir.x) / (2.0f * pi) + 0.5f,
+//                            atan2(-dir.y, sqrtf(dir.x * dir.x + dir.z * dir.z)) / pi + 0.5f)).  Anything else: the null sample.
+//                6 value     restir_fetch_light, `contribution` as for any sample; visibility = 1 where the contribution has a component
+//                            > 0, else 0, in every visibility mode: no shadow ray.  Limit: an environment sample's direction is rebuilt
+//                            from its uv and differs from the traced one by rounding.
+//                7 p_l       light candidate: its pdf above.  Found triangle: A, B, C = tl.pos[k] - pos; the solid angle of
+//                            sample_spherical_triangle operation for operation (nA .. G2, solid = 2.0f * atan2(G0, G1 + G2));
+//                            tri_pdf = 1.0f / solid; len = ray_plane_intersection_dist(contribution's dir, A, B, C); tri_pdf = 1e9f when it
+//                            is inf, <= 0, len <= min_ray_dist or dir has a NaN;  sel = 1.0f / float(n_tri), power selection:
+//                            table[n_point + index].pdf;  p_l = (tri_pdf * sel) * prob_tri.  Found environment sample:
+//                            pixel = clamp(int(floorf(data * size)), 0, size - 1) per axis; p_l = alias_table[pixel].pdf * prob_env.
+//                            A class of probability 0, or an invalid sample: 0.
+//                8 p_b of a light candidate: types 0 and 2: 0; types 1 and 3: item 3 at the contribution's dir.
+//                9 weight    denom = float(L) * p_l + float(B) * p_b (two products, one sum);  mis = float(M) / (float(M) + prev_confidence);
+//                            weight = (mis * target) / denom;  NaN, or not denom > 0: 0.  update_reservoir, confidence += 1 as above.
+//                            After the loops everything is as above.
+//                The pdfs enter only the candidate weight; B changes only without history.  Rays a pixel: B closest-hit rays more in
+//                every visibility mode.  Records: the candidate record's pdf is p_l; RestirBsdfRecord (restir_di_bsdf.h) next to it.
 //   reprojection m = get_camera_projection(previous camera, surface_prev_pos).xy;  m.y = 1.0f - m.y;  m = m * size - 0.5f;  im = int(m)
 //                (truncation);  off = m - float(im);  pixel = im + (off.x < u.x ? 0 : 1, off.y < u.y ? 0 : 1)   (restir_di.glsl:138-153)
 //   reuse        there is history, the pixel is on screen, and not (dot(prev.mapped_normal, mapped_normal) < 0.95f or
@@ -147,6 +178,7 @@ namespace tr {
 
 constexpr uint RESTIR_NULL_INDEX = (1u << 30) - 1u;
 constexpr int RESTIR_MAX_CANDIDATES = 32;
+constexpr int RESTIR_MAX_BSDF_CANDIDATES = 8;      // `bsdf candidates`; light and BSDF candidates together: RESTIR_MAX_CANDIDATES
 
 struct alignas(16) RestirReservoir {     // trhip_restir_di_reservoir
     float uc_weight, target_function; uint light; float confidence;

@@ -11,6 +11,8 @@
 // choice once behind the loop.
 // The power-proportional light selection (trhip_restir_di_set_light_selection; `light selection` of restir_di.h) has its canonical kernel
 // and its weights kernel in restir_di_power.hip; its host side - the table, the setter, the refresh, the power mode's frame - is here.
+// The BSDF-sampled candidates (trhip_restir_di_set_bsdf_candidates; `bsdf candidates` of restir_di.h) have their canonical kernel in
+// restir_di_bsdf.hip; the setter, their two record buffers and their frame are here.
 // Constants, layouts, the order of operations and the order of random draws: restir_di.h.  The temporal and the spatial merge and the
 // host skeleton are restir_resample.h's, shared with ReSTIR GI.  Both kernels are IEEE fp32, evaluated without
 // contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  The front half is first_hit.h's, the one
@@ -19,7 +21,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "restir_di_power.h"
+#include "restir_di_bsdf.h"
 #include "../../include/tauray_alias.hh"
 
 namespace tr {
@@ -236,14 +238,20 @@ struct trhip_restir_di : RestirStageHost<3> {
     bool has_table = false;
     uint32_t table_points = 0, table_tris = 0;
     std::vector<float> host_weights;
-    ~trhip_restir_di() { (void)hipFree(light_weights); (void)hipFree(light_table); }
+    // trhip_restir_di_set_bsdf_candidates (restir_di.h `bsdf candidates`).  With record and B > 0 the candidate records are [pixel][L + B]
+    // in an allocation of the setter's, next to the records of download 10; opt.candidates stays L and rec_candidates the buffer of create.
+    uint32_t bsdf_candidates = 0;
+    RestirCandidateRecord* rec_candidates_bsdf = nullptr;
+    RestirBsdfRecord* rec_bsdf = nullptr;
+    ~trhip_restir_di() { (void)hipFree(light_weights); (void)hipFree(light_table); (void)hipFree(rec_candidates_bsdf); (void)hipFree(rec_bsdf); }
 };
 static_assert(sizeof(alias_entry) == sizeof(AliasEntry), "the host builder's entry is the kernels'");
 
 static_assert(sizeof(trhip_restir_di_surface) == sizeof(RestirSurface) && sizeof(trhip_restir_di_reservoir) == sizeof(RestirReservoir), "downloads are the kernels' records");
 static_assert(sizeof(trhip_restir_di_candidate) == sizeof(RestirCandidateRecord) && sizeof(trhip_restir_di_temporal) == sizeof(RestirTemporalRecord), "downloads are the kernels' records");
 static_assert(sizeof(trhip_restir_di_spatial) == sizeof(RestirSpatialRecord) && sizeof(trhip_restir_di_final) == sizeof(RestirFinalRecord), "downloads are the kernels' records");
-static_assert(sizeof(trhip_restir_di_sampled) == sizeof(RestirSampledRecord), "downloads are the kernels' records");
+static_assert(sizeof(trhip_restir_di_sampled) == sizeof(RestirSampledRecord) && sizeof(trhip_restir_di_bsdf_candidate) == sizeof(RestirBsdfRecord), "downloads are the kernels' records");
+static_assert(sizeof(trhip_restir_di_options) == 32, "the options keep their size");
 
 // The per-target mode's `sampled` record: no ray and nothing multiplied, (visibility 1, uc_weight_before 0) on every pixel.  Written where
 // the mode is decided - at create and when the setter goes back to per-target - never in a frame.  Waits for the device.
@@ -298,6 +306,42 @@ static int restir_di_render_power(trhip_restir_di* s, DeviceScene* scene, int pr
             P.canonical = s->canonical + off; P.history = s->history + off;
             P.out = (f4*)out_color_dev + off;
             P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
+            if constexpr (VISIBILITY != 0) P.rec_sampled = s->rec_sampled ? s->rec_sampled + off : nullptr;
+        })) return r;
+    return restir_end_frame(s, viewports, count);
+}
+
+// A frame with BSDF candidates: the canonical pass is restir_di_bsdf.hip's kernel with a parameter block of its own - its POWER instances
+// when the selection is power -, the spatial pass the instance every other frame launches
+template <int VISIBILITY>
+static int restir_di_render_bsdf(trhip_restir_di* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const bool power = s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER;
+    const size_t per_pixel = (size_t)s->opt.candidates + s->bsdf_candidates;
+    RestirBsdfParams cbase{};
+    cbase.candidates = (int)s->opt.candidates;
+    cbase.bsdf_candidates = (int)s->bsdf_candidates;
+    restir_fill_params(cbase, *s, *scene);
+    cbase.light_table = power ? s->light_table : nullptr;
+    ParamsOf<VISIBILITY> sbase{};
+    sbase.candidates = (int)s->opt.candidates;
+    restir_fill_params(sbase, *s, *scene);
+    const RestirBsdfKernel canonical = restir_di_bsdf_canonical_kernel(scene->two_level, s->opt.temporal_reuse != 0, VISIBILITY, power);
+    const RestirKernel<VISIBILITY> spatial = scene->two_level ? spatial_kernel<true, VISIBILITY>(s->opt.spatial_samples) : spatial_kernel<false, VISIBILITY>(s->opt.spatial_samples);
+    if (int r = restir_begin_frame(s, st)) return r;
+    if (int r = restir_run_pass(s, scene, projection, viewports, count, st, cbase, canonical, 0, [&](RestirBsdfParams& P, size_t off) {
+            P.canonical = s->canonical + off; P.history = s->history + off;
+            P.out = (f4*)out_color_dev + off;
+            // both or neither: the kernel tests the first
+            const bool rec = s->rec_candidates_bsdf && s->rec_bsdf;
+            P.rec_candidates = rec ? s->rec_candidates_bsdf + off * per_pixel : nullptr;
+            P.rec_bsdf = rec ? s->rec_bsdf + off * per_pixel : nullptr;
+            P.rec_sampled = VISIBILITY != 0 && s->rec_sampled ? s->rec_sampled + off : nullptr;
+        })) return r;
+    if (int r = restir_run_pass(s, scene, projection, viewports, count, st, sbase, spatial, 1, [&](ParamsOf<VISIBILITY>& P, size_t off) {
+            P.canonical = s->canonical + off; P.history = s->history + off;
+            P.out = (f4*)out_color_dev + off;
+            P.rec_candidates = nullptr;      // the spatial pass reads no candidate record
             if constexpr (VISIBILITY != 0) P.rec_sampled = s->rec_sampled ? s->rec_sampled + off : nullptr;
         })) return r;
     return restir_end_frame(s, viewports, count);
@@ -396,6 +440,39 @@ int trhip_restir_di_set_light_selection(trhip_restir_di* s, int mode, float unif
     return 0;
 }
 
+int trhip_restir_di_set_bsdf_candidates(trhip_restir_di* s, uint32_t n) {
+    const std::string fn = std::string(API) + "_set_bsdf_candidates";
+    if (!s) return set_error(fn + ": null stage");
+    if (n > (uint32_t)RESTIR_MAX_BSDF_CANDIDATES) return set_error(fn + ": bsdf_candidates " + std::to_string(n) + " is outside 0..8");
+    if (s->opt.candidates + n > (uint32_t)RESTIR_MAX_CANDIDATES)
+        return set_error(fn + ": candidates " + std::to_string(s->opt.candidates) + " + bsdf_candidates " + std::to_string(n) + " is above 32");
+    // uc_weight must not mix two candidate distributions silently (as decisions 22 and 27)
+    if (s->frame > 0 && n != s->bsdf_candidates)
+        return set_error(fn + ": the stage holds history of " + std::to_string(s->bsdf_candidates) + " bsdf candidates: call " + API + "_reset first");
+    if (n != s->bsdf_candidates && s->opt.record) {      // the records of L + n candidates a pixel; a frame in flight writes the old ones
+        DEVCHK(s->hip_device);
+        HIPCHK(hipDeviceSynchronize());
+        (void)hipFree(s->rec_candidates_bsdf); (void)hipFree(s->rec_bsdf);
+        s->rec_candidates_bsdf = nullptr; s->rec_bsdf = nullptr;
+        s->bsdf_candidates = 0;      // what the stage is left with when the allocation fails
+        if (n > 0) {
+            const size_t records = s->pixels() * ((size_t)s->opt.candidates + n);
+            hipError_t e = hipMalloc((void**)&s->rec_candidates_bsdf, records * sizeof(RestirCandidateRecord));
+            if (e == hipSuccess) e = hipMalloc((void**)&s->rec_bsdf, records * sizeof(RestirBsdfRecord));
+            if (e == hipSuccess) e = hipMemset(s->rec_candidates_bsdf, 0, records * sizeof(RestirCandidateRecord));
+            if (e == hipSuccess) e = hipMemset(s->rec_bsdf, 0, records * sizeof(RestirBsdfRecord));
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) {
+                (void)hipFree(s->rec_candidates_bsdf); (void)hipFree(s->rec_bsdf);
+                s->rec_candidates_bsdf = nullptr; s->rec_bsdf = nullptr;
+                return set_error(fn + ": " + hipGetErrorString(e));
+            }
+        }
+    }
+    s->bsdf_candidates = n;
+    return 0;
+}
+
 int trhip_restir_di_refresh_light_selection(trhip_restir_di* s, uint32_t* rebuilt) {
     const std::string fn = std::string(API) + "_refresh_light_selection";
     if (rebuilt) *rebuilt = 0;
@@ -407,11 +484,21 @@ int trhip_restir_di_refresh_light_selection(trhip_restir_di* s, uint32_t* rebuil
 int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
     DeviceScene* scene = nullptr;
     if (int r = restir_begin_render(API, s, viewports, count, out_color_dev, scene)) return r;
-    if (s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER) {
+    const bool power = s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER;
+    if (power) {
         if (scene->point_light_count != s->table_points || scene->tri_light_count != s->table_tris)
             return set_error(std::string(API) + "_render: the scene has " + std::to_string(scene->point_light_count) + " point and " + std::to_string(scene->tri_light_count) +
                              " triangle lights, the light selection table was built for " + std::to_string(s->table_points) + " and " + std::to_string(s->table_tris) +
                              ": call " + API + "_refresh_light_selection first");
+    }
+    if (s->bsdf_candidates > 0) {
+        switch (s->visibility) {
+            case TRHIP_RESTIR_VISIBILITY_PER_TARGET: return restir_di_render_bsdf<0>(s, scene, projection, viewports, count, out_color_dev, stream);
+            case TRHIP_RESTIR_VISIBILITY_SHARED: return restir_di_render_bsdf<1>(s, scene, projection, viewports, count, out_color_dev, stream);
+            default: return restir_di_render_bsdf<2>(s, scene, projection, viewports, count, out_color_dev, stream);
+        }
+    }
+    if (power) {
         switch (s->visibility) {
             case TRHIP_RESTIR_VISIBILITY_PER_TARGET: return restir_di_render_power<0>(s, scene, projection, viewports, count, out_color_dev, stream);
             case TRHIP_RESTIR_VISIBILITY_SHARED: return restir_di_render_power<1>(s, scene, projection, viewports, count, out_color_dev, stream);
@@ -440,7 +527,10 @@ int trhip_restir_di_download(trhip_restir_di* s, int which, void* host, size_t b
     // the weights and the table of the power mode are no decision records: they are there with and without `record`
     if (s && (which == TRHIP_RESTIR_DI_LIGHT_WEIGHTS || which == TRHIP_RESTIR_DI_LIGHT_TABLE) && !(s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER && s->has_table))
         return set_error(std::string(API) + "_download: the stage has no light selection table (" + API + "_set_light_selection)");
-    return restir_download(API, s, which, host, bytes, which >= TRHIP_RESTIR_DI_CANDIDATES && which <= TRHIP_RESTIR_DI_SAMPLED, shared,
+    if (s && which == TRHIP_RESTIR_DI_BSDF_CANDIDATES && s->opt.record && s->bsdf_candidates == 0)
+        return set_error(std::string(API) + "_download: the stage has no bsdf candidates (" + API + "_set_bsdf_candidates)");
+    const bool decision = (which >= TRHIP_RESTIR_DI_CANDIDATES && which <= TRHIP_RESTIR_DI_SAMPLED) || which == TRHIP_RESTIR_DI_BSDF_CANDIDATES;
+    return restir_download(API, s, which, host, bytes, decision, shared,
         [&](size_t n, const void*& src, size_t& size) {
             switch (which) {
                 case TRHIP_RESTIR_DI_CANONICAL: src = s->canonical; size = n * sizeof(RestirReservoir); return true;
@@ -448,7 +538,10 @@ int trhip_restir_di_download(trhip_restir_di* s, int which, void* host, size_t b
                 case TRHIP_RESTIR_DI_SAMPLED: src = s->rec_sampled; size = n * sizeof(RestirSampledRecord); return true;
                 case TRHIP_RESTIR_DI_LIGHT_WEIGHTS: src = s->light_weights; size = ((size_t)s->table_points + s->table_tris) * sizeof(float); return true;
                 case TRHIP_RESTIR_DI_LIGHT_TABLE: src = s->light_table; size = ((size_t)s->table_points + s->table_tris) * sizeof(AliasEntry); return true;
-                case TRHIP_RESTIR_DI_CANDIDATES: src = s->rec_candidates; size = n * s->opt.candidates * sizeof(RestirCandidateRecord); return true;
+                case TRHIP_RESTIR_DI_CANDIDATES:      // [pixel][L + B]: with B > 0 the setter's buffer
+                    src = s->bsdf_candidates ? s->rec_candidates_bsdf : s->rec_candidates;
+                    size = n * ((size_t)s->opt.candidates + s->bsdf_candidates) * sizeof(RestirCandidateRecord); return true;
+                case TRHIP_RESTIR_DI_BSDF_CANDIDATES: src = s->rec_bsdf; size = n * ((size_t)s->opt.candidates + s->bsdf_candidates) * sizeof(RestirBsdfRecord); return true;
                 default: return false;
             }
         });

@@ -265,6 +265,7 @@ TR_DEV void ggx_brdf_inner(f3 out_dir, f3 view_dir, f3 h, float fresnel, float d
     bsdf.dielectric_reflection += fresnel * geometry * distribution * cos_l * (1.0f - mat.metallic);
     bsdf.metallic_reflection += geometry * distribution * cos_l * mat.metallic;
 }
+template <class M = LibMath>
 TR_DEV f3 ggx_vndf_sample(f3 view, float roughness, float u1, float u2) {  // ggx.glsl:215-236
     f3 v = normalize(F3(roughness * view.x, roughness * view.y, view.z));
     f3 t1 = v.z < 0.9999f ? normalize(cross(v, F3(0, 0, 1))) : F3(1, 0, 0);
@@ -273,8 +274,8 @@ TR_DEV f3 ggx_vndf_sample(f3 view, float roughness, float u1, float u2) {  // gg
     float a = 1.0f / inv_a;
     float r = sqrtf(u1);
     float phi = u2 < a ? u2 * inv_a * TR_PI : TR_PI + (u2 - a) / (1.0f - a) * TR_PI;
-    float p1 = r * tcos(phi);
-    float p2 = r * tsin(phi) * (u2 < a ? 1.0f : v.z);
+    float p1 = r * M::cos(phi);
+    float p2 = r * M::sin(phi) * (u2 < a ? 1.0f : v.z);
     float p3 = sqrtf(fmax2(0.0f, 1.0f - p1 * p1 - p2 * p2));
     f3 n = p1 * t1 + p2 * t2 + p3 * v;
     return normalize(F3(roughness * n.x, roughness * n.y, fmax2(0.0f, n.z)));
@@ -286,15 +287,17 @@ TR_DEV f3 refract3(f3 I, f3 N, float eta) {
     if (k < 0.0f) return F3(0.0f);
     return eta * I - (eta * d + sqrtf(k)) * N;
 }
-// ggx_bsdf_sample = ggx_bsdf_sample_core(eval_all_lobes = true) (ggx.glsl:240-388)
+// ggx_bsdf_sample = ggx_bsdf_sample_core(eval_all_lobes = true) (ggx.glsl:240-388).  M: the library math of the sampler and of what it calls
+// (ggx_vndf_sample's sin and cos, the Fresnel terms' pow, sample_cosine_hemisphere); ReSTIR DI's BSDF candidates take RoundedMath
+template <class M = LibMath>
 TR_DEV void ggx_bsdf_sample(f4 ur, f3 view_dir, const SampledMaterial& mat, f3& out_dir, Lobes& bsdf, float& pdf) {
     const bool zero_roughness = mat.roughness < 0.001f;
-    f3 h = zero_roughness ? F3(0, 0, 1) : ggx_vndf_sample(view_dir, mat.roughness, ur.x, ur.y);
+    f3 h = zero_roughness ? F3(0, 0, 1) : ggx_vndf_sample<M>(view_dir, mat.roughness, ur.x, ur.y);
     float cos_d = dot(view_dir, h);
-    float fresnel = ggx_fresnel(cos_d, mat);
+    float fresnel = ggx_fresnel<M>(cos_d, mat);
     float cos_v = view_dir.z;
     float max_albedo = fmax2(mat.albedo.x, fmax2(mat.albedo.y, mat.albedo.z));
-    float specular_cutoff = mixf(1.0f, fresnel_importance(view_dir.z, mat), (1 - mat.metallic) * max_albedo);
+    float specular_cutoff = mixf(1.0f, fresnel_importance<M>(view_dir.z, mat), (1 - mat.metallic) * max_albedo);
     float diffuse_cutoff = 1.0f - mat.transmittance;
     float specular_probability = specular_cutoff;
     float diffuse_probability = (1.0f - specular_cutoff) * diffuse_cutoff;
@@ -321,11 +324,11 @@ TR_DEV void ggx_bsdf_sample(f4 ur, f3 view_dir, const SampledMaterial& mat, f3& 
         u = clampf((u - specular_cutoff) / (1 - specular_cutoff), 0.0f, 0.99999f);
         if (u <= diffuse_cutoff) {
             u = clampf(u / diffuse_cutoff, 0.0f, 0.99999f);
-            out_dir = sample_cosine_hemisphere(F2(u, ur.w));
+            out_dir = sample_cosine_hemisphere<M>(F2(u, ur.w));
             h = normalize(view_dir + out_dir);
             float cos_h = h.z;
             cos_d = dot(view_dir, h);
-            fresnel = ggx_fresnel_schlick(cos_d, mat.f0);   // ggx_fresnel_refl
+            fresnel = ggx_fresnel_schlick<M>(cos_d, mat.f0);   // ggx_fresnel_refl
             float G1 = ggx_masking(cos_v, cos_d, mat.roughness);
             float D = (zero_roughness ? 0 : ggx_distribution(cos_h, mat.roughness));
             pdf = pdf_cosine_hemisphere(out_dir) * diffuse_probability;

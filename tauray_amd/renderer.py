@@ -1364,15 +1364,17 @@ def restir_di_options(**kw) -> dict:
     """trhip_restir_di_options at the command line's defaults (--restir=4,2,32,16,on), and `visibility` (--restir-visibility=per-target):
     "per-target", "shared" or "sampled", which the stage applies through trhip_restir_di_set_visibility, and `light_selection`
     (--restir-light-selection=uniform): "uniform" or "power" with `uniform_fraction` in (0, 1], applied through
-    trhip_restir_di_set_light_selection."""
+    trhip_restir_di_set_light_selection, and `bsdf_candidates` (--restir-bsdf-candidates=0): 0..8 candidates a pixel drawn from the
+    surface's BSDF behind the `candidates` light candidates, at most 32 together, applied through trhip_restir_di_set_bsdf_candidates."""
     o = dict(candidates=4, spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0,
-             record=False, visibility="per-target", light_selection="uniform", uniform_fraction=0.1)
+             record=False, visibility="per-target", light_selection="uniform", uniform_fraction=0.1, bsdf_candidates=0)
     unknown = set(kw) - set(o)
     if unknown:
         raise AttributeError(f"unknown ReSTIR DI option {sorted(unknown)}")
     o.update(kw)
     _restir_visibility_mode(o["visibility"])
     _restir_light_selection_mode(o["light_selection"], o["uniform_fraction"])
+    _restir_bsdf_candidates(o["bsdf_candidates"], o["candidates"])
     return o
 
 
@@ -1388,6 +1390,14 @@ def _restir_light_selection_mode(name, uniform_fraction) -> int:
     if not 0.0 < float(uniform_fraction) <= 1.0:      # a NaN fails both comparisons
         raise ValueError(f"ReSTIR DI uniform_fraction {uniform_fraction!r} is outside (0, 1]")
     return _lib.RESTIR_LIGHT_SELECTION[name]
+
+
+def _restir_bsdf_candidates(n, candidates) -> int:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= 8:
+        raise ValueError(f"ReSTIR DI bsdf_candidates {n!r} is outside 0..8")
+    if int(n) > 0 and int(candidates) + int(n) > 32:      # without BSDF candidates, `candidates` alone is create's to refuse
+        raise ValueError(f"ReSTIR DI candidates {candidates!r} + bsdf_candidates {n!r} is above 32")
+    return int(n)
 
 
 class _RestirStage(_PostStage):
@@ -1423,7 +1433,8 @@ class RestirDiStage(_RestirStage):
     """ReSTIR DI (trhip_restir_di_*, include/trhip.h; written after shader/restir_di.glsl and its two ray generation shaders): per frame
     the canonical kernel (first hit, RIS over light candidates, temporal merge) and the spatial kernel (neighbour merge, shading).
     `options`: restir_di_options(); with record, download() has "candidates", "temporal", "spatial", "final", "sampled"; with the power
-    light selection, "light_weights" (float [n_point + n_tri]) and "light_table" (the alias entries in the same order)."""
+    light selection, "light_weights" (float [n_point + n_tri]) and "light_table" (the alias entries in the same order); with record and
+    bsdf_candidates > 0, "candidates" has candidates + bsdf_candidates records a pixel and "bsdf_candidates" one record next to each."""
 
     PREFIX, TIMINGS = "restir_di", _lib.RestirDiTimingsC
     _RECORDS = {"surface": (_lib.RESTIR_DI_SURFACE, _lib.RESTIR_DI_SURFACE_DTYPE), "canonical": (_lib.RESTIR_DI_CANONICAL, _lib.RESTIR_DI_RESERVOIR_DTYPE),
@@ -1440,8 +1451,11 @@ class RestirDiStage(_RestirStage):
             raise TrhipError("RestirDiStage: candidates and spatial_samples are counts")
         visibility, o["visibility"] = o["visibility"], "per-target"
         selection, o["light_selection"] = o["light_selection"], "uniform"
+        bsdf_candidates, o["bsdf_candidates"] = o["bsdf_candidates"], 0
         self._create_stage(ctx, scene_stage, size, layers, projection, opt)
         try:
+            if bsdf_candidates != 0:
+                self.set_bsdf_candidates(bsdf_candidates)
             if visibility != "per-target":
                 self.set_visibility(visibility)
             if selection != "uniform":
@@ -1463,6 +1477,13 @@ class RestirDiStage(_RestirStage):
         check(self._fn("set_light_selection")(self.h, _restir_light_selection_mode(light_selection, uniform_fraction), float(uniform_fraction)))
         self.options["light_selection"], self.options["uniform_fraction"] = light_selection, float(uniform_fraction)
 
+    def set_bsdf_candidates(self, n: int):
+        """The candidates a pixel draws from its surface's BSDF behind the light candidates, 0..8 and at most 32 together
+        (trhip_restir_di_set_bsdf_candidates): a closest-hit ray each, weighted with the light candidates by the balance heuristic.
+        A change is refused while there is history."""
+        check(self._fn("set_bsdf_candidates")(self.h, _restir_bsdf_candidates(n, self.options["candidates"])))
+        self.options["bsdf_candidates"] = int(n)
+
     def refresh_light_selection(self) -> bool:
         """Rebuilds the power selection's table after the scene's lights or instances changed (trhip_restir_di_refresh_light_selection);
         allowed while there is history.  True when the table was rebuilt, False when the lights' weights were those it holds (or the
@@ -1478,6 +1499,11 @@ class RestirDiStage(_RestirStage):
             n = len(self.scene_stage.scene.point_lights) + int(self.scene_stage.accel["tri_light_count"])
             # one entry more than the table has: an empty table still has an address to copy to
             return self._download_prefix(code, n, np.dtype(dtype))
+        if name in ("candidates", "bsdf_candidates"):      # one record per candidate of either technique
+            code, dtype = (_lib.RESTIR_DI_CANDIDATES, _lib.RESTIR_DI_CANDIDATE_DTYPE) if name == "candidates" else (
+                _lib.RESTIR_DI_BSDF_CANDIDATES, _lib.RESTIR_DI_BSDF_CANDIDATE_DTYPE)
+            per_pixel = int(self.options["candidates"]) + int(self.options["bsdf_candidates"])
+            return self._download(code, (self.layers, self.size[1], self.size[0], per_pixel), np.dtype(dtype))
         return super().download(name)
 
     def _download_prefix(self, code, n, dtype) -> np.ndarray:
