@@ -1096,8 +1096,10 @@ public:
         // --restir-bsdf-candidates=N (trhip_restir_di_set_bsdf_candidates): candidates a pixel draws from its surface's BSDF behind the light
         // candidates, 0..8, at most 32 together
         uint32_t bsdf_candidates = 0;
-        // what trhip_restir_di_create, trhip_restir_di_set_visibility, trhip_restir_di_set_light_selection and
-        // trhip_restir_di_set_bsdf_candidates refuse, said without a device
+        // --restir-sphere-lights=point|area (trhip_restir_di_set_sphere_lights): a point light with a radius lit as a point or as a sphere
+        int sphere_lights = TRHIP_RESTIR_SPHERE_LIGHTS_POINT;
+        // what trhip_restir_di_create, trhip_restir_di_set_visibility, trhip_restir_di_set_light_selection,
+        // trhip_restir_di_set_bsdf_candidates and trhip_restir_di_set_sphere_lights refuse, said without a device
         void check() const
         {
             if(candidates < 1 || candidates > 32) throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " is outside 1..32");
@@ -1109,7 +1111,16 @@ public:
             if(bsdf_candidates > 8) throw std::runtime_error("restir-di: bsdf_candidates " + std::to_string(bsdf_candidates) + " is outside 0..8");
             if(candidates + bsdf_candidates > 32)
                 throw std::runtime_error("restir-di: candidates " + std::to_string(candidates) + " + bsdf_candidates " + std::to_string(bsdf_candidates) + " is above 32");
+            if(sphere_lights < TRHIP_RESTIR_SPHERE_LIGHTS_POINT || sphere_lights > TRHIP_RESTIR_SPHERE_LIGHTS_AREA)
+                throw std::runtime_error("restir-di: sphere_lights " + std::to_string(sphere_lights) + " is outside 0..1");
             check_shared("restir-di");
+        }
+        // --restir-sphere-lights=MODE
+        void parse_sphere_lights(const std::string& text)
+        {
+            if(text == "point") sphere_lights = TRHIP_RESTIR_SPHERE_LIGHTS_POINT;
+            else if(text == "area") sphere_lights = TRHIP_RESTIR_SPHERE_LIGHTS_AREA;
+            else throw std::runtime_error("--restir-sphere-lights: " + text + " is neither point nor area");
         }
         // --restir-light-selection=uniform|power[,fraction]
         void parse_light_selection(const std::string& text)
@@ -1164,7 +1175,8 @@ public:
         check(trhip_restir_di_create(dev.h, &o, size.x, size.y, layers, &h));
         if((opt.visibility != TRHIP_RESTIR_VISIBILITY_PER_TARGET && trhip_restir_di_set_visibility(h, opt.visibility) != 0) ||
            (opt.light_selection != TRHIP_RESTIR_LIGHT_SELECTION_UNIFORM && trhip_restir_di_set_light_selection(h, opt.light_selection, opt.uniform_fraction) != 0) ||
-           (opt.bsdf_candidates != 0 && trhip_restir_di_set_bsdf_candidates(h, opt.bsdf_candidates) != 0))
+           (opt.bsdf_candidates != 0 && trhip_restir_di_set_bsdf_candidates(h, opt.bsdf_candidates) != 0) ||
+           (opt.sphere_lights != TRHIP_RESTIR_SPHERE_LIGHTS_POINT && trhip_restir_di_set_sphere_lights(h, opt.sphere_lights) != 0))
         {
             trhip_restir_di_destroy(h);
             check(1);
@@ -1188,6 +1200,8 @@ public:
     }
     // a change is refused while there is history
     void set_bsdf_candidates(uint32_t n) { check(trhip_restir_di_set_bsdf_candidates(h, n)); opt.bsdf_candidates = n; }
+    // another mode than the history's is refused until reset()
+    void set_sphere_lights(int mode) { check(trhip_restir_di_set_sphere_lights(h, mode)); opt.sphere_lights = mode; }
     // after the scene's lights or instances changed: rebuilds the power mode's table unless the lights' weights are those it holds (then false)
     bool refresh_light_selection() { uint32_t rebuilt = 0; check(trhip_restir_di_refresh_light_selection(h, &rebuilt)); return rebuilt != 0; }
     trhip_restir_di_timings get_timings() { trhip_restir_di_timings t; check(trhip_restir_di_get_timings(h, &t)); return t; }

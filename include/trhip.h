@@ -1044,7 +1044,36 @@ int trhip_brdf_integration_generate(trhip_device* dev, uint32_t size, uint32_t s
  *      denom; a NaN weight or denom <= 0 gives 0.  confidence += 1 per candidate of either technique.  Everything behind the loops -
  *      uc_weight, the sampled mode's ray, the temporal merge - is unchanged.  With B = 0 the stage launches the kernels it launched.
  *  36. The pdfs enter only the candidate weight.  bsdf_candidates changes only while the stage holds no history (as decisions 22 and
- *      27).  ReSTIR GI's kernels are untouched.  Out of scope: sphere lights (the stage lights them as points), delta lobes. */
+ *      27).  ReSTIR GI's kernels are untouched.  Out of scope: sphere lights (the stage lights them as points), delta lobes.
+ *  37. Sphere lights (trhip_restir_di_set_sphere_lights).  point, the default, is decision 10 and the kernels that
+ *      were.  area: a point-light sample whose light has radius != 0 is a point on that sphere; a light of radius 0 is what it was in
+ *      both modes.  The sample keeps type 0 and its index; light_data is the octahedral encoding of the outward unit normal n of the
+ *      point (encode: p = n.xy / (|n.x| + |n.y| + |n.z|), for n.z < 0 p = (1 - |p.yx|) * sign(p.xy) with sign(0) = 1; decode:
+ *      n = (p.x, p.y, 1 - |p.x| - |p.y|), t = max(-n.z, 0), n.x += n.x >= 0 ? -t : t, likewise n.y, normalise).  No transcendental
+ *      function: the model repeats the bits.  A point fixed in the world is what a neighbour or the next frame can evaluate again; the
+ *      cone's random numbers are not kept.
+ *  38. The draw.  Behind either sampler of the light candidates (uniform or power; its u.x chose the index, u.y and u.z are free) a
+ *      type-0 sample with radius != 0 follows sample_point_light: d = pos - pl.pos, dist2 = dot(d, d), k = 1 - r^2 / dist2,
+ *      cutoff = k > 0 ? sqrt(k) : -1, dir = sample_cone((u.y, u.z), -normalize(d), cutoff), b = dot(d, dir),
+ *      len = -b - sqrt(max(b^2 - dist2 + r^2, 0)), x = pos + dir * len, n = normalize(x - pl.pos), data = encode(n),
+ *      solid_pdf = 1 / (2 pi (1 - cutoff)), 1e9 when n has a NaN or len <= min_ray_dist; light_pdf = (the index's pdf) * solid_pdf.
+ *      No draw is added or removed; both streams stay where they are.
+ *  39. The contribution of such a sample: n = decode(data), x = pl.pos + r * n, p = x - pos, dir = normalize(p), dist2 = dot(p, p),
+ *      normal = n, colour = pl.color * spot(normalize(pl.pos - pos)) / (r^2 pi) - the direct stage's radiance and its argument of the
+ *      spot cone -, 0 when dot(n, dir) >= 0: the point faces away, or the receiver is inside the sphere.  The candidate's own
+ *      contribution is evaluated from data like everyone else's (one code path; the limit environment samples have).  The flat-normal
+ *      test, the lobes, modulate_bsdf and the NaN test are unchanged.
+ *      Limit: a receiver inside a sphere gets 0 from it, while the direct stage and the path tracer light it (their shadow ray there
+ *      has a negative length and finds nothing): on such pixels area mode does not converge to the direct stage's image.
+ *  40. Jacobian, visibility and the merges are unchanged code: the normal is no longer 0, so the reconnection Jacobian is the
+ *      solid-angle ratio a triangle sample gets; the shadow ray ends min_ray_dist short of x; shadow rays go on not seeing lights.
+ *  41. Power selection: the weights keep ignoring the radius.
+ *  42. BSDF candidates: a BSDF ray does not return a sphere light and type-0 samples keep p_b = 0.  Unbiased - the light technique
+ *      alone covers the whole visible cap -, a limit on glossy surfaces under large lamps.
+ *  43. The mode is a compile-time parameter of the sample kind (RestirDiKindT<SPHERE>, restir_di.h) and the area mode's kernels are a
+ *      translation unit of their own (restir_di_sphere.hip): the point instances are the code they were.
+ *  44. A reservoir does not mix samples of two meanings of light_data: the mode changes only while the stage holds no history.  Limits:
+ *      ReSTIR GI's own light sample at a secondary hit stays a point; the camera ray does not see sphere lights. */
 typedef struct trhip_restir_di trhip_restir_di;
 typedef struct trhip_restir_di_options {
     uint32_t candidates;              /* 1..32 light samples per pixel (RIS_SAMPLE_COUNT) */
@@ -1127,6 +1156,12 @@ int trhip_restir_di_set_light_selection(trhip_restir_di* stage, int mode, float 
  * is accepted again after trhip_restir_di_reset.  With record it allocates the records of candidates + n candidates a pixel and waits
  * for the device. */
 int trhip_restir_di_set_bsdf_candidates(trhip_restir_di* stage, uint32_t n);
+/* How a point light with a radius is lit (decisions 37 to 44); a stage is created point, and in that mode it launches the kernels it
+ * always launched.  Refuses a null stage, a mode outside 0..1 and, while the stage holds history, any mode but the history's; it is
+ * accepted again after trhip_restir_di_reset. */
+#define TRHIP_RESTIR_SPHERE_LIGHTS_POINT 0
+#define TRHIP_RESTIR_SPHERE_LIGHTS_AREA 1
+int trhip_restir_di_set_sphere_lights(trhip_restir_di* stage, int mode);
 /* Rebuilds the table after the scene's lights or instances changed; allowed while the stage holds history (decision 27).  The build is
  * skipped when the lights' weights are byte-equal to those the table was built from: *rebuilt (may be null) is 1 or 0.  Waits for the
  * device.  A uniform stage: nothing, 0.  trhip_restir_di_render refuses, in power mode, a scene whose point or triangle light count

@@ -267,6 +267,7 @@ class RestirDiTimingsC(C.Structure):
 RESTIR_VISIBILITY = {"per-target": 0, "shared": 1, "sampled": 2}
 # trhip_restir_di_set_light_selection: the modes by their command-line names; the table's 16-byte entries (download code 9)
 RESTIR_LIGHT_SELECTION = {"uniform": 0, "power": 1}
+RESTIR_SPHERE_LIGHTS = {"point": 0, "area": 1}      # TRHIP_RESTIR_SPHERE_LIGHTS_*
 RESTIR_DI_LIGHT_TABLE_DTYPE = [("alias_id", "<u4"), ("probability", "<u4"), ("pdf", "<f4"), ("alias_pdf", "<f4")]
 # trhip_restir_di_bsdf_candidate (download code 10): one per candidate of a stage with BSDF candidates
 RESTIR_DI_BSDF_CANDIDATE_DTYPE = [("technique", "<u4"), ("dir", "<f4", 3), ("p_b", "<f4"), ("instance_id", "<i4"), ("primitive_id", "<i4"), ("u", "<f4"),
@@ -469,6 +470,7 @@ SYMBOLS = {
     "trhip_restir_di_set_light_selection": (_i, [_vp, _i, C.c_float]),
     "trhip_restir_di_refresh_light_selection": (_i, [_vp, C.POINTER(_u32)]),
     "trhip_restir_di_set_bsdf_candidates": (_i, [_vp, _u32]),
+    "trhip_restir_di_set_sphere_lights": (_i, [_vp, _i]),
     "trhip_restir_di_render": (_i, [_vp, _i, C.POINTER(_u32), _u32, _vp, _vp]),
     "trhip_restir_di_get_timings": (_i, [_vp, C.POINTER(RestirDiTimingsC)]),
     "trhip_restir_di_download": (_i, [_vp, _i, _vp, C.c_size_t]),

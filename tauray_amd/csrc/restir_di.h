@@ -109,6 +109,33 @@
 //                            After the loops everything is as above.
 //                The pdfs enter only the candidate weight; B changes only without history.  Rays a pixel: B closest-hit rays more in
 //                every visibility mode.  Records: the candidate record's pdf is p_l; RestirBsdfRecord (restir_di_bsdf.h) next to it.
+//   sphere lights (trhip_restir_di_set_sphere_lights; decisions 37 to 44 of trhip.h; restir_di_sphere.h, restir_di_sphere.hip; point, the
+//                default, is everything above word for word and the kernels that were; area: a type-0 sample whose light has
+//                radius != 0 is a point on that sphere; a light of radius 0 is what it was, in both modes):
+//                1 sample    type 0 and the index stay; light_data = the octahedral encoding of the outward unit normal n of the point.
+//                            encode: s = |n.x| + |n.y| + |n.z|; p = (n.x / s, n.y / s); n.z < 0: p = ((1.0f - |p.y|) * sign(p.x),
+//                            (1.0f - |p.x|) * sign(p.y)) with sign(v) = v >= 0 ? 1 : -1.  decode: n = (p.x, p.y, (1.0f - |p.x|) - |p.y|);
+//                            t = max(-n.z, 0); n.x += n.x >= 0 ? -t : t, likewise n.y; normalize(n).  No transcendental function.
+//                            The point is fixed in the world: a neighbour or the next frame evaluates the same sample.
+//                2 draw      behind restir_sample_canonical or restir_sample_canonical_power, for a type-0 sample with radius != 0
+//                            (restir_sphere_draw; u.x chose the index, u.y and u.z are free): d = pos - pl.pos; dist2 = dot(d, d);
+//                            k = 1.0f - r * r / dist2; cutoff = k > 0 ? sqrtf(k) : -1; dir = sample_cone((u.y, u.z), -normalize(d), cutoff);
+//                            b = dot(d, dir); len = -b - sqrtf(max(b * b - dist2 + r * r, 0)); x = pos + dir * len;
+//                            n = normalize(x - pl.pos); data = encode(n); solid_pdf = 1 / (2.0f * pi * (1.0f - cutoff));
+//                            solid_pdf = 1e9f when n has a NaN or len <= min_ray_dist; light_pdf = (the sampler's light_pdf) * solid_pdf.
+//                            No draw is added or removed.
+//                3 contribution (type 0, radius != 0): n = decode(data); x = pl.pos + r * n; p = x - pos; dir = normalize(p);
+//                            dist2 = dot(p, p); normal = n;
+//                            colour = (pl.color * get_spotlight_intensity(pl, normalize(pl.pos - pos))) / (r * r * pi), 0 when
+//                            dot(n, dir) >= 0 (the point faces away, or the receiver is inside the sphere; written !(dot < 0), so that
+//                            the NaN of a point that is the receiver itself gives 0 too).  The candidate's own
+//                            contribution is evaluated from data like every other.  Everything behind the colour is unchanged.
+//                4 jacobian, visibility, merges: unchanged code; normal != 0 gives the solid-angle ratio, the shadow ray ends
+//                            min_ray_dist short of x, shadow rays do not see lights.
+//                5 power selection: the weights ignore the radius.  6 bsdf candidates: a BSDF ray does not return a sphere light,
+//                            type-0 samples keep p_b = 0; unbiased, the light technique covers the whole visible cap.
+//                Limits: ReSTIR GI's own light sample at a secondary hit stays a point; the camera ray does not see sphere lights.
+//                A reservoir does not mix two meanings of light_data: the mode changes only while the stage holds no history.
 //   reprojection m = get_camera_projection(previous camera, surface_prev_pos).xy;  m.y = 1.0f - m.y;  m = m * size - 0.5f;  im = int(m)
 //                (truncation);  off = m - float(im);  pixel = im + (off.x < u.x ? 0 : 1, off.y < u.y ? 0 : 1)   (restir_di.glsl:138-153)
 //   reuse        there is history, the pixel is on screen, and not (dot(prev.mapped_normal, mapped_normal) < 0.95f or
@@ -216,7 +243,24 @@ TR_DEV RestirLightRecord restir_fetch_light(const SceneView& sv, const RestirSam
     return L;
 }
 
-// light_contribution (restir_di.glsl:155-249), the BSDF as the direct stage's light sample gets it (k_direct, path_tracer.hip)
+// `sphere lights` 1: the octahedral map of a unit vector and back
+TR_DEV f2 restir_oct_encode(f3 n) {
+    const float s = fabsf(n.x) + fabsf(n.y) + fabsf(n.z);
+    f2 p = F2(n.x / s, n.y / s);
+    if (n.z < 0.0f) p = F2((1.0f - fabsf(p.y)) * (p.x >= 0.0f ? 1.0f : -1.0f), (1.0f - fabsf(p.x)) * (p.y >= 0.0f ? 1.0f : -1.0f));
+    return p;
+}
+TR_DEV f3 restir_oct_decode(f2 p) {
+    f3 n = F3(p.x, p.y, (1.0f - fabsf(p.x)) - fabsf(p.y));
+    const float t = fmax2(-n.z, 0.0f);
+    n.x += n.x >= 0.0f ? -t : t;
+    n.y += n.y >= 0.0f ? -t : t;
+    return normalize(n);
+}
+
+// light_contribution (restir_di.glsl:155-249), the BSDF as the direct stage's light sample gets it (k_direct, path_tracer.hip).
+// SPHERE: `sphere lights` 3; false, the default, is the code as it was.
+template <bool SPHERE = false>
 TR_DEV f3 restir_contribution(const SceneView& sv, const RestirSample& s, const RestirLightRecord& L, const RestirDomain& dom, f3& dir, float& dist2, f3& normal) {
 #define TR_F(x) __uint_as_float(x)
     dir = F3(0.0f); dist2 = 0.0f; normal = F3(0.0f);
@@ -227,9 +271,19 @@ TR_DEV f3 restir_contribution(const SceneView& sv, const RestirSample& s, const 
         pl.color = F3(TR_F(L.r0.x), TR_F(L.r0.y), TR_F(L.r0.z)); pl.dir = F3(TR_F(L.r0.w), TR_F(L.r1.x), TR_F(L.r1.y)); pl.pos = F3(TR_F(L.r1.z), TR_F(L.r1.w), TR_F(L.r2.x));
         pl.radius = TR_F(L.r2.y); pl.dir_cutoff = TR_F(L.r2.z); pl.dir_falloff = TR_F(L.r2.w);
         const f3 to_light = pl.pos - dom.pos;
-        dir = normalize(to_light);
-        dist2 = dot(to_light, to_light);
-        light_color = (pl.color * get_spotlight_intensity<RoundedMath>(pl, dir)) / fmax2(dist2, 1e-7f);
+        if (SPHERE && pl.radius != 0.0f) {
+            const f3 n = restir_oct_decode(s.data);
+            const f3 p = (pl.pos + pl.radius * n) - dom.pos;
+            dir = normalize(p);
+            dist2 = dot(p, p);
+            normal = n;
+            light_color = (pl.color * get_spotlight_intensity<RoundedMath>(pl, normalize(to_light))) / (pl.radius * pl.radius * TR_PI);
+            if (!(dot(n, dir) < 0.0f)) light_color = F3(0.0f);      // >= 0, or a NaN: the point is the receiver itself
+        } else {
+            dir = normalize(to_light);
+            dist2 = dot(to_light, to_light);
+            light_color = (pl.color * get_spotlight_intensity<RoundedMath>(pl, dir)) / fmax2(dist2, 1e-7f);
+        }
     } else if (s.type == 1u) {
         const f3 P0 = F3(TR_F(L.r0.x), TR_F(L.r0.y), TR_F(L.r0.z)), P1 = F3(TR_F(L.r0.w), TR_F(L.r1.x), TR_F(L.r1.y)), P2 = F3(TR_F(L.r1.z), TR_F(L.r1.w), TR_F(L.r2.x));
         const f3 A = P0 - dom.pos, B = P1 - dom.pos, C = P2 - dom.pos;
@@ -271,8 +325,10 @@ TR_DEV f3 restir_contribution(const SceneView& sv, const RestirSample& s, const 
     return value;
 }
 
-// What restir_resample.h asks of a sample: a light sample (type, index, data)
-struct RestirDiKind {
+// What restir_resample.h asks of a sample: a light sample (type, index, data).  SPHERE: `sphere lights`, the area mode's meaning of a
+// type-0 sample's data; RestirDiKind, the point mode, is what every kernel outside restir_di_sphere.hip is written over.
+template <bool SPHERE>
+struct RestirDiKindT {
     using Sample = RestirSample;
     using State = RestirState<Sample>;
     using Reservoir = RestirReservoir;
@@ -299,7 +355,7 @@ struct RestirDiKind {
     // the light's record is fetched per evaluation, not held across the spatial merge's loop
     static TR_DEV f3 contribution(const SceneView& sv, const Sample& s, const RestirDomain& dom, Eval& e) {
         const RestirLightRecord L = restir_fetch_light(sv, s);
-        return restir_contribution(sv, s, L, dom, e.dir, e.dist2, e.normal);
+        return restir_contribution<SPHERE>(sv, s, L, dom, e.dir, e.dist2, e.normal);
     }
     // the reconnection point is where the shadow ray ends; a directional or environment sample has none
     static TR_DEV float jacobian(const Sample& s, const Eval& e, f3 from, f3 at) {
@@ -307,6 +363,7 @@ struct RestirDiKind {
         return s.type > 1u ? 1.0f : restir_jacobian(from, at, x, e.normal);
     }
 };
+using RestirDiKind = RestirDiKindT<false>;
 
 // sample_canonical (restir_di.glsl:251-354): select, fetch, compute, as sample_explicit_light.  The record stays in L for the contribution.
 // Params: the kernel parameters of the stage that draws (prob_point, prob_tri, prob_dir, prob_env: nee_probabilities; min_ray_dist) -

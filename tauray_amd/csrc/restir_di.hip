@@ -13,6 +13,8 @@
 // and its weights kernel in restir_di_power.hip; its host side - the table, the setter, the refresh, the power mode's frame - is here.
 // The BSDF-sampled candidates (trhip_restir_di_set_bsdf_candidates; `bsdf candidates` of restir_di.h) have their canonical kernel in
 // restir_di_bsdf.hip; the setter, their two record buffers and their frame are here.
+// Sphere lights as area lights (trhip_restir_di_set_sphere_lights; `sphere lights` of restir_di.h) have both their kernels in
+// restir_di_sphere.hip; the setter and the area mode's frame are here.
 // Constants, layouts, the order of operations and the order of random draws: restir_di.h.  The temporal and the spatial merge and the
 // host skeleton are restir_resample.h's, shared with ReSTIR GI.  Both kernels are IEEE fp32, evaluated without
 // contraction in a fixed order, no atomics: two runs of the same inputs give the same bits.  The front half is first_hit.h's, the one
@@ -21,7 +23,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "restir_di_bsdf.h"
+#include "restir_di_sphere.h"
 #include "../../include/tauray_alias.hh"
 
 namespace tr {
@@ -243,6 +245,7 @@ struct trhip_restir_di : RestirStageHost<3> {
     uint32_t bsdf_candidates = 0;
     RestirCandidateRecord* rec_candidates_bsdf = nullptr;
     RestirBsdfRecord* rec_bsdf = nullptr;
+    int sphere_lights = TRHIP_RESTIR_SPHERE_LIGHTS_POINT;      // trhip_restir_di_set_sphere_lights (restir_di.h `sphere lights`)
     ~trhip_restir_di() { (void)hipFree(light_weights); (void)hipFree(light_table); (void)hipFree(rec_candidates_bsdf); (void)hipFree(rec_bsdf); }
 };
 static_assert(sizeof(alias_entry) == sizeof(AliasEntry), "the host builder's entry is the kernels'");
@@ -344,6 +347,39 @@ static int restir_di_render_bsdf(trhip_restir_di* s, DeviceScene* scene, int pro
             P.rec_candidates = nullptr;      // the spatial pass reads no candidate record
             if constexpr (VISIBILITY != 0) P.rec_sampled = s->rec_sampled ? s->rec_sampled + off : nullptr;
         })) return r;
+    return restir_end_frame(s, viewports, count);
+}
+
+// A frame of the area mode (`sphere lights`): both passes are restir_di_sphere.hip's kernels over one parameter block; the canonical
+// instance is chosen by the selection and by whether there are BSDF candidates, whose record buffers it then writes
+static int restir_di_render_sphere(trhip_restir_di* s, DeviceScene* scene, int projection, const uint32_t* viewports, uint32_t count, void* out_color_dev, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const bool power = s->selection == TRHIP_RESTIR_LIGHT_SELECTION_POWER, bsdf = s->bsdf_candidates > 0;
+    const bool sampled = s->visibility != TRHIP_RESTIR_VISIBILITY_PER_TARGET;
+    const size_t per_pixel = (size_t)s->opt.candidates + s->bsdf_candidates;
+    RestirBsdfParams base{};
+    base.candidates = (int)s->opt.candidates;
+    base.bsdf_candidates = (int)s->bsdf_candidates;
+    restir_fill_params(base, *s, *scene);
+    base.light_table = power ? s->light_table : nullptr;
+    const RestirSphereKernel canonical = restir_di_sphere_canonical_kernel(scene->two_level, s->opt.temporal_reuse != 0, s->visibility, power, bsdf);
+    const RestirSphereKernel spatial = restir_di_sphere_spatial_kernel(scene->two_level, s->opt.spatial_samples, s->visibility);
+    const auto fill = [&](RestirBsdfParams& P, size_t off) {
+        P.canonical = s->canonical + off; P.history = s->history + off;
+        P.out = (f4*)out_color_dev + off;
+        if (bsdf) {      // both or neither: the kernel tests the first
+            const bool rec = s->rec_candidates_bsdf && s->rec_bsdf;
+            P.rec_candidates = rec ? s->rec_candidates_bsdf + off * per_pixel : nullptr;
+            P.rec_bsdf = rec ? s->rec_bsdf + off * per_pixel : nullptr;
+        } else {
+            P.rec_candidates = s->rec_candidates ? s->rec_candidates + off * s->opt.candidates : nullptr;
+            P.rec_bsdf = nullptr;
+        }
+        P.rec_sampled = sampled && s->rec_sampled ? s->rec_sampled + off : nullptr;
+    };
+    if (int r = restir_begin_frame(s, st)) return r;
+    if (int r = restir_run_pass(s, scene, projection, viewports, count, st, base, canonical, 0, fill)) return r;
+    if (int r = restir_run_pass(s, scene, projection, viewports, count, st, base, spatial, 1, fill)) return r;
     return restir_end_frame(s, viewports, count);
 }
 
@@ -473,6 +509,18 @@ int trhip_restir_di_set_bsdf_candidates(trhip_restir_di* s, uint32_t n) {
     return 0;
 }
 
+int trhip_restir_di_set_sphere_lights(trhip_restir_di* s, int mode) {
+    static const char* const names[2] = {"point", "area"};
+    const std::string fn = std::string(API) + "_set_sphere_lights";
+    if (!s) return set_error(fn + ": null stage");
+    if (mode < TRHIP_RESTIR_SPHERE_LIGHTS_POINT || mode > TRHIP_RESTIR_SPHERE_LIGHTS_AREA) return set_error(fn + ": mode " + std::to_string(mode) + " is outside 0..1");
+    // a reservoir must not mix the samples of two meanings of light_data silently
+    if (s->frame > 0 && mode != s->sphere_lights)
+        return set_error(fn + ": the stage holds history of the " + names[s->sphere_lights] + " mode: call " + API + "_reset first");
+    s->sphere_lights = mode;
+    return 0;
+}
+
 int trhip_restir_di_refresh_light_selection(trhip_restir_di* s, uint32_t* rebuilt) {
     const std::string fn = std::string(API) + "_refresh_light_selection";
     if (rebuilt) *rebuilt = 0;
@@ -491,6 +539,7 @@ int trhip_restir_di_render(trhip_restir_di* s, int projection, const uint32_t* v
                              " triangle lights, the light selection table was built for " + std::to_string(s->table_points) + " and " + std::to_string(s->table_tris) +
                              ": call " + API + "_refresh_light_selection first");
     }
+    if (s->sphere_lights == TRHIP_RESTIR_SPHERE_LIGHTS_AREA) return restir_di_render_sphere(s, scene, projection, viewports, count, out_color_dev, stream);
     if (s->bsdf_candidates > 0) {
         switch (s->visibility) {
             case TRHIP_RESTIR_VISIBILITY_PER_TARGET: return restir_di_render_bsdf<0>(s, scene, projection, viewports, count, out_color_dev, stream);

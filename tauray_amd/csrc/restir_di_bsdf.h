@@ -44,6 +44,32 @@ struct RestirBsdfParams {
 using RestirBsdfKernel = void (*)(SceneView, LaunchCtx, int, ViewportList, RestirBsdfParams, uint*);
 RestirBsdfKernel restir_di_bsdf_canonical_kernel(bool two_level, bool temporal, int visibility, bool power);      // restir_di_bsdf.hip
 
+// What the canonical kernels with BSDF candidates share (restir_di_bsdf.hip, and restir_di_sphere.hip's BSDF instances)
+// `bsdf candidates` 3: p_b of a world direction at a surface
+TR_DEV float restir_bsdf_pdf(const RestirDomain& dom, const m3& tbn, f3 shading_view, f3 dir) {
+    Lobes lobes = {0, 0, 0, 0};
+    return ggx_bsdf_pdf<RoundedMath>(mulT(dir, tbn), shading_view, dom.mat, lobes);
+}
+
+// `bsdf candidates` 9
+TR_DEV float restir_balance_weight(float mis_weight, float target, float denom) {
+    float weight = (mis_weight * target) / denom;
+    if (isnan(weight) || !(denom > 0.0f)) weight = 0.0f;
+    return weight;
+}
+
+TR_DEV void restir_write_candidate(const RestirBsdfParams& P, size_t slot, const RestirSample& s, float p_l, f3 contrib, float visibility, float weight, float u, bool selected,
+                                   uint technique, f3 dir, float p_b, const HitRecord& hit, bool traced, float denom) {
+    RestirCandidateRecord* rec = P.rec_candidates + slot;
+    restir_set_word(rec, 0, u4{s.type << 30 | s.index, TR_U(s.data.x), TR_U(s.data.y), TR_U(p_l)});
+    restir_set_word(rec, 1, u4{TR_U(contrib.x), TR_U(contrib.y), TR_U(contrib.z), TR_U(visibility)});
+    restir_set_word(rec, 2, u4{TR_U(weight), TR_U(u), selected ? 1u : 0u, 0u});
+    RestirBsdfRecord* brec = P.rec_bsdf + slot;
+    restir_set_word(brec, 0, u4{technique, TR_U(dir.x), TR_U(dir.y), TR_U(dir.z)});
+    restir_set_word(brec, 1, u4{TR_U(p_b), (uint)hit.instance_id, (uint)hit.primitive_id, TR_U(hit.u)});
+    restir_set_word(brec, 2, u4{TR_U(hit.v), TR_U(hit.t), TR_U(denom), traced ? 1u : 0u});
+}
+
 // `bsdf candidates` 5: the lat-long uv of a direction, the inverse of uv_to_latlong_direction, with atan2 alone
 template <class M>
 TR_DEV f2 restir_latlong_uv(f3 dir) {

@@ -14,31 +14,6 @@ namespace {
 constexpr int KB = TR_BLOCK;
 using Kind = RestirDiKind;
 
-// `bsdf candidates` 3: p_b of a world direction at a surface
-TR_DEV float restir_bsdf_pdf(const RestirDomain& dom, const m3& tbn, f3 shading_view, f3 dir) {
-    Lobes lobes = {0, 0, 0, 0};
-    return ggx_bsdf_pdf<RoundedMath>(mulT(dir, tbn), shading_view, dom.mat, lobes);
-}
-
-// `bsdf candidates` 9
-TR_DEV float restir_balance_weight(float mis_weight, float target, float denom) {
-    float weight = (mis_weight * target) / denom;
-    if (isnan(weight) || !(denom > 0.0f)) weight = 0.0f;
-    return weight;
-}
-
-TR_DEV void restir_write_candidate(const RestirBsdfParams& P, size_t slot, const RestirSample& s, float p_l, f3 contrib, float visibility, float weight, float u, bool selected,
-                                   uint technique, f3 dir, float p_b, const HitRecord& hit, bool traced, float denom) {
-    RestirCandidateRecord* rec = P.rec_candidates + slot;
-    restir_set_word(rec, 0, u4{s.type << 30 | s.index, TR_U(s.data.x), TR_U(s.data.y), TR_U(p_l)});
-    restir_set_word(rec, 1, u4{TR_U(contrib.x), TR_U(contrib.y), TR_U(contrib.z), TR_U(visibility)});
-    restir_set_word(rec, 2, u4{TR_U(weight), TR_U(u), selected ? 1u : 0u, 0u});
-    RestirBsdfRecord* brec = P.rec_bsdf + slot;
-    restir_set_word(brec, 0, u4{technique, TR_U(dir.x), TR_U(dir.y), TR_U(dir.z)});
-    restir_set_word(brec, 1, u4{TR_U(p_b), (uint)hit.instance_id, (uint)hit.primitive_id, TR_U(hit.u)});
-    restir_set_word(brec, 2, u4{TR_U(hit.v), TR_U(hit.t), TR_U(denom), traced ? 1u : 0u});
-}
-
 // k_restir_di_canonical of restir_di.hip, line for line, but for the weights of the light candidates' loop, the second loop behind it
 // and the parameter block
 template <bool TWO_LEVEL, bool TEMPORAL, int VISIBILITY, bool POWER>

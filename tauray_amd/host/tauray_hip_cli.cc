@@ -13,6 +13,7 @@
 //              [--restir-visibility=per-target|shared|sampled]   (with --renderer=restir-di and restir-gi)
 //              [--restir-light-selection=uniform|power[,fraction]]   (with --renderer=restir-di and restir-gi)
 //              [--restir-bsdf-candidates=N]   (with --renderer=restir-di and restir-gi)
+//              [--restir-sphere-lights=point|area]   (with --renderer=restir-di and restir-gi)
 //              [--renderer=restir-gi [--restir-gi=spatial_samples,search_radius,max_confidence,temporal_reuse] [--restir-gi-bounces=N] [--restir=...]]
 //              [--renderer=path-tracer|direct|sh-probes|dshgi [--samples-per-probe=512] [--sh-order=2] [--dshgi-temporal-ratio=0.01]
 //               [--use-probe-visibility] [--brdf-integration=FILE.exr]] [--denoiser=none|bmfr] [--spatial-reprojection=i,j,...] [--temporal-reprojection=r]
@@ -79,6 +80,8 @@ static const char* const usage_text =
     "  --restir-bsdf-candidates=N   (0) candidates a pixel of ReSTIR DI draws from its surface's BSDF behind the light candidates, 0..8 and at\n"
     "                         most 32 together, with --renderer=restir-di and restir-gi: each traces one closest-hit ray and takes the emissive\n"
     "                         triangle or the environment it finds; all candidates are weighted by the balance heuristic over the two techniques\n"
+    "  --restir-sphere-lights=point|area   (point) how ReSTIR DI lights a point light that has a radius, with --renderer=restir-di and\n"
+    "                         restir-gi: point: as a point, hard shadows; area: by samples on the sphere, soft shadows as --renderer=direct draws them\n"
     "  --restir-gi-bounces=N  the vertices of a ReSTIR GI sample's path behind the pixel, 1..8 (1): above 1 the radiance of a sample is that of a\n"
     "                         path continued from the ray's hit by cosine-hemisphere bounces with one light sample at each vertex, no\n"
     "                         Russian roulette (--max-ray-depth is not read by this renderer)\n"
@@ -128,6 +131,7 @@ int main(int argc, char** argv)
         bool restir_given = false, restir_visibility_given = false;         // --restir-visibility
         bool restir_light_selection_given = false;                          // --restir-light-selection
         bool restir_bsdf_candidates_given = false;                          // --restir-bsdf-candidates
+        bool restir_sphere_lights_given = false;                            // --restir-sphere-lights
         restir_gi_stage::options restir_gi;                                 // --restir-gi
         bool restir_gi_given = false, restir_gi_bounces_given = false;       // --restir-gi-bounces
         std::vector<int> devices;
@@ -264,6 +268,7 @@ int main(int argc, char** argv)
             else if(starts(a, "--restir-visibility=")) { restir.parse_visibility(val("--restir-visibility=")); restir_visibility_given = true; }
             else if(starts(a, "--restir-light-selection=")) { restir.parse_light_selection(val("--restir-light-selection=")); restir_light_selection_given = true; }
             else if(starts(a, "--restir-bsdf-candidates=")) { restir.parse_bsdf_candidates(val("--restir-bsdf-candidates=")); restir_bsdf_candidates_given = true; }
+            else if(starts(a, "--restir-sphere-lights=")) { restir.parse_sphere_lights(val("--restir-sphere-lights=")); restir_sphere_lights_given = true; }
             else if(starts(a, "--restir-gi=")) { restir_gi.parse(val("--restir-gi=")); restir_gi_given = true; }
             else if(starts(a, "--restir-gi-bounces=")) { restir_gi.parse_bounces(val("--restir-gi-bounces=")); restir_gi_bounces_given = true; }
             else if(a == "--use-probe-visibility") use_probe_visibility = true;
@@ -386,6 +391,8 @@ int main(int argc, char** argv)
             throw std::runtime_error("--restir-light-selection sets the light selection of --renderer=restir-di");
         if(restir_bsdf_candidates_given && renderer != "restir-di" && renderer != "restir-gi")
             throw std::runtime_error("--restir-bsdf-candidates sets the BSDF candidates of --renderer=restir-di");
+        if(restir_sphere_lights_given && renderer != "restir-di" && renderer != "restir-gi")
+            throw std::runtime_error("--restir-sphere-lights sets how --renderer=restir-di lights a point light that has a radius");
         if(restir_bsdf_candidates_given) restir.check();      // the two counts together, said before a scene is read
         if(restir_gi_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi sets the options of --renderer=restir-gi");
         if(restir_gi_bounces_given && renderer != "restir-gi") throw std::runtime_error("--restir-gi-bounces sets the path length of --renderer=restir-gi");

@@ -1365,9 +1365,11 @@ def restir_di_options(**kw) -> dict:
     "per-target", "shared" or "sampled", which the stage applies through trhip_restir_di_set_visibility, and `light_selection`
     (--restir-light-selection=uniform): "uniform" or "power" with `uniform_fraction` in (0, 1], applied through
     trhip_restir_di_set_light_selection, and `bsdf_candidates` (--restir-bsdf-candidates=0): 0..8 candidates a pixel drawn from the
-    surface's BSDF behind the `candidates` light candidates, at most 32 together, applied through trhip_restir_di_set_bsdf_candidates."""
+    surface's BSDF behind the `candidates` light candidates, at most 32 together, applied through trhip_restir_di_set_bsdf_candidates,
+    and `sphere_lights` (--restir-sphere-lights=point): "point" or "area" - a point light with a radius lit as a point or as the sphere it
+    is -, applied through trhip_restir_di_set_sphere_lights."""
     o = dict(candidates=4, spatial_samples=2, search_radius=32.0, max_confidence=16.0, temporal_reuse=True, min_ray_dist=1e-4, rng_seed=0,
-             record=False, visibility="per-target", light_selection="uniform", uniform_fraction=0.1, bsdf_candidates=0)
+             record=False, visibility="per-target", light_selection="uniform", uniform_fraction=0.1, bsdf_candidates=0, sphere_lights="point")
     unknown = set(kw) - set(o)
     if unknown:
         raise AttributeError(f"unknown ReSTIR DI option {sorted(unknown)}")
@@ -1375,6 +1377,7 @@ def restir_di_options(**kw) -> dict:
     _restir_visibility_mode(o["visibility"])
     _restir_light_selection_mode(o["light_selection"], o["uniform_fraction"])
     _restir_bsdf_candidates(o["bsdf_candidates"], o["candidates"])
+    _restir_sphere_lights_mode(o["sphere_lights"])
     return o
 
 
@@ -1390,6 +1393,12 @@ def _restir_light_selection_mode(name, uniform_fraction) -> int:
     if not 0.0 < float(uniform_fraction) <= 1.0:      # a NaN fails both comparisons
         raise ValueError(f"ReSTIR DI uniform_fraction {uniform_fraction!r} is outside (0, 1]")
     return _lib.RESTIR_LIGHT_SELECTION[name]
+
+
+def _restir_sphere_lights_mode(name) -> int:
+    if name not in _lib.RESTIR_SPHERE_LIGHTS:
+        raise ValueError(f"unknown ReSTIR DI sphere lights mode {name!r} ({', '.join(_lib.RESTIR_SPHERE_LIGHTS)})")
+    return _lib.RESTIR_SPHERE_LIGHTS[name]
 
 
 def _restir_bsdf_candidates(n, candidates) -> int:
@@ -1452,8 +1461,11 @@ class RestirDiStage(_RestirStage):
         visibility, o["visibility"] = o["visibility"], "per-target"
         selection, o["light_selection"] = o["light_selection"], "uniform"
         bsdf_candidates, o["bsdf_candidates"] = o["bsdf_candidates"], 0
+        sphere_lights, o["sphere_lights"] = o["sphere_lights"], "point"
         self._create_stage(ctx, scene_stage, size, layers, projection, opt)
         try:
+            if sphere_lights != "point":
+                self.set_sphere_lights(sphere_lights)
             if bsdf_candidates != 0:
                 self.set_bsdf_candidates(bsdf_candidates)
             if visibility != "per-target":
@@ -1483,6 +1495,12 @@ class RestirDiStage(_RestirStage):
         A change is refused while there is history."""
         check(self._fn("set_bsdf_candidates")(self.h, _restir_bsdf_candidates(n, self.options["candidates"])))
         self.options["bsdf_candidates"] = int(n)
+
+    def set_sphere_lights(self, sphere_lights: str):
+        """How a point light with a radius is lit, "point" or "area" (trhip_restir_di_set_sphere_lights): as a point, or by samples on
+        the sphere, which gives its shadows a penumbra.  Another mode than the history's is refused while there is history."""
+        check(self._fn("set_sphere_lights")(self.h, _restir_sphere_lights_mode(sphere_lights)))
+        self.options["sphere_lights"] = sphere_lights
 
     def refresh_light_selection(self) -> bool:
         """Rebuilds the power selection's table after the scene's lights or instances changed (trhip_restir_di_refresh_light_selection);
